@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- stereo frame-pairs/sec of the openVO hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU, started by any launcher that sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR /
      MASTER_PORT, e.g. `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`;
      nothing of torch is imported here -- the ranks meet on a local socket and gather poses over RCCL)
@@ -10,10 +10,15 @@ One step = one StereoOdometer.update() on one 1280x720 stereo pair of the synthe
 sequence (BASELINE config 2, "C2": SGBM D=128 5-path + ORB 500 + Hamming kNN/ratio + 3-D lookup +
 rigid-clique filter + Umeyama), inputs already resident in HBM.  Each rank owns one GPU and a
 contiguous chunk of the sequence (weak scaling); the only exchange is the final gather of the relative
-poses (RCCL all-gather bound behind the C ABI, include/vo355.h vo_mgpu_*).  Rank 0 prints ONE JSON line
-with the contract fields plus `roofline` (dominant kernel: the SGBM path aggregation, timed with HIP
-events on the library's own stream) and `cpu_baseline` (the CPU path timed on this box's host cores,
-N = 1 only: one thread and all cores; a real cv2 when one is importable, the oracle port otherwise).
+poses (RCCL all-gather bound behind the C ABI, include/vo355.h vo_mgpu_*).  A plain run warms up with W
+steps, times ONE cold window of exactly K steps and prints ONE JSON line (rank 0): the contract fields and
+`roofline` (dominant kernel: the SGBM path aggregation, timed with HIP events on the library's own stream
+inside the timed window; whole-job algorithmic bytes x pairs/s).  --dump-outputs DIR writes what the last
+timed step handed its caller as DIR/<name>.npy.  --full adds everything else, as before: `value` as the
+median of five windows, the steady-state, default-odometer and from-host passes, the per-stage and
+copy-ceiling post-passes, `cpu_baseline` (the CPU path timed on this box's host cores, N = 1 only: one
+thread and all cores; a real cv2 when one is importable, the oracle port otherwise) and the C4 / C5
+configs as `other_configs`.
 """
 import argparse
 import json
@@ -54,24 +59,35 @@ def main():
                     help="diagnostic: hand host numpy images to the odometer every step (StereoOdometer.run: pinned "
                          "staging + async upload ahead) instead of HBM-resident inputs -- the PCIe-inclusive rate")
     ap.add_argument("--ndisp", type=int, default=0, help="diagnostic: override numDisparities (changes the workload!)")
-    ap.add_argument("--cpu-pairs", type=int, default=8, help="pairs the single-thread CPU baseline is timed on (0 = skip both CPU legs)")
-    ap.add_argument("--no-post", action="store_true", help="skip the untimed post-passes (per-stage breakdown, from-host rate, other configs)")
-    ap.add_argument("--no-other", action="store_true", help="skip the C4 / C5 runs attached to the C2 line as `other_configs`")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: five windows, steady-state / default-odometer / from-host passes, "
+                         "per-stage and copy-ceiling post-passes, CPU baseline, other configs (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (pose, disparity, 3-D points, keypoints, descriptors) as DIR/<name>.npy")
+    ap.add_argument("--cpu-pairs", type=int, default=8, help="--full: pairs the single-thread CPU baseline is timed on (0 = skip both CPU legs)")
+    ap.add_argument("--no-post", action="store_true", help="--full: skip the untimed post-passes (per-stage breakdown, from-host rate, other configs)")
+    ap.add_argument("--no-other", action="store_true", help="--full: skip the C4 / C5 runs attached to the C2 line as `other_configs`")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="cold-start windows of --steps pairs each, back to back on consecutive frames; `value` is their median "
-                         "(capped so that at most 600 frames are rendered)")
+                         "(capped so that at most 600 frames are rendered; default 1, with --full 5)")
     ap.add_argument("--mix-stages", action="store_true",
-                    help="diagnostic: one more steady pass with HIP events around EVERY stage on its own stream -> `stage_ms_per_pair_in_mix` "
+                    help="--full diagnostic: one more steady pass with HIP events around EVERY stage on its own stream -> `stage_ms_per_pair_in_mix` "
                          "(a stage's latency beside the other pairs' kernels; the events themselves cost some throughput)")
     ap.add_argument("--steady", type=int, default=960,
-                    help="pairs of the untimed-for-`value` steady-state pass reported as `steady_state` (0 = skip)")
+                    help="--full: pairs of the untimed-for-`value` steady-state pass reported as `steady_state` (0 = skip)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else: set up, warm up, one window of --steps pairs
+        args.no_post, args.no_other, args.mix_stages = True, True, False
+        args.cpu_pairs = args.steady = 0
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     from openvo_amd import sharding
 
     group, device = sharding.init_from_env()
     if args.workload == "C5":
-        out = bench_c5(args, group, device, args.steps, args.warmup)
+        out = bench_c5(args, group, device, args.steps, args.warmup, full=args.full, dump=args.dump_outputs)
     else:
         out = bench_stereo(args, group, device, args.workload, args.steps, args.warmup, light=False)
     if group.rank == 0:
@@ -110,18 +126,21 @@ def bench_stereo(args, group, device, workload, K, W, light):
                        max_keypoints=ODO_KW["nfeatures"])
     odo = StereoOdometer(cam, **ODO_KW)
     # this rank's frames: W warm-up frames (they also provide the halo), then R windows of K timed frames each on consecutive
-    # frames (`value` = the median window).  The steady-state pass walks the same frames forwards and backwards (consecutive
-    # frames either way: every step is a real pair of the sequence with the same work) so that nothing more has to be rendered.
+    # frames (`value` = the median window).  At most 600 frames are rendered: a longer run, and the steady-state pass, walk the
+    # same frames forwards and backwards (consecutive frames either way: every step is a real pair of the sequence with the
+    # same work) so that nothing more has to be rendered.
     R = 1 if (light or args.from_host) else max(1, min(args.repeats, max(1, (600 - W) // K)))
     n_unique = W + R * K
+    n_render = max(2, min(n_unique, 600))
     first = rank * R * K
-    frames = c.pairs(first, n_unique)
+    frames = c.pairs(first, n_render)
     S_steady = 0 if (light or args.no_post or args.from_host or args.ndisp) else max(0, args.steady)
-    walk = list(range(n_unique))
-    while S_steady and len(walk) < W + S_steady:          # 0 .. n-1, n-2 .. 0, 1 .. n-1, ...
-        walk += list(range(n_unique - 2, -1, -1)) + list(range(1, n_unique))
+    walk = list(range(n_render))
+    while len(walk) < max(n_unique, W + S_steady):        # 0 .. n-1, n-2 .. 0, 1 .. n-1, ...
+        walk += list(range(n_render - 2, -1, -1)) + list(range(1, n_render))
     walk = walk[:max(n_unique, W + S_steady)]
-    staged = cam.stage_pairs([frames[i] for i in walk])   # inputs resident in HBM before any clock starts
+    seq = [frames[i] for i in walk]                        # the host pair of every step
+    staged = cam.stage_pairs(seq)                           # inputs resident in HBM before any clock starts
     ctx = cam._ctx
 
     def sync_all():
@@ -134,7 +153,7 @@ def bench_stereo(args, group, device, workload, K, W, light):
     gc.freeze()
     gc.disable()
     if args.from_host and not light:
-        for ok in odo.run(frames[:W]):          # warm the path that is timed (pinned staging is allocated on first use)
+        for ok in odo.run(seq[:W]):             # warm the path that is timed (pinned staging is allocated on first use)
             pass
     else:
         for i in range(W):
@@ -154,7 +173,7 @@ def bench_stereo(args, group, device, workload, K, W, light):
         t0 = time.perf_counter()
         if args.from_host and not light:
             before = od.c_T_w
-            for ok in od.run(frames[lo:lo + n]):
+            for ok in od.run(seq[lo:lo + n]):
                 acc.append(bool(ok))
                 rel.append(sharding.relative_from_chain(before, od.c_T_w) if ok else np.eye(4))
                 before = od.c_T_w
@@ -167,7 +186,7 @@ def bench_stereo(args, group, device, workload, K, W, light):
                     rel.append(sharding.relative_from_chain(before, od.c_T_w) if ok else np.eye(4))
         ctx.synchronize()                         # every stream of this rank's context has drained: this rank's n steps are done
         dt = time.perf_counter() - t0             # (the MAX over ranks is taken below; the closing barrier is not part of any rank's work)
-        if record:
+        if record and args.full:
             clocks.append(round(ctx.shader_clock(200), 0))   # after the clock has stopped: the shader clock this window ended at
         group.barrier()
         cam.lookahead_stop = None
@@ -175,6 +194,8 @@ def bench_stereo(args, group, device, workload, K, W, light):
 
     for r in range(R):                            # R windows of exactly K steps each, on consecutive frames
         dts.append(window(odo, W + r * K, K, True))
+    if args.dump_outputs and rank == 0 and not light:
+        dump_outputs(args.dump_outputs, stereo_outputs(odo, acc[-1]))
     tm = ctx.timings(reset=True)
     ctx.enable_timing(False)
     odo.reset_lookahead()
@@ -388,11 +409,12 @@ def bench_stereo(args, group, device, workload, K, W, light):
             # stream drained and all look-ahead work dropped before each clock starts); the samples, in order:
             "window_values": [round(K * world / d, 2) for d in dt_windows],
             "window_ms": [round(1e3 * d, 3) for d in dt_windows],
-            # the shader clock (MHz) rank 0 read right after each window's clock had stopped (vo_shader_clock: one wave, 200 us):
-            # a GPU that was idle before the run ramps its clock over the first windows
-            "window_clock_mhz": clocks[:len(dt_windows)],
             "cores_per_rank": cores_per_rank(world),
         }
+        if clocks:
+            # (--full) the shader clock (MHz) rank 0 read right after each window's clock had stopped (vo_shader_clock: one
+            # wave, 200 us): a GPU that was idle before the run ramps its clock over the first windows
+            out["window_clock_mhz"] = clocks[:len(dt_windows)]
         if dt_default:
             out["default_odometer"] = {
                 "value": round(K * world / dt_default, 3), "unit": "frame-pairs/s", "steps": K, "ms_per_step": round(1e3 * dt_default / K, 4),
@@ -423,8 +445,8 @@ def bench_stereo(args, group, device, workload, K, W, light):
         # trajectory error vs the analytic ground truth (information only)
         poses = sharding.compose(all_rel, all_ok)
         if world == 1:
-            gt0 = np.linalg.inv(Corridor.gt_pose(first + W - 1))
-            err = [np.linalg.norm(poses[i][:3, 3] - (gt0 @ Corridor.gt_pose(first + W + i))[:3, 3]) for i in range(R * K)]
+            gt0 = np.linalg.inv(Corridor.gt_pose(first + (walk[W - 1] if W else -1)))
+            err = [np.linalg.norm(poses[i][:3, 3] - (gt0 @ Corridor.gt_pose(first + walk[W + i]))[:3, 3]) for i in range(R * K)]
             out["ate_vs_ground_truth_m"] = round(float(np.sqrt(np.mean(np.square(err)))), 5)
         if world == 1 and args.cpu_pairs > 0 and not light:
             out["cpu_baseline"], out["ate_vs_cpu_m"] = cpu_baseline(c, cam, sgbm, frames, W, min(args.cpu_pairs, K), odo_poses=poses)
@@ -432,11 +454,11 @@ def bench_stereo(args, group, device, workload, K, W, light):
     return out
 
 
-def bench_c5(args, group, device, K_steps, W):
+def bench_c5(args, group, device, K_steps, W, full=True, dump=None):
     """BASELINE config 5 (no openVO counterpart): monocular 1920x1080, ORB 8000 keypoints per frame, ~8000 x 8000
     Hamming kNN-2 + ratio, 5000-hypothesis essential-matrix RANSAC -- one MonoOdometer.update per step, frames
-    resident in HBM, one host synchronisation per pair.  Not HBM-bound: the roofline block prices the
-    two op-counts against the vector-ALU peak instead."""
+    resident in HBM, one host synchronisation per pair.  Not HBM-bound: the roofline block (full only: it
+    takes an untimed pass of its own) prices the two op-counts against the vector-ALU peak instead."""
     from openvo_amd.mono import MonoOdometer
     from openvo_amd.synth import Corridor
     c = Corridor("C5")
@@ -466,25 +488,29 @@ def bench_c5(args, group, device, K_steps, W):
     group.barrier()
     dt = group.all_reduce_max(dt)
     spec, spec_depth = dict(odo.speculation), odo.speculate
-    # per-stage device times from an untimed pass of the same steps with HIP events on (event packets around every stage of
-    # every stream cost throughput: they stay out of the timed region)
-    n_ev = min(K_steps, 40)
-    odo.restart()                # (the pass replays the timed frames: its first one is a first frame again)
-    odo.speculate = 0            # one pair's chain at a time: a stage's event pair then brackets that stage's own kernels only
-    ctx.synchronize()
-    ctx.enable_timing(True)
-    ctx.timings(reset=True)
-    resid_ev = 0
-    for k in order[W:W + n_ev]:
-        odo.update(k)
-        if odo.last is not None:
-            resid_ev += iters * odo.last["matches"]
-    ctx.synchronize()
-    tm = ctx.timings(reset=True)
-    ctx.enable_timing(False)
-    out = None
+    if dump and group.rank == 0:
+        dump_outputs(dump, mono_outputs(odo, ok))
+    tm, n_ev, resid_ev = None, 0, 0
+    if full:
+        # per-stage device times from an untimed pass of the same steps with HIP events on (event packets around every stage of
+        # every stream cost throughput: they stay out of the timed region)
+        n_ev = min(K_steps, 40)
+        odo.restart()                # (the pass replays the timed frames: its first one is a first frame again)
+        odo.speculate = 0            # one pair's chain at a time: a stage's event pair then brackets that stage's own kernels only
+        ctx.synchronize()
+        ctx.enable_timing(True)
+        ctx.timings(reset=True)
+        for k in order[W:W + n_ev]:
+            odo.update(k)
+            if odo.last is not None:
+                resid_ev += iters * odo.last["matches"]
+        ctx.synchronize()
+        tm = ctx.timings(reset=True)
+        ctx.enable_timing(False)
+    out = roof = None
     if group.rank == 0:
         n_kp = ctx.orb_slot_count(odo._ref[0], nfeat, 0)
+    if group.rank == 0 and tm is not None:
         pair_dists = float(n_kp) * n_kp * n_ev          # ~ keypoints^2 Hamming distances (256 bit) per pair
         match_s, pose_s = tm["match"][0] / 1e3, tm["pose"][0] / 1e3
         knn_s = tm["knn"][0] / 1e3                       # the kNN kernel alone (the match stage also holds the ratio compaction)
@@ -506,6 +532,17 @@ def bench_c5(args, group, device, K_steps, W):
         # multiply-adds per pair against the dense int8 MFMA peak (1024 MAC / cycle / SIMD: MI355X_MICROARCH.md, matrix cores)
         mfma_i8_peak = 1024 * 2 * 1024 * 2.4e9
         res_rate = resid_ev / pose_s if pose_s > 0 else 0.0
+        roof = {"bound": "mfma", "kernel": "k_bf_knn2 (Hamming kNN-2 as an exact int8 contraction: v_mfma_i32_16x16x64_i8)",
+                "achieved": round(ham_rate * 512 / 1e12, 2), "peak": round(mfma_i8_peak / 1e12, 1), "unit": "TOP/s",
+                "frac": round(ham_rate * 512 / mfma_i8_peak, 5), "traffic": None,
+                "knn_us_per_launch": round(1e6 * knn_s / max(n_ev, 1), 2),
+                "knn_us_per_launch_single_event_pair": round(1e3 * tm["knn"][0] / max(n_ev, 1), 2),
+                "knn_condition": "20 launches back to back between two HIP events on the main stream (the frame's %d descriptors against themselves)" % int(n_kp),
+                "hamming_pair_distances_per_s": round(ham_rate, 0), "residual_evaluations_per_s": round(res_rate, 0),
+                "residual_frac_of_valu_peak": round(res_rate * 30 / lane_ops, 5),
+                "stage_ms_per_pair": {k: round(v[0] / n_ev, 4) for k, v in tm.items() if v[0] > 0},
+                "stage_pass": "%d untimed steps with HIP events on, one pair step at a time" % n_ev}
+    if group.rank == 0:
         out = {"metric": "mono frame-pairs/sec (1920x1080)", "value": round(K_steps * group.world / dt, 3), "unit": "frame-pairs/s",
                "n_gpus": group.world, "steps": K_steps, "warmup": W, "ms_per_step": round(1e3 * dt / K_steps, 4), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "u8/f32", "data": "synthetic",
@@ -513,22 +550,49 @@ def bench_c5(args, group, device, K_steps, W):
                                       "(%s minimal solver), one host sync per pair" % (nfeat, iters, "five-point" if solver == 5 else "eight-point"),
                           "parallelism": "frame-sharded x%d" % group.world, "inputs": "resident in HBM",
                           "oracle": "none in openVO (no RANSAC, no monocular path): parity vs the build's own CPU restatement only"},
-               "roofline": {"bound": "mfma", "kernel": "k_bf_knn2 (Hamming kNN-2 as an exact int8 contraction: v_mfma_i32_16x16x64_i8)",
-                            "achieved": round(ham_rate * 512 / 1e12, 2), "peak": round(mfma_i8_peak / 1e12, 1), "unit": "TOP/s",
-                            "frac": round(ham_rate * 512 / mfma_i8_peak, 5), "traffic": None,
-                            "knn_us_per_launch": round(1e6 * knn_s / max(n_ev, 1), 2),
-                            "knn_us_per_launch_single_event_pair": round(1e3 * tm["knn"][0] / max(n_ev, 1), 2),
-                            "knn_condition": "20 launches back to back between two HIP events on the main stream (the frame's %d descriptors against themselves)" % int(n_kp),
-                            "hamming_pair_distances_per_s": round(ham_rate, 0), "residual_evaluations_per_s": round(res_rate, 0),
-                            "residual_frac_of_valu_peak": round(res_rate * 30 / lane_ops, 5),
-                            "stage_ms_per_pair": {k: round(v[0] / n_ev, 4) for k, v in tm.items() if v[0] > 0},
-                            "stage_pass": "%d untimed steps with HIP events on, one pair step at a time" % n_ev},
                "pairs_in_flight": {"speculate": spec_depth, "orb_lookahead": odo.lookahead, "steps_begun_ahead": spec["begun"],
                                    "used": spec["used"], "voided": spec["void"]},
                "accepted_frames": int(acc), "frames": K_steps, "keypoints_per_frame": int(n_kp),
                "matches_per_pair": int(resid / iters / max(K_steps, 1))}
+        if roof is not None:
+            out["roofline"] = roof
     odo.close()
     return out if group.rank == 0 else None
+
+
+def stereo_outputs(odo, accepted):
+    """What a caller of StereoOdometer.update() holds after the step: its return value, the chained pose and the current
+    frame's disparity, 3-D points, keypoints and descriptors (all cropped to the valid region, as the odometer hands them out).
+    reprojectImageTo3D divides by zero where the disparity is invalid: such points are written as 0 and `points_3d_finite`
+    (1 where all three coordinates are finite) says where they were, so that every written value is finite."""
+    out = {"accepted": np.array([float(accepted)]), "c_T_w": odo.c_T_w, "pose": odo.current_pose()}
+    if odo.current_kps is not None:
+        xyz = np.asarray(odo.current_3d)
+        finite = np.isfinite(xyz).all(axis=-1)
+        out.update(disparity=np.asarray(odo.current_disparity), points_3d=np.where(finite[..., None], xyz, 0),
+                   points_3d_finite=finite, keypoints_xy=odo.current_kps.xy, descriptors=np.asarray(odo.current_desc))
+    return out
+
+
+def mono_outputs(odo, accepted):
+    """What a caller of MonoOdometer.update() holds after the step: its return value, the chained pose and the last pair's
+    RANSAC result (essential matrix, inlier mask, match / inlier counts)."""
+    out = {"accepted": np.array([float(accepted)]), "c_T_w": odo.c_T_w, "pose": odo.current_pose()}
+    if odo.last is not None:
+        out.update(essential=odo.last["E"], inlier_mask=odo.last["mask"],
+                   counts=np.array([odo.last["matches"], odo.last["best_count"]], np.float64))
+    return out
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array: float64 stays float64, anything else is written as float32 (the largest workload, C4,
+    writes 60 MiB: disparity, 3-D points and their mask of one 2048x1536 frame).  Every value must be finite."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError("--dump-outputs: %s holds non-finite values" % name)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cores_per_rank(world):

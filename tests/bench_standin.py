@@ -52,8 +52,12 @@ class FakeOdometer:
     """update() accepts every frame and chains a fixed forward motion: the composed trajectory is checkable."""
     def __init__(self, cam, **kw):
         self.cam, self.c_T_w, self.skipped_frames, self.first = cam, np.eye(4), 0, True
+        self.current_kps = None                     # (no frame images on the host side: --dump-outputs writes the pose only)
 
     def reset_lookahead(self): pass
+
+    def current_pose(self):
+        return np.linalg.inv(self.c_T_w)
 
     def update(self, staged, _):
         assert 0 <= staged.index < len(self.cam.frames)

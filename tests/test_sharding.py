@@ -399,7 +399,7 @@ def test_bench_orchestration_with_eight_socket_ranks(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world),
                PYTHONPATH=ROOT, VO_NO_RCCL="1", VO_RUN_ID="standin-%d" % os.getpid())
     cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_standin.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
-           "--repeats", "2", "--cpu-pairs", "0", "--no-post", "--no-other"]
+           "--full", "--repeats", "2", "--cpu-pairs", "0", "--no-post", "--no-other"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in range(world)]
     outs = [p.communicate(timeout=600) for p in procs]
@@ -414,3 +414,65 @@ def test_bench_orchestration_with_eight_socket_ranks(tmp_path):
     assert d["frames"] == world * 8 and d["accepted_frames"] == world * 8 and d["shard_boundaries_inexact"] == []
     assert d["cores_per_rank"] == pytest.approx(len(os.sched_getaffinity(0)) / world, abs=0.01)
     assert d["rccl"]["transport"] == "socket" and d["rccl"]["world"] == world
+
+
+def test_plain_bench_run_times_exactly_steps_pairs_and_dumps_its_last_step(tmp_path):
+    """bench.py without --full (two socket ranks, GPU work replaced by stand-ins as above): ONE window of exactly --steps pairs
+    per rank, none of the --full extras in the line, and --dump-outputs writes the last timed step's pose as float64 .npy
+    files that are the same in a second run with the same arguments."""
+    import json
+    world, steps = 2, 5
+
+    def run(dump):
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world),
+                   PYTHONPATH=ROOT, VO_NO_RCCL="1", VO_RUN_ID="standin-plain-%d-%s" % (os.getpid(), dump.name))
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_standin.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", "2",
+               "--dump-outputs", str(dump)]
+        procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+                 for r in range(world)]
+        outs = [p.communicate(timeout=600) for p in procs]
+        assert all(p.returncode == 0 for p in procs), "\n".join(o[1][-2000:] for o in outs)
+        lines = [l for l in outs[0][0].splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "a")
+    assert d["steps"] == steps and d["warmup"] == 2 and len(d["window_ms"]) == 1 and d["frames"] == world * steps
+    assert d["ms_per_step"] == pytest.approx(d["window_ms"][0] / steps, rel=1e-3)
+    assert d["value"] == pytest.approx(steps * world / (d["window_ms"][0] / 1e3), rel=1e-3)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "roofline"):
+        assert k in d
+    for k in ("window_clock_mhz", "steady_state", "default_odometer", "stage_ms_per_pair_alone", "from_host_pairs_per_s",
+              "cpu_baseline", "other_configs"):
+        assert k not in d, k
+    first = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(first) == ["accepted", "c_T_w", "pose"]
+    assert all(a.dtype == np.float64 for a in first.values())
+    assert first["accepted"].tolist() == [1.0] and first["c_T_w"][2, 3] == pytest.approx(-0.25 * (2 + steps - 1))
+    assert np.allclose(first["pose"] @ first["c_T_w"], np.eye(4))
+    run(tmp_path / "b")
+    assert sorted(os.listdir(tmp_path / "b")) == sorted(f + ".npy" for f in first)
+    assert all(np.array_equal(np.load(tmp_path / "b" / (f + ".npy")), a) for f, a in first.items())
+
+
+def test_dumped_stereo_outputs_are_finite_and_keep_where_the_3d_points_were_not(tmp_path):
+    """reprojectImageTo3D divides by zero at invalid disparities: bench.py --dump-outputs writes those points as 0 with a
+    per-pixel mask beside them (every written value finite), and refuses to write an array that holds a non-finite value."""
+    import types
+    import bench
+    xyz = np.arange(2 * 3 * 3, dtype=np.float32).reshape(2, 3, 3)
+    xyz[0, 1] = np.inf
+    xyz[1, 2, 0] = -np.inf
+    xyz[1, 0, 2] = np.nan
+    odo = types.SimpleNamespace(c_T_w=np.eye(4), current_pose=lambda: np.eye(4), current_3d=xyz,
+                                current_disparity=np.full((2, 3), -1.0, np.float32), current_desc=np.zeros((1, 32), np.uint8),
+                                current_kps=types.SimpleNamespace(xy=np.zeros((1, 2), np.float32)))
+    bench.dump_outputs(str(tmp_path), bench.stereo_outputs(odo, True))
+    pts, fin = np.load(tmp_path / "points_3d.npy"), np.load(tmp_path / "points_3d_finite.npy")
+    assert pts.dtype == fin.dtype == np.float32 and np.isfinite(pts).all()
+    assert fin.tolist() == [[1, 0, 1], [0, 1, 0]]
+    assert np.array_equal(pts[fin == 1], xyz[fin == 1]) and not pts[fin == 0].any()
+    for f in os.listdir(tmp_path):
+        assert np.isfinite(np.load(tmp_path / f)).all(), f
+    with pytest.raises(ValueError, match="non-finite"):
+        bench.dump_outputs(str(tmp_path / "x"), {"points_3d": xyz})

@@ -7,7 +7,7 @@ R=$1; shift
 out=gpurun_out/ab_$$.txt
 for r in $(seq 1 $R); do
 for e in "$@"; do
-  v=$(env $e python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-pairs 0 --no-other 2>/dev/null | python -c "
+  v=$(env $e python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-pairs 0 --no-other 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['steady_state']['value'], d['default_odometer']['value'], d.get('from_host_pairs_per_s'))")
   echo "cfg [$e] $v"
