@@ -158,6 +158,23 @@ int vo_download_keypoints(vo_ctx* ctx, int slot, float* kp_xy, float* kp_size, f
  * lower train index; -1 / INT32_MAX where the train set has fewer than 2 rows */
 int vo_bf_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt,
                        int32_t* idx, int32_t* dist);
+/* Cross-check (mutual nearest neighbours), an EXTENSION of the matcher [stereo_odometer.py:21 "# TODO crosscheck", above
+ * cv2.BFMatcher.create(cv2.NORM_HAMMING)]:
+ *   b(i) = the nearest train of query i, ties -> lower train index (= idx[2 i] of vo_bf_knn2_hamming);
+ *   a(j) = the nearest query of train j, ties -> lower query index;
+ *   query i passes iff b(i) exists and a(b(i)) == i.
+ * That is mutual nearest neighbour with OpenCV's tie rule in both directions, which is what OpenCV's
+ * BFMatcher(NORM_HAMMING, crossCheck=true) / batchDistance(crosscheck=true) is believed to produce -- from memory of its code,
+ * parity unpinned (no OpenCV to compare against where this was written; tests/test_crosscheck_host.py pins it wherever a cv2
+ * is importable).  a(j) comes out of the SAME kernel launch as the kNN-2 (column minima of the distance tiles): the matcher
+ * runs once, not twice.  Cross-check needs nq <= 65535 (VO_E_CAP otherwise).
+ * match_flags of the _ex entries below: bit 0 = VO_MATCH_CROSSCHECK; every other bit must be 0.  The entries without _ex are
+ * the same calls with match_flags = 0, unchanged. */
+#define VO_MATCH_CROSSCHECK 1
+/* vo_bf_knn2_hamming's idx / dist of the same launch, plus mutual (nq bytes: 1 = query i passes the cross-check) and, when
+ * t_best is not NULL, t_best (nt x 2 int32): {a(j), its distance}, {-1, INT32_MAX} when there is no query */
+int vo_bf_knn2_hamming_mutual(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx, int32_t* dist,
+                              uint8_t* mutual, int32_t* t_best);
 /* m[0].distance < ratio * m[1].distance in double on float32 distances [:164]; host only */
 int vo_ratio_filter(const int32_t* idx, const int32_t* dist, int nq, double ratio, int32_t* q_out,
                     int32_t* t_out, int* m_out);
@@ -177,6 +194,10 @@ int vo_bilinear_at(vo_ctx* ctx, const float* img3d, int w, int h, const float* x
 int vo_point_clouds(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int32_t* q_idx,
                     int32_t* t_idx, float* pts_a /*cap*3*/, float* pts_b, uint8_t* status_a,
                     uint8_t* status_b, int cap, int* m_out);
+/* the same; with VO_MATCH_CROSSCHECK a match must pass the ratio test AND its m[0] the cross-check */
+int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int32_t* q_idx,
+                       int32_t* t_idx, float* pts_a, float* pts_b, uint8_t* status_a,
+                       uint8_t* status_b, int cap, int* m_out);
 
 /* fused pair step with ONE host synchronisation: point_clouds [:162-175] followed by the filtering
  * and fitting part of point_cloud_transform [:177-205] for two device-resident slots.
@@ -197,6 +218,13 @@ int vo_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matc
 int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matches, double rigidity_thr,
                        double outlier_thr, int* ticket_out);
 int vo_pose_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* rc2, double* T1_12, double* T2_12);
+/* vo_pose_pair / vo_pose_pair_begin with match_flags (VO_MATCH_CROSSCHECK: as vo_point_clouds_ex; M counts the matches that
+ * pass both tests, every later stage works on them).  A ticket's flags are part of its parameters (vo_pose_pair_end returns
+ * what vo_pose_pair_ex with the same flags would have). */
+int vo_pose_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int min_matches, double rigidity_thr,
+                    double outlier_thr, int32_t* counts4, int32_t* rc2, double* T1_12, double* T2_12);
+int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int min_matches, double rigidity_thr,
+                          double outlier_thr, int* ticket_out);
 
 /* pose (stereo_odometer.py:82-105,177-223) ---------------------------------------------- */
 /* cv2.estimateAffine3D(src, dst, force_rotation) Umeyama [:190,204]: T 3x4 row-major, scale */
@@ -251,6 +279,12 @@ int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, const 
                        int solver, int want_matches, int* ticket_out);
 int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx,
                      float* xy_b_out, int cap);
+/* vo_mono_pair / vo_mono_pair_begin with match_flags (VO_MATCH_CROSSCHECK: kNN-2 -> ratio test -> cross-check -> RANSAC;
+ * counts3[0] counts the matches that pass both tests) */
+int vo_mono_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                    uint32_t seed, int solver, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
+int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                          uint32_t seed, int solver, int want_matches, int* ticket_out);
 
 /* RANSAC solvePnP hypothesis scoring (north star; BASELINE config 2 names "ORB+SGBM+PnP") ----------
  * NOT part of the reference either (openVO fits 3-D/3-D, stereo_odometer.py:187-205): defined by this
@@ -290,6 +324,9 @@ int vo_measure_copy(vo_ctx* ctx, int64_t bytes, int reps, int nontemporal, doubl
  * stream between two HIP events -> microseconds per launch (the event pair's own cost is spread over the launches).  The result
  * arrays are the context's match scratch; nothing the caller holds changes.  Semantics of the kernel: stereo_odometer.py:163. */
 int vo_measure_knn(vo_ctx* ctx, int slot_a, int slot_b, int reps, double* us_per_launch);
+/* the same for either form of the kernel: match_flags 0 = the plain kNN-2, VO_MATCH_CROSSCHECK = kNN-2 + column minima (and the
+ * reset of the column words on the stream in front of each launch, which is part of what a cross-check launch costs) */
+int vo_measure_knn_ex(vo_ctx* ctx, int slot_a, int slot_b, int reps, int match_flags, double* us_per_launch);
 /* the shader clock the GPU holds right now (MHz): one wave counts its cycles (s_memtime) against the 100 MHz wall counter
  * (s_memrealtime) for `micros` microseconds on the context's main stream; synchronous.  Measurement aid (bench.py records it
  * after every timed window: a GPU that has been idle ramps its clock up over the first tens of milliseconds of work). */

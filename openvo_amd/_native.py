@@ -35,6 +35,8 @@ SYMBOLS = [
     "vo_upload_mono", "vo_prefetch_staged_mono", "vo_mono_pair", "vo_mono_pair_begin", "vo_mono_pair_end", "vo_slot_ready", "vo_host_stage_begin", "vo_host_stage_wait",
     "vo_device_count", "vo_mgpu_unique_id", "vo_mgpu_create", "vo_mgpu_destroy", "vo_mgpu_info", "vo_mgpu_last_error",
     "vo_mgpu_gather_poses", "vo_mgpu_all_gather_f64", "vo_mgpu_all_reduce_max_f64",
+    "vo_bf_knn2_hamming_mutual", "vo_point_clouds_ex", "vo_pose_pair_ex", "vo_pose_pair_begin_ex", "vo_mono_pair_ex",
+    "vo_mono_pair_begin_ex", "vo_measure_knn_ex",
 ]
 
 
@@ -184,6 +186,13 @@ def lib():
         L.vo_host_stage_wait.argtypes = [vp, ci]
         L.vo_mono_pair_begin.argtypes = [vp, ci, ci, cd, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
         L.vo_mono_pair_end.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci]
+        L.vo_bf_knn2_hamming_mutual.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp]
+        L.vo_point_clouds_ex.argtypes = [vp, ci, ci, cd, ci, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.vo_pose_pair_ex.argtypes = [vp, ci, ci, cd, ci, ci, cd, cd, vp, vp, vp, vp]
+        L.vo_pose_pair_begin_ex.argtypes = [vp, ci, ci, cd, ci, ci, cd, cd, vp]
+        L.vo_mono_pair_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, ci]
+        L.vo_mono_pair_begin_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
+        L.vo_measure_knn_ex.argtypes = [vp, ci, ci, ci, ci, vp]
         L.vo_device_count.argtypes = [vp]
         L.vo_mgpu_unique_id.argtypes = [vp]
         L.vo_mgpu_create.argtypes = [ci, ci, ci, vp, vp]
@@ -196,6 +205,14 @@ def lib():
         L.vo_mgpu_all_reduce_max_f64.argtypes = [vp, vp, ci]
         _lib = L
     return _lib
+
+
+VO_MATCH_CROSSCHECK = 1
+
+
+def _flags(cross_check):
+    """match_flags of the _ex entries"""
+    return VO_MATCH_CROSSCHECK if cross_check else 0
 
 
 def _p(a):
@@ -484,6 +501,18 @@ class Context:
         self._ck(self._lib.vo_bf_knn2_hamming(self._h, _p(q), len(q), _p(t), len(t), _p(idx), _p(dist)))
         return idx, dist
 
+    def bf_knn2_mutual(self, q, t):
+        """bf_knn2 plus the cross-check of the same launch -> (idx, dist, mutual, t_best): mutual[i] = 1 when the nearest train of
+        query i has query i as ITS nearest query (ties -> lower index both ways); t_best (nt x 2) = that nearest query of every
+        train descriptor and its distance ({-1, INT32_MAX} when there is no query)."""
+        q, t = _c(q, np.uint8).reshape(-1, 32), _c(t, np.uint8).reshape(-1, 32)
+        idx = np.empty((len(q), 2), np.int32)
+        dist = np.empty((len(q), 2), np.int32)
+        mutual = np.empty(len(q), np.uint8)
+        t_best = np.empty((len(t), 2), np.int32)
+        self._ck(self._lib.vo_bf_knn2_hamming_mutual(self._h, _p(q), len(q), _p(t), len(t), _p(idx), _p(dist), _p(mutual), _p(t_best)))
+        return idx, dist, mutual, t_best
+
     def ratio_filter(self, idx, dist, ratio):
         idx, dist = _c(idx, np.int32), _c(dist, np.int32)
         qo, to = np.empty(len(idx), np.int32), np.empty(len(idx), np.int32)
@@ -508,32 +537,32 @@ class Context:
         self._ck(self._lib.vo_bilinear_at(self._h, _p(img3d), w, h, _p(xy), len(xy), _p(out), _p(st)))
         return out, st
 
-    def point_clouds(self, slot_a, slot_b, ratio):
+    def point_clouds(self, slot_a, slot_b, ratio, cross_check=False):
         cap = self.kp_cap
         q, t = np.empty(cap, np.int32), np.empty(cap, np.int32)
         pa, pb = np.empty((cap, 3), np.float32), np.empty((cap, 3), np.float32)
         sa, sb = np.empty(cap, np.uint8), np.empty(cap, np.uint8)
         m = ctypes.c_int(0)
-        self._ck(self._lib.vo_point_clouds(self._h, slot_a, slot_b, float(ratio), _p(q), _p(t), _p(pa), _p(pb),
-                                           _p(sa), _p(sb), cap, ctypes.byref(m)))
+        self._ck(self._lib.vo_point_clouds_ex(self._h, slot_a, slot_b, float(ratio), _flags(cross_check), _p(q), _p(t), _p(pa), _p(pb),
+                                              _p(sa), _p(sb), cap, ctypes.byref(m)))
         m = m.value
         return q[:m], t[:m], pa[:m], pb[:m], sa[:m], sb[:m]
 
-    def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr):
+    def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False):
         """Fused match + ratio + 3-D lookup + clique filter + outlier pass + Umeyama for two slots.
         Returns (counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4)."""
         counts = np.zeros(4, np.int32)
         rc = np.ones(2, np.int32)
         T1 = np.full((3, 4), np.nan)
         T2 = np.full((3, 4), np.nan)
-        self._ck(self._lib.vo_pose_pair(self._h, int(slot_a), int(slot_b), float(ratio), int(min_matches),
-                                        float(rigidity_thr), float(outlier_thr), _p(counts), _p(rc), _p(T1), _p(T2)))
+        self._ck(self._lib.vo_pose_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), int(min_matches),
+                                           float(rigidity_thr), float(outlier_thr), _p(counts), _p(rc), _p(T1), _p(T2)))
         return counts, rc, T1, T2
 
-    def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr):
+    def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False):
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_pose_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), int(min_matches),
-                                              float(rigidity_thr), float(outlier_thr), ctypes.byref(t)))
+        self._ck(self._lib.vo_pose_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), int(min_matches),
+                                                 float(rigidity_thr), float(outlier_thr), ctypes.byref(t)))
         return t.value
 
     def pose_pair_end(self, ticket):
@@ -570,7 +599,7 @@ class Context:
     def prefetch_staged_mono(self, slot, index, nfeatures):
         self._ck(self._lib.vo_prefetch_staged_mono(self._h, int(slot), int(index), int(nfeatures)))
 
-    def mono_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8):
+    def mono_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False):
         """kNN-2 + ratio + essential-matrix RANSAC between two slots' keypoints, all on the device, one sync.
         -> dict(E 3x3, matches M, best_iter, best_count[, mask, q, t of length M])."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
@@ -580,8 +609,8 @@ class Context:
         mask = np.zeros(cap, np.uint8) if want_matches else None
         q = np.zeros(cap, np.int32) if want_matches else None
         t = np.zeros(cap, np.int32) if want_matches else None
-        self._ck(self._lib.vo_mono_pair(self._h, int(slot_a), int(slot_b), float(ratio), _p(K4), int(iters), float(thr), int(seed) & 0xFFFFFFFF,
-                                        int(solver), _p(E), _p(c3), _p(mask) if want_matches else None, _p(q) if want_matches else None,
+        self._ck(self._lib.vo_mono_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+                                           int(seed) & 0xFFFFFFFF, int(solver), _p(E), _p(c3), _p(mask) if want_matches else None, _p(q) if want_matches else None,
                                         _p(t) if want_matches else None, cap))
         out = {"E": E.reshape(3, 3), "matches": int(c3[0]), "best_iter": int(c3[1]), "best_count": int(c3[2])}
         if want_matches:
@@ -594,11 +623,11 @@ class Context:
         self._ck(self._lib.vo_slot_ready(self._h, int(slot), ctypes.byref(r)))
         return bool(r.value)
 
-    def mono_pair_begin(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8):
+    def mono_pair_begin(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False):
         """mono_pair in two halves (several pairs in flight): -> ticket for mono_pair_end."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_mono_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_mono_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
                                               int(seed) & 0xFFFFFFFF, int(solver), int(bool(want_matches)), ctypes.byref(t)))
         return t.value
 
@@ -692,10 +721,11 @@ class Context:
         self._ck(self._lib.vo_measure_copy(self._h, int(nbytes), int(reps), 1 if nontemporal else 0, ctypes.byref(g)))
         return g.value
 
-    def measure_knn(self, slot_a, slot_b, reps=20):
-        """microseconds per launch of the Hamming kNN-2 kernel on two slots' descriptors (`reps` launches between two events)."""
+    def measure_knn(self, slot_a, slot_b, reps=20, cross_check=False):
+        """microseconds per launch of the Hamming kNN-2 kernel on two slots' descriptors (`reps` launches between two events);
+        cross_check=True times the cross-check form of the kernel (with the reset of its column words)."""
         g = ctypes.c_double(0.0)
-        self._ck(self._lib.vo_measure_knn(self._h, int(slot_a), int(slot_b), int(reps), ctypes.byref(g)))
+        self._ck(self._lib.vo_measure_knn_ex(self._h, int(slot_a), int(slot_b), int(reps), _flags(cross_check), ctypes.byref(g)))
         return g.value
 
     def shader_clock(self, micros=200):

@@ -257,10 +257,12 @@ extern "C" int vo_ratio_filter(const int32_t* idx, const int32_t* dist, int nq, 
 // ballots, the per-(batch row, wave) counts go through LDS where the first wave turns them into exclusive offsets (one
 // wave-wide prefix over 128 counts), and the survivors' coordinates are gathered and stored.  Three global round trips per
 // 8192 queries (the one-element-per-thread loop this replaces paid three per 1024: 22 us at 8000 queries, now 6).
+// CROSS: the survivors of the ratio test must also pass the cross-check (colmin: column words of the same kNN launch, nt of them)
+template <bool CROSS>
 __global__ void __launch_bounds__(1024) k_ratio_compact(const int32_t* __restrict__ idx, const int32_t* __restrict__ dist, int nq, double ratio,
                                                         const float* __restrict__ xy_q, const float* __restrict__ xy_t, int32_t* __restrict__ q_out,
                                                         int32_t* __restrict__ t_out, float* __restrict__ xyq_out, float* __restrict__ xyt_out,
-                                                        int32_t* __restrict__ m_out)
+                                                        int32_t* __restrict__ m_out, const uint32_t* __restrict__ colmin, int nt_c)
 {
     constexpr int K = 8;
     __shared__ int s_cnt[K * 16 + 1];
@@ -280,7 +282,8 @@ __global__ void __launch_bounds__(1024) k_ratio_compact(const int32_t* __restric
         for (int k = 0; k < K; k++) {
             const int i = i0 + k * nt + threadIdx.x;
             const double a = (double)(float)ds[k].x, b = (double)(float)ds[k].y;
-            const bool keep = i < nq && id[k].y >= 0 && a < ratio * b;
+            bool keep = i < nq && id[k].y >= 0 && a < ratio * b;
+            if constexpr (CROSS) keep = keep && knn_mutual(id[k].x, i, colmin, nt_c);
             bal[k] = __ballot(keep);
             if (lane == 0) s_cnt[k * nw + wv] = __popcll(bal[k]);
             pq[k] = make_float2(0.f, 0.f); pt[k] = pq[k];
@@ -311,12 +314,17 @@ __global__ void __launch_bounds__(1024) k_ratio_compact(const int32_t* __restric
     }
     if (threadIdx.x == 0) *m_out = base;
 }
+template __global__ void k_ratio_compact<false>(const int32_t*, const int32_t*, int, double, const float*, const float*, int32_t*, int32_t*, float*,
+                                                float*, int32_t*, const uint32_t*, int);
+template __global__ void k_ratio_compact<true>(const int32_t*, const int32_t*, int, double, const float*, const float*, int32_t*, int32_t*, float*,
+                                               float*, int32_t*, const uint32_t*, int);
 
-extern "C" int vo_point_clouds(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int32_t* q_idx, int32_t* t_idx,
-                               float* pts_a, float* pts_b, uint8_t* status_a, uint8_t* status_b, int cap, int* m_out)
+extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int32_t* q_idx, int32_t* t_idx,
+                                  float* pts_a, float* pts_b, uint8_t* status_a, uint8_t* status_b, int cap, int* m_out)
 {
-    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !m_out)
+    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !m_out || (match_flags & ~VO_MATCH_CROSSCHECK))
         return vo_fail(ctx, VO_E_ARG, "vo_point_clouds: bad argument");
+    const int cross = match_flags & VO_MATCH_CROSSCHECK;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
     if (!a.has_kp || !b.has_kp || !a.has_disp || !b.has_disp) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
@@ -328,10 +336,15 @@ extern "C" int vo_point_clouds(vo_ctx* ctx, int slot_a, int slot_b, double ratio
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist);
+        rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_ratio_compact, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy,
-                           b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count);
+        if (cross)
+            hipLaunchKernelGGL(k_ratio_compact<true>, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio,
+                               a.kp_xy, b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
+                               (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap), b.n_kp);
+        else
+            hipLaunchKernelGGL(k_ratio_compact<false>, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio,
+                               a.kp_xy, b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count, (const uint32_t*)nullptr, 0);
         VO_CHECK_LAUNCH(ctx);
         // 3-D lookups for every query slot position (n_kp upper bound); only the first M are meaningful
         VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -359,6 +372,12 @@ extern "C" int vo_point_clouds(vo_ctx* ctx, int slot_a, int slot_b, double ratio
     if (status_b && !rc) rc = xfer_d2h(ctx, status_b, ctx->mw->st_b, (size_t)m);
     if (rc) return rc;
     return xfer_flush(ctx);
+}
+
+extern "C" int vo_point_clouds(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int32_t* q_idx, int32_t* t_idx,
+                               float* pts_a, float* pts_b, uint8_t* status_a, uint8_t* status_b, int cap, int* m_out)
+{
+    return vo_point_clouds_ex(ctx, slot_a, slot_b, ratio, 0, q_idx, t_idx, pts_a, pts_b, status_a, status_b, cap, m_out);
 }
 
 // ---- Umeyama: two-pass float64 reductions on the device, 3x3 SVD on the host -------------
@@ -1179,13 +1198,15 @@ __device__ void pose_fit_block(float* __restrict__ qa, float* __restrict__ qb, d
 // First half of the fused pose step in ONE block (was five launches): wave 0 runs the ratio test with ordered
 // compaction, then the whole block looks up the matched keypoints' 3-D positions in both frames and clears the
 // consistency counters.  A short chain of launches is what the step costs under load, not its arithmetic.
+// CROSS: a match must also pass the cross-check (colmin: column words of the same kNN launch, nt of them)
+template <bool CROSS>
 __global__ void __launch_bounds__(256) k_pose_prep(const int32_t* __restrict__ idx, const int32_t* __restrict__ dist, int nq, double ratio,
                                                    const float* __restrict__ xy_q, const float* __restrict__ xy_t,
                                                    int32_t* __restrict__ q_out, int32_t* __restrict__ t_out, float* __restrict__ xyq_out,
                                                    float* __restrict__ xyt_out, int32_t* __restrict__ m_out, PoseOut* __restrict__ out,
                                                    int* __restrict__ flags_dev, TapDisp ta, TapDisp tb, int cw, int ch,
                                                    float* __restrict__ pts_a, float* __restrict__ pts_b, uint8_t* __restrict__ st_a,
-                                                   uint8_t* __restrict__ st_b, int* __restrict__ ncons)
+                                                   uint8_t* __restrict__ st_b, int* __restrict__ ncons, const uint32_t* __restrict__ colmin, int nt_c)
 {
     __shared__ int s_m;
     if (threadIdx.x < 64) {
@@ -1199,6 +1220,7 @@ __global__ void __launch_bounds__(256) k_pose_prep(const int32_t* __restrict__ i
                 t = idx[2 * i];
                 double a = (double)(float)dist[2 * i], b = (double)(float)dist[2 * i + 1];
                 keep = idx[2 * i + 1] >= 0 && a < ratio * b;
+                if constexpr (CROSS) keep = keep && knn_mutual(t, i, colmin, nt_c);
             }
             unsigned long long bal = __ballot(keep);
             if (keep) {
@@ -1312,7 +1334,7 @@ size_t pose_ws_bytes(int nq)
 
 // k_pose_solve writes the finished PoseOut record into host_out (pinned host memory the device can address) itself.  No host
 // synchronisation, no copy command.
-static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int min_matches, double rigidity_thr,
+static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, int min_matches, double rigidity_thr,
                         double outlier_thr, void* host_out)
 {
     const int nq = a.n_kp;
@@ -1342,7 +1364,7 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist);
+        rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
         if (rc) return rc;
     }
     {
@@ -1351,9 +1373,14 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
         if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < a.w ? ctx->roi[2] : a.w; y1 = ctx->roi[3] < a.h ? ctx->roi[3] : a.h; }
         TapDisp ta{ a.disp16, a.w, x0, y0, make_q(ctx->Q) };
         TapDisp tb{ b.disp16, b.w, x0, y0, make_q(ctx->Q) };
-        hipLaunchKernelGGL(k_pose_prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
-                           ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a,
-                           ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b, d_ncons);
+        if (cross)
+            hipLaunchKernelGGL(k_pose_prep<true>, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
+                               ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a,
+                               ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b, d_ncons, (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap), b.n_kp);
+        else
+            hipLaunchKernelGGL(k_pose_prep<false>, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
+                               ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a,
+                               ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b, d_ncons, (const uint32_t*)nullptr, 0);
         const int use_filter = rigidity_thr > 0;
         // LDS: 4 int arrays of nq (rounded to even so the bit matrix stays 8-byte aligned) + bit matrix if <= 48 KB
         const int m_cap = (nq + 1) & ~1;
@@ -1397,11 +1424,11 @@ static void pose_unpack(const void* rec, int32_t* counts4, int32_t* rc2, double*
     memcpy(T2_12, o->T2, sizeof(o->T2));
 }
 
-extern "C" int vo_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matches, double rigidity_thr,
-                            double outlier_thr, int32_t* counts4 /*M,n1,n2,flags*/, int32_t* rc2 /*first,final*/,
-                            double* T1_12, double* T2_12)
+extern "C" int vo_pose_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int min_matches, double rigidity_thr,
+                               double outlier_thr, int32_t* counts4 /*M,n1,n2,flags*/, int32_t* rc2 /*first,final*/,
+                               double* T1_12, double* T2_12)
 {
-    if (!counts4 || !rc2 || !T2_12) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair: bad argument");
+    if (!counts4 || !rc2 || !T2_12 || (match_flags & ~VO_MATCH_CROSSCHECK)) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair: bad argument");
     int rc = pose_check(ctx, slot_a, slot_b);
     if (rc) return rc;
     FrameSlot& a = ctx->slots[slot_a];
@@ -1411,11 +1438,17 @@ extern "C" int vo_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, i
     counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
     rc2[0] = rc2[1] = 1;
     if (a.n_kp == 0) return VO_OK;
-    if ((rc = pose_enqueue(ctx, a, b, ratio, min_matches, rigidity_thr, outlier_thr, ctx->pinned))) return rc;
+    if ((rc = pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, min_matches, rigidity_thr, outlier_thr, ctx->pinned))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;
     if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // never a pose from an undefined disparity
     pose_unpack(ctx->pinned, counts4, rc2, T1_12, T2_12);
     return VO_OK;
+}
+
+extern "C" int vo_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matches, double rigidity_thr,
+                            double outlier_thr, int32_t* counts4, int32_t* rc2, double* T1_12, double* T2_12)
+{
+    return vo_pose_pair_ex(ctx, slot_a, slot_b, ratio, 0, min_matches, rigidity_thr, outlier_thr, counts4, rc2, T1_12, T2_12);
 }
 
 // The context works on alternate k's stream and in its match scratch for the lifetime of the object, whatever leaves the scope
@@ -1477,10 +1510,10 @@ void pose_alt_free(vo_ctx* ctx)
     }
 }
 
-extern "C" int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matches, double rigidity_thr,
-                                  double outlier_thr, int* ticket_out)
+extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int min_matches, double rigidity_thr,
+                                     double outlier_thr, int* ticket_out)
 {
-    if (!ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair_begin: bad argument");
+    if (!ticket_out || (match_flags & ~VO_MATCH_CROSSCHECK)) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair_begin: bad argument");
     int rc = pose_check(ctx, slot_a, slot_b);
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
@@ -1508,7 +1541,7 @@ extern "C" int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ra
         if (e == hipSuccess && a.pending) e = hipStreamWaitEvent(ctx->stream, a.ready, 0);
         if (e == hipSuccess && b.pending) e = hipStreamWaitEvent(ctx->stream, b.ready, 0);
         rc = e == hipSuccess ? VO_OK : vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-        if (!rc && a.n_kp > 0) rc = pose_enqueue(ctx, a, b, ratio, min_matches, rigidity_thr, outlier_thr, rec);
+        if (!rc && a.n_kp > 0) rc = pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, min_matches, rigidity_thr, outlier_thr, rec);
         if (!rc && hipEventRecord(p.done, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
     }
     if (rc) return rc;
@@ -1519,9 +1552,16 @@ extern "C" int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ra
     p.busy = true; p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
     p.params[0] = ratio; p.params[1] = min_matches; p.params[2] = rigidity_thr; p.params[3] = outlier_thr;
+    p.match_flags = match_flags;
     ctx->pose_next = (k + 1) % vo_ctx::N_POSE_ALT;
     *ticket_out = k;
     return VO_OK;
+}
+
+extern "C" int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matches, double rigidity_thr,
+                                  double outlier_thr, int* ticket_out)
+{
+    return vo_pose_pair_begin_ex(ctx, slot_a, slot_b, ratio, 0, min_matches, rigidity_thr, outlier_thr, ticket_out);
 }
 
 extern "C" int vo_pose_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* rc2, double* T1_12, double* T2_12)

@@ -21,6 +21,9 @@
 //   * the train set is cut into up to 16 slices (about 2000 waves at 8000 x 8000: two per SIMD); a slice's pairs go to scratch
 //     behind the distances, the wave that draws a group's last ticket merges them (agent-scope release / acquire around the
 //     ticket) and writes idx / dist.  One launch; 4 MB of L2 traffic at config 5 (every workgroup reads its slice once).
+//   * k_bf_knn2<true> (cross-check, DESIGN 4d'): the same tiles also give every train descriptor its nearest query (column minima:
+//     16 keys per lane -> permlane swaps across the four lane groups -> ds_min across the waves -> one global atomicMin per train
+//     descriptor and LDS chunk).  k_bf_knn2<false> is the kernel above, instruction for instruction.
 #include "vo_internal.h"
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -55,9 +58,10 @@ __device__ __forceinline__ void merge2(uint32_t& a0, uint32_t& a1, uint32_t b0, 
 
 #define KNN_WAVES 8              // waves (= groups of 64 queries) per workgroup: they share one slice of the train set in LDS
 #define KNN_CHUNK 32            // tiles of 16 train descriptors expanded into LDS at a time: 32 x 4 KB + their bit counts = 130 KB
+template <bool CROSS>
 __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __restrict__ q, int nq, const uint8_t* __restrict__ t, int nt, int splits,
                                                int tiles_per_split, int ngroups, unsigned long long* __restrict__ part, int* __restrict__ tickets,
-                                               int32_t* __restrict__ idx, int32_t* __restrict__ dist)
+                                               int32_t* __restrict__ idx, int32_t* __restrict__ dist, uint32_t* __restrict__ colmin)
 {
     const int lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
     const int gblock = blockIdx.x / splits, split = blockIdx.x - gblock * splits;
@@ -76,6 +80,7 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
     const int chunk_tiles = min(KNN_CHUNK, max(1, tiles_per_split));
     uint4* const s_B = s_lds4;                                           // [chunk_tiles][4][64]
     int* const s_tn = (int*)(s_lds4 + (size_t)chunk_tiles * 256);        // [chunk_tiles * 16]: |t| + 256, or 0x7FFF past the end
+    uint32_t* const s_col = (uint32_t*)(s_tn + chunk_tiles * 16);         // CROSS: [chunk_tiles * 16] column minima of the chunk
 
     v4i A[4][4];
 #pragma unroll
@@ -86,6 +91,22 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
 #pragma unroll
         for (int m = 0; m < 4; m++) A[s][m] *= 0xFF;      // bytes of {0, -1}: the accumulators hold -(q.t), and the key below is ONE v_lshl_add_u32
     }
+    // CROSS: the column key of accumulator register r of sub-tile s is cb[s][r] + (-(q.t) << 17) = ((|q| - 2 q.t + 256) << 16) | query
+    // for query 16 s + 4 g + r of the wave (|t| is the same for every candidate of a train column and is added at the decode).
+    // Rows past nq repeat query nq - 1 (as the A operands do) under ITS index: an exact copy of a key that is present anyway.
+    uint32_t cb[4][4];
+    if constexpr (CROSS) {
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int qi = max(0, min(q0 + 16 * s + 4 * g + r, nq - 1));
+                const uint4* qp = (const uint4*)(q + (size_t)qi * 32);
+                const uint4 a = qp[0], b = qp[1];
+                const int qn = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
+                cb[s][r] = ((uint32_t)(qn + 256) << 16) | (uint32_t)qi;
+            }
+    }
     uint32_t k0[4][4], k1[4][4];
 #pragma unroll
     for (int s = 0; s < 4; s++)
@@ -95,6 +116,16 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
     for (int c0 = t0; c0 < t1; c0 += KNN_CHUNK) {
         const int c1 = min(t1, c0 + KNN_CHUNK);
         if (c0 != t0) __syncthreads();                    // (every wave is done with the previous chunk)
+        if constexpr (CROSS) {
+            // the previous chunk's column minima go out (one global atomic per train descriptor), the words start over
+            if (threadIdx.x < chunk_tiles * 16) {
+                if (c0 != t0) {
+                    const int j = (c0 - KNN_CHUNK) * 16 + threadIdx.x;
+                    if (j < nt) __hip_atomic_fetch_min(colmin + j, s_col[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                s_col[threadIdx.x] = 0xFFFFFFFFu;
+            }
+        }
         for (int i = threadIdx.x; i < (c1 - c0) * 16; i += KNN_WAVES * 64) {     // one train descriptor per thread
             const int j = c0 * 16 + i;
             uint4 a = make_uint4(0, 0, 0, 0), b = a;
@@ -132,6 +163,7 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
                 tn_nxt = s_n[(tile + 1 - c0) * 16];
             }
             const uint32_t base = ((uint32_t)tn << 16) | (uint32_t)((tile * 16 + col) & 0xFFFF);
+            uint32_t cm = 0xFFFFFFFFu;
 #pragma unroll
             for (int s = 0; s < 4; s++) {
                 v4i acc = { 0, 0, 0, 0 };
@@ -145,8 +177,24 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
                     const uint32_t key = base + ((uint32_t)acc[r] << 17);
                     k1[s][r] = med3_u32(k0[s][r], k1[s][r], key);
                     k0[s][r] = min(k0[s][r], key);
+                    if constexpr (CROSS) cm = min(cm, cb[s][r] + ((uint32_t)acc[r] << 17));
                 }
             }
+            if constexpr (CROSS) {
+                // the 16 keys of train 16 tile + col this lane holds -> the four lane groups (rows of 16 lanes) -> every wave
+                const auto x = __builtin_amdgcn_permlane32_swap(cm, cm, false, false);     // rows 0 1 | 2 3
+                cm = min(x[0], x[1]);
+                const auto y = __builtin_amdgcn_permlane16_swap(cm, cm, false, false);     // rows 0 | 1
+                cm = min(y[0], y[1]);
+                if (lane < 16) atomicMin(s_col + (tile - c0) * 16 + col, cm);
+            }
+        }
+    }
+    if constexpr (CROSS) {
+        __syncthreads();                                  // (every wave is done with the last chunk)
+        if (t1 > t0 && threadIdx.x < chunk_tiles * 16) {
+            const int j = (t0 + (t1 - t0 - 1) / KNN_CHUNK * KNN_CHUNK) * 16 + threadIdx.x;
+            if (j < nt && j < t1 * 16) __hip_atomic_fetch_min(colmin + j, s_col[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (!active) return;
@@ -212,10 +260,14 @@ int match_dist_alloc(vo_ctx* ctx, int32_t** p)
 }
 
 // d_dist must be an allocation of match_dist_bytes(kp_cap): the distances, then the slices' partial pairs, then the tickets
-// (zeroed once at allocation; every launch leaves them zero)
-int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx, int32_t* d_dist)
+// (zeroed once at allocation; every launch leaves them zero), then the per-train column words of the cross-check.
+// cross != 0: the same launch also leaves, for every train descriptor j, the key of its nearest query in match_colmin(d_dist)
+// (reset on the launching stream first; read by the consumers of the next launches, never inside this one)
+int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx, int32_t* d_dist, int cross)
 {
     if (nt > 65535) return vo_fail(ctx, VO_E_CAP, "train set of %d descriptors exceeds 65535", nt);
+    if (cross && nq > 65535) return vo_fail(ctx, VO_E_CAP, "cross-check: query set of %d descriptors exceeds 65535", nq);
+    if (cross && nt > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "cross-check: train set of %d descriptors exceeds capacity %d", nt, ctx->kp_cap);
     if (nq <= 0) return VO_OK;
     if (nq > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "query set of %d descriptors exceeds capacity %d", nq, ctx->kp_cap);
     const int groups = div_up(nq, 64), gblocks = div_up(groups, KNN_WAVES), ntiles = div_up(nt, 16);
@@ -226,25 +278,36 @@ int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt
     const size_t capq = ((size_t)ctx->kp_cap + 63) & ~(size_t)63;
     unsigned long long* part = (unsigned long long*)(d_dist + 2 * capq);
     int* tickets = (int*)(part + (size_t)VO_KNN_SPLITS * capq);
-    const size_t lds = (size_t)std::min(per, KNN_CHUNK) * 16 * (256 + 4);
+    uint32_t* colmin = cross ? match_colmin(d_dist, ctx->kp_cap) : nullptr;
+    const size_t lds = (size_t)std::min(per, KNN_CHUNK) * 16 * (256 + 4 + (cross ? 4 : 0));
+    const void* fn = cross ? (const void*)k_bf_knn2<true> : (const void*)k_bf_knn2<false>;
     if (lds > 64 * 1024) {                                 // (allow more than 64 KB of dynamic LDS)
-        static unsigned long long attr_set = 0;
-        if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-            VO_HIP(ctx, hipFuncSetAttribute((const void*)k_bf_knn2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set |= 1ull << (ctx->device & 63);
+        static unsigned long long attr_set[2] = {0, 0};
+        if (!((attr_set[cross ? 1 : 0] >> (ctx->device & 63)) & 1ull)) {
+            VO_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_set[cross ? 1 : 0] |= 1ull << (ctx->device & 63);
         }
     }
+    // (the column words are reset on the stream that launches: a null-stream memset does not order itself against the
+    // alternates' streams)
+    if (cross && nt > 0) VO_HIP(ctx, hipMemsetAsync(colmin, 0xFF, (size_t)nt * 4, ctx->stream));
     StageTimer tk(ctx, VO_T_KNN);
-    hipLaunchKernelGGL(k_bf_knn2, dim3(gblocks * splits), dim3(KNN_WAVES * 64), lds, ctx->stream, dq, nq, dt, nt, splits, per, groups, part,
-                       tickets, d_idx, d_dist);
+    if (cross)
+        hipLaunchKernelGGL(k_bf_knn2<true>, dim3(gblocks * splits), dim3(KNN_WAVES * 64), lds, ctx->stream, dq, nq, dt, nt, splits, per, groups, part,
+                           tickets, d_idx, d_dist, colmin);
+    else
+        hipLaunchKernelGGL(k_bf_knn2<false>, dim3(gblocks * splits), dim3(KNN_WAVES * 64), lds, ctx->stream, dq, nq, dt, nt, splits, per, groups, part,
+                           tickets, d_idx, d_dist, (uint32_t*)nullptr);
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }
 
-extern "C" int vo_measure_knn(vo_ctx* ctx, int slot_a, int slot_b, int reps, double* us_per_launch)
+extern "C" int vo_measure_knn_ex(vo_ctx* ctx, int slot_a, int slot_b, int reps, int match_flags, double* us_per_launch)
 {
-    if (!ctx || !us_per_launch || reps <= 0 || reps > 10000 || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS)
+    if (!ctx || !us_per_launch || reps <= 0 || reps > 10000 || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS ||
+        (match_flags & ~VO_MATCH_CROSSCHECK))
         return vo_fail(ctx, VO_E_ARG, "vo_measure_knn: bad argument");
+    const int cross = match_flags & VO_MATCH_CROSSCHECK;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
     if (!a.has_kp || !b.has_kp || a.n_kp <= 0) return vo_fail(ctx, VO_E_STATE, "vo_measure_knn: both slots need keypoints");
@@ -253,9 +316,9 @@ extern "C" int vo_measure_knn(vo_ctx* ctx, int slot_a, int slot_b, int reps, dou
     hipEvent_t e0, e1;
     VO_HIP(ctx, hipEventCreate(&e0));
     VO_HIP(ctx, hipEventCreate(&e1));
-    int rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist);      // warm-up (LDS attribute, caches)
+    int rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);      // warm-up (LDS attribute, caches)
     if (!rc && hipEventRecord(e0, ctx->stream) != hipSuccess) rc = VO_E_HIP;
-    for (int r = 0; r < reps && !rc; r++) rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist);
+    for (int r = 0; r < reps && !rc; r++) rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
     if (!rc && hipEventRecord(e1, ctx->stream) != hipSuccess) rc = VO_E_HIP;
     float ms = 0.f;
     if (!rc && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) rc = VO_E_HIP;
@@ -264,6 +327,11 @@ extern "C" int vo_measure_knn(vo_ctx* ctx, int slot_a, int slot_b, int reps, dou
     if (rc) return rc == VO_E_HIP ? vo_fail(ctx, VO_E_HIP, "vo_measure_knn: HIP error") : rc;
     *us_per_launch = 1e3 * (double)ms / reps;
     return VO_OK;
+}
+
+extern "C" int vo_measure_knn(vo_ctx* ctx, int slot_a, int slot_b, int reps, double* us_per_launch)
+{
+    return vo_measure_knn_ex(ctx, slot_a, slot_b, reps, 0, us_per_launch);
 }
 
 extern "C" int vo_bf_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx,
@@ -281,6 +349,52 @@ extern "C" int vo_bf_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const u
     if (rc) return rc;
     rc = xfer_d2h(ctx, idx, ctx->mw->m_idx, (size_t)nq * 8);
     if (!rc) rc = xfer_d2h(ctx, dist, ctx->mw->m_dist, (size_t)nq * 8);
+    if (rc) return rc;
+    return xfer_flush(ctx);
+}
+
+// column words -> the mutual flag of every query and (a(j), its distance) of every train descriptor
+__global__ void k_mutual_decode(const int32_t* __restrict__ idx, int nq, const uint32_t* __restrict__ colmin, const uint8_t* __restrict__ t, int nt,
+                                uint8_t* __restrict__ mutual, int32_t* __restrict__ t_best)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nq) mutual[i] = knn_mutual(idx[2 * i], i, colmin, nt) ? 1 : 0;
+    if (i < nt) {
+        const uint32_t key = colmin[i];
+        const uint4* tp = (const uint4*)(t + (size_t)i * 32);
+        const uint4 a = tp[0], b = tp[1];
+        const int tn = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
+        const bool h = key != 0xFFFFFFFFu;
+        t_best[2 * i] = h ? (int32_t)(key & 0xFFFFu) : -1;
+        t_best[2 * i + 1] = h ? (int32_t)(key >> 16) - 256 + tn : 0x7FFFFFFF;
+    }
+}
+
+extern "C" int vo_bf_knn2_hamming_mutual(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx, int32_t* dist,
+                                         uint8_t* mutual, int32_t* t_best)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq && (!q || !idx || !dist || !mutual)) || (nt && !t))
+        return vo_fail(ctx, VO_E_ARG, "vo_bf_knn2_hamming_mutual: bad argument");
+    if (nq > ctx->kp_cap || nt > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "descriptor count exceeds capacity %d", ctx->kp_cap);
+    if (nq > 65535) return vo_fail(ctx, VO_E_CAP, "cross-check: query set of %d descriptors exceeds 65535", nq);
+    if (t_best)
+        for (int j = 0; j < nt; j++) { t_best[2 * j] = -1; t_best[2 * j + 1] = 0x7FFFFFFF; }
+    if (nq == 0) return VO_OK;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    StageTimer tm(ctx, VO_T_MATCH);
+    int rc = xfer_h2d(ctx, ctx->mq, q, (size_t)nq * 32);
+    if (!rc && nt) rc = xfer_h2d(ctx, ctx->mt, t, (size_t)nt * 32);
+    if (rc) return rc;
+    if ((rc = match_knn2(ctx, ctx->mq, nq, ctx->mt, nt, ctx->mw->m_idx, ctx->mw->m_dist, 1))) return rc;
+    // (the decoded words land in match scratch that nothing else of this call uses: st_a holds kp_cap bytes, xy_a kp_cap pairs)
+    int32_t* d_tbest = (int32_t*)ctx->mw->xy_a;
+    hipLaunchKernelGGL(k_mutual_decode, dim3(div_up(std::max(nq, std::max(nt, 1)), 256)), dim3(256), 0, ctx->stream, ctx->mw->m_idx, nq,
+                       match_colmin(ctx->mw->m_dist, ctx->kp_cap), ctx->mt, nt, ctx->mw->st_a, d_tbest);
+    VO_CHECK_LAUNCH(ctx);
+    rc = xfer_d2h(ctx, idx, ctx->mw->m_idx, (size_t)nq * 8);
+    if (!rc) rc = xfer_d2h(ctx, dist, ctx->mw->m_dist, (size_t)nq * 8);
+    if (!rc) rc = xfer_d2h(ctx, mutual, ctx->mw->st_a, (size_t)nq);
+    if (!rc && t_best && nt) rc = xfer_d2h(ctx, t_best, d_tbest, (size_t)nt * 8);
     if (rc) return rc;
     return xfer_flush(ctx);
 }

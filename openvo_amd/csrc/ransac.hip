@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(1024) k_mono_finish(const int32_t* __restrict_
 }
 
 struct MonoTail { const int32_t* counts; const double* E; const float* F; float thr2; int min_n; };
-static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, const double* K4v, int iters, float thr, uint32_t seed,
+static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
                         int solver, MonoDev& o, MonoTail* tail = nullptr)
 {
     const int min_n = solver == 5 ? 6 : 8;
@@ -401,9 +401,14 @@ static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, c
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        if ((rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist))) return rc;
-        hipLaunchKernelGGL(k_ratio_compact, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy, b.kp_xy,
-                           ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count);
+        if ((rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross))) return rc;
+        if (cross)
+            hipLaunchKernelGGL(k_ratio_compact<true>, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy,
+                               b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
+                               (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap), b.n_kp);
+        else
+            hipLaunchKernelGGL(k_ratio_compact<false>, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy,
+                               b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count, (const uint32_t*)nullptr, 0);
     }
     {
         StageTimer t(ctx, VO_T_POSE);
@@ -442,10 +447,10 @@ static int mono_check(vo_ctx* ctx, int slot_a, int slot_b, const double* K4v, in
     return VO_OK;
 }
 
-extern "C" int vo_mono_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, const double* K4v, int iters, float thr, uint32_t seed,
-                            int solver, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+extern "C" int vo_mono_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                               uint32_t seed, int solver, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
 {
-    if (ctx && (!E9_out || !counts3)) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair: bad argument");
+    if (ctx && (!E9_out || !counts3 || (match_flags & ~VO_MATCH_CROSSCHECK))) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair: bad argument");
     int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, "vo_mono_pair");
     if (rc) return rc;
     const int min_n = solver == 5 ? 6 : 8;
@@ -459,7 +464,7 @@ extern "C" int vo_mono_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, c
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     const int nq = a.n_kp;
     MonoDev o;
-    if ((rc = mono_enqueue(ctx, a, b, ratio, K4v, iters, thr, seed, solver, o))) return rc;
+    if ((rc = mono_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, o))) return rc;
     int32_t* h = (int32_t*)ctx->pinned;         // [0] M, [1..2] best, then E9 at byte 64
     VO_HIP(ctx, hipMemcpyAsync(h, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     VO_HIP(ctx, hipMemcpyAsync(h + 1, o.d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -471,6 +476,12 @@ extern "C" int vo_mono_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, c
     counts3[0] = h[0]; counts3[1] = h[1]; counts3[2] = h[0] >= min_n ? h[2] : 0;
     memcpy(E9_out, (uint8_t*)ctx->pinned + 64, 72);
     return VO_OK;
+}
+
+extern "C" int vo_mono_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, const double* K4v, int iters, float thr, uint32_t seed,
+                            int solver, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+{
+    return vo_mono_pair_ex(ctx, slot_a, slot_b, ratio, 0, K4v, iters, thr, seed, solver, E9_out, counts3, mask_out, q_idx, t_idx, cap);
 }
 
 // ---- the same step, asynchronous: several pairs' chains in flight (each on an alternate's own stream and scratch) ----------
@@ -535,10 +546,10 @@ void mono_alt_free(vo_ctx* ctx)
     for (int k = 0; k < vo_ctx::N_MONO_ALT; k++) mono_alt_release(ctx->mono_alt[k]);
 }
 
-extern "C" int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, const double* K4v, int iters, float thr, uint32_t seed,
-                                  int solver, int want_matches, int* ticket_out)
+extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                                     uint32_t seed, int solver, int want_matches, int* ticket_out)
 {
-    if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair_begin: bad argument");
+    if (ctx && (!ticket_out || (match_flags & ~VO_MATCH_CROSSCHECK))) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair_begin: bad argument");
     int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, "vo_mono_pair_begin");
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
@@ -565,7 +576,7 @@ extern "C" int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ra
         if (!rc && a.n_kp > 0) {
             MonoDev o;
             MonoTail tl;
-            rc = mono_enqueue(ctx, a, b, ratio, K4v, iters, thr, seed, solver, o, &tl);
+            rc = mono_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, o, &tl);
             if (!rc) {
                 // (p.result is pinned host memory: the kernel writes the record across the link itself -- no copy command)
                 hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(1024), 0, ctx->stream, tl.counts, iters, tl.E, tl.F, ctx->mw->xy_a, ctx->mw->xy_b, a.n_kp,
@@ -585,6 +596,12 @@ extern "C" int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ra
     ctx->mono_next = (k + 1) % vo_ctx::N_MONO_ALT;
     *ticket_out = k;
     return VO_OK;
+}
+
+extern "C" int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, const double* K4v, int iters, float thr, uint32_t seed,
+                                  int solver, int want_matches, int* ticket_out)
+{
+    return vo_mono_pair_begin_ex(ctx, slot_a, slot_b, ratio, 0, K4v, iters, thr, seed, solver, want_matches, ticket_out);
 }
 
 extern "C" int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx,

@@ -212,6 +212,7 @@ struct vo_ctx {
         int slot_a = -1, slot_b = -1;
         int32_t gen_a = 0, gen_b = 0;      // disparity generations of the two slots when the step was begun (slot health at _end)
         double params[4] = {0, 0, 0, 0};   // ratio, min_matches, rigidity_thr, outlier_thr
+        int match_flags = 0;               // VO_MATCH_* the step was begun with
         MatchWs mw;
     } pose_alt[N_POSE_ALT];
     int pose_next = 0;
@@ -313,8 +314,11 @@ int orb_slot_enqueue(vo_ctx* ctx, FrameSlot& f, int nfeatures, int mask_mode, in
 void pose_alt_free(vo_ctx* ctx);
 void mono_alt_free(vo_ctx* ctx);
 size_t pose_ws_bytes(int nq);
+// CROSS: a match must also pass the cross-check (knn_mutual on the column words of the same kNN launch)
+template <bool CROSS>
 __global__ void k_ratio_compact(const int32_t* idx, const int32_t* dist, int nq, double ratio, const float* xy_q, const float* xy_t,
-                                int32_t* q_out, int32_t* t_out, float* xyq_out, float* xyt_out, int32_t* m_out);   // pose / clique scratch for nq query keypoints
+                                int32_t* q_out, int32_t* t_out, float* xyq_out, float* xyt_out, int32_t* m_out,
+                                const uint32_t* colmin, int nt);   // pose / clique scratch for nq query keypoints
 
 // implemented in the per-stage files
 // f.left, f.right (w x h) -> f.disp16; gives the run its generation.  srcL / srcR (both or neither): the rectified gray pair lies
@@ -328,16 +332,31 @@ int orb_run(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, in
             int nfeatures, int mask_mode, const int16_t* d_disp16, int disp_stride, int min_d16,
             int max_d16, const uint8_t* d_mask, int mask_stride);
 // the kNN kernel's scratch lives behind the distances in ONE allocation (MatchWs::m_dist): 2 distances per query, then up to
-// VO_KNN_SPLITS partial (best, second) pairs per query, then one ticket word per 64 queries (zero between launches)
+// VO_KNN_SPLITS partial (best, second) pairs per query, then one ticket word per 64 queries (zero between launches), then one
+// column word per train descriptor (cross-check launches only: reset to 0xFFFFFFFF on the launching stream before each of them)
 #define VO_KNN_SPLITS 16
 static inline size_t match_dist_bytes(int kp_cap)
 {
     const size_t capq = ((size_t)kp_cap + 63) & ~(size_t)63;
-    return capq * 8 + (size_t)VO_KNN_SPLITS * capq * 8 + (capq / 64 + 1) * 4 + 256;
+    return capq * 8 + (size_t)VO_KNN_SPLITS * capq * 8 + (capq / 64 + 1) * 4 + capq * 4 + 256;
+}
+// the column words: ((|q| - 2 q.t + 256) << 16) | query of the nearest query of each train descriptor, ties to the lower query
+static inline uint32_t* match_colmin(int32_t* d_dist, int kp_cap)
+{
+    const size_t capq = ((size_t)kp_cap + 63) & ~(size_t)63;
+    return (uint32_t*)((uint8_t*)d_dist + capq * 8 + (size_t)VO_KNN_SPLITS * capq * 8 + (capq / 64 + 1) * 4);
+}
+// query i with nearest train t passes the cross-check iff t is a train index (checked BEFORE the column word is read) and i is
+// the nearest query of t
+__device__ __forceinline__ bool knn_mutual(int t, int i, const uint32_t* __restrict__ colmin, int nt)
+{
+    if (t < 0 || t >= nt) return false;
+    const uint32_t key = colmin[t];
+    return key != 0xFFFFFFFFu && (key & 0xFFFFu) == (uint32_t)i;
 }
 int match_dist_alloc(vo_ctx* ctx, int32_t** p);      // hipMalloc + the tickets cleared
 int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx,
-               int32_t* d_dist);
+               int32_t* d_dist, int cross = 0);
 int points3d_launch(vo_ctx* ctx, const int16_t* d_disp16, int w, int h, const float* d_xy, int n,
                     float* d_xyz, uint8_t* d_status);
 void host_svd3(const double* A, double* U, double* w, double* Vt);

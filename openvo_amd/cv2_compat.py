@@ -16,6 +16,8 @@ Every name below is one call site of the reference (paths relative to /root/refe
   stereo_odometer.py:22    ORB_create, BFMatcher.create(NORM_HAMMING)
   stereo_odometer.py:117   orb.detectAndCompute     -> vo_orb_detect_and_compute_host
   stereo_odometer.py:163   matcher.knnMatch(k=2)    -> vo_bf_knn2_hamming
+  stereo_odometer.py:21    BFMatcher(NORM_HAMMING, crossCheck=True): match / knnMatch(k=1) -> vo_bf_knn2_hamming_mutual
+                           (the reference's "# TODO crosscheck"; an extension, parity with OpenCV unpinned without a cv2)
   stereo_odometer.py:190,204  estimateAffine3D(force_rotation=True) -> vo_umeyama
   stereo_odometer.py:212   Rodrigues                -> vo_rodrigues
   utils/drawPoseOnImage.py:29-36  putText           -> no-op (no font rasteriser; the overlay is out of scope)
@@ -130,19 +132,30 @@ def ORB_create(nfeatures=500, *args, **kw):
 
 
 class BFMatcher:
+    """BFMatcher(NORM_HAMMING, crossCheck): knnMatch(k=2) is the reference's call; match() and knnMatch(k=1) serve crossCheck=True
+    (mutual nearest neighbours, one kernel launch for both directions; OpenCV refuses k = 2 on such a matcher, and so does this)."""
+
     def __init__(self, normType=NORM_HAMMING, crossCheck=False):
-        if normType != NORM_HAMMING or crossCheck:
-            raise error("only NORM_HAMMING without cross-check is implemented (what the reference asks for)")
+        if normType != NORM_HAMMING:
+            raise error("only NORM_HAMMING is implemented (what the reference asks for)")
+        self.crossCheck = bool(crossCheck)
 
     @classmethod
     def create(cls, normType=NORM_HAMMING, crossCheck=False):
         return cls(normType, crossCheck)
 
-    def knnMatch(self, queryDescriptors, trainDescriptors, k=2):
-        q = np.asarray(queryDescriptors)
-        n = max(len(q), 0 if trainDescriptors is None else len(trainDescriptors))
+    def _matcher(self, queryDescriptors, trainDescriptors):
+        n = max(0 if queryDescriptors is None else len(queryDescriptors), 0 if trainDescriptors is None else len(trainDescriptors))
         ctx = _context(*_state["geom"][:3], max_kp=max(n, 16))
-        return _BFMatcher(ctx).knnMatch(queryDescriptors, trainDescriptors, k)
+        return _BFMatcher(ctx, self.crossCheck)
+
+    def match(self, queryDescriptors, trainDescriptors):
+        return self._matcher(queryDescriptors, trainDescriptors).match(queryDescriptors, trainDescriptors)
+
+    def knnMatch(self, queryDescriptors, trainDescriptors, k=2):
+        if self.crossCheck and k != 1:
+            raise error("knnMatch with crossCheck=True needs k=1 (as in OpenCV)")
+        return self._matcher(queryDescriptors, trainDescriptors).knnMatch(queryDescriptors, trainDescriptors, k)
 
 
 def estimateAffine3D(src, dst, force_rotation=True):

@@ -342,19 +342,47 @@ class ORB:
 
 
 class BFMatcher:
-    """cv2.BFMatcher.create(cv2.NORM_HAMMING) stand-in: knnMatch(query, train, k=2)."""
+    """cv2.BFMatcher.create(cv2.NORM_HAMMING, crossCheck) stand-in: knnMatch(query, train, k=2) (what the reference calls,
+    stereo_odometer.py:163), plus match(query, train) and knnMatch(..., k=1).
 
-    def __init__(self, ctx):
-        self._ctx = ctx
+    crossCheck=True keeps a match only when query and train are each other's nearest neighbour (ties -> lower index both ways,
+    include/vo355.h): queries that fail get no DMatch from match() and an empty tuple from knnMatch(k=1).  Like OpenCV, such a
+    matcher refuses knnMatch with k = 2.  Both directions come out of ONE launch of the kNN kernel."""
+
+    def __init__(self, ctx, crossCheck=False):
+        self._ctx, self.crossCheck = ctx, bool(crossCheck)
 
     def knn2_arrays(self, q, t):
         return self._ctx.bf_knn2(q, t)
 
-    def knnMatch(self, queryDescriptors, trainDescriptors, k=2):
-        if k != 2:
-            raise NotImplementedError("only k=2 is implemented (what the reference uses)")
-        q = np.asarray(queryDescriptors, np.uint8)
+    @staticmethod
+    def _arrays(queryDescriptors, trainDescriptors):
+        q = np.asarray(queryDescriptors, np.uint8) if queryDescriptors is not None else np.empty((0, 32), np.uint8)
         t = np.asarray(trainDescriptors, np.uint8) if trainDescriptors is not None else np.empty((0, 32), np.uint8)
+        return q, t
+
+    def _best(self, queryDescriptors, trainDescriptors):
+        """-> per query (train index, distance) of its nearest train, or None (no train row / failed cross-check)"""
+        q, t = self._arrays(queryDescriptors, trainDescriptors)
+        if self.crossCheck:
+            idx, dist, mutual, _ = self._ctx.bf_knn2_mutual(q, t)
+        else:
+            idx, dist = self._ctx.bf_knn2(q, t)
+            mutual = idx[:, 0] >= 0
+        return [(idx[i, 0], dist[i, 0]) if mutual[i] and idx[i, 0] >= 0 else None for i in range(len(q))]
+
+    def match(self, queryDescriptors, trainDescriptors):
+        """One DMatch per query (its nearest train), in query order; with crossCheck only the mutual ones."""
+        return tuple(DMatch(i, b[0], b[1]) for i, b in enumerate(self._best(queryDescriptors, trainDescriptors)) if b is not None)
+
+    def knnMatch(self, queryDescriptors, trainDescriptors, k=2):
+        if k == 1:
+            return tuple((DMatch(i, b[0], b[1]),) if b is not None else () for i, b in enumerate(self._best(queryDescriptors, trainDescriptors)))
+        if k != 2:
+            raise NotImplementedError("only k=1 and k=2 are implemented (the reference uses k=2)")
+        if self.crossCheck:
+            raise ValueError("knnMatch with crossCheck=True needs k=1 (as in OpenCV)")
+        q, t = self._arrays(queryDescriptors, trainDescriptors)
         idx, dist = self._ctx.bf_knn2(q, t)
         out = []
         for i in range(len(q)):

@@ -64,11 +64,15 @@ def recover_pose(E, x1, x2):
 
 class MonoOdometer:
     def __init__(self, K, img_size, nfeatures=8000, match_threshold=0.8, ransac_iters=5000, ransac_threshold=1.0,
-                 min_inliers=30, seed=4321, device=0, context=None, solver=5):
+                 min_inliers=30, seed=4321, device=0, context=None, solver=5, cross_check=False):
         """K: 3x3 intrinsics; img_size = (width, height).  ransac_threshold is the Sampson distance in pixels.
-        solver: 5 = five-point minimal solver (what cv2.findEssentialMat runs), 8 = eight-point."""
+        solver: 5 = five-point minimal solver (what cv2.findEssentialMat runs), 8 = eight-point.
+        cross_check: the matches of the ratio test must also be mutual nearest neighbours (include/vo355.h)."""
         if solver not in (5, 8):
             raise ValueError("solver is 5 or 8")
+        if not isinstance(cross_check, (bool, np.bool_)):
+            raise ValueError("cross_check must be True or False")
+        self.cross_check = bool(cross_check)
         self.solver = int(solver)
         K = np.asarray(K, np.float64)
         self.K, self.K4 = K, [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
@@ -133,7 +137,7 @@ class MonoOdometer:
 
     def _begin(self, a, b):
         t = self._ctx.mono_pair_begin(a, b, self.match_threshold, self.K4, self.ransac_iters, self.ransac_threshold, self.seed,
-                                      want_matches=True, solver=self.solver)
+                                      want_matches=True, solver=self.solver, cross_check=self.cross_check)
         self._open[(a, b)] = t
         return t
 

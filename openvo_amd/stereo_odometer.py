@@ -24,13 +24,19 @@ class StereoOdometer:
 
     def __init__(self, stereo_camera, nfeatures=500, match_threshold=0.8, rigidity_threshold=0,
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
-                 pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321):
+                 pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
-        the rigidity / outlier stages are then not used, the motion gates still apply."""
+        the rigidity / outlier stages are then not used, the motion gates still apply.
+        cross_check=True is an extension too (the reference's "# TODO crosscheck", :21; cv2 itself refuses
+        knnMatch(k=2) on a cross-checking matcher): a match must pass the ratio test AND its m[0] must be a mutual
+        nearest neighbour (include/vo355.h); every later decision is the reference's, on the smaller set."""
         if pose_method not in ("umeyama", "pnp"):
             raise ValueError("pose_method must be 'umeyama' or 'pnp'")
+        if not isinstance(cross_check, (bool, np.bool_)):
+            raise ValueError("cross_check must be True or False")
+        self.cross_check = bool(cross_check)
         self.pose_method, self.pnp_iters, self.pnp_threshold, self.pnp_seed = pose_method, pnp_iters, pnp_threshold, pnp_seed
         self.stereo = stereo_camera
         self.current_img = self.current_disparity = self.current_3d = None
@@ -135,7 +141,7 @@ class StereoOdometer:
 
     def _pose_params(self):
         return (float(self.match_threshold), int(self.min_matches), float(max(self.rigidity_threshold, 0)),
-                float(max(self.outlier_threshold, 0)))
+                float(max(self.outlier_threshold, 0)), bool(self.cross_check))
 
     def _fused_ok(self):
         return (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and self.pose_method == "umeyama"
@@ -319,7 +325,7 @@ class StereoOdometer:
         """Extension: pose of the pair by RANSAC solvePnP (3-D of frame a, pixels of frame b)."""
         if not (self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b) and len(kps_b) >= 2):
             raise ValueError("pose_method='pnp' needs the device-resident frames compute_3d returns")
-        q, t, pts_a, _, st_a, _ = self._ctx.point_clouds(kps_a.frame.slot, kps_b.frame.slot, self.match_threshold)
+        q, t, pts_a, _, st_a, _ = self._ctx.point_clouds(kps_a.frame.slot, kps_b.frame.slot, self.match_threshold, self.cross_check)
         if len(q) < self.min_matches:
             self.skip_cause = "matches"
             return None
@@ -375,7 +381,7 @@ class StereoOdometer:
                  and self._on_device(kps2, desc2, im3d2) and len(kps2) >= 2)
         if fused:
             q, t, pts1, pts2, st1, st2 = self._ctx.point_clouds(kps1.frame.slot, kps2.frame.slot,
-                                                                self.match_threshold)
+                                                                self.match_threshold, self.cross_check)
             if len(q) < self.min_matches:
                 return None, None
             if (st1 == 2).any() or (st2 == 2).any():
@@ -384,6 +390,10 @@ class StereoOdometer:
         # generic path: the same steps through the public seams (any matcher / arrays)
         matches = self.matcher.knnMatch(desc1, desc2, k=2)
         matches = [m[0] for m in matches if m[0].distance < self.match_threshold * m[1].distance]
+        if self.cross_check:
+            # a(j), the nearest query of every train descriptor: the matcher with the roles swapped (k = 1, ties -> lower index)
+            back = self.matcher.knnMatch(desc2, desc1, k=1)
+            matches = [m for m in matches if len(back[m.trainIdx]) and back[m.trainIdx][0].trainIdx == m.queryIdx]
         if len(matches) < self.min_matches:
             return None, None
         pts1 = [self.bilinear_interpolate_pixels(im3d1, *kps1[m.queryIdx].pt) for m in matches]
