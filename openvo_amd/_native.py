@@ -56,30 +56,23 @@ class SweepTimeout(VoError):
 VO_E_SWEEP = -6
 
 
-def _image_pair(left, right):
-    """(left, right, channels) as C-contiguous uint8 arrays of one shape: HxW or HxWx3 (HxWx1 is squeezed); anything else
-    -- e.g. HxWx4 -- is refused here, before a pointer reaches native code that would read w*h*channels bytes from it."""
-    left, right = np.asarray(left), np.asarray(right)
-    out = []
-    for a in (left, right):
-        if a.ndim == 3 and a.shape[2] == 1:
-            a = a[:, :, 0]
-        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
-            raise ValueError("an image must be HxW or HxWx3 (got shape %s)" % (a.shape,))
-        out.append(_c(a, np.uint8))
-    if out[0].shape != out[1].shape:
-        raise ValueError("left/right shapes differ")
-    return out[0], out[1], (3 if out[0].ndim == 3 else 1)
-
-
 def _image(img):
-    """(img, channels) for ONE image under the same rule as _image_pair (monocular entry points)."""
+    """(img, channels) as a C-contiguous uint8 array: HxW or HxWx3 (HxWx1 is squeezed); anything else -- e.g. HxWx4 -- is
+    refused here, before a pointer reaches native code that would read w*h*channels bytes from it."""
     a = np.asarray(img)
     if a.ndim == 3 and a.shape[2] == 1:
         a = a[:, :, 0]
     if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
         raise ValueError("an image must be HxW or HxWx3 (got shape %s)" % (a.shape,))
     return _c(a, np.uint8), (3 if a.ndim == 3 else 1)
+
+
+def _image_pair(left, right):
+    """(left, right, channels): two images of one shape, each under the rule of _image."""
+    (left, ch), (right, _) = _image(left), _image(right)
+    if left.shape != right.shape:
+        raise ValueError("left/right shapes differ")
+    return left, right, ch
 
 
 def csrc_digest():
@@ -426,6 +419,11 @@ class Context:
                     octave=np.empty(cap, np.int32), desc=np.empty((cap, 32), np.uint8))
 
     @staticmethod
+    def _kp_args(b):
+        """the six keypoint output pointers, in the order every keypoint-returning entry takes them"""
+        return [_p(b[k]) for k in ("xy", "size", "angle", "response", "octave", "desc")]
+
+    @staticmethod
     def _trim(b, n):
         return {k: v[:n] for k, v in b.items()}
 
@@ -441,9 +439,7 @@ class Context:
         b = self._kp_buffers(cap)
         n = ctypes.c_int(0)
         self._ck(self._lib.vo_orb_detect_and_compute(self._h, slot, int(nfeatures), int(mask_mode), int(min_d16),
-                                                     int(max_d16), _p(b["xy"]), _p(b["size"]), _p(b["angle"]),
-                                                     _p(b["response"]), _p(b["octave"]), _p(b["desc"]), cap,
-                                                     ctypes.byref(n)))
+                                                     int(max_d16), *self._kp_args(b), cap, ctypes.byref(n)))
         return self._trim(b, n.value)
 
     def orb_slot_count(self, slot, nfeatures, mask_mode, min_d16=0, max_d16=0):
@@ -457,8 +453,7 @@ class Context:
         cap = self.kp_cap
         b = self._kp_buffers(cap)
         n = ctypes.c_int(0)
-        self._ck(self._lib.vo_download_keypoints(self._h, slot, _p(b["xy"]), _p(b["size"]), _p(b["angle"]), _p(b["response"]),
-                                                 _p(b["octave"]), _p(b["desc"]), cap, ctypes.byref(n)))
+        self._ck(self._lib.vo_download_keypoints(self._h, slot, *self._kp_args(b), cap, ctypes.byref(n)))
         return self._trim(b, n.value)
 
     def download_keypoints_xy(self, slot):
@@ -488,9 +483,7 @@ class Context:
         b = self._kp_buffers(cap)
         n = ctypes.c_int(0)
         self._ck(self._lib.vo_orb_detect_and_compute_host(self._h, _p(img), w, h, img.strides[0], _p(mask), mstride,
-                                                          int(nfeatures), _p(b["xy"]), _p(b["size"]), _p(b["angle"]),
-                                                          _p(b["response"]), _p(b["octave"]), _p(b["desc"]), cap,
-                                                          ctypes.byref(n)))
+                                                          int(nfeatures), *self._kp_args(b), cap, ctypes.byref(n)))
         return self._trim(b, n.value)
 
     # ---- matching / 3-D / pose
@@ -548,16 +541,18 @@ class Context:
         m = m.value
         return q[:m], t[:m], pa[:m], pb[:m], sa[:m], sb[:m]
 
+    @staticmethod
+    def _pose_out():
+        """(counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4) as the pose entries expect them on entry"""
+        return np.zeros(4, np.int32), np.ones(2, np.int32), np.full((3, 4), np.nan), np.full((3, 4), np.nan)
+
     def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False):
         """Fused match + ratio + 3-D lookup + clique filter + outlier pass + Umeyama for two slots.
         Returns (counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4)."""
-        counts = np.zeros(4, np.int32)
-        rc = np.ones(2, np.int32)
-        T1 = np.full((3, 4), np.nan)
-        T2 = np.full((3, 4), np.nan)
+        out = self._pose_out()
         self._ck(self._lib.vo_pose_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), int(min_matches),
-                                           float(rigidity_thr), float(outlier_thr), _p(counts), _p(rc), _p(T1), _p(T2)))
-        return counts, rc, T1, T2
+                                           float(rigidity_thr), float(outlier_thr), *[_p(a) for a in out]))
+        return out
 
     def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False):
         t = ctypes.c_int(-1)
@@ -566,12 +561,9 @@ class Context:
         return t.value
 
     def pose_pair_end(self, ticket):
-        counts = np.zeros(4, np.int32)
-        rc = np.ones(2, np.int32)
-        T1 = np.full((3, 4), np.nan)
-        T2 = np.full((3, 4), np.nan)
-        self._ck(self._lib.vo_pose_pair_end(self._h, int(ticket), _p(counts), _p(rc), _p(T1), _p(T2)))
-        return counts, rc, T1, T2
+        out = self._pose_out()
+        self._ck(self._lib.vo_pose_pair_end(self._h, int(ticket), *[_p(a) for a in out]))
+        return out
 
     def ransac_essential(self, pts1, pts2, K4, iters=5000, thr=1.0, seed=4321, want_counts=False, solver=8):
         if solver not in (5, 8):
@@ -599,6 +591,13 @@ class Context:
     def prefetch_staged_mono(self, slot, index, nfeatures):
         self._ck(self._lib.vo_prefetch_staged_mono(self._h, int(slot), int(index), int(nfeatures)))
 
+    @staticmethod
+    def _mono_result(E, c3, **arrays):
+        """header of a monocular step (+ its per-match arrays cut to the M matches, xy_b whole) -> the dict mono_pair returns"""
+        out = {"E": E.reshape(3, 3), "matches": int(c3[0]), "best_iter": int(c3[1]), "best_count": int(c3[2])}
+        out.update((k, (v if k == "xy_b" else v[:int(c3[0])]).copy()) for k, v in arrays.items())
+        return out
+
     def mono_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False):
         """kNN-2 + ratio + essential-matrix RANSAC between two slots' keypoints, all on the device, one sync.
         -> dict(E 3x3, matches M, best_iter, best_count[, mask, q, t of length M])."""
@@ -606,17 +605,11 @@ class Context:
         E = np.zeros(9, np.float64)
         c3 = np.zeros(3, np.int32)
         cap = self.kp_cap
-        mask = np.zeros(cap, np.uint8) if want_matches else None
-        q = np.zeros(cap, np.int32) if want_matches else None
-        t = np.zeros(cap, np.int32) if want_matches else None
+        arrays = dict(mask=np.zeros(cap, np.uint8), q=np.zeros(cap, np.int32), t=np.zeros(cap, np.int32)) if want_matches else {}
         self._ck(self._lib.vo_mono_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
-                                           int(seed) & 0xFFFFFFFF, int(solver), _p(E), _p(c3), _p(mask) if want_matches else None, _p(q) if want_matches else None,
-                                        _p(t) if want_matches else None, cap))
-        out = {"E": E.reshape(3, 3), "matches": int(c3[0]), "best_iter": int(c3[1]), "best_count": int(c3[2])}
-        if want_matches:
-            m = int(c3[0])
-            out.update(mask=mask[:m].copy(), q=q[:m].copy(), t=t[:m].copy())
-        return out
+                                           int(seed) & 0xFFFFFFFF, int(solver), _p(E), _p(c3), _p(arrays.get("mask")), _p(arrays.get("q")),
+                                           _p(arrays.get("t")), cap))
+        return self._mono_result(E, c3, **arrays)
 
     def slot_ready(self, slot):
         r = ctypes.c_int(0)
@@ -636,20 +629,16 @@ class Context:
         E = np.zeros(9, np.float64)
         c3 = np.zeros(3, np.int32)
         cap = self.kp_cap
+        arrays = {}
         if want_matches:
-            # one set of output arrays per context, reused call after call (the slices handed out are copies)
-            buf = self.__dict__.get("_mono_out")
-            if buf is None or len(buf[0]) != cap:
-                buf = self._mono_out = (np.empty(cap, np.uint8), np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty((cap, 2), np.float32))
-            mask, q, t, xy = buf
-            self._ck(self._lib.vo_mono_pair_end(self._h, int(ticket), _p(E), _p(c3), _p(mask), _p(q), _p(t), _p(xy), cap))
-        else:
-            self._ck(self._lib.vo_mono_pair_end(self._h, int(ticket), _p(E), _p(c3), None, None, None, None, cap))
-        out = {"E": E.reshape(3, 3), "matches": int(c3[0]), "best_iter": int(c3[1]), "best_count": int(c3[2])}
-        if want_matches:
-            m = int(c3[0])
-            out.update(mask=mask[:m].copy(), q=q[:m].copy(), t=t[:m].copy(), xy_b=xy.copy())
-        return out
+            # one set of output arrays per context, reused call after call (what is handed out are copies)
+            arrays = self.__dict__.get("_mono_out")
+            if arrays is None or len(arrays["mask"]) != cap:
+                arrays = self._mono_out = dict(mask=np.empty(cap, np.uint8), q=np.empty(cap, np.int32), t=np.empty(cap, np.int32),
+                                               xy_b=np.empty((cap, 2), np.float32))
+        self._ck(self._lib.vo_mono_pair_end(self._h, int(ticket), _p(E), _p(c3), _p(arrays.get("mask")), _p(arrays.get("q")), _p(arrays.get("t")),
+                                            _p(arrays.get("xy_b")), cap))
+        return self._mono_result(E, c3, **arrays)
 
     def ransac_pnp(self, pts3d, pts2d, K4, iters=5000, thr=2.0, seed=4321, want_counts=False):
         pts3d, pts2d = _c(pts3d, np.float32).reshape(-1, 3), _c(pts2d, np.float32).reshape(-1, 2)

@@ -338,13 +338,10 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
         StageTimer t(ctx, VO_T_MATCH);
         rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
         if (rc) return rc;
-        if (cross)
-            hipLaunchKernelGGL(k_ratio_compact<true>, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio,
-                               a.kp_xy, b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
-                               (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap), b.n_kp);
-        else
-            hipLaunchKernelGGL(k_ratio_compact<false>, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio,
-                               a.kp_xy, b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count, (const uint32_t*)nullptr, 0);
+        auto kern = cross ? k_ratio_compact<true> : k_ratio_compact<false>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
+                           ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
+                           cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, cross ? b.n_kp : 0);
         VO_CHECK_LAUNCH(ctx);
         // 3-D lookups for every query slot position (n_kp upper bound); only the first M are meaningful
         VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1338,7 +1335,7 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
                         double outlier_thr, void* host_out)
 {
     const int nq = a.n_kp;
-    // workspace: bit matrix + ncons + filtered point sets + residuals + result.  vo_create / pose_alt_prepare size it
+    // workspace: bit matrix + ncons + filtered point sets + residuals + result.  match_ws_alloc sizes it
     // for kp_cap query keypoints, so the branch below (a device-wide synchronisation) is never taken on the hot path
     const int words = (nq + 63) / 64;
     const size_t need = pose_ws_bytes(nq);
@@ -1373,14 +1370,11 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
         if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < a.w ? ctx->roi[2] : a.w; y1 = ctx->roi[3] < a.h ? ctx->roi[3] : a.h; }
         TapDisp ta{ a.disp16, a.w, x0, y0, make_q(ctx->Q) };
         TapDisp tb{ b.disp16, b.w, x0, y0, make_q(ctx->Q) };
-        if (cross)
-            hipLaunchKernelGGL(k_pose_prep<true>, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
-                               ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a,
-                               ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b, d_ncons, (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap), b.n_kp);
-        else
-            hipLaunchKernelGGL(k_pose_prep<false>, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
-                               ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a,
-                               ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b, d_ncons, (const uint32_t*)nullptr, 0);
+        auto prep = cross ? k_pose_prep<true> : k_pose_prep<false>;
+        hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, ctx->mw->mq_idx,
+                           ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a, ctx->mw->pts_b,
+                           ctx->mw->st_a, ctx->mw->st_b, d_ncons, cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr,
+                           cross ? b.n_kp : 0);
         const int use_filter = rigidity_thr > 0;
         // LDS: 4 int arrays of nq (rounded to even so the bit matrix stays 8-byte aligned) + bit matrix if <= 48 KB
         const int m_cap = (nq + 1) & ~1;
@@ -1451,65 +1445,6 @@ extern "C" int vo_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, i
     return vo_pose_pair_ex(ctx, slot_a, slot_b, ratio, 0, min_matches, rigidity_thr, outlier_thr, counts4, rc2, T1_12, T2_12);
 }
 
-// The context works on alternate k's stream and in its match scratch for the lifetime of the object, whatever leaves the scope
-// (the stream handle changes places with the main one, `mw` is retargeted; no member of a workspace is copied)
-struct PoseScope {
-    vo_ctx* c;
-    int k;
-    PoseScope(vo_ctx* c_, int k_) : c(c_), k(k_)
-    {
-        std::swap(c->stream, c->pose_alt[k].stream);
-        c->mw = &c->pose_alt[k].mw;
-    }
-    ~PoseScope()
-    {
-        c->mw = &c->main_mw;
-        std::swap(c->stream, c->pose_alt[k].stream);
-    }
-    PoseScope(const PoseScope&) = delete;
-    PoseScope& operator=(const PoseScope&) = delete;
-};
-
-static int pose_alt_prepare(vo_ctx* ctx, int k)
-{
-    vo_ctx::PoseAlt& p = ctx->pose_alt[k];
-    if (p.ready) return VO_OK;
-    const size_t cap = (size_t)ctx->kp_cap;
-    hipStream_t& shared = ctx->pose_streams[k % ctx->n_pose_streams];
-    if (!shared) VO_HIP(ctx, hipStreamCreateWithFlags(&shared, hipStreamNonBlocking));
-    p.stream = shared;                            // (not owned by the alternate)
-    VO_HIP(ctx, hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
-    VO_HIP(ctx, hipHostMalloc(&p.result, 1024, hipHostMallocDefault));
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.m_idx, cap * 8 + 256));
-    if (match_dist_alloc(ctx, &p.mw.m_dist)) return vo_fail(ctx, VO_E_HIP, "asynchronous pose step: allocation failed");
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.m_count, 256));
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.mq_idx, cap * 4 + 256)); VO_HIP(ctx, hipMalloc((void**)&p.mw.mt_idx, cap * 4 + 256));
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.pts_a, cap * 12 + 256)); VO_HIP(ctx, hipMalloc((void**)&p.mw.pts_b, cap * 12 + 256));
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.xy_a, cap * 8 + 256)); VO_HIP(ctx, hipMalloc((void**)&p.mw.xy_b, cap * 8 + 256));
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.st_a, cap + 256)); VO_HIP(ctx, hipMalloc((void**)&p.mw.st_b, cap + 256));
-    p.mw.clique_ws_bytes = pose_ws_bytes(ctx->kp_cap);
-    VO_HIP(ctx, hipMalloc((void**)&p.mw.clique_ws, p.mw.clique_ws_bytes));
-    p.ready = true;
-    return VO_OK;
-}
-
-void pose_alt_free(vo_ctx* ctx)
-{
-    for (int k = 0; k < vo_ctx::N_POSE_ALT; k++) {
-        vo_ctx::PoseAlt& p = ctx->pose_alt[k];
-        if (p.stream) (void)hipStreamSynchronize(p.stream);
-        void* ps[] = { p.mw.m_idx, p.mw.m_dist, p.mw.m_count, p.mw.mq_idx, p.mw.mt_idx, p.mw.pts_a, p.mw.pts_b, p.mw.xy_a, p.mw.xy_b, p.mw.st_a, p.mw.st_b, p.mw.clique_ws };
-        for (void* q : ps) if (q) (void)hipFree(q);
-        if (p.result) (void)hipHostFree(p.result);
-        if (p.done) (void)hipEventDestroy(p.done);
-        p = vo_ctx::PoseAlt();
-    }
-    for (hipStream_t& st : ctx->pose_streams) {
-        if (st) (void)hipStreamDestroy(st);
-        st = nullptr;
-    }
-}
-
 extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int min_matches, double rigidity_thr,
                                      double outlier_thr, int* ticket_out)
 {
@@ -1517,45 +1452,22 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     int rc = pose_check(ctx, slot_a, slot_b);
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
-    int k = -1;                                   // the first free alternate from the round-robin position on (tickets need not end in order)
-    for (int i = 0; i < vo_ctx::N_POSE_ALT && k < 0; i++)
-        if (!ctx->pose_alt[(ctx->pose_next + i) % vo_ctx::N_POSE_ALT].busy) k = (ctx->pose_next + i) % vo_ctx::N_POSE_ALT;
-    if (k < 0) return vo_fail(ctx, VO_E_STATE, "vo_pose_pair_begin: every asynchronous pose step is still open (end one first)");
-    vo_ctx::PoseAlt& p = ctx->pose_alt[k];
-    // the first step begun builds EVERY alternate (a dozen allocations, a pinned record and an event each: ~1 ms apiece): built one
-    // by one as the round-robin first reaches them, the later ones fell into whatever the caller was timing by then (the first two
-    // of bench.py's five cold windows read 10 % low)
-    for (int i = 0; i < vo_ctx::N_POSE_ALT; i++)
-        if ((rc = pose_alt_prepare(ctx, (k + i) % vo_ctx::N_POSE_ALT))) return rc;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
+    int k;
+    if ((rc = alt_open(ctx, vo_ctx::ALT_POSE, a, b, "vo_pose_pair_begin", &k))) return rc;
+    vo_ctx::PoseAlt& p = ctx->pose_alt[k];
     PoseOut* rec = (PoseOut*)p.result;
     memset(rec, 0, sizeof(PoseOut));
     rec->rc1 = rec->rc2 = 1;
-    // the step runs on the alternate's own stream: order it behind whatever still produces the two slots
-    // (look-ahead engines) and behind the main stream's work on them
-    VO_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    {
-        PoseScope on_alt(ctx, k);
-        hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev0, 0);
-        if (e == hipSuccess && a.pending) e = hipStreamWaitEvent(ctx->stream, a.ready, 0);
-        if (e == hipSuccess && b.pending) e = hipStreamWaitEvent(ctx->stream, b.ready, 0);
-        rc = e == hipSuccess ? VO_OK : vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-        if (!rc && a.n_kp > 0) rc = pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, min_matches, rigidity_thr, outlier_thr, rec);
-        if (!rc && hipEventRecord(p.done, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+    if (a.n_kp > 0) {
+        AltScope on_alt(ctx, p);
+        rc = pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, min_matches, rigidity_thr, outlier_thr, rec);
     }
     if (rc) return rc;
-    // both slots are read on this alternate's stream until p.done: whoever refills one of them waits for it first
-    for (FrameSlot* f : { &a, &b }) {
-        slot_add_reader(*f, p.done);
-    }
-    p.busy = true; p.slot_a = slot_a; p.slot_b = slot_b;
+    p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
-    p.params[0] = ratio; p.params[1] = min_matches; p.params[2] = rigidity_thr; p.params[3] = outlier_thr;
-    p.match_flags = match_flags;
-    ctx->pose_next = (k + 1) % vo_ctx::N_POSE_ALT;
-    *ticket_out = k;
-    return VO_OK;
+    return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }
 
 extern "C" int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int min_matches, double rigidity_thr,
@@ -1566,12 +1478,10 @@ extern "C" int vo_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ra
 
 extern "C" int vo_pose_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* rc2, double* T1_12, double* T2_12)
 {
-    if (!ctx || ticket < 0 || ticket >= vo_ctx::N_POSE_ALT || !counts4 || !rc2 || !T2_12) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair_end: bad argument");
+    int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && rc2 && T2_12, "vo_pose_pair_end");
+    if (rc) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
-    if (!p.busy) return vo_fail(ctx, VO_E_STATE, "vo_pose_pair_end: ticket %d is not open", ticket);
-    VO_HIP(ctx, hipSetDevice(ctx->device));
-    p.busy = false;
-    VO_HIP(ctx, hipEventSynchronize(p.done));
+    if ((rc = alt_wait(ctx, p))) return rc;
     // the step read the disparities the two slots held when it was begun: were those runs healthy?  (a slot refilled since
     // then carries another generation and another word value)
     const int32_t gens[2] = { p.gen_a, p.gen_b };

@@ -176,10 +176,9 @@ int orb_prepare_tables(vo_ctx* ctx, int w, int h)
     // new image size (rare: once per size).  What those extractions produced stays valid.
     for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
         if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
-    for (int k = 0; k < vo_ctx::N_POSE_ALT; k++)
-        if (ctx->pose_alt[k].stream) VO_HIP(ctx, hipStreamSynchronize(ctx->pose_alt[k].stream));
-    for (int k = 0; k < vo_ctx::N_MONO_ALT; k++)
-        if (ctx->mono_alt[k].stream) VO_HIP(ctx, hipStreamSynchronize(ctx->mono_alt[k].stream));
+    for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
+        for (int k = 0; k < vo_ctx::alt_count(kind); k++)
+            if (ctx->alt(kind, k).stream) VO_HIP(ctx, hipStreamSynchronize(ctx->alt(kind, k).stream));
     VO_HIP(ctx, hipMemcpyAsync(ctx->rs_ofs, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     VO_HIP(ctx, hipMemcpyAsync(ctx->rs_coef, coef.data(), coef.size() * 2, hipMemcpyHostToDevice, ctx->stream));
     VO_HIP(ctx, hipMemcpyAsync(ctx->pyr_rects, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1044,11 +1043,7 @@ static int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img
         const size_t lds = (size_t)(with_mask ? 2 : 1) * (pa.bufA + pa.bufB) + (size_t)(NL - 1) * 2 * pa.tab * 8 + NL * 16;
         if (lds > 150 * 1024) return vo_fail(ctx, VO_E_CAP, "pyramid cones of %dx%d need %zu bytes of LDS", w, h, lds);
         auto kp = with_mask ? k_orb_pyramid<true> : k_orb_pyramid<false>;
-        static unsigned long long attr_set[2] = { 0, 0 };     // per instantiation and device: allow more than 64 KB of dynamic LDS
-        if (!((attr_set[with_mask] >> (ctx->device & 63)) & 1ull)) {
-            VO_HIP(ctx, hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[with_mask] |= 1ull << (ctx->device & 63);
-        }
+        if (int rca = lds_allow_big(ctx, (const void*)kp)) return rca;
         hipLaunchKernelGGL(kp, dim3(pa.nbx, pa.nby), dim3(256), lds, ctx->stream, dL, pa, ctx->pyr_rects, ctx->rs_ofs, ctx->rs_coef,
                            ctx->orbws->pyr_img, ctx->orbws->pyr_mask, ctx->orbws->counters);
     }

@@ -402,13 +402,10 @@ static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
     {
         StageTimer t(ctx, VO_T_MATCH);
         if ((rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross))) return rc;
-        if (cross)
-            hipLaunchKernelGGL(k_ratio_compact<true>, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy,
-                               b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
-                               (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap), b.n_kp);
-        else
-            hipLaunchKernelGGL(k_ratio_compact<false>, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy,
-                               b.kp_xy, ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count, (const uint32_t*)nullptr, 0);
+        auto kern = cross ? k_ratio_compact<true> : k_ratio_compact<false>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy, b.kp_xy,
+                           ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
+                           cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, cross ? b.n_kp : 0);
     }
     {
         StageTimer t(ctx, VO_T_POSE);
@@ -489,63 +486,6 @@ extern "C" int vo_mono_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, c
 // five-point kernel alone runs 0.26 ms on 79 of the 1024 SIMDs).  Consecutive pairs do not depend on each other's result --
 // only on the caller's decision which frame is the reference -- so a caller that knows the next frame may begin its pair
 // before it collects this one's.  Results land in the alternate's pinned record; vo_mono_pair_end waits for its event only.
-static const size_t MONO_HDR = 4096;             // record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on
-
-// the context works on alternate k's stream and in its match / RANSAC scratch for the lifetime of the object
-struct MonoScope {
-    vo_ctx* c;
-    int k;
-    MonoScope(vo_ctx* c_, int k_) : c(c_), k(k_)
-    {
-        std::swap(c->stream, c->mono_alt[k].stream);
-        c->mw = &c->mono_alt[k].mw;
-    }
-    ~MonoScope()
-    {
-        c->mw = &c->main_mw;
-        std::swap(c->stream, c->mono_alt[k].stream);
-    }
-    MonoScope(const MonoScope&) = delete;
-    MonoScope& operator=(const MonoScope&) = delete;
-};
-
-static void mono_alt_release(vo_ctx::MonoAlt& p)
-{
-    if (p.stream) (void)hipStreamSynchronize(p.stream);
-    void* ps[] = { p.mw.m_idx, p.mw.m_dist, p.mw.m_count, p.mw.mq_idx, p.mw.mt_idx, p.mw.xy_a, p.mw.xy_b, p.mw.ransac_ws };
-    for (void* q : ps) if (q) (void)hipFree(q);
-    if (p.result) (void)hipHostFree(p.result);
-    if (p.done) (void)hipEventDestroy(p.done);
-    if (p.stream) (void)hipStreamDestroy(p.stream);
-    p = vo_ctx::MonoAlt();
-}
-
-static int mono_alt_prepare(vo_ctx* ctx, int k)
-{
-    vo_ctx::MonoAlt& p = ctx->mono_alt[k];
-    if (p.ready) return VO_OK;
-    const size_t cap = (size_t)ctx->kp_cap;
-    hipError_t e = hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p.done, hipEventDisableTiming);
-    p.result_bytes = MONO_HDR + cap * (1 + 4 + 4 + 8) + 64;
-    if (e == hipSuccess) e = hipHostMalloc((void**)&p.result, p.result_bytes, hipHostMallocDefault);
-    void** ps[] = { (void**)&p.mw.m_idx, (void**)&p.mw.m_count, (void**)&p.mw.mq_idx, (void**)&p.mw.mt_idx, (void**)&p.mw.xy_a, (void**)&p.mw.xy_b };
-    const size_t sz[] = { cap * 8, 256, cap * 4, cap * 4, cap * 8, cap * 8 };
-    for (size_t i = 0; i < sizeof(ps) / sizeof(ps[0]) && e == hipSuccess; i++) e = hipMalloc(ps[i], sz[i] + 256);
-    if (e == hipSuccess && match_dist_alloc(ctx, &p.mw.m_dist)) e = hipErrorOutOfMemory;
-    if (e != hipSuccess) {
-        mono_alt_release(p);                      // a partly built alternate is given back whole
-        return vo_fail(ctx, VO_E_HIP, "asynchronous monocular step: allocation failed: %s", hipGetErrorString(e));
-    }
-    p.ready = true;
-    return VO_OK;
-}
-
-void mono_alt_free(vo_ctx* ctx)
-{
-    for (int k = 0; k < vo_ctx::N_MONO_ALT; k++) mono_alt_release(ctx->mono_alt[k]);
-}
-
 extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
                                      uint32_t seed, int solver, int want_matches, int* ticket_out)
 {
@@ -553,49 +493,28 @@ extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, "vo_mono_pair_begin");
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
-    int k = -1;                                   // the first free alternate from the round-robin position on (tickets need not end in order)
-    for (int i = 0; i < vo_ctx::N_MONO_ALT && k < 0; i++)
-        if (!ctx->mono_alt[(ctx->mono_next + i) % vo_ctx::N_MONO_ALT].busy) k = (ctx->mono_next + i) % vo_ctx::N_MONO_ALT;
-    if (k < 0) return vo_fail(ctx, VO_E_STATE, "vo_mono_pair_begin: every asynchronous step is still open (end one first)");
-    vo_ctx::MonoAlt& p = ctx->mono_alt[k];
-    for (int i = 0; i < vo_ctx::N_MONO_ALT; i++)            // (every alternate with the first step: see vo_pose_pair_begin)
-        if ((rc = mono_alt_prepare(ctx, (k + i) % vo_ctx::N_MONO_ALT))) return rc;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
+    int k;
+    if ((rc = alt_open(ctx, vo_ctx::ALT_MONO, a, b, "vo_mono_pair_begin", &k))) return rc;
+    vo_ctx::MonoAlt& p = ctx->mono_alt[k];
     memset(p.result, 0, MONO_HDR);
     p.nq = a.n_kp; p.nb = b.n_kp; p.min_n = solver == 5 ? 6 : 8; p.want = want_matches != 0;
-    // the step runs on the alternate's own stream: behind whatever still produces the two slots (look-ahead engines) and
-    // behind the main stream's work on them
-    VO_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    {
-        MonoScope on_alt(ctx, k);
-        hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev0, 0);
-        if (e == hipSuccess && a.pending) e = hipStreamWaitEvent(ctx->stream, a.ready, 0);
-        if (e == hipSuccess && b.pending) e = hipStreamWaitEvent(ctx->stream, b.ready, 0);
-        rc = e == hipSuccess ? VO_OK : vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-        if (!rc && a.n_kp > 0) {
-            MonoDev o;
-            MonoTail tl;
-            rc = mono_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, o, &tl);
-            if (!rc) {
-                // (p.result is pinned host memory: the kernel writes the record across the link itself -- no copy command)
-                hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(1024), 0, ctx->stream, tl.counts, iters, tl.E, tl.F, ctx->mw->xy_a, ctx->mw->xy_b, a.n_kp,
-                                   ctx->mw->m_count, tl.min_n, tl.thr2, ctx->mw->mq_idx, ctx->mw->mt_idx, b.kp_xy, b.n_kp, p.want ? 1 : 0, (size_t)ctx->kp_cap,
-                                   p.result, MONO_HDR);
-                if (hipGetLastError() != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "k_mono_finish: launch failed");
-            }
+    if (a.n_kp > 0) {
+        AltScope on_alt(ctx, p);
+        MonoDev o;
+        MonoTail tl;
+        rc = mono_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, o, &tl);
+        if (!rc) {
+            // (p.result is pinned host memory: the kernel writes the record across the link itself -- no copy command)
+            hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(1024), 0, ctx->stream, tl.counts, iters, tl.E, tl.F, ctx->mw->xy_a, ctx->mw->xy_b, a.n_kp,
+                               ctx->mw->m_count, tl.min_n, tl.thr2, ctx->mw->mq_idx, ctx->mw->mt_idx, b.kp_xy, b.n_kp, p.want ? 1 : 0, (size_t)ctx->kp_cap,
+                               p.result, MONO_HDR);
+            if (hipGetLastError() != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "k_mono_finish: launch failed");
         }
-        if (!rc && hipEventRecord(p.done, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
     }
     if (rc) return rc;
-    // both slots are read on this alternate's stream until p.done: whoever refills one of them waits for it first
-    for (FrameSlot* f : { &a, &b }) {
-        slot_add_reader(*f, p.done);
-    }
-    p.busy = true;
-    ctx->mono_next = (k + 1) % vo_ctx::N_MONO_ALT;
-    *ticket_out = k;
-    return VO_OK;
+    return alt_close(ctx, vo_ctx::ALT_MONO, k, a, b, ticket_out);
 }
 
 extern "C" int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, const double* K4v, int iters, float thr, uint32_t seed,
@@ -607,14 +526,12 @@ extern "C" int vo_mono_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ra
 extern "C" int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx,
                                 float* xy_b_out, int cap)
 {
-    if (!ctx || ticket < 0 || ticket >= vo_ctx::N_MONO_ALT || !E9_out || !counts3) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair_end: bad argument");
+    int rc = alt_ticket(ctx, vo_ctx::ALT_MONO, ticket, E9_out && counts3, "vo_mono_pair_end");
+    if (rc) return rc;
     vo_ctx::MonoAlt& p = ctx->mono_alt[ticket];
-    if (!p.busy) return vo_fail(ctx, VO_E_STATE, "vo_mono_pair_end: ticket %d is not open", ticket);
     if ((mask_out || q_idx || t_idx) && (!p.want || cap < p.nq)) return vo_fail(ctx, VO_E_CAP, "vo_mono_pair_end: outputs hold %d entries, %d keypoints (or the step was begun without want_matches)", cap, p.nq);
     if (xy_b_out && (!p.want || cap < p.nb)) return vo_fail(ctx, VO_E_CAP, "vo_mono_pair_end: xy_b_out holds %d entries, %d keypoints", cap, p.nb);
-    VO_HIP(ctx, hipSetDevice(ctx->device));
-    p.busy = false;
-    VO_HIP(ctx, hipEventSynchronize(p.done));
+    if ((rc = alt_wait(ctx, p))) return rc;
     const int32_t* h = (const int32_t*)p.result;
     counts3[0] = h[0]; counts3[1] = h[1]; counts3[2] = h[0] >= p.min_n ? h[2] : 0;
     memcpy(E9_out, p.result + 64, 72);

@@ -1588,11 +1588,7 @@ static int launch_diag_k(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1, int
     }
     const size_t lds = (size_t)DG_RING * 2 * CW * g.Dp * 2 + (WTA ? (size_t)NWC * 4 * 2 * g.Dp * 2 : 0) + 64 * 4;
     auto kern = k_sgbm_diag<NP, PAD, NWC, REV, WTA>;
-    static unsigned long long attr_set = 0;     // per instantiation and device: allow more than 64 KB of dynamic LDS
-    if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-        VO_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set |= 1ull << (ctx->device & 63);
-    }
+    if (int rca = lds_allow_big(ctx, (const void*)kern)) return rca;
     // strips that can be active at the same time: one image row's worth (+ slack for the hand-over between strips)
     const int wgs = ctx->tune_diag_wgs > 0 ? min(jobs.nstrips, ctx->tune_diag_wgs) : min(jobs.nstrips, div_up(g.W1, UW) + 2);
     hipLaunchKernelGGL(kern, dim3(wgs), dim3((NWC + 1) * 64), lds, ctx->stream, jobs, g, ctl, ctx->dump, ctx->sw_ctl_words / 2);
@@ -1817,11 +1813,7 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
         const int rb = post_rows_per_block(w);
         if (ctx->last_schedule != VO_SCHED_UNFUSED && rb >= 1) {
             // records of the diagonal sweep -> sub-pixel disp1 + disp2 -> left-right check -> medianBlur(3) -> labelled runs: one launch
-            static unsigned long long attr_set = 0;
-            if (!((attr_set >> (ctx->device & 63)) & 1ull)) {
-                VO_HIP(ctx, hipFuncSetAttribute((const void*)k_sgbm_post_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_set |= 1ull << (ctx->device & 63);
-            }
+            if (int rca = lds_allow_big(ctx, (const void*)k_sgbm_post_rows)) return rca;
             const int* const ctlA = ctx->ws->sw_ctl;
             const int* const ctlB = ctx->ws->sw_ctl + ctx->sw_ctl_words / 2;
             hipLaunchKernelGGL(k_sgbm_post_rows, dim3(div_up(h, rb)), dim3(512), (size_t)(rb + 2) * w * 6, ctx->stream, ctx->ws->rec,

@@ -112,6 +112,45 @@ static void orb_ws_free(OrbWs& o)
     o = OrbWs();
 }
 
+// The one allocator of an SGBM workspace (the main one in vo_create, an engine's on that engine's first use): what a disparity
+// run writes, and the `done` event.  sw_bnd comes with the first diagonal sweep (sgbm.hip).  A partly built workspace is given
+// back whole.  The ORB scratch, staging and events of the ENGINE that sit in the same struct are engine_prepare's.
+static void sgbm_ws_free(vo_ctx::SgbmWs& a)
+{
+    void** ps[] = { (void**)&a.planesL, (void**)&a.planesR, (void**)&a.C, (void**)&a.S, (void**)&a.sw_ctl, (void**)&a.disp_tmp,
+                    (void**)&a.ccl_runlen, (void**)&a.ccl_label, (void**)&a.ccl_size, (void**)&a.rec, (void**)&a.sw_bnd };
+    for (void** q : ps) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    if (a.done) (void)hipEventDestroy(a.done);
+    a.done = nullptr;
+    a.S_vols = 0; a.sw_bnd_bytes = 0; a.ready = false; a.done_valid = false;
+}
+
+static hipError_t sgbm_ws_alloc(vo_ctx* ctx, vo_ctx::SgbmWs& a)
+{
+    const size_t npx = (size_t)ctx->max_w * ctx->max_h;
+    const int vols = 3;                          // L_W + L_E, MODE_HH's reverse-pass sum, checkpoints (ensure_S grows it for uniquenessRatio >= 100)
+    void** ps[] = { (void**)&a.planesL, (void**)&a.planesR, (void**)&a.C, (void**)&a.S, (void**)&a.sw_ctl, (void**)&a.disp_tmp,
+                    (void**)&a.ccl_runlen, (void**)&a.ccl_label, (void**)&a.ccl_size, (void**)&a.rec };
+    const size_t sz[] = { npx * 2 * 4, npx * 6 * 4, ctx->vol_cells * 2, ctx->vol_cells * 2 * vols, ctx->sw_ctl_words * sizeof(int), npx * 2,
+                          npx * 4, npx * 4, npx * 4, (npx + 64) * 8 };
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < sizeof(ps) / sizeof(ps[0]) && e == hipSuccess; k++) e = hipMalloc(ps[k], sz[k] + 256);
+    if (e == hipSuccess) e = dev_zero(a.sw_ctl, ctx->sw_ctl_words * sizeof(int));      // (the first sweep runs on an engine's or the main stream)
+    if (e == hipSuccess && !a.done) e = hipEventCreateWithFlags(&a.done, hipEventDisableTiming);
+    if (e != hipSuccess) { sgbm_ws_free(a); return e; }
+    a.S_vols = vols;
+    a.ready = true;
+    return hipSuccess;
+}
+
+int lds_allow_big(vo_ctx* ctx, const void* fn)
+{
+    for (const void* f : ctx->big_lds) if (f == fn) return VO_OK;
+    VO_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    ctx->big_lds.push_back(fn);
+    return VO_OK;
+}
+
 extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int max_kp, vo_ctx** out)
 {
     if (!out) return VO_E_ARG;
@@ -140,7 +179,6 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         snprintf(ctx->devname, sizeof(ctx->devname), "%s (%s)", prop.name[0] ? prop.name : generic, prop.gcnArchName);
     }
     if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete ctx; return VO_E_HIP; }
-    (void)hipEventCreateWithFlags(&ctx->ws->done, hipEventDisableTiming);
     (void)hipEventCreate(&ctx->ev0);
     (void)hipEventCreate(&ctx->ev1);
 
@@ -157,18 +195,10 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     ctx->stage_bytes = npx * 3;
     DALLOC(ctx->stage_in, ctx->stage_bytes * 2);
     for (int c = 0; c < 2; c++) { DALLOC(ctx->map1[c], npx * 2); DALLOC(ctx->map2[c], npx); }
-    DALLOC(ctx->ws->planesL, npx * 2); DALLOC(ctx->ws->planesR, npx * 6);
     ctx->vol_cells = npx * (size_t)((max_disp + 31) & ~31);
-    DALLOC(ctx->ws->C, ctx->vol_cells);
-    // aggregated volumes: L_W + L_E, MODE_HH's reverse-pass sum, checkpoints (grown on demand for uniquenessRatio >= 100)
-    ctx->ws->S_vols = 3;
-    DALLOC(ctx->ws->S, ctx->vol_cells * ctx->ws->S_vols);
     ctx->sw_ctl_words = 2 * 2048;                        // two control blocks: {work items taken, sticky error, ...} + per-strip timeline
-    DALLOC(ctx->ws->sw_ctl, ctx->sw_ctl_words);
-    VO_HIP(ctx, hipMemset(ctx->ws->sw_ctl, 0, ctx->sw_ctl_words * sizeof(int)));
-    DALLOC(ctx->ws->disp_tmp, npx); DALLOC(ctx->dump, 4096);
-    DALLOC(ctx->ws->ccl_label, npx); DALLOC(ctx->ws->ccl_size, npx); DALLOC(ctx->ws->ccl_runlen, npx);
-    DALLOC(ctx->ws->rec, 2 * (npx + 64));
+    if (sgbm_ws_alloc(ctx, ctx->main_ws) != hipSuccess) { g_create_err = "hipMalloc failed (SGBM workspace)"; vo_destroy(ctx); return VO_E_HIP; }
+    DALLOC(ctx->dump, 4096);
     // ORB: 8-level pyramid is < 3.2x the base image
     ctx->pyr_bytes = npx * 4;
     DALLOC(ctx->rs_ofs, (size_t)(max_w + max_h) * 2 * VO_ORB_LEVELS);
@@ -178,18 +208,10 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     ctx->cand_cap = (int)((size_t)((max_w + 1) / 2) * ((max_h + 1) / 2));
     // (summed over the 8 levels: < 3.2x that)
     if (orb_ws_alloc(ctx, (*ctx->orbws))) { g_create_err = "hipMalloc failed (ORB workspace)"; vo_destroy(ctx); return VO_E_HIP; }
-    DALLOC(ctx->mw->m_count, 64);
     DALLOC(ctx->host_mask_dev, npx);
     DALLOC(ctx->mq, (size_t)ctx->kp_cap * 32); DALLOC(ctx->mt, (size_t)ctx->kp_cap * 32);
-    DALLOC(ctx->mw->m_idx, (size_t)ctx->kp_cap * 2);
-    if (match_dist_alloc(ctx, &ctx->mw->m_dist)) { g_create_err = "hipMalloc failed (match scratch)"; vo_destroy(ctx); return VO_E_HIP; }
-    DALLOC(ctx->mw->pts_a, (size_t)ctx->kp_cap * 3); DALLOC(ctx->mw->pts_b, (size_t)ctx->kp_cap * 3);
-    DALLOC(ctx->mw->st_a, ctx->kp_cap); DALLOC(ctx->mw->st_b, ctx->kp_cap);
-    DALLOC(ctx->mw->xy_a, (size_t)ctx->kp_cap * 2); DALLOC(ctx->mw->xy_b, (size_t)ctx->kp_cap * 2);
-    DALLOC(ctx->mw->mq_idx, ctx->kp_cap); DALLOC(ctx->mw->mt_idx, ctx->kp_cap);
+    if (match_ws_alloc(ctx, ctx->main_mw, MATCH_WS_POSE) != hipSuccess) { g_create_err = "hipMalloc failed (match scratch)"; vo_destroy(ctx); return VO_E_HIP; }
     DALLOC(ctx->red, 4096);
-    ctx->mw->clique_ws_bytes = pose_ws_bytes(ctx->kp_cap);     // sized once: the pose step never reallocates mid-stream
-    DALLOC(ctx->mw->clique_ws, ctx->mw->clique_ws_bytes);
     ctx->pinned_bytes = 8 << 20;
     if (hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void**)&ctx->slot_words, 128 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
@@ -198,7 +220,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     memset(ctx->slot_words, 0, 128 * sizeof(int32_t));
     for (int s = 0; s <= VO_NUM_SLOTS; s++) { ctx->slots[s].n_kp_host = ctx->slot_words + s; ctx->slots[s].sweep_word = ctx->slot_words + 64 + s; }
     DALLOC(ctx->d_sweep_errs, 64);
-    VO_HIP(ctx, hipMemset(ctx->d_sweep_errs, 0, 64 * sizeof(int)));
+    if (dev_zero(ctx->d_sweep_errs, 64 * sizeof(int)) != hipSuccess) { g_create_err = "clearing the sweep error counter failed"; vo_destroy(ctx); return VO_E_HIP; }
     if (const char* e8 = getenv("VO_ENGINES")) { int v = atoi(e8); if (v >= 1 && v <= vo_ctx::MAX_ENGINES) ctx->n_engines = v; }
     {
         // every engine owns a full SGBM workspace: cost volume + 3 aggregated volumes + boundary granules (< 1 volume) + planes.
@@ -245,25 +267,22 @@ extern "C" void vo_destroy(vo_ctx* ctx)
         for (void* p : ps) if (p) (void)hipFree(p);
         if (f.ready) (void)hipEventDestroy(f.ready);
     }
-    void* ps[] = { ctx->stage_in, ctx->map1[0], ctx->map1[1], ctx->map2[0], ctx->map2[1], ctx->ws->planesL, ctx->ws->planesR,
-                   ctx->ws->C, ctx->ws->S, ctx->ws->sw_bnd, ctx->ws->sw_ctl, ctx->ws->disp_tmp, ctx->dump, ctx->ws->ccl_runlen, ctx->ws->ccl_label, ctx->ws->ccl_size, ctx->ws->rec, ctx->rs_ofs, ctx->rs_coef, ctx->pyr_rects, ctx->mw->m_count, ctx->host_mask_dev, ctx->mq, ctx->mt,
-                   ctx->mw->m_idx, ctx->mw->m_dist, ctx->mw->pts_a, ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b, ctx->mw->xy_a, ctx->mw->xy_b,
-                   ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->red, ctx->mw->clique_ws, ctx->img3_ws, ctx->mw->ransac_ws, ctx->d_sweep_errs };
+    void* ps[] = { ctx->stage_in, ctx->map1[0], ctx->map1[1], ctx->map2[0], ctx->map2[1], ctx->dump, ctx->rs_ofs, ctx->rs_coef, ctx->pyr_rects,
+                   ctx->host_mask_dev, ctx->mq, ctx->mt, ctx->red, ctx->img3_ws, ctx->d_sweep_errs };
     for (void* p : ps) if (p) (void)hipFree(p);
-    orb_ws_free(*ctx->orbws);
-    pose_alt_free(ctx);
-    mono_alt_free(ctx);
+    alt_free(ctx);
+    match_ws_free(ctx->main_mw);
+    sgbm_ws_free(ctx->main_ws);
+    orb_ws_free(ctx->main_ws.orb);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->slot_words) (void)hipHostFree(ctx->slot_words);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->staged) (void)hipFree(ctx->staged);
-    if (ctx->ws->done) (void)hipEventDestroy(ctx->ws->done);
     for (int k = 0; k < vo_ctx::MAX_ENGINES; k++) {
         vo_ctx::SgbmWs& a = ctx->ws_alt[k];
-        void* pa[] = { a.planesL, a.planesR, a.C, a.S, a.sw_bnd, a.sw_ctl, a.disp_tmp, a.ccl_runlen, a.ccl_label, a.ccl_size, a.rec, ctx->la_stage[k] };
-        for (void* q : pa) if (q) (void)hipFree(q);
-        if (a.done) (void)hipEventDestroy(a.done);
+        sgbm_ws_free(a);
         orb_ws_free(a.orb);
+        if (ctx->la_stage[k]) (void)hipFree(ctx->la_stage[k]);
         if (a.pinned) (void)hipHostFree(a.pinned);
         if (a.h2d_done) (void)hipEventDestroy(a.h2d_done);
         if (a.mid) (void)hipEventDestroy(a.mid);
@@ -303,10 +322,9 @@ extern "C" int vo_synchronize(vo_ctx* ctx)
     if (!ctx) return VO_E_ARG;
     for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
         if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
-    for (int k = 0; k < vo_ctx::N_POSE_ALT; k++)
-        if (ctx->pose_alt[k].stream) VO_HIP(ctx, hipStreamSynchronize(ctx->pose_alt[k].stream));
-    for (int k = 0; k < vo_ctx::N_MONO_ALT; k++)
-        if (ctx->mono_alt[k].stream) VO_HIP(ctx, hipStreamSynchronize(ctx->mono_alt[k].stream));
+    for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
+        for (int k = 0; k < vo_ctx::alt_count(kind); k++)
+            if (ctx->alt(kind, k).stream) VO_HIP(ctx, hipStreamSynchronize(ctx->alt(kind, k).stream));
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VO_OK;
 }
@@ -578,24 +596,8 @@ static int engine_prepare(vo_ctx* ctx, int engine)
         if (orb_ws_alloc(ctx, ctx->ws_alt[engine].orb)) return vo_fail(ctx, VO_E_HIP, "hipMalloc failed (look-ahead ORB workspace)");
     }
     if (engine == 0 || ctx->ws_alt[engine].ready) return VO_OK;
-    vo_ctx::SgbmWs& a = ctx->ws_alt[engine];
-    const size_t npx = (size_t)ctx->max_w * ctx->max_h;
-    const int vols = 3;                          // L_W + L_E, MODE_HH's reverse-pass sum, checkpoints (ensure_S grows it if ever needed)
-    void** ps[] = { (void**)&a.planesL, (void**)&a.planesR, (void**)&a.C, (void**)&a.S, (void**)&a.sw_ctl, (void**)&a.disp_tmp,
-                    (void**)&a.ccl_runlen, (void**)&a.ccl_label, (void**)&a.ccl_size, (void**)&a.rec };
-    const size_t sz[] = { npx * 2 * 4, npx * 6 * 4, ctx->vol_cells * 2, ctx->vol_cells * 2 * vols, ctx->sw_ctl_words * sizeof(int), npx * 2,
-                          npx * 4, npx * 4, npx * 4, (npx + 64) * 8 };
-    hipError_t e = hipSuccess;
-    for (size_t k = 0; k < sizeof(ps) / sizeof(ps[0]) && e == hipSuccess; k++) e = hipMalloc(ps[k], sz[k] + 256);
-    if (e == hipSuccess) e = hipMemset(a.sw_ctl, 0, ctx->sw_ctl_words * sizeof(int));
-    if (e == hipSuccess && !a.done) e = hipEventCreateWithFlags(&a.done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        // a partly built workspace is given back whole: the next call starts from nothing instead of leaking these
-        for (void** q : ps) { if (*q) (void)hipFree(*q); *q = nullptr; }
-        return vo_fail(ctx, VO_E_HIP, "look-ahead engine %d: workspace allocation failed: %s", engine, hipGetErrorString(e));
-    }
-    a.S_vols = vols;
-    a.ready = true;
+    const hipError_t e = sgbm_ws_alloc(ctx, ctx->ws_alt[engine]);
+    if (e != hipSuccess) return vo_fail(ctx, VO_E_HIP, "look-ahead engine %d: workspace allocation failed: %s", engine, hipGetErrorString(e));
     return VO_OK;
 }
 
@@ -1183,10 +1185,8 @@ extern "C" int vo_measure_copy(vo_ctx* ctx, int64_t bytes, int reps, int nontemp
     VO_HIP(ctx, hipEventCreate(&e1));
     const size_t n16 = (size_t)bytes / 16;
     const int blocks = 256 * 16;                           // 16 workgroups per CU, grid-stride
-    auto launch = [&]() {
-        if (nontemporal) hipLaunchKernelGGL(k_copy_stream<true>, dim3(blocks), dim3(256), 0, ctx->stream, (const copy_u32x4*)ctx->ws->S, (copy_u32x4*)ctx->ws->C, n16);
-        else hipLaunchKernelGGL(k_copy_stream<false>, dim3(blocks), dim3(256), 0, ctx->stream, (const copy_u32x4*)ctx->ws->S, (copy_u32x4*)ctx->ws->C, n16);
-    };
+    auto kern = nontemporal ? k_copy_stream<true> : k_copy_stream<false>;
+    auto launch = [&]() { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, ctx->stream, (const copy_u32x4*)ctx->ws->S, (copy_u32x4*)ctx->ws->C, n16); };
     launch();                                               // warm-up (page tables, clocks)
     VO_HIP(ctx, hipEventRecord(e0, ctx->stream));
     for (int r = 0; r < reps; r++) launch();

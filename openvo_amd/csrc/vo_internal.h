@@ -180,13 +180,14 @@ struct vo_ctx {
 
     // match / pose workspace.  MatchWs = what one matching + pose (or essential-matrix) step writes; the context owns one
     // (`main_mw`) and one per asynchronous alternate, `mw` names the one the code in match.hip / geom.hip / ransac.hip works in
-    // right now (PoseScope / MonoScope retarget it together with the stream; nothing is swapped member by member).
+    // right now (AltScope retargets it together with the stream; nothing is swapped member by member).  match_ws_alloc /
+    // match_ws_free (match.hip) hold the one member / size table.
     struct MatchWs {
         int32_t *m_idx = nullptr, *m_count = nullptr, *m_dist = nullptr, *mq_idx = nullptr, *mt_idx = nullptr;   // m_count: match counter of the ratio filter
         float *pts_a = nullptr, *pts_b = nullptr, *xy_a = nullptr, *xy_b = nullptr;
         uint8_t *st_a = nullptr, *st_b = nullptr, *clique_ws = nullptr;
         size_t clique_ws_bytes = 0;
-        uint8_t* ransac_ws = nullptr;
+        uint8_t* ransac_ws = nullptr;    // grown on demand (mono_enqueue, vo_ransac_pnp)
         size_t ransac_ws_bytes = 0;
     };
     MatchWs main_mw;
@@ -194,40 +195,41 @@ struct vo_ctx {
     uint8_t* mq = nullptr;
     uint8_t* mt = nullptr;
     double* red = nullptr;         // reduction scratch
-    // asynchronous pose steps (vo_pose_pair_begin / _end): two alternates of the match / pose scratch above,
-    // each with its own stream, a pinned result record and a completion event
+    // Asynchronous steps (vo_pose_pair_begin / _end, vo_mono_pair_begin / _end): an alternate = a match scratch of its own, a
+    // stream, a pinned result record and a completion event; a ticket is an alternate's index.  One mechanism (alt_open /
+    // AltScope / alt_close / alt_ticket / alt_wait in match.hip) serves both kinds.  What differs between them:
+    //   * the pose alternates run on n_pose_streams streams they SHARE and do not own (alternate k on stream k % n): a context
+    //     must stay at about twenty HIP streams (16 engines + main + these) -- beyond that the hardware queues are time-sliced
+    //     in ~10 ms quanta and a pair's diagonal sweep stalls behind a descheduled neighbour (measured: 23 streams -> 200-1000
+    //     pairs/s).  Steps that share a stream run back to back without the host in between; their scratch and records are
+    //     separate.  Every monocular alternate owns its stream.
+    //   * the pose alternates' scratch has the 3-D / clique members (MATCH_WS_POSE), the monocular ones' has not.
+    //   * only the pose step depends on disparities: it remembers its slots and their generations for the health check at _end.
+    struct AsyncAlt {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;
+        uint8_t* result = nullptr;     // pinned record the step's last kernel writes (pose: PoseOut; monocular: see MONO_HDR)
+        bool ready = false, busy = false;
+        MatchWs mw;
+    };
+    enum { ALT_POSE = 0, ALT_MONO = 1 };
     static const int N_POSE_ALT = VO_NUM_POSE_ASYNC;
-    // the alternates' steps run on THREE streams (alternate k on stream k % 3): a context must stay at about twenty HIP streams
-    // (16 engines + main + these) -- beyond that the hardware queues are time-sliced in ~10 ms quanta and a pair's diagonal
-    // sweep stalls behind a descheduled neighbour (measured: 23 streams -> 200-1000 pairs/s).  Steps that share a stream run
-    // back to back without the host in between; their scratch and records are separate.
     static const int N_POSE_STREAMS = 3;
     int n_pose_streams = N_POSE_STREAMS;     // VO_POSE_STREAMS (1..3): fewer when the GPU's hardware queues are shared with other processes
     hipStream_t pose_streams[N_POSE_STREAMS] = {};
-    struct PoseAlt {
-        hipStream_t stream = nullptr;
-        hipEvent_t done = nullptr;
-        void* result = nullptr;        // pinned PoseOut
-        bool ready = false, busy = false;
+    struct PoseAlt : AsyncAlt {
         int slot_a = -1, slot_b = -1;
         int32_t gen_a = 0, gen_b = 0;      // disparity generations of the two slots when the step was begun (slot health at _end)
-        double params[4] = {0, 0, 0, 0};   // ratio, min_matches, rigidity_thr, outlier_thr
-        int match_flags = 0;               // VO_MATCH_* the step was begun with
-        MatchWs mw;
     } pose_alt[N_POSE_ALT];
-    int pose_next = 0;
-    // asynchronous monocular pair steps (vo_mono_pair_begin / _end): match scratch + RANSAC workspace + stream + pinned record each
     static const int N_MONO_ALT = VO_NUM_MONO_ASYNC;
-    struct MonoAlt {
-        hipStream_t stream = nullptr;
-        hipEvent_t done = nullptr;
-        uint8_t* result = nullptr;     // pinned: header (M, best, E) + mask / q / t / xy of the second frame
-        size_t result_bytes = 0;
-        bool ready = false, busy = false, want = false;
+    struct MonoAlt : AsyncAlt {
+        bool want = false;                 // the record carries mask / q / t / xy of the second frame behind its header
         int nq = 0, nb = 0, min_n = 0;
-        MatchWs mw;
     } mono_alt[N_MONO_ALT];
-    int mono_next = 0;
+    int alt_next[2] = {0, 0};              // round-robin position per kind
+    AsyncAlt& alt(int kind, int k) { return kind == ALT_POSE ? static_cast<AsyncAlt&>(pose_alt[k]) : mono_alt[k]; }
+    static int alt_count(int kind) { return kind == ALT_POSE ? N_POSE_ALT : N_MONO_ALT; }
+    std::vector<const void*> big_lds;      // kernels this context has allowed more than 64 KB of dynamic LDS (lds_allow_big)
     float* img3_ws = nullptr;
     size_t img3_ws_bytes = 0;
     void* pinned = nullptr;        // pinned host buffer: first 4 KB scalar readbacks, rest = transfer arena
@@ -311,8 +313,16 @@ int slot_before_overwrite(vo_ctx* ctx, FrameSlot& f);
 // `done` marks the end of an asynchronous step that reads the slot: whoever overwrites the slot waits for it first
 void slot_add_reader(FrameSlot& f, hipEvent_t done);
 int orb_slot_enqueue(vo_ctx* ctx, FrameSlot& f, int nfeatures, int mask_mode, int min_disp16, int max_disp16);
-void pose_alt_free(vo_ctx* ctx);
-void mono_alt_free(vo_ctx* ctx);
+// kernel `fn` may use up to 160 KB of dynamic LDS: set once per context, before its first launch that needs more than 64 KB
+int lds_allow_big(vo_ctx* ctx, const void* fn);
+// Device memory that must read zero before its first use on WHATEVER stream: the context's streams are non-blocking, they do
+// not synchronise with the null stream a plain memset runs on, and a memset landing in the middle of a launch clears state that
+// launch has written (kNN tickets that have been drawn: the group's result is then never written).  So: cleared AND waited for.
+static inline hipError_t dev_zero(void* p, size_t bytes)
+{
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, nullptr);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
 size_t pose_ws_bytes(int nq);
 // CROSS: a match must also pass the cross-check (knn_mutual on the column words of the same kNN launch)
 template <bool CROSS>
@@ -354,9 +364,45 @@ __device__ __forceinline__ bool knn_mutual(int t, int i, const uint32_t* __restr
     const uint32_t key = colmin[t];
     return key != 0xFFFFFFFFu && (key & 0xFFFFu) == (uint32_t)i;
 }
-int match_dist_alloc(vo_ctx* ctx, int32_t** p);      // hipMalloc + the tickets cleared
+// The one allocator of a MatchWs.  `what`: the member groups the owner needs beyond matching (m_*, mq / mt_idx, xy_*) --
+// MATCH_WS_POSE = the 3-D / clique members (pts_*, st_*, clique_ws for kp_cap query keypoints: tens of megabytes at 8000
+// features, which is why the monocular alternates go without).  On failure the workspace is given back whole.
+enum { MATCH_WS_POSE = 1 };
+hipError_t match_ws_alloc(vo_ctx* ctx, vo_ctx::MatchWs& m, int what);
+void match_ws_free(vo_ctx::MatchWs& m);
 int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx,
                int32_t* d_dist, int cross = 0);
 int points3d_launch(vo_ctx* ctx, const int16_t* d_disp16, int w, int h, const float* d_xy, int n,
                     float* d_xyz, uint8_t* d_status);
 void host_svd3(const double* A, double* U, double* w, double* Vt);
+
+// ---- asynchronous steps (match.hip): see vo_ctx::AsyncAlt -------------------------------------------------------------------
+static const size_t MONO_HDR = 4096;             // monocular record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on
+// picks the first free alternate of `kind` from the round-robin position on (-> *k_out), builds every alternate with the first
+// step, and orders the alternate's stream behind the main stream and behind whatever still produces the two slots
+int alt_open(vo_ctx* ctx, int kind, FrameSlot& a, FrameSlot& b, const char* who, int* k_out);
+// The context works on the alternate's stream and in its match scratch for the lifetime of the object, whatever leaves the scope
+// (the stream handle changes places with the main one, `mw` is retargeted; no member of a workspace is copied)
+struct AltScope {
+    vo_ctx* c;
+    vo_ctx::AsyncAlt& p;
+    AltScope(vo_ctx* c_, vo_ctx::AsyncAlt& p_) : c(c_), p(p_)
+    {
+        std::swap(c->stream, p.stream);
+        c->mw = &p.mw;
+    }
+    ~AltScope()
+    {
+        c->mw = &c->main_mw;
+        std::swap(c->stream, p.stream);
+    }
+    AltScope(const AltScope&) = delete;
+    AltScope& operator=(const AltScope&) = delete;
+};
+// the step is enqueued: `done` recorded behind it, both slots get the reader, alternate k is busy and is the ticket
+int alt_close(vo_ctx* ctx, int kind, int k, FrameSlot& a, FrameSlot& b, int* ticket_out);
+// _end: VO_OK when the caller's own arguments are fine (args_ok) and `ticket` names an open step of `kind` ...
+int alt_ticket(vo_ctx* ctx, int kind, int ticket, bool args_ok, const char* who);
+// ... which is then closed and waited for
+int alt_wait(vo_ctx* ctx, vo_ctx::AsyncAlt& p);
+void alt_free(vo_ctx* ctx);                      // every alternate of both kinds and the pose streams
