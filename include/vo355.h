@@ -87,6 +87,21 @@ int vo_prefetch_staged_pair(vo_ctx* ctx, int slot, int index, int preprocessed);
 int vo_lookahead_depth(vo_ctx* ctx, int* depth_out);
 /* the caller gives up a look-ahead slot without consuming it (a prediction of the next pair that did not come true) */
 int vo_lookahead_drop(vo_ctx* ctx, int slot);
+/* Sweep groups.  With a hardware queue per stream (GPU_MAX_HW_QUEUES >= engines + 4) every look-ahead pair's kernels are
+ * enqueued when it is submitted.  With fewer queues the library collects up to B submitted pairs whose early stages are
+ * enqueued and runs their aggregation sweeps as ONE launch; a pair's remaining work follows when its group closes: when it
+ * has B members, when anything is about to wait on, read, refill or drop a member's slot (so no call ever sees a half-done
+ * slot), or when the caller says that no further pair follows now (vo_lookahead_flush).  Results do not depend on B.
+ * vo_set_sweep_group: n <= 0 only asks, otherwise B = min(n, VO_MAX_SWEEP_GROUP) from now on (the open group is closed);
+ * returns the size in force (never above the number of engines) or a negative status.  VO_SWEEP_GROUP in the environment
+ * does the same at vo_create.  vo_lookahead_flush closes the open group and returns the size in force as well -- 1 tells a
+ * caller that flushing never matters.  vo_sweep_group_stats: groups closed so far {full, by a consumer, by a flush, by a
+ * change of parameters / engines / geometry} and the members of the open one (instrumentation).  The reference has no
+ * counterpart (it computes one pair per call, stereo_odometer.py:115-117). */
+#define VO_MAX_SWEEP_GROUP 12
+int vo_set_sweep_group(vo_ctx* ctx, int n);
+int vo_lookahead_flush(vo_ctx* ctx);
+int vo_sweep_group_stats(vo_ctx* ctx, int64_t* closed4, int* open_members);
 /* the same from host images -- the caller's decode/ingest step in front of update():
  * copied to pinned staging, uploaded asynchronously on the engine's stream, then as above.  The host
  * buffers are free again when the call returns. */

@@ -37,6 +37,7 @@ SYMBOLS = [
     "vo_mgpu_gather_poses", "vo_mgpu_all_gather_f64", "vo_mgpu_all_reduce_max_f64",
     "vo_bf_knn2_hamming_mutual", "vo_point_clouds_ex", "vo_pose_pair_ex", "vo_pose_pair_begin_ex", "vo_mono_pair_ex",
     "vo_mono_pair_begin_ex", "vo_measure_knn_ex",
+    "vo_set_sweep_group", "vo_lookahead_flush", "vo_sweep_group_stats",
 ]
 
 
@@ -186,6 +187,10 @@ def lib():
         L.vo_mono_pair_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, ci]
         L.vo_mono_pair_begin_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
         L.vo_measure_knn_ex.argtypes = [vp, ci, ci, ci, ci, vp]
+        if hasattr(L, "vo_lookahead_flush"):        # (an older build of the ABI loaded through VO355_LIB for an A/B run has no sweep groups)
+            L.vo_set_sweep_group.argtypes = [vp, ci]
+            L.vo_lookahead_flush.argtypes = [vp]
+            L.vo_sweep_group_stats.argtypes = [vp, vp, vp]
         L.vo_device_count.argtypes = [vp]
         L.vo_mgpu_unique_id.argtypes = [vp]
         L.vo_mgpu_create.argtypes = [ci, ci, ci, vp, vp]
@@ -243,6 +248,31 @@ class Context:
         if rc < 0:
             raise VoError(rc, "vo_set_engines")
         return rc
+
+    def set_sweep_group(self, n=0):
+        """-> how many look-ahead pairs share one aggregation sweep launch (n <= 0 only asks; 1 = every pair on its own)."""
+        if not hasattr(self._lib, "vo_set_sweep_group"):
+            return 1
+        rc = self._lib.vo_set_sweep_group(self._h, int(n))
+        if rc < 0:
+            raise VoError(rc, (self._lib.vo_last_error(self._h) or b"").decode())
+        return rc
+
+    def lookahead_flush(self):
+        """No further look-ahead pair follows now: the pairs the library still collects for a shared sweep are started as they
+        stand.  -> the sweep group size in force."""
+        if not hasattr(self._lib, "vo_lookahead_flush"):
+            return 1
+        rc = self._lib.vo_lookahead_flush(self._h)
+        if rc < 0:
+            raise VoError(rc, (self._lib.vo_last_error(self._h) or b"").decode())
+        return rc
+
+    def sweep_group_stats(self):
+        """-> {"full", "consumer", "flush", "other"}: sweep groups closed so far by cause, and "open": members of the open one."""
+        closed, n_open = np.zeros(4, np.int64), ctypes.c_int(0)
+        self._ck(self._lib.vo_sweep_group_stats(self._h, _p(closed), ctypes.byref(n_open)))
+        return dict(zip(("full", "consumer", "flush", "other"), (int(v) for v in closed)), open=n_open.value)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -468,6 +468,8 @@ int alt_open(vo_ctx* ctx, int kind, FrameSlot& a, FrameSlot& b, const char* who,
         if (int rc = alt_prepare(ctx, kind, (k + i) % n)) return rc;
     // the step runs on the alternate's own stream: order it behind whatever still produces the two slots (look-ahead engines)
     // and behind the main stream's work on them
+    if (int rc = sweep_group_close_for(ctx, a)) return rc;
+    if (int rc = sweep_group_close_for(ctx, b)) return rc;
     const hipStream_t st = ctx->alt(kind, k).stream;
     VO_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     hipError_t e = hipStreamWaitEvent(st, ctx->ev0, 0);

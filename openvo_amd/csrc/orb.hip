@@ -1134,6 +1134,7 @@ extern "C" int vo_orb_detect_and_compute(vo_ctx* ctx, int slot, int nfeatures, i
     if (!f.has_pair) return vo_fail(ctx, VO_E_STATE, "slot %d holds no image", slot);
     if (mask_mode == 1 && !f.has_disp) return vo_fail(ctx, VO_E_STATE, "slot %d holds no disparity for the fused mask", slot);
     VO_HIP(ctx, hipSetDevice(ctx->device));
+    { int rcg = sweep_group_close_for(ctx, f); if (rcg) return rcg; }   // (the slot's look-ahead ORB chain is enqueued when its group closes)
     const int params[4] = { nfeatures, mask_mode, min_disp16, max_disp16 };
     const bool same = !memcmp(params, f.kp_params, sizeof(params));
     const bool prefetched = f.kp_pending && same;

@@ -1555,10 +1555,51 @@ static int ensure_S(vo_ctx* ctx, int vols)
 }
 
 // ---- diagonal sweep (sgbm_diag.inc) ------------------------------------------------------------------------------------
+// The open sweep group of a context (vo_internal.h): what each member contributes to the one launch (its DiagJob, complete
+// when the member's early stages are enqueued) and what its back part needs.  Members share the kernel instance (`launch`:
+// one function per <NP, PAD, NWC>), the strip count and the geometry -- one kernel argument each.
+static_assert(VO_MAX_SWEEP_GROUP == DG_MAXJOBS, "include/vo355.h promises what one sweep launch carries");
+struct SweepGroup {
+    typedef int (*Launch)(vo_ctx*, const DiagJobs&, const SgbmGeom&);
+    struct Member {
+        int engine;
+        FrameSlot* f;
+        int w, h;
+        SgbmGeom g;
+        DiagJob job;
+    };
+    Launch launch = nullptr;
+    int nstrips = 0;
+    int n = 0;
+    Member m[DG_MAXJOBS];
+    // hand-over between sgbm_run and the forward sweep's launch site: want_defer = this run's sweep joins the group instead of
+    // being launched; did_defer = it has (cand* are filled)
+    bool want_defer = false, did_defer = false;
+    Member cand;
+    Launch cand_launch = nullptr;
+    int cand_nstrips = 0;
+};
+
+// one launch for jobs.n pairs on the current stream; ticket counter and strip timeline in job 0's control block
+template <int NP, bool PAD, int NWC, bool REV, bool WTA>
+static int diag_launch_jobs(vo_ctx* ctx, const DiagJobs& jobs, const SgbmGeom& g)
+{
+    constexpr int UW = 4 * NWC, CW = UW + 2;
+    const size_t lds = (size_t)DG_RING * 2 * CW * g.Dp * 2 + (WTA ? (size_t)NWC * 4 * 2 * g.Dp * 2 : 0) + 64 * 4;
+    auto kern = k_sgbm_diag<NP, PAD, NWC, REV, WTA>;
+    if (int rca = lds_allow_big(ctx, (const void*)kern)) return rca;
+    // strips of one pair that can be active at the same time: one image row's worth (+ slack for the hand-over between strips)
+    const int per = ctx->tune_diag_wgs > 0 ? ctx->tune_diag_wgs : div_up(g.W1, UW) + 2;
+    const int wgs = jobs.n * min(jobs.nstrips, per);
+    hipLaunchKernelGGL(kern, dim3(wgs), dim3((NWC + 1) * 64), lds, ctx->stream, jobs, g, jobs.j[0].ctl, ctx->dump, ctx->sw_ctl_words / 2);
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
 template <int NP, bool PAD, int NWC, bool REV, bool WTA>
 static int launch_diag_k(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1, int16_t* sout, int* ctl)
 {
-    constexpr int UW = 4 * NWC, CW = UW + 2;
+    constexpr int UW = 4 * NWC;
     DiagJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     jobs.n = 1;
@@ -1566,12 +1607,14 @@ static int launch_diag_k(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1, int
     // boundary granules of this workspace: [strip][H + 1 rows][NP][48 lanes] x 8 bytes, allocated (and cleared: tags start at
     // 1, no stale granule may match) when first needed or outgrown
     const size_t need = (size_t)jobs.nstrips * (g.H + 1) * DG_GLANES * NP * sizeof(uint64_t);
+    bool cleared = false;
     if (need > ctx->ws->sw_bnd_bytes) {
         if (ctx->ws->sw_bnd) (void)hipFree(ctx->ws->sw_bnd);
         ctx->ws->sw_bnd = nullptr; ctx->ws->sw_bnd_bytes = 0;
         VO_HIP(ctx, hipMalloc((void**)&ctx->ws->sw_bnd, need + 256));
         ctx->ws->sw_bnd_bytes = need;
         VO_HIP(ctx, hipMemsetAsync(ctx->ws->sw_bnd, 0, need, ctx->stream));
+        cleared = true;
     }
     DiagJob& j = jobs.j[0];
     j.C = ctx->ws->C; j.in1 = in1; j.sout = sout; j.bnd = ctx->ws->sw_bnd; j.aux0 = ctx->ws->rec; j.aux1 = ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64;
@@ -1582,18 +1625,25 @@ static int launch_diag_k(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1, int
     j.spin_limit = ctx->tune_spin_limit;
     j.vol_bytes = (uint32_t)(((size_t)g.W1 * g.H + 1) * g.Dp * 2);            // one volume + the dummy row behind C
     j.rec_bytes = (uint32_t)(((size_t)ctx->max_w * ctx->max_h + 64) * 4);
+    j.ctl = ctl;
     if (ctx->fault_sweep > 0 && --ctx->fault_sweep == 0) {   // (only the test-hooks build ever sets it: this launch's strips export
         j.dbg |= 2;                                          //  nothing, so every import misses and gives up after a few polls)
         j.spin_limit = 64;
     }
-    const size_t lds = (size_t)DG_RING * 2 * CW * g.Dp * 2 + (WTA ? (size_t)NWC * 4 * 2 * g.Dp * 2 : 0) + 64 * 4;
-    auto kern = k_sgbm_diag<NP, PAD, NWC, REV, WTA>;
-    if (int rca = lds_allow_big(ctx, (const void*)kern)) return rca;
-    // strips that can be active at the same time: one image row's worth (+ slack for the hand-over between strips)
-    const int wgs = ctx->tune_diag_wgs > 0 ? min(jobs.nstrips, ctx->tune_diag_wgs) : min(jobs.nstrips, div_up(g.W1, UW) + 2);
-    hipLaunchKernelGGL(kern, dim3(wgs), dim3((NWC + 1) * 64), lds, ctx->stream, jobs, g, ctl, ctx->dump, ctx->sw_ctl_words / 2);
-    VO_CHECK_LAUNCH(ctx);
-    return VO_OK;
+    if constexpr (WTA && !REV) {
+        SweepGroup* const G = ctx->grp;
+        if (G && G->want_defer) {
+            // this pair's sweep joins the open group: everything the launch needs of it is in `j`.  The group's launch runs on
+            // another member's stream behind this engine's `mid` event, which must therefore cover the clearing above as well.
+            if (cleared) VO_HIP(ctx, hipEventRecord(ctx->ws_alt[ctx->cur_engine].mid, ctx->stream));
+            G->cand.job = j; G->cand.g = g;
+            G->cand_launch = &diag_launch_jobs<NP, PAD, NWC, REV, WTA>;
+            G->cand_nstrips = jobs.nstrips;
+            G->did_defer = true;
+            return VO_OK;
+        }
+    }
+    return diag_launch_jobs<NP, PAD, NWC, REV, WTA>(ctx, jobs, g);
 }
 
 template <int NP, bool REV, bool WTA>
@@ -1673,7 +1723,7 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
             if (hh && (rc = launch_diag<NP, true, false>(ctx, g, Swe, Srev, ctlA))) return rc;
         }
         {
-            StageTimer t(ctx, VO_T_SGBM_WTA);
+            StageTimer t(ctx, VO_T_SGBM_WTA, ctx->grp && ctx->grp->want_defer ? 0 : 1);     // (a deferred sweep is timed where its group is launched)
             if (!(ctx->tune_diag_dbg & 16) && (rc = launch_diag<NP, false, true>(ctx, g, hh ? Srev : Swe, nullptr, hh ? ctlB : ctlA))) return rc;
         }
         ctx->last_paths = 3;
@@ -1703,6 +1753,7 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
 }
 
 static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const uint8_t* srcR);
+static int sgbm_post(vo_ctx* ctx, FrameSlot& f, int w, int h, const SgbmGeom& g);
 // rows per block of k_sgbm_post_rows: (RB + 2) rows of disp1 (2 bytes per pixel) and disp2 keys (4 bytes) must fit in LDS
 static uint32_t pk_rep_host(int v) { return (uint32_t)(v & 0xFFFF) * 0x00010001u; }
 static int post_rows_per_block(int w) { return std::min(6, (int)(150 * 1024 / ((size_t)w * 6)) - 2); }
@@ -1711,16 +1762,147 @@ static int post_rows_per_block(int w) { return std::min(6, (int)(150 * 1024 / ((
 // one of them must not start before the previous run -- possibly on the other -- has finished.  An event chain orders them on
 // the device without blocking the host.  An engine's own workspace is only ever used on that engine's stream, which is ordered
 // already: no wait, no record (two packets less per pair on the engine's queue).
-int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const uint8_t* srcR)
+static int sgbm_run_done(vo_ctx* ctx)
 {
+    if (ctx->ws == &ctx->main_ws && ctx->ws->done) {
+        VO_HIP(ctx, hipEventRecord(ctx->ws->done, ctx->stream));
+        ctx->ws->done_valid = true;
+    }
+    return VO_OK;
+}
+
+// A run is three parts on one stream.  Front: planes, cost volume, W + E (the engine's `mid` event behind them).  Sweep: the
+// forward diagonal launch.  Back: the post filters (sgbm_post).  A synchronous call and a look-ahead run with group size 1
+// enqueue them back to back.  A look-ahead run with a group size above 1 (MODE_SGBM, the fused schedule) stops behind its
+// front and becomes a member of the open group; sweep_group_close enqueues the rest.
+int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const uint8_t* srcR, bool* deferred)
+{
+    int rc;
+    if (deferred) *deferred = false;
+    // a run on the main stream works in the main workspace: engine 0's member of the open group still needs what is in there
+    if (ctx->cur_engine < 0 && sweep_group_has_engine(ctx, 0) && (rc = sweep_group_close(ctx, VO_GRP_CONSUMER))) return rc;
     const bool shared = ctx->ws == &ctx->main_ws;
     if (shared && ctx->ws->done_valid) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ws->done, 0));
     if (++ctx->sweep_gen_next <= 0) ctx->sweep_gen_next = 1;     // this run's generation: never 0 (FrameSlot::sweep_word)
     f.disp_gen = ctx->sweep_gen_next;
-    int rc = sgbm_run_impl(ctx, f, w, h, srcL, srcR);
-    if (shared && ctx->ws->done) {
-        VO_HIP(ctx, hipEventRecord(ctx->ws->done, ctx->stream));
-        ctx->ws->done_valid = true;
+    const bool defer = deferred && ctx->cur_engine >= 0 && sweep_group_size(ctx) > 1 && ctx->sg.set && ctx->sg.ur < 100 && ctx->sg.mode == 0 &&
+                       ctx->ws_alt[ctx->cur_engine].mid != nullptr;
+    if (defer) {
+        if (!ctx->grp) ctx->grp = new SweepGroup();
+        ctx->grp->want_defer = true;
+        ctx->grp->did_defer = false;
+    }
+    rc = sgbm_run_impl(ctx, f, w, h, srcL, srcR);
+    if (defer) {
+        SweepGroup* const G = ctx->grp;
+        G->want_defer = false;
+        if (!rc && G->did_defer) {
+            G->did_defer = false;
+            // one launch = one kernel instance, one strip count, one geometry: a pair that differs starts a group of its own
+            if (G->n > 0 && (G->n >= DG_MAXJOBS || G->launch != G->cand_launch || G->nstrips != G->cand_nstrips || memcmp(&G->m[0].g, &G->cand.g, sizeof(SgbmGeom))) &&
+                (rc = sweep_group_close(ctx, VO_GRP_OTHER)))
+                return rc;
+            SweepGroup::Member& m = G->m[G->n++];
+            m = G->cand;
+            m.engine = ctx->cur_engine; m.f = &f; m.w = w; m.h = h;
+            G->launch = G->cand_launch; G->nstrips = G->cand_nstrips;
+            f.in_group = true;
+            *deferred = true;
+            return VO_OK;
+        }
+    }
+    if (int rcd = sgbm_run_done(ctx)) return rcd;
+    return rc;
+}
+
+bool sweep_group_has_engine(const vo_ctx* ctx, int engine)
+{
+    if (ctx->grp)
+        for (int i = 0; i < ctx->grp->n; i++)
+            if (ctx->grp->m[i].engine == engine) return true;
+    return false;
+}
+int sweep_group_members(const vo_ctx* ctx) { return ctx->grp ? ctx->grp->n : 0; }
+void sweep_group_free(vo_ctx* ctx) { delete ctx->grp; ctx->grp = nullptr; }
+
+// the context works on a look-ahead engine's stream and in its workspaces until the object goes (the group's members are
+// served one after the other, possibly from inside another engine's scope: everything is put back as it was found)
+struct MemberScope {
+    vo_ctx* c;
+    hipStream_t stream; uint8_t* stage_in; vo_ctx::SgbmWs* ws; OrbWs* orbws; int cur_engine;
+    explicit MemberScope(vo_ctx* ctx) : c(ctx), stream(ctx->stream), stage_in(ctx->stage_in), ws(ctx->ws), orbws(ctx->orbws), cur_engine(ctx->cur_engine) {}
+    void enter(int e)
+    {
+        c->stream = c->la_stream[e]; c->stage_in = c->la_stage[e];
+        c->ws = e == 0 ? &c->main_ws : &c->ws_alt[e]; c->orbws = &c->ws_alt[e].orb; c->cur_engine = e;
+    }
+    ~MemberScope() { c->stream = stream; c->stage_in = stage_in; c->ws = ws; c->orbws = orbws; c->cur_engine = cur_engine; }
+    MemberScope(const MemberScope&) = delete;
+    MemberScope& operator=(const MemberScope&) = delete;
+};
+
+// back part of one member on its engine's stream (the current one): post filters, the ORB chain, the slot's `ready` record
+static int sweep_member_back(vo_ctx* ctx, SweepGroup::Member& m)
+{
+    FrameSlot& f = *m.f;
+    int rc = sgbm_post(ctx, f, m.w, m.h, m.g);
+    if (!rc) rc = sgbm_run_done(ctx);
+    if (!rc && ctx->la_orb) {
+        const int* q = ctx->la_orb_params;
+        rc = orb_slot_enqueue(ctx, f, q[0], q[1], q[2], q[3]);
+        if (!rc) { memcpy(f.kp_params, q, sizeof(f.kp_params)); f.kp_pending = true; }
+    }
+    if (!rc && hipEventRecord(f.ready, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+    return rc;
+}
+
+int sweep_group_close(vo_ctx* ctx, int why)
+{
+    SweepGroup* const G = ctx->grp;
+    if (!G || G->n == 0) return VO_OK;
+    (void)hipSetDevice(ctx->device);
+    const int n = G->n;
+    G->n = 0;                                    // (closed whatever happens below: nothing re-enters with these members)
+    for (int i = 0; i < n; i++) G->m[i].f->in_group = false;
+    ctx->grp_closed[why]++;
+    int rc = VO_OK;
+    {
+        MemberScope scope(ctx);
+        // the member submitted last closes: its stream waits for the others' early stages, carries the launch (its control
+        // block holds the ticket counter: its next front, which clears the block, is ordered behind the launch there) ...
+        SweepGroup::Member& last = G->m[n - 1];
+        scope.enter(last.engine);
+        DiagJobs jobs;
+        memset(&jobs, 0, sizeof(jobs));
+        jobs.n = n; jobs.nstrips = G->nstrips;
+        jobs.j[0] = last.job;
+        for (int i = 0; i + 1 < n && !rc; i++) {
+            jobs.j[i + 1] = G->m[i].job;
+            const vo_ctx::SgbmWs& a = ctx->ws_alt[G->m[i].engine];
+            if (!a.mid_valid || hipStreamWaitEvent(ctx->stream, a.mid, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "sweep group: waiting for a member's early stages failed");
+        }
+        if (!rc) {
+            StageTimer t(ctx, VO_T_SGBM_WTA, n);
+            rc = G->launch(ctx, jobs, last.g);
+        }
+        hipEvent_t const swept = ctx->ws_alt[last.engine].swept;
+        if (!rc && n > 1 && hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+        // ... and every member finishes on its own engine's stream behind it
+        if (!rc) rc = sweep_member_back(ctx, last);
+        for (int i = 0; i + 1 < n && !rc; i++) {
+            scope.enter(G->m[i].engine);
+            if (hipStreamWaitEvent(ctx->stream, swept, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed");
+            if (!rc) rc = sweep_member_back(ctx, G->m[i]);
+        }
+    }
+    if (rc) {
+        // no member's slot may hand anything out (some of them may even be complete: the caller cannot tell which)
+        for (int i = 0; i < n; i++) {
+            FrameSlot& f = *G->m[i].f;
+            f.kp_pending = false; f.has_pair = false; f.has_disp = false;
+            if (f.counted && ctx->inflight > 0) ctx->inflight--;
+            f.counted = false;
+        }
     }
     return rc;
 }
@@ -1805,13 +1987,24 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
         default: rc = launch_agg<8>(ctx, g, plan, vol); break;
     }
     if (rc) return rc;
+    if (ctx->grp && ctx->grp->did_defer) return VO_OK;             // the sweep and the back part follow when the group closes
+    return sgbm_post(ctx, f, w, h, g);
+}
+
+// back part of a run: the sweep's records (or the unfused schedule's disp_tmp) -> f.disp16
+static int sgbm_post(vo_ctx* ctx, FrameSlot& f, int w, int h, const SgbmGeom& g)
+{
+    const SgbmEff& e = ctx->sg;
+    int16_t* const d_disp = f.disp16;
+    const int n = w * h;
+    const bool fused = g.ur < 100;               // the schedule follows from the parameters alone (launch_agg)
     if (!(ctx->tune_diag_dbg & 32)) {
         StageTimer t(ctx, VO_T_SGBM_POST);
         const int newVal = g.invalid16, maxDiff = 16 * e.speckleRange;
         const bool speckle = e.speckleWindow > 0;
         // rows per block of the fused kernel: (RB + 2) rows of disp1 (2 bytes) and disp2 keys (4 bytes) must fit in LDS
         const int rb = post_rows_per_block(w);
-        if (ctx->last_schedule != VO_SCHED_UNFUSED && rb >= 1) {
+        if (fused && rb >= 1) {
             // records of the diagonal sweep -> sub-pixel disp1 + disp2 -> left-right check -> medianBlur(3) -> labelled runs: one launch
             if (int rca = lds_allow_big(ctx, (const void*)k_sgbm_post_rows)) return rca;
             const int* const ctlA = ctx->ws->sw_ctl;
@@ -1820,7 +2013,7 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
                                ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64, g, rb, d_disp, speckle ? 1 : 0, maxDiff, ctx->ws->ccl_label,
                                ctx->ws->ccl_runlen, ctx->ws->ccl_size, ctlA, ctlB, f.sweep_word, f.disp_gen, ctx->d_sweep_errs);
         } else {
-            if (ctx->last_schedule != VO_SCHED_UNFUSED) {
+            if (fused) {
                 // (an image too wide for the fused kernel's LDS rows: the same steps as separate passes over HBM)
                 hipLaunchKernelGGL(k_sgbm_fin, dim3(div_up(g.W1, 256), g.H), dim3(256), 0, ctx->stream, ctx->ws->rec, ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64,
                                    g, ctx->ws->disp_tmp, ctx->ws->ccl_size, ctx->ws->sw_ctl, ctx->ws->sw_ctl + ctx->sw_ctl_words / 2, f.sweep_word, f.disp_gen, ctx->d_sweep_errs);

@@ -25,16 +25,19 @@
 // agent-scope load of the helper wave only; the tag is this launch's sequence number of the workspace, so a granule is
 // valid exactly when its tag matches: no flag, no counter, no wait on the producing side.  The importing helper issues
 // its loads DG_AHEAD rows ahead and re-polls only the rows that had not arrived; a strip thus trails its right
-// neighbour by a few rows.  Every wait is bounded: after `spin_limit` polls (2^22) a wave raises word 1 of the launch's control
-// block and stops waiting, the other waves see the word and stop waiting too: every workgroup terminates, the results of THIS
-// launch are undefined.  k_sgbm_fin then marks the slot the pair fills (FrameSlot::sweep_word): whoever picks up anything
-// computed from that disparity gets VO_E_SWEEP instead.  The word is per launch (k_sgbm_planes of the workspace's next run
-// clears it): the next pair is exact again.
+// neighbour by a few rows.  Every wait is bounded: after `spin_limit` polls (2^22) a wave raises word 1 of ITS PAIR's control
+// block (DiagJob::ctl) and stops waiting, the pair's other waves see the word and stop waiting too: every workgroup terminates,
+// the results of THIS pair are undefined.  k_sgbm_fin then marks the slot the pair fills (FrameSlot::sweep_word): whoever picks
+// up anything computed from that disparity gets VO_E_SWEEP instead.  The word is per pair and per run (k_sgbm_planes of the
+// workspace's next run clears it; a strip only ever waits for strips of its own pair, so the other pairs of a launch lose
+// nothing): the next pair is exact again.
 //
 // Scheduling.  Workgroups are persistent: each takes (pair, strip) work items off a ticket counter, right-most strip
 // first, so a strip only ever waits for a strip that a running (or finished) workgroup has already taken -- no wait
-// depends on dispatch order or residency.  One launch can carry several queued pairs (DiagJobs): occupancy then no
-// longer depends on the number of streams.
+// depends on dispatch order or residency.  One launch can carry several queued pairs (DiagJobs; the look-ahead path's sweep
+// groups, sgbm.hip): occupancy then no longer depends on the number of streams.  Tickets run through the pairs first -- ticket
+// t is strip t / n from the right of pair t % n -- so the pairs advance side by side and the launch takes about as long as one
+// pair's.  The ticket counter and the strip timeline (pair 0's) live in the control block the launch is given.
 //
 // HBM traffic of the pass in units of one volume: C read once, the input volume read once, + 6 / UW for the boundary
 // granules (3 records of 2 x 2 bytes per cell, written and read) -- against one read of C per direction and a write +
@@ -65,6 +68,7 @@ struct DiagJob {
     int spin_limit;        // polls before a wait is declared dead (vo_ctx::tune_spin_limit)
     uint32_t vol_bytes;    // bytes of one volume + one more pixel's cells (behind C: the dummy row holding P2, k_sgbm_planes)
     uint32_t rec_bytes;    // bytes of one record array (64 spare words included)
+    int* ctl;              // this pair's own control block: word 1 = its sticky give-up flag (the pair's post kernel reads it)
 };
 
 // buffer addressing for the sweep's streams: a descriptor (scalar registers) + one 32-bit byte offset per lane -- no 64-bit
@@ -274,9 +278,9 @@ __device__ __forceinline__ void dg_helper(const DiagJob& job, const SgbmGeom& g,
     bool dead = false;
     auto give_up = [&]() -> bool {
         if (++spins > job.spin_limit ||
-            ((spins & 255) == 0 && __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))) {
-            dead = true;                           // (or somebody else did): never wait again
-            if (lane == 0) atomicExch(ctl + 1, 1);
+            ((spins & 255) == 0 && __builtin_amdgcn_readfirstlane(__hip_atomic_load(job.ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))) {
+            dead = true;                           // (or somebody else of this pair did): never wait again
+            if (lane == 0) atomicExch(job.ctl + 1, 1);
             W[1] = 1;
         }
         return dead;
@@ -536,7 +540,7 @@ __device__ __forceinline__ void dg_strip(const DiagJob& job, const SgbmGeom& g, 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         finish_record();
     }
-    if (__builtin_amdgcn_readfirstlane(*(lds_vint*)(W + 4 + NWC + wv)) && lane == 0) atomicExch(ctl + 1, 1);   // this wave gave up a wait
+    if (__builtin_amdgcn_readfirstlane(*(lds_vint*)(W + 4 + NWC + wv)) && lane == 0) atomicExch(job.ctl + 1, 1);   // this wave gave up a wait
 }
 
 // persistent workgroups: (pair, strip) work items off a ticket counter, right-most strip of a pair first
@@ -555,7 +559,9 @@ __global__ void __launch_bounds__((NWC + 1) * 64, NP <= 4 ? 4 : 2) k_sgbm_diag(D
         __syncthreads();
         const int t = __builtin_amdgcn_readfirstlane(words[0]);
         if (t >= total) return;
-        const int pair = t / jobs.nstrips, strip = jobs.nstrips - 1 - (t - pair * jobs.nstrips);
+        // pairs interleaved: the n pairs of a launch advance side by side, each over its own right-most strips first (a strip
+        // still only waits for strips of its own pair with lower tickets)
+        const int k = t / jobs.n, pair = t - k * jobs.n, strip = jobs.nstrips - 1 - k;
         dg_strip<NP, PAD, NWC, REV, WTA>(jobs.j[pair], g, strip, jobs.nstrips, ctl, dump, bufs, scr, words, pair == 0 ? stats_words : 0);
     }
 }

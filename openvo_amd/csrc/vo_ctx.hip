@@ -234,6 +234,9 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         ctx->engines_fit = fit < 2 ? 2 : fit;
         if (ctx->n_engines > ctx->engines_fit) ctx->n_engines = ctx->engines_fit;
     }
+    // the hardware queues this process may open decide whether the look-ahead pairs' sweeps are grouped (sweep_group_size)
+    if (const char* eq = getenv("GPU_MAX_HW_QUEUES")) { int v = atoi(eq); if (v >= 1) ctx->hw_queues = v; }
+    if (const char* eg = getenv("VO_SWEEP_GROUP")) { int v = atoi(eg); if (v >= 1 && v <= VO_MAX_SWEEP_GROUP) ctx->sweep_group_req = v; }
     if (const char* e9 = getenv("VO_POSE_STREAMS")) { int v = atoi(e9); if (v >= 1 && v <= vo_ctx::N_POSE_STREAMS) ctx->n_pose_streams = v; }
     if (const char* e27 = getenv("VO_STAGGER")) ctx->tune_stagger = atoi(e27);
     if (const char* e25 = getenv("VO_DIAG_WAVES")) { const int v = atoi(e25); ctx->tune_diag_nwc = (v == 7 || v == 11 || v == 15) ? v : 0; }   // the three strip widths that are built
@@ -254,6 +257,8 @@ extern "C" void vo_destroy(vo_ctx* ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    (void)sweep_group_close(ctx, VO_GRP_OTHER);      // (its members' slots are mid-run: finished like any other work in flight)
+    sweep_group_free(ctx);
     if (ctx->stage_thread.joinable()) {
         { std::lock_guard<std::mutex> lk(ctx->stage_mu); ctx->stage_stop = true; }
         ctx->stage_cv.notify_all();
@@ -286,6 +291,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
         if (a.pinned) (void)hipHostFree(a.pinned);
         if (a.h2d_done) (void)hipEventDestroy(a.h2d_done);
         if (a.mid) (void)hipEventDestroy(a.mid);
+        if (a.swept) (void)hipEventDestroy(a.swept);
         if (ctx->la_stream[k]) (void)hipStreamDestroy(ctx->la_stream[k]);
     }
     for (vo_ctx::HostStage& hs : ctx->host_stage) {
@@ -302,12 +308,44 @@ extern "C" int vo_set_engines(vo_ctx* ctx, int n)
 {
     if (!ctx) return VO_E_ARG;
     if (n > 0) {
+        if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;
         if (n > vo_ctx::MAX_ENGINES) n = vo_ctx::MAX_ENGINES;
         if (n > ctx->engines_fit) n = ctx->engines_fit;
         ctx->n_engines = n;
         ctx->next_engine %= n;          // (the stagger wait and the monocular span index modulo n_engines: nothing else remembers one)
     }
     return ctx->n_engines;
+}
+
+// How many look-ahead pairs share one diagonal sweep launch (see vo_ctx::grp).  n <= 0 only asks; otherwise n (clamped to
+// VO_MAX_SWEEP_GROUP) is the request from now on and the open group is closed.  Returns the size in force.
+extern "C" int vo_set_sweep_group(vo_ctx* ctx, int n)
+{
+    if (!ctx) return VO_E_ARG;
+    if (n > 0) {
+        if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;
+        ctx->sweep_group_req = n > VO_MAX_SWEEP_GROUP ? VO_MAX_SWEEP_GROUP : n;
+    }
+    return sweep_group_size(ctx);
+}
+
+// no further look-ahead pair follows now: the open group, if any, is swept as it stands
+extern "C" int vo_lookahead_flush(vo_ctx* ctx)
+{
+    if (!ctx) return VO_E_ARG;
+    if (sweep_group_members(ctx) > 0) {
+        VO_HIP(ctx, hipSetDevice(ctx->device));
+        if (int rc = sweep_group_close(ctx, VO_GRP_FLUSH)) return rc;
+    }
+    return sweep_group_size(ctx);
+}
+
+extern "C" int vo_sweep_group_stats(vo_ctx* ctx, int64_t* closed4, int* open_members)
+{
+    if (!ctx || !closed4) return vo_fail(ctx, VO_E_ARG, "vo_sweep_group_stats: bad argument");
+    for (int i = 0; i < 4; i++) closed4[i] = ctx->grp_closed[i];
+    if (open_members) *open_members = sweep_group_members(ctx);
+    return VO_OK;
 }
 
 extern "C" int vo_device_name(const vo_ctx* ctx, char* buf, int buflen)
@@ -320,6 +358,7 @@ extern "C" int vo_device_name(const vo_ctx* ctx, char* buf, int buflen)
 extern "C" int vo_synchronize(vo_ctx* ctx)
 {
     if (!ctx) return VO_E_ARG;
+    if (int rc = sweep_group_close(ctx, VO_GRP_CONSUMER)) return rc;
     for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
         if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
     for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
@@ -349,6 +388,7 @@ extern "C" int vo_set_sgbm(vo_ctx* ctx, int minDisparity, int numDisparities, in
     if (numDisparities <= 0 || numDisparities % 16) return vo_fail(ctx, VO_E_ARG, "numDisparities must be a positive multiple of 16");
     if (numDisparities > ctx->max_disp) return vo_fail(ctx, VO_E_CAP, "numDisparities %d > max_disp %d", numDisparities, ctx->max_disp);
     if (mode != 0 && mode != 1) return vo_fail(ctx, VO_E_ARG, "mode must be 0 (MODE_SGBM) or 1 (MODE_HH)");
+    if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;     // its members finish under the parameters they began with
     // effective parameters exactly as computeDisparitySGBM derives them
     SgbmEff& e = ctx->sg;
     e.minD = minDisparity; e.D = numDisparities; e.maxD = minDisparity + numDisparities;
@@ -387,6 +427,7 @@ extern "C" int vo_set_roi(vo_ctx* ctx, int x0, int y0, int x1, int y1)
 {
     if (!ctx) return VO_E_ARG;
     if (x0 < 0 || y0 < 0) return vo_fail(ctx, VO_E_ARG, "negative ROI origin is not supported");
+    if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;
     ctx->roi[0] = x0; ctx->roi[1] = y0; ctx->roi[2] = x1; ctx->roi[3] = y1;
     ctx->has_roi = true;
     return VO_OK;
@@ -560,16 +601,17 @@ extern "C" int vo_load_staged_pair(vo_ctx* ctx, int slot, int index, int preproc
     return VO_OK;
 }
 
-// Retargets the context at a look-ahead engine for the lifetime of the object: its stream and staging buffer change places
-// with the main ones, `ws` / `orbws` point at the engine's SGBM workspace (engine 0: the main one) and ORB scratch.  No member
+// Retargets the context at a look-ahead engine for the lifetime of the object: its stream stands in for the main one, its staging
+// buffer changes places with the main one, `ws` / `orbws` point at the engine's SGBM workspace (engine 0: the main one) and ORB scratch.  No member
 // of any workspace is copied or swapped.  Whatever path leaves the scope -- a status funnelled through rc or an early return of
 // a VO_HIP check added later -- the context comes back pointing at its own.
 struct EngineScope {
     vo_ctx* ctx;
     int engine;
-    EngineScope(vo_ctx* c, int e) : ctx(c), engine(e)
+    hipStream_t stream0;
+    EngineScope(vo_ctx* c, int e) : ctx(c), engine(e), stream0(c->stream)
     {
-        std::swap(ctx->stream, ctx->la_stream[engine]);
+        ctx->stream = ctx->la_stream[engine];
         std::swap(ctx->stage_in, ctx->la_stage[engine]);
         ctx->ws = engine == 0 ? &ctx->main_ws : &ctx->ws_alt[engine];
         ctx->orbws = &ctx->ws_alt[engine].orb;
@@ -581,7 +623,7 @@ struct EngineScope {
         ctx->ws = &ctx->main_ws;
         ctx->orbws = &ctx->main_ws.orb;
         std::swap(ctx->stage_in, ctx->la_stage[engine]);
-        std::swap(ctx->stream, ctx->la_stream[engine]);
+        ctx->stream = stream0;
     }
     EngineScope(const EngineScope&) = delete;
     EngineScope& operator=(const EngineScope&) = delete;
@@ -589,9 +631,12 @@ struct EngineScope {
 
 static int engine_prepare(vo_ctx* ctx, int engine)
 {
-    if (!ctx->la_stream[engine]) {
-        VO_HIP(ctx, hipStreamCreateWithFlags(&ctx->la_stream[engine], hipStreamNonBlocking));
+    if (!ctx->la_stream[engine]) VO_HIP(ctx, hipStreamCreateWithFlags(&ctx->la_stream[engine], hipStreamNonBlocking));
+    if (!ctx->ws_alt[engine].mid) {
         VO_HIP(ctx, hipEventCreateWithFlags(&ctx->ws_alt[engine].mid, hipEventDisableTiming));
+        VO_HIP(ctx, hipEventCreateWithFlags(&ctx->ws_alt[engine].swept, hipEventDisableTiming));
+    }
+    if (!ctx->la_stage[engine]) {
         VO_HIP(ctx, hipMalloc((void**)&ctx->la_stage[engine], ctx->stage_bytes * 2 + 256));
         if (orb_ws_alloc(ctx, ctx->ws_alt[engine].orb)) return vo_fail(ctx, VO_E_HIP, "hipMalloc failed (look-ahead ORB workspace)");
     }
@@ -603,6 +648,7 @@ static int engine_prepare(vo_ctx* ctx, int engine)
 
 int slot_wait(vo_ctx* ctx, FrameSlot& f)
 {
+    if (int rc = sweep_group_close_for(ctx, f)) return rc;       // (`ready` is recorded for this run only once its group has closed)
     if (f.pending) {
         VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, f.ready, 0));
         f.pending = false;
@@ -618,6 +664,7 @@ extern "C" int vo_lookahead_drop(vo_ctx* ctx, int slot)
 {
     if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS) return vo_fail(ctx, VO_E_ARG, "vo_lookahead_drop: bad slot");
     FrameSlot& f = ctx->slots[slot];
+    if (int rc = sweep_group_close_for(ctx, f)) return rc;
     if (f.pending && f.counted && ctx->inflight > 0) ctx->inflight--;
     f.counted = false;
     return VO_OK;
@@ -627,6 +674,7 @@ int slot_before_overwrite(vo_ctx* ctx, FrameSlot& f)
 {
     // an earlier look-ahead run into this slot that nobody waited for (a voided prediction) may still be writing it on
     // another engine's stream, and pose steps started ahead may still be reading it on theirs
+    if (int rc = sweep_group_close_for(ctx, f)) return rc;
     if (f.pending) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, f.ready, 0));
     for (hipEvent_t& r : f.readers)
         if (r) { VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, r, 0)); r = nullptr; }
@@ -656,6 +704,10 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
     FrameSlot& f = ctx->slots[slot];
     const int engine = ctx->next_engine;
     if ((rc = engine_prepare(ctx, engine))) return rc;
+    // an engine holds one member of the open group at a time (this pair's front would land on its stream ahead of that member's
+    // back part and reuse its workspace), and a slot that is a member is not refilled before its run is complete
+    if ((f.in_group || sweep_group_has_engine(ctx, engine)) && (rc = sweep_group_close(ctx, f.in_group ? VO_GRP_CONSUMER : VO_GRP_OTHER))) return rc;
+    bool deferred = false;
     const size_t per = (size_t)w * h * channels;
     hipMemcpyKind kind = hipMemcpyDeviceToDevice;
     if (hs) {
@@ -706,13 +758,13 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
         if (!rc && ctx->fault_prefetch > 0 && --ctx->fault_prefetch == 0)
             rc = vo_fail(ctx, VO_E_STATE, "injected failure (VO_FAULT_PREFETCH) inside the engine scope");
 #endif
-        if (!rc) rc = in_place ? sgbm_run(ctx, f, w, h, srcL, srcR) : sgbm_run(ctx, f, w, h);
-        if (!rc && ctx->la_orb) {
+        if (!rc) rc = in_place ? sgbm_run(ctx, f, w, h, srcL, srcR, &deferred) : sgbm_run(ctx, f, w, h, nullptr, nullptr, &deferred);
+        if (!rc && !deferred && ctx->la_orb) {
             const int* q = ctx->la_orb_params;
             rc = orb_slot_enqueue(ctx, f, q[0], q[1], q[2], q[3]);
             if (!rc) { memcpy(f.kp_params, q, sizeof(f.kp_params)); f.kp_pending = true; }
         }
-        if (!rc && hipEventRecord(f.ready, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+        if (!rc && !deferred && hipEventRecord(f.ready, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
     }
     if (rc) {
         // the slot holds a half-processed pair: nothing in it may be handed out
@@ -724,6 +776,8 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
     f.has_pair = true; f.has_disp = true;
     if (!f.counted) ctx->inflight++;
     f.pending = true; f.counted = true;
+    // (a member of the open group: the sweep, the post filters, the ORB chain and `ready` follow when the group closes)
+    if (deferred && sweep_group_members(ctx) >= sweep_group_size(ctx)) return sweep_group_close(ctx, VO_GRP_FULL);
     return VO_OK;
 }
 
@@ -756,6 +810,7 @@ extern "C" int vo_prefetch_staged_mono(vo_ctx* ctx, int slot, int index, int nfe
     const int span = ctx->n_engines < 4 ? ctx->n_engines : 4;
     const int engine = ctx->mono_engine % span;
     if ((rc = engine_prepare(ctx, engine))) return rc;
+    if ((f.in_group || sweep_group_has_engine(ctx, engine)) && (rc = sweep_group_close(ctx, f.in_group ? VO_GRP_CONSUMER : VO_GRP_OTHER))) return rc;
     ctx->mono_engine = (engine + 1) % span;
     const size_t per = (size_t)ctx->staged_w * ctx->staged_h * ctx->staged_ch;
     const int w = ctx->staged_w, h = ctx->staged_h;
@@ -937,6 +992,7 @@ extern "C" int vo_set_lookahead_orb(vo_ctx* ctx, int enable, int nfeatures, int 
         if (nfeatures < 0 || nfeatures > ctx->max_kp) return vo_fail(ctx, VO_E_CAP, "nfeatures %d exceeds max_kp %d", nfeatures, ctx->max_kp);
         if (mask_mode != 0 && mask_mode != 1) return vo_fail(ctx, VO_E_ARG, "mask_mode must be 0 or 1");
     }
+    if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;     // its members' ORB chains run with the parameters they were submitted under
     ctx->la_orb = enable != 0;
     ctx->la_orb_params[0] = nfeatures; ctx->la_orb_params[1] = mask_mode;
     ctx->la_orb_params[2] = min_disp16; ctx->la_orb_params[3] = max_disp16;
@@ -1095,15 +1151,15 @@ static void resolve_events(vo_ctx* ctx)
         float ms = 0;
         if (hipEventElapsedTime(&ms, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]) == hipSuccess) {
             ctx->t_ms[ctx->ev_stage[i]] += ms;
-            ctx->t_n[ctx->ev_stage[i]] += 1;
+            ctx->t_n[ctx->ev_stage[i]] += ctx->ev_entries[i];
         }
     }
     ctx->ev_used = 0;
 }
 
-StageTimer::StageTimer(vo_ctx* ctx, int s) : c(ctx), stage(s), idx(-1)
+StageTimer::StageTimer(vo_ctx* ctx, int s, int entries) : c(ctx), stage(s), idx(-1)
 {
-    if (!c->timing || !((c->timing_mask >> s) & 1u)) return;
+    if (!c->timing || !((c->timing_mask >> s) & 1u) || entries <= 0) return;
     if (c->ev_used * 2 + 2 > c->ev_pool.size()) {
         if (c->ev_pool.size() >= 32768) resolve_events(c);
         else
@@ -1111,8 +1167,9 @@ StageTimer::StageTimer(vo_ctx* ctx, int s) : c(ctx), stage(s), idx(-1)
     }
     if (c->ev_used * 2 + 2 > c->ev_pool.size()) return;
     idx = (long)c->ev_used++;
-    if (c->ev_stage.size() <= (size_t)idx) c->ev_stage.resize(idx + 1);
+    if (c->ev_stage.size() <= (size_t)idx) { c->ev_stage.resize(idx + 1); c->ev_entries.resize(idx + 1); }
     c->ev_stage[idx] = s;
+    c->ev_entries[idx] = entries;
     (void)hipEventRecord(c->ev_pool[2 * idx], c->stream);
 }
 StageTimer::~StageTimer()
@@ -1256,6 +1313,7 @@ extern "C" int vo_slot_ready(vo_ctx* ctx, int slot, int* ready_out)
     if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS || !ready_out) return vo_fail(ctx, VO_E_ARG, "vo_slot_ready: bad argument");
     FrameSlot& f = ctx->slots[slot];
     *ready_out = 1;
+    if (int rc = sweep_group_close_for(ctx, f)) return rc;           // (enqueues the rest of the slot's run: still no wait)
     if (f.pending) {
         const hipError_t e = hipEventQuery(f.ready);
         if (e == hipErrorNotReady) *ready_out = 0;

@@ -61,6 +61,10 @@ struct FrameSlot {
     int32_t* sweep_word = nullptr;
     int32_t disp_gen = 0;
     int kp_params[4] = {0, 0, 0, 0};   // nfeatures, mask_mode, min_disp16, max_disp16 of the pending run
+    // the slot's look-ahead run is a member of the context's open sweep group: its diagonal sweep, post filters and ORB chain are
+    // not enqueued and `ready` is NOT recorded for this run yet -- whoever is about to wait on, read, refill or drop the slot
+    // closes the group first (sweep_group_close_for)
+    bool in_group = false;
 };
 
 // scratch of one ORB run (pyramids, candidate lists, counters); one per look-ahead engine
@@ -110,6 +114,7 @@ struct vo_ctx {
         bool h2d_valid = false;
         hipEvent_t mid = nullptr;        // the early stages (cost volume, W + E) of the engine's latest pair have finished
         bool mid_valid = false;
+        hipEvent_t swept = nullptr;      // the sweep launch of the latest group this engine closed has finished
     } ws_alt[MAX_ENGINES];           // [0]: only its ORB scratch / staging / events are used (engine 0 works in main_ws)
     SgbmWs main_ws;
     SgbmWs* ws = &main_ws;
@@ -123,8 +128,17 @@ struct vo_ctx {
     int tune_spin_limit = 1 << 22;   // polls before a wait inside the diagonal sweep is declared dead
     int fault_sweep = 0;             // VO_FAULT_SWEEP=n (VO_TEST_HOOKS builds only): the n-th diagonal sweep exports nothing and gives up after a few polls
     int engines_fit = 24;            // what 40 % of the device's free memory held at vo_create (vo_set_engines clamps to it)
-    int n_engines = 16;              // VO_ENGINES (needs GPU_MAX_HW_QUEUES >= engines + 4: streams sharing a hardware queue serialise)
+    int n_engines = 16;              // VO_ENGINES (wants GPU_MAX_HW_QUEUES >= engines + 4: streams sharing a hardware queue serialise; with fewer the sweeps are grouped, see grp)
     int next_engine = 0;
+    // Sweep groups (sgbm.hip): with fewer hardware queues than streams a pair's kernels queue up behind other pairs' on the same
+    // queue, and the diagonal sweep -- a latency chain that keeps ~28 CUs busy for a millisecond -- is the longest of them.  The
+    // look-ahead path then collects up to B pairs whose early stages are enqueued (the open group) and sweeps them in ONE launch.
+    // hw_queues: GPU_MAX_HW_QUEUES as the process sees it (unset: HIP's 4).  sweep_group_req: VO_SWEEP_GROUP / vo_set_sweep_group,
+    // 0 = follow the queue budget (sweep_group_size).  grp_closed: groups closed so far, by cause (VO_GRP_*).
+    int hw_queues = 4;
+    int sweep_group_req = 0;
+    struct SweepGroup* grp = nullptr;
+    int64_t grp_closed[4] = {0, 0, 0, 0};
     int max_w = 0, max_h = 0, max_disp = 0, max_kp = 0, kp_cap = 0;
     std::string err;
     char devname[256] = {0};
@@ -270,6 +284,7 @@ struct vo_ctx {
     unsigned timing_mask = ~0u;
     std::vector<hipEvent_t> ev_pool;
     std::vector<int> ev_stage;
+    std::vector<int> ev_entries;   // launches' worth of work per bracket (StageTimer)
     size_t ev_used = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double t_ms[VO_T_NSTAGES] = {0};
@@ -289,11 +304,13 @@ int vo_fail(vo_ctx* ctx, int code, const char* fmt, ...);
 
 // hipEvent pair around a stage, recorded on the context stream WITHOUT blocking it; the pairs are
 // resolved in vo_get_timings.
+// `entries`: how many launches' worth of work the bracket holds (a sweep group's one launch carries that many pairs: the
+// stage's time / count stays a per-pair figure).
 struct StageTimer {
     vo_ctx* c;
     int stage;
     long idx;
-    StageTimer(vo_ctx* ctx, int s);
+    StageTimer(vo_ctx* ctx, int s, int entries = 1);
     ~StageTimer();
 };
 
@@ -333,7 +350,27 @@ __global__ void k_ratio_compact(const int32_t* idx, const int32_t* dist, int nq,
 // implemented in the per-stage files
 // f.left, f.right (w x h) -> f.disp16; gives the run its generation.  srcL / srcR (both or neither): the rectified gray pair lies
 // THERE in device memory and f.left / f.right still have to receive their copy (done by the run's first kernel)
-int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL = nullptr, const uint8_t* srcR = nullptr);
+// `deferred` (look-ahead engines only): with a sweep group size above 1 the run may stop behind its early stages and join the
+// open group instead (*deferred = true): the sweep, the post filters, the ORB chain and the slot's `ready` record then follow
+// when the group closes.
+int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL = nullptr, const uint8_t* srcR = nullptr, bool* deferred = nullptr);
+// ---- sweep groups (sgbm.hip) ----
+enum { VO_GRP_FULL = 0, VO_GRP_CONSUMER = 1, VO_GRP_FLUSH = 2, VO_GRP_OTHER = 3 };
+// the group size in force: the request if there is one, else 1 with a hardware queue per stream (GPU_MAX_HW_QUEUES >= engines
+// + 4) and VO_SWEEP_GROUP_FEW_QUEUES without; never above the number of engines (an engine holds one member at a time)
+#define VO_SWEEP_GROUP_FEW_QUEUES 12
+static inline int sweep_group_size(const vo_ctx* ctx)
+{
+    int b = ctx->sweep_group_req > 0 ? ctx->sweep_group_req : (ctx->hw_queues >= ctx->n_engines + 4 ? 1 : VO_SWEEP_GROUP_FEW_QUEUES);
+    return b < ctx->n_engines ? b : ctx->n_engines;
+}
+// One sweep launch for the open group's members, then each member's post filters, ORB chain and `ready` record on its own
+// engine's stream.  Nothing to do without an open group.  On failure every member's slot is left holding nothing.
+int sweep_group_close(vo_ctx* ctx, int why);
+bool sweep_group_has_engine(const vo_ctx* ctx, int engine);
+int sweep_group_members(const vo_ctx* ctx);
+void sweep_group_free(vo_ctx* ctx);
+static inline int sweep_group_close_for(vo_ctx* ctx, const FrameSlot& f) { return f.in_group ? sweep_group_close(ctx, VO_GRP_CONSUMER) : VO_OK; }
 // VO_E_SWEEP when the disparity the slot holds comes from a run whose sweep gave up a hand-off.  Only meaningful once the host
 // has waited for work that depends on that run (a stream or event synchronisation).
 int slot_health(vo_ctx* ctx, const FrameSlot& f, int slot);

@@ -352,6 +352,7 @@ class StereoCamera:
             # pair's ORB / matching / pose kernels (only into free slots -- never evict for a guess)
             have = {h[0][0] for h in self._lookahead}
             stop = self._n_staged if self.lookahead_stop is None else min(self._n_staged, int(self.lookahead_stop))
+            started, last = 0, None
             for idx in range(img_left.index + 1, min(img_left.index + 1 + int(self.lookahead), stop)):
                 if idx in have:
                     continue
@@ -362,4 +363,11 @@ class StereoCamera:
                 self._slot_gen[nxt] += 1
                 self._slot_owner[nxt] = _RESERVED
                 self._lookahead.append(((idx, bool(preprocessed)), nxt, shape))
+                started, last = started + 1, idx
+            # the library may hold submitted pairs back to sweep several of them in one launch: after a burst (the cold start) or
+            # the last pair there is to start, none follows soon enough to wait for
+            if started > 1 or (started and last == stop - 1):
+                flush = getattr(self._ctx, "lookahead_flush", None)
+                if flush is not None:
+                    flush()
         return DeviceImage(frame, "xyz"), DeviceImage(frame, "disp"), DeviceImage(frame, "left")

@@ -265,7 +265,9 @@ class StereoOdometer:
         try:
             while True:
                 keep_one_ahead()
+                started = 0
                 while len(queue) <= depth and copying and (len(copying) >= 2 or state["done"]):
+                    started += 1
                     item = copying.popleft()
                     if item[0] is None:
                         queue.append(cam.submit(item[1], item[2], preprocessed=self.preprocessed_frames))
@@ -275,6 +277,12 @@ class StereoOdometer:
                             state["inflight"] = None                     # (submit_staged waits for the copy)
                         queue.append(cam.submit_staged(buf, w, h, ch, self.preprocessed_frames))
                     keep_one_ahead()
+                # (see StereoCamera.compute_3d: after a burst or at the end of the input nothing follows that a held-back pair
+                # could share its sweep launch with)
+                if started > 1 or (started and state["done"] and not copying):
+                    flush = getattr(ctx, "lookahead_flush", None)
+                    if flush is not None:
+                        flush()
                 if not queue:
                     return
                 head = queue.popleft()
