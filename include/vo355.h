@@ -313,6 +313,36 @@ int vo_ransac_pnp(vo_ctx* ctx, const float* pts3d, const float* pts2d, int n, co
                   float thr, uint32_t seed, double* Rt12_out, uint8_t* mask_out, int32_t* counts_out,
                   int32_t* best2_out);
 
+/* Stereo PnP pair step (NOT part of the reference): what StereoOdometer(pose_method="pnp") computes per pair, for two
+ * device-resident slots and with ONE host synchronisation: kNN-2 (+ ratio, + cross-check with VO_MATCH_CROSSCHECK) between the
+ * two slots' descriptors -> 3-D lookup of the matched keypoints in slot_a (as vo_point_clouds) -> compaction of the usable
+ * correspondences (status 0 and all three coordinates finite), pixels = slot_b's keypoint + the ROI origin (float32 add) ->
+ * P3P RANSAC exactly as vo_ransac_pnp on those arrays (bit for bit) -> winner, mask [-> refine_iters (0 .. 20) Gauss-Newton
+ * steps on the winner's inliers].
+ *   counts4 = {M matches after the ratio test (and the cross-check), n usable correspondences, winning hypothesis, its inliers}
+ *   flags   bit 0: a 3-D lookup in slot_a had no usable tap (the reference raises ZeroDivisionError); bit 1: a match index was
+ *           outside the train set -- nothing is read through it and the call returns VO_E_STATE (a refused pair, never a wrong pose)
+ *   Rt12    the winner as vo_ransac_pnp returns it (row-major 3x4); all zeros when n < 4 or no hypothesis produced a pose
+ *   refine2 = {status, steps run}: 0 ok, 1 not requested or not attempted (fewer than 6 inliers), -1 the normal matrix was not
+ *           positive definite or a value was not finite.  Rt12_refined (may be NULL) is valid only for status 0.
+ *   mask_out / q_idx / t_idx (each `cap` >= slot_a's keypoint count entries, may be NULL): inlier flag, query and train keypoint
+ *           index of the n usable correspondences (0 / -1 behind them).
+ * The refinement, in float64: the inlier set is the winner's mask and stays fixed; residual (fx X'/Z' + cx - u, fy Y'/Z' + cy - v)
+ * with X' = R X + t; a step sums J^T J and J^T r (d X'/d(w, v) = [-[X']x | I]) in a fixed order, solves the 6x6 system by
+ * Cholesky and updates R <- Exp(w) R, t <- Exp(w) t + v; exactly refine_iters steps, no early exit: a function of the inputs alone. */
+int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
+/* The same step in two halves, as vo_pose_pair_begin / _end.  The tickets ARE pose tickets: they come from the same
+ * VO_NUM_POSE_ASYNC alternates and run on the same three streams, so that number bounds the open pose and PnP steps together;
+ * a ticket is ended by the _end of the kind that began it (VO_E_STATE otherwise).  want_matches != 0: mask / q / t travel with
+ * the record.  _end checks both slots' disparity health (VO_E_SWEEP) like vo_pose_pair_end and delivers what vo_pnp_pair would
+ * have, bit for bit.  A slot read by an open ticket may be refilled at any time. */
+int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                      uint32_t seed, int refine_iters, int want_matches, int* ticket_out);
+int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                    uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */
@@ -349,7 +379,7 @@ int vo_shader_clock(vo_ctx* ctx, int micros, double* mhz);
 /* health of the diagonal aggregation sweeps (synchronises): *error_out = number of SGBM runs of this context in which a wait
  * between strips exceeded its poll limit (the affected pair's results are refused with VO_E_SWEEP where they are picked up:
  * vo_sgbm_compute with an output pointer, vo_download_disparity_f32 / _xyz, vo_orb_detect_and_compute with the fused mask,
- * vo_points3d_at, vo_point_clouds, vo_pose_pair, vo_pose_pair_end); the count is sticky until vo_destroy, a later pair in
+ * vo_points3d_at, vo_point_clouds, vo_pose_pair, vo_pose_pair_end, vo_pnp_pair, vo_pnp_pair_end); the count is sticky until vo_destroy, a later pair in
  * the same workspace is unaffected */
 int vo_sgbm_sweep_status(vo_ctx* ctx, int* error_out);
 /* development aid: control block `block` (0 | 1) of the latest aggregation sweep in the main workspace -- word 0 = work items

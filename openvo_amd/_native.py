@@ -38,6 +38,7 @@ SYMBOLS = [
     "vo_bf_knn2_hamming_mutual", "vo_point_clouds_ex", "vo_pose_pair_ex", "vo_pose_pair_begin_ex", "vo_mono_pair_ex",
     "vo_mono_pair_begin_ex", "vo_measure_knn_ex",
     "vo_set_sweep_group", "vo_lookahead_flush", "vo_sweep_group_stats",
+    "vo_pnp_pair", "vo_pnp_pair_begin", "vo_pnp_pair_end",
 ]
 
 
@@ -187,6 +188,10 @@ def lib():
         L.vo_mono_pair_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, ci]
         L.vo_mono_pair_begin_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
         L.vo_measure_knn_ex.argtypes = [vp, ci, ci, ci, ci, vp]
+        if hasattr(L, "vo_pnp_pair"):               # (likewise: an older build has no fused PnP step)
+            L.vo_pnp_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
+            L.vo_pnp_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
+            L.vo_pnp_pair_end.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
         if hasattr(L, "vo_lookahead_flush"):        # (an older build of the ABI loaded through VO355_LIB for an A/B run has no sweep groups)
             L.vo_set_sweep_group.argtypes = [vp, ci]
             L.vo_lookahead_flush.argtypes = [vp]
@@ -683,6 +688,50 @@ class Context:
         self._ck(self._lib.vo_ransac_pnp(self._h, _p(pts3d), _p(pts2d), n, _p(K4), int(iters), float(thr), int(seed),
                                          _p(Rt), _p(mask), _p(counts), _p(best)))
         return dict(Rt=Rt.reshape(3, 4), mask=mask, counts=counts, best_iter=int(best[0]), best_count=int(best[1]))
+
+    def _pnp_out(self, want_matches):
+        """the output arrays of the PnP pair entries, in the order they take them (mask / q / t: one set per context, reused)"""
+        head = [np.zeros(4, np.int32), np.zeros(1, np.int32), np.zeros(12, np.float64), np.zeros(12, np.float64), np.zeros(2, np.int32)]
+        arrays = [None, None, None]
+        if want_matches:
+            arrays = self.__dict__.get("_pnp_arrays")
+            if arrays is None or len(arrays[0]) != self.kp_cap:
+                arrays = self._pnp_arrays = [np.empty(self.kp_cap, np.uint8), np.empty(self.kp_cap, np.int32), np.empty(self.kp_cap, np.int32)]
+        return head, arrays
+
+    @staticmethod
+    def _pnp_result(head, arrays):
+        c4, fl, Rt, Rtr, r2 = head
+        n = int(c4[1])
+        out = dict(matches=int(c4[0]), n=n, best_iter=int(c4[2]), best_count=int(c4[3]), flags=int(fl[0]), Rt=Rt.reshape(3, 4),
+                   Rt_refined=Rtr.reshape(3, 4), refine_status=int(r2[0]), refine_steps=int(r2[1]))
+        if arrays[0] is not None:
+            out.update(mask=arrays[0][:n].copy(), q=arrays[1][:n].copy(), t=arrays[2][:n].copy())
+        return out
+
+    def pnp_pair(self, slot_a, slot_b, ratio, K4, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False, cross_check=False):
+        """kNN-2 + ratio (+ cross-check) + 3-D lookup in slot_a + P3P RANSAC (+ `refine` Gauss-Newton steps on the winner's inliers)
+        for two slots, all on the device, one synchronisation (vo_pnp_pair).  -> dict(matches M, n usable correspondences,
+        best_iter, best_count, flags, Rt 3x4, Rt_refined 3x4 (valid when refine_status == 0), refine_status, refine_steps
+        [, mask, q, t of length n])."""
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        head, arrays = self._pnp_out(want_matches)
+        self._ck(self._lib.vo_pnp_pair(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+                                       int(seed) & 0xFFFFFFFF, int(refine), *[_p(a) for a in head + arrays], self.kp_cap))
+        return self._pnp_result(head, arrays)
+
+    def pnp_pair_begin(self, slot_a, slot_b, ratio, K4, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False, cross_check=False):
+        """pnp_pair in two halves -> a ticket for pnp_pair_end (a pose ticket: VO_NUM_POSE_ASYNC bounds both kinds together)."""
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        t = ctypes.c_int(-1)
+        self._ck(self._lib.vo_pnp_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+                                             int(seed) & 0xFFFFFFFF, int(refine), int(bool(want_matches)), ctypes.byref(t)))
+        return t.value
+
+    def pnp_pair_end(self, ticket, want_matches=False):
+        head, arrays = self._pnp_out(want_matches)
+        self._ck(self._lib.vo_pnp_pair_end(self._h, int(ticket), *[_p(a) for a in head + arrays], self.kp_cap))
+        return self._pnp_result(head, arrays)
 
     def umeyama(self, src, dst, force_rotation=True):
         src, dst = _c(src, np.float32).reshape(-1, 3), _c(dst, np.float32).reshape(-1, 3)

@@ -760,21 +760,6 @@ __device__ __forceinline__ int wave_sum_i32_dpp(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-// float64 wave sum on DPP moves (two per step); every lane of the result is NOT valid -- lane 63 is, and it is broadcast
-__device__ __forceinline__ double wave_sum_f64_dpp(double v)
-{
-#define DPP_ADD64(ctrl, rmask)                                                                             \
-    {                                                                                                      \
-        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rmask, 0xf, false);         \
-        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, rmask, 0xf, false);         \
-        v += __hiloint2double(hi, lo);                                                                     \
-    }
-    DPP_ADD64(0x111, 0xf) DPP_ADD64(0x112, 0xf) DPP_ADD64(0x114, 0xf) DPP_ADD64(0x118, 0xf)
-    DPP_ADD64(0x142, 0xa) DPP_ADD64(0x143, 0xc)
-#undef DPP_ADD64
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-
 // register-resident greedy clique (m <= 64 * KREG <= 512), one wave: lane holds elements j = lane + 64 k; the clique and
 // the set of nodes adjacent to every member are K-bit masks per lane.  A node stays in that set exactly when it is
 // adjacent to the member just added, so one byte per (row, lane) -- the row's bits for this lane's K elements, laid out
@@ -1467,6 +1452,7 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
+    p.pnp = false;
     return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }
 
@@ -1481,6 +1467,7 @@ extern "C" int vo_pose_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32
     int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && rc2 && T2_12, "vo_pose_pair_end");
     if (rc) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
+    if (p.pnp) return vo_fail(ctx, VO_E_STATE, "vo_pose_pair_end: ticket %d belongs to vo_pnp_pair_begin (end it with vo_pnp_pair_end)", ticket);
     if ((rc = alt_wait(ctx, p))) return rc;
     // the step read the disparities the two slots held when it was begun: were those runs healthy?  (a slot refilled since
     // then carries another generation and another word value)
@@ -1493,5 +1480,92 @@ extern "C" int vo_pose_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32
                                             "disparity is undefined and no pose is derived from it", ticket, slots[i]);
     }
     pose_unpack(p.result, counts4, rc2, T1_12, T2_12);
+    return VO_OK;
+}
+
+// First half of the stereo PnP step (vo_pnp_pair) in ONE block, modelled on k_pose_prep: wave 0 runs the ratio test (+ cross-check)
+// with ordered compaction -> M matches (mq, mt); then the whole block looks up the 3-D position of every matched keypoint of
+// slot a (bilinear_one: the arithmetic of vo_point_clouds) and compacts, again in match order, the usable correspondences --
+// status 0, all three coordinates finite -- into X (3-D, frame a) and uv (pixel of slot b's keypoint + the ROI origin, a float32
+// add) with their keypoint indices (q2, t2).  A match index outside [0, nt_range) sets flag bit 1 and nothing is read through it
+// (nt_range = nt, the train set's size, except when the test-only build narrows it to reach this path).  hdr = {M, n, flags}.
+template <bool CROSS>
+__global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ idx, const int32_t* __restrict__ dist, int nq, double ratio,
+                                                  const float* __restrict__ xy_q, const float* __restrict__ xy_t, int nt,
+                                                  int32_t* __restrict__ mq, int32_t* __restrict__ mt, TapDisp ta, int cw, int ch, float x0f,
+                                                  float y0f, int32_t* __restrict__ q2, int32_t* __restrict__ t2, float* __restrict__ X,
+                                                  float* __restrict__ uv, int32_t* __restrict__ hdr, const uint32_t* __restrict__ colmin,
+                                                  int nt_range)
+{
+    __shared__ int s_m, s_flags, s_cnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (wv == 0) {
+        int base = 0, fl = 0;
+        for (int i0 = 0; i0 < nq; i0 += 64) {
+            const int i = i0 + lane;
+            bool keep = false;
+            int t = -1;
+            if (i < nq) {
+                t = idx[2 * i];
+                const double a = (double)(float)dist[2 * i], b = (double)(float)dist[2 * i + 1];
+                keep = idx[2 * i + 1] >= 0 && a < ratio * b;
+                if constexpr (CROSS) keep = keep && knn_mutual(t, i, colmin, nt);
+            }
+            const unsigned long long bal = __ballot(keep);
+            if (__ballot(keep && (t < 0 || t >= nt_range))) fl = 2;
+            if (keep) {
+                const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+                mq[pos] = i; mt[pos] = t;
+            }
+            base += __popcll(bal);
+        }
+        if (lane == 0) { s_m = base; s_flags = fl; }
+    }
+    __syncthreads();
+    const int m = s_m;
+    int n = 0, bad = 0;
+    for (int i0 = 0; i0 < m; i0 += blockDim.x) {
+        const int i = i0 + threadIdx.x;
+        bool use = false;
+        int q = -1, t = -1;
+        float p[3] = { 0.f, 0.f, 0.f };
+        if (i < m) {
+            q = mq[i]; t = mt[i];
+            uint8_t st;
+            bilinear_one(ta, cw, ch, xy_q[2 * q], xy_q[2 * q + 1], p, &st);
+            bad |= st == 2;
+            use = st == 0 && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && t >= 0 && t < nt_range;
+        }
+        const unsigned long long bal = __ballot(use);
+        if (lane == 0) s_cnt[wv] = __popcll(bal);
+        __syncthreads();
+        int off = n;
+        for (int w = 0; w < wv; w++) off += s_cnt[w];
+        if (use) {
+            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+            X[3 * pos] = p[0]; X[3 * pos + 1] = p[1]; X[3 * pos + 2] = p[2];
+            uv[2 * pos] = xy_t[2 * t] + x0f; uv[2 * pos + 1] = xy_t[2 * t + 1] + y0f;
+            q2[pos] = q; t2[pos] = t;
+        }
+        n += (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        __syncthreads();
+    }
+    if (bad) atomicOr(&s_flags, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) { hdr[0] = m; hdr[1] = n; hdr[2] = s_flags; }
+}
+
+int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d)
+{
+    int x0 = 0, y0 = 0, x1 = a.w, y1 = a.h;
+    if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < a.w ? ctx->roi[2] : a.w; y1 = ctx->roi[3] < a.h ? ctx->roi[3] : a.h; }
+    TapDisp ta{ a.disp16, a.w, x0, y0, make_q(ctx->Q) };
+    auto prep = cross ? k_pnp_prep<true> : k_pnp_prep<false>;
+    int nt_range = b.n_kp;
+    if (ctx->fault_pnp_range > 0 && --ctx->fault_pnp_range == 0) nt_range = 1;   // (only the test-hooks build ever sets it)
+    hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, b.n_kp,
+                       ctx->mw->mq_idx, ctx->mw->mt_idx, ta, x1 - x0, y1 - y0, (float)x0, (float)y0, d.q, d.t, d.X, d.uv, d.hdr,
+                       cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, nt_range);
+    VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }

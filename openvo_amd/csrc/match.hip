@@ -432,7 +432,8 @@ static int alt_prepare(vo_ctx* ctx, int kind, int k)
     } else
         e = hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p.done, hipEventDisableTiming);
-    const size_t record = pose ? 1024 : MONO_HDR + (size_t)ctx->kp_cap * (1 + 4 + 4 + 8) + 64;
+    // (a pose alternate serves vo_pose_pair_begin and vo_pnp_pair_begin alike: its record holds a PnpRec with its arrays)
+    const size_t record = pose ? PNP_HDR + pnp_cap(ctx->kp_cap) * 9 + 64 : MONO_HDR + (size_t)ctx->kp_cap * (1 + 4 + 4 + 8) + 64;
     if (e == hipSuccess) e = hipHostMalloc((void**)&p.result, record, hipHostMallocDefault);
     if (e == hipSuccess) e = match_ws_alloc(ctx, p.mw, pose ? MATCH_WS_POSE : 0);
     if (e != hipSuccess) {

@@ -553,6 +553,7 @@ extern "C" int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t
 //                 picks the pose; P = K [R|t] rounded to float32
 //   k_pnp_score   one wave per hypothesis; division-free reprojection test in float32
 //                 ((xc - u zc)^2 + (yc - v zc)^2 < thr^2 zc^2, zc > 0), ballot + popcount
+//   k_pnp_finish  (vo_pnp_pair) one block: winner, its mask, Gauss-Newton refinement on the mask, the record into pinned memory
 // =========================================================================================
 __device__ __forceinline__ double pn_det3(const double m[3][3])
 {
@@ -722,10 +723,20 @@ __device__ int pn_p3p(const double* y, const double* x, double* Rs, double* ts)
 }
 
 __global__ void __launch_bounds__(64) k_pnp_hyp(const float* __restrict__ X, const float* __restrict__ uv, int n, K4 K, int iters,
-                                                uint32_t seed, double* __restrict__ Rt_out, float* __restrict__ P_out)
+                                                uint32_t seed, double* __restrict__ Rt_out, float* __restrict__ P_out,
+                                                const int* __restrict__ n_dev)
 {
     const int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= iters) return;
+    // n_dev (may be NULL): the number of correspondences when only the device knows it (vo_pnp_pair: what k_pnp_prep kept);
+    // fewer than 4 give no pose: an all-zero hypothesis that scores no inlier
+    if (n_dev) {
+        n = *n_dev;
+        if (n < 4) {
+            for (int k = 0; k < 12; k++) { Rt_out[(size_t)h * 12 + k] = 0.0; P_out[(size_t)h * 12 + k] = 0.0f; }
+            return;
+        }
+    }
     int idx[4];
     for (int j = 0; j < 4; j++) {
         uint32_t attempt = 0;
@@ -791,11 +802,13 @@ __device__ __forceinline__ bool reproj_inlier(const float* P, float X, float Y, 
 
 // one wave per hypothesis
 __global__ void __launch_bounds__(256) k_pnp_score(const float* __restrict__ X, const float* __restrict__ uv, int n,
-                                                  const float* __restrict__ P_all, int iters, float thr2, int32_t* __restrict__ counts)
+                                                  const float* __restrict__ P_all, int iters, float thr2, int32_t* __restrict__ counts,
+                                                  const int* __restrict__ n_dev)
 {
     const int lane = threadIdx.x & 63;
     const int h = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (h >= iters) return;
+    if (n_dev) n = *n_dev < 4 ? 0 : *n_dev;
     float P[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) P[k] = P_all[(size_t)h * 12 + k];
@@ -852,8 +865,8 @@ extern "C" int vo_ransac_pnp(vo_ctx* ctx, const float* pts3d, const float* pts2d
     if (rc) return rc;
     const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
     const float thr2 = thr * thr;
-    hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d_X, d_uv, n, K, iters, seed, d_Rt, d_P);
-    hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d_X, d_uv, n, d_P, iters, thr2, d_counts);
+    hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d_X, d_uv, n, K, iters, seed, d_Rt, d_P, nullptr);
+    hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d_X, d_uv, n, d_P, iters, thr2, d_counts, nullptr);
     hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, d_counts, iters, d_best);
     hipLaunchKernelGGL(k_pnp_mask, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_X, d_uv, n, d_P, d_best, thr2, d_mask);
     VO_CHECK_LAUNCH(ctx);
@@ -865,4 +878,360 @@ extern "C" int vo_ransac_pnp(vo_ctx* ctx, const float* pts3d, const float* pts2d
     best2_out[1] = ((int32_t*)ctx->pinned)[1];
     VO_HIP(ctx, hipMemcpy(Rt12_out, d_Rt + (size_t)best2_out[0] * 12, 96, hipMemcpyDeviceToHost));
     return VO_OK;
+}
+
+// =========================================================================================
+// Stereo PnP pair step (vo_pnp_pair / _begin / _end; no openVO counterpart): the keypoints, descriptors and disparity two slots
+// already hold -> kNN-2 -> k_pnp_prep (ratio test, 3-D lookup in slot a, compaction of the usable correspondences) -> k_pnp_hyp ->
+// k_pnp_score -> k_pnp_finish.  Five queue entries, no copy command, ONE host synchronisation; the arithmetic of
+// vo_point_clouds -> host filter -> vo_ransac_pnp value for value (the count n stays on the device: the kernels are launched
+// for the upper bound and read it), plus an optional refinement of the winner on its inliers.
+// =========================================================================================
+
+// One Gauss-Newton step's solve in one lane: H (6x6, symmetric, upper triangle in packed row order) d = -g by Cholesky, every index
+// a compile-time constant so that the factor stays in registers.  false: a pivot was not positive.
+__device__ __forceinline__ bool pn_solve6(const double* Hp, const double* g, double* d)
+{
+    double L[6][6];
+#pragma unroll
+    for (int i = 0, k = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++, k++) L[j][i] = Hp[k];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double s = L[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
+        ok = ok && s > 0.0;
+        const double dj = sqrt(s);
+        L[j][j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = L[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
+            L[i][j] = v / dj;
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double v = -g[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) v -= L[k][i] * d[k];
+        d[i] = v / L[i][i];
+    }
+    return ok;
+}
+
+// Rt <- [Exp(w) R | Exp(w) t + v]   (Rodrigues; the series below 1e-4 rad, where sin / cos lose digits in the quotients)
+__device__ __forceinline__ void pn_apply_twist(double* Rt, const double* d)
+{
+    const double wx = d[0], wy = d[1], wz = d[2];
+    const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
+    double A, B;
+    if (th < 1e-4) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
+    else { A = sin(th) / th; B = (1.0 - cos(th)) / th2; }
+    const double W[9] = { 0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0 };
+    const double w3[3] = { wx, wy, wz };
+    double E[9], out[12];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) E[r * 3 + c] = ((r == c ? 1.0 : 0.0) + A * W[r * 3 + c]) + B * (w3[r] * w3[c] - (r == c ? th2 : 0.0));
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) out[r * 4 + c] = (E[r * 3] * Rt[c] + E[r * 3 + 1] * Rt[4 + c]) + E[r * 3 + 2] * Rt[8 + c];
+    for (int r = 0; r < 3; r++) out[r * 4 + 3] += d[3 + r];
+    for (int k = 0; k < 12; k++) Rt[k] = out[k];
+}
+
+// The end of the step in ONE block of four waves: argmax of the inlier counts (most inliers, then the lowest index: k_ransac_best)
+// -> the winner's mask (k_pnp_mask's arithmetic) -> refine_iters Gauss-Newton steps in float64 on the winner's inliers: residual
+// (fx X'/Z' + cx - u, fy Y'/Z' + cy - v), X' = R X + t, d X' / d (w, v) = [-[X']x | I]; every thread sums its points (i = thread
+// + 256 k, ascending) into the 21 + 6 sums of J^T J and J^T r, a DPP tree sums the wave, lane 0 adds the four waves' values from
+// LDS in wave order and solves -- a fixed order, so the result is a function of the inputs alone; no early exit -> the whole
+// record (and the mask / q / t arrays when `arr` is given) written straight into pinned host memory.
+__global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ counts, int iters, const double* __restrict__ Rt_all,
+                                                    const float* __restrict__ P_all, const float* __restrict__ X, const float* __restrict__ uv,
+                                                    int nq, const int32_t* __restrict__ hdr, const int32_t* __restrict__ q2,
+                                                    const int32_t* __restrict__ t2, float thr2, K4 K, int refine_iters,
+                                                    uint8_t* __restrict__ mask, PnpRec* __restrict__ rec, uint8_t* __restrict__ arr, size_t cap)
+{
+    __shared__ long long s_key[4];
+    __shared__ int s_best[2], s_status;
+    __shared__ double s_pose[12], s_red[4][27];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long key = -1;
+    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
+        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);   // most inliers, then lowest index
+        key = k > key ? k : key;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
+    if (lane == 0) s_key[wv] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; q++) key = s_key[q] > key ? s_key[q] : key;
+        s_best[0] = 0x7fffffff - (int)(key & 0x7fffffffLL);
+        s_best[1] = (int)(key >> 32);
+        s_status = 1;
+    }
+    __syncthreads();
+    const int best = s_best[0], best_count = s_best[1], n = hdr[1], live = n < 4 ? 0 : n;
+    if (threadIdx.x < 12) s_pose[threadIdx.x] = Rt_all[(size_t)best * 12 + threadIdx.x];
+    float P[12];
+    for (int k = 0; k < 12; k++) P[k] = P_all[(size_t)best * 12 + k];
+    for (int i = threadIdx.x; i < nq; i += blockDim.x) {
+        uint8_t in = 0;
+        if (i < live) {
+            const float2 b = ((const float2*)uv)[i];
+            in = reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2) ? 1 : 0;
+        }
+        mask[i] = in;                       // (read back below by the thread that wrote it)
+        if (arr) {
+            arr[i] = in;
+            ((int32_t*)(arr + cap))[i] = i < n ? q2[i] : -1;
+            ((int32_t*)(arr + cap * 5))[i] = i < n ? t2[i] : -1;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        rec->M = hdr[0]; rec->n = n; rec->best_iter = best; rec->best_count = best_count; rec->flags = hdr[2]; rec->pad = 0;
+        for (int k = 0; k < 12; k++) rec->Rt[k] = s_pose[k];
+    }
+    const bool refine = refine_iters > 0 && best_count >= 6;
+    int steps = 0;
+    if (refine) {
+        if (threadIdx.x == 0) s_status = 0;
+        for (; steps < refine_iters; steps++) {
+            double R[12], acc[27];
+#pragma unroll
+            for (int k = 0; k < 12; k++) R[k] = s_pose[k];
+#pragma unroll
+            for (int k = 0; k < 27; k++) acc[k] = 0.0;
+            for (int i = threadIdx.x; i < live; i += blockDim.x) {
+                if (!mask[i]) continue;
+                const double x = (double)X[3 * i], y = (double)X[3 * i + 1], z = (double)X[3 * i + 2];
+                const double xc = ((R[0] * x + R[1] * y) + R[2] * z) + R[3];
+                const double yc = ((R[4] * x + R[5] * y) + R[6] * z) + R[7];
+                const double zc = ((R[8] * x + R[9] * y) + R[10] * z) + R[11];
+                const double iz = 1.0 / zc;
+                const double r[2] = { (K.fx * xc * iz + K.cx) - (double)uv[2 * i], (K.fy * yc * iz + K.cy) - (double)uv[2 * i + 1] };
+                const double a[2][3] = { { K.fx * iz, 0.0, -K.fx * xc * iz * iz }, { 0.0, K.fy * iz, -K.fy * yc * iz * iz } };
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const double j[6] = { a[e][2] * yc - a[e][1] * zc, a[e][0] * zc - a[e][2] * xc, a[e][1] * xc - a[e][0] * yc,
+                                          a[e][0], a[e][1], a[e][2] };
+#pragma unroll
+                    for (int u = 0, k = 0; u < 6; u++)
+#pragma unroll
+                        for (int v = u; v < 6; v++, k++) acc[k] += j[u] * j[v];
+#pragma unroll
+                    for (int u = 0; u < 6; u++) acc[21 + u] += j[u] * r[e];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 27; k++) {
+                const double sum = wave_sum_f64_dpp(acc[k]);
+                if (lane == 0) s_red[wv][k] = sum;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double H[21], g[6], d[6] = { 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+                for (int k = 0; k < 27; k++) {
+                    const double sum = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
+                    if (k < 21) H[k] = sum; else g[k - 21] = sum;
+                }
+                bool ok = true;
+#pragma unroll
+                for (int k = 0; k < 21; k++) ok = ok && isfinite(H[k]);
+#pragma unroll
+                for (int k = 0; k < 6; k++) ok = ok && isfinite(g[k]);
+                ok = ok && pn_solve6(H, g, d);
+                double Rn[12];
+                for (int k = 0; k < 12; k++) Rn[k] = s_pose[k];
+                if (ok) pn_apply_twist(Rn, d);
+                for (int k = 0; k < 12; k++) ok = ok && isfinite(Rn[k]);
+                if (ok) for (int k = 0; k < 12; k++) s_pose[k] = Rn[k];
+                else s_status = -1;
+            }
+            __syncthreads();
+            if (s_status < 0) break;
+        }
+    }
+    if (threadIdx.x == 0) {
+        rec->rstatus = s_status; rec->rsteps = steps;
+        for (int k = 0; k < 12; k++) rec->Rtr[k] = s_pose[k];
+    }
+}
+
+static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who)
+{
+    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v || (match_flags & ~VO_MATCH_CROSSCHECK))
+        return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
+    if (iters <= 0 || iters > (1 << 22)) return vo_fail(ctx, VO_E_ARG, "%s: need 0 < iters <= 4194304", who);
+    if (refine_iters < 0 || refine_iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: refine_iters is 0 .. 20", who);
+    if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    if (!a.has_kp || !b.has_kp || !a.has_disp || !b.has_disp) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
+    if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
+    if (a.n_kp > 0 && b.n_kp < 2) return vo_fail(ctx, VO_E_ARG, "train set has fewer than 2 descriptors");
+    return VO_OK;
+}
+
+// the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
+// pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
+static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
+                       int refine_iters, PnpRec* rec, uint8_t* arr)
+{
+    const int nq = a.n_kp;
+    // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
+    const size_t need = (size_t)iters * (96 + 48 + 4) + (size_t)nq * (12 + 8 + 4 + 4 + 1) + 4096;
+    if (ctx->mw->ransac_ws_bytes < need) {       // first use of this workspace (or a larger step than any before): never on the steady path
+        VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
+        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
+        const size_t take = std::max(need, (size_t)256 * (96 + 48 + 4) + (size_t)ctx->kp_cap * 29 + 4096);
+        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, take));
+        ctx->mw->ransac_ws_bytes = take;
+    }
+    uint8_t* w = ctx->mw->ransac_ws;
+    double* d_Rt = (double*)w; w += (size_t)iters * 96;
+    float* d_P = (float*)w; w += (size_t)iters * 48;
+    int32_t* d_counts = (int32_t*)w; w += (size_t)iters * 4;
+    w = (uint8_t*)(((uintptr_t)w + 255) & ~(uintptr_t)255);
+    PnpDev d;
+    d.hdr = (int32_t*)w; w += 256;
+    d.uv = (float*)w; w += (size_t)nq * 8;
+    d.X = (float*)w; w += (size_t)nq * 12;
+    d.q = (int32_t*)w; w += (size_t)nq * 4;
+    d.t = (int32_t*)w; w += (size_t)nq * 4;
+    uint8_t* d_mask = w;
+    int rc;
+    {
+        StageTimer t(ctx, VO_T_MATCH);
+        if ((rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross))) return rc;
+    }
+    {
+        StageTimer t(ctx, VO_T_POSE);
+        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, d))) return rc;
+        const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
+        const float thr2 = thr * thr;
+        hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d.X, d.uv, nq, K, iters, seed, d_Rt, d_P, d.hdr + 1);
+        hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d.X, d.uv, nq, d_P, iters, thr2, d_counts, d.hdr + 1);
+        hipLaunchKernelGGL(k_pnp_finish, dim3(1), dim3(256), 0, ctx->stream, d_counts, iters, d_Rt, d_P, d.X, d.uv, nq, d.hdr, d.q, d.t, thr2, K,
+                           refine_iters, d_mask, rec, arr, pnp_cap(ctx->kp_cap));
+        VO_CHECK_LAUNCH(ctx);
+    }
+    return VO_OK;
+}
+
+static void pnp_rec_clear(PnpRec* r)
+{
+    memset(r, 0, sizeof(PnpRec));
+    r->rstatus = 1;
+}
+
+// record (+ arrays) -> the caller's outputs; VO_E_STATE for a pair the step refused
+static int pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                      int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, const char* who)
+{
+    counts4[0] = r->M; counts4[1] = r->n; counts4[2] = r->best_iter; counts4[3] = r->best_count;
+    *flags = r->flags;
+    memcpy(Rt12, r->Rt, sizeof(r->Rt));
+    refine2[0] = r->rstatus; refine2[1] = r->rsteps;
+    if (Rt12_refined) memcpy(Rt12_refined, r->Rtr, sizeof(r->Rtr));
+    if (arr) {
+        const size_t cap = pnp_cap(ctx->kp_cap);
+        if (mask_out) memcpy(mask_out, arr, (size_t)nq);
+        if (q_idx) memcpy(q_idx, arr + cap, (size_t)nq * 4);
+        if (t_idx) memcpy(t_idx, arr + cap * 5, (size_t)nq * 4);
+    }
+    if (r->flags & 2) return vo_fail(ctx, VO_E_STATE, "%s: a match index lies outside the train set: the pair is refused", who);
+    return VO_OK;
+}
+
+extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                           uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                           int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+{
+    if (ctx && (!counts4 || !flags || !Rt12 || !refine2)) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair: bad argument");
+    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair");
+    if (rc) return rc;
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    const bool want = mask_out || q_idx || t_idx;
+    if (want && cap < a.n_kp) return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair: outputs hold %d entries, %d keypoints", cap, a.n_kp);
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
+    PnpRec* rec = (PnpRec*)ctx->pinned;
+    pnp_rec_clear(rec);
+    uint8_t* arr = nullptr;
+    if (a.n_kp > 0) {
+        const size_t bytes = pnp_cap(ctx->kp_cap) * 9;
+        if (want && !(arr = (uint8_t*)xfer_stage(ctx, bytes))) {
+            if ((rc = xfer_flush(ctx))) return rc;
+            if (!(arr = (uint8_t*)xfer_stage(ctx, bytes))) return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair: the transfer arena cannot hold %d keypoints", a.n_kp);
+        }
+        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, refine_iters, rec, arr))) return rc;
+        if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
+        if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // never a pose from an undefined disparity
+    }
+    return pnp_unpack(ctx, rec, arr, a.n_kp, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, t_idx, "vo_pnp_pair");
+}
+
+// The same step in two halves on a POSE alternate (vo_ctx::ALT_POSE: the tickets, streams and scratch of vo_pose_pair_begin --
+// VO_NUM_POSE_ASYNC bounds both kinds together, no stream is added)
+extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                                 uint32_t seed, int refine_iters, int want_matches, int* ticket_out)
+{
+    if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair_begin: bad argument");
+    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair_begin");
+    if (rc) return rc;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    int k;
+    if ((rc = alt_open(ctx, vo_ctx::ALT_POSE, a, b, "vo_pnp_pair_begin", &k))) return rc;
+    vo_ctx::PoseAlt& p = ctx->pose_alt[k];
+    pnp_rec_clear((PnpRec*)p.result);
+    if (a.n_kp > 0) {
+        AltScope on_alt(ctx, p);
+        rc = pnp_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, refine_iters, (PnpRec*)p.result,
+                         want_matches ? p.result + PNP_HDR : nullptr);
+    }
+    if (rc) return rc;
+    p.slot_a = slot_a; p.slot_b = slot_b;
+    p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
+    p.pnp = true; p.want = want_matches != 0 && a.n_kp > 0; p.nq = a.n_kp;
+    return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
+}
+
+extern "C" int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                               uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+{
+    int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && flags && Rt12 && refine2, "vo_pnp_pair_end");
+    if (rc) return rc;
+    vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
+    if (!p.pnp) return vo_fail(ctx, VO_E_STATE, "vo_pnp_pair_end: ticket %d belongs to vo_pose_pair_begin (end it with vo_pose_pair_end)", ticket);
+    if ((mask_out || q_idx || t_idx) && p.nq > 0 && (!p.want || cap < p.nq))
+        return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair_end: outputs hold %d entries, %d keypoints (or the step was begun without want_matches)", cap, p.nq);
+    if ((rc = alt_wait(ctx, p))) return rc;
+    const int32_t gens[2] = { p.gen_a, p.gen_b };
+    const int slots[2] = { p.slot_a, p.slot_b };
+    for (int i = 0; i < 2; i++) {
+        const FrameSlot& f = ctx->slots[slots[i]];
+        if (gens[i] != 0 && *(volatile int32_t*)f.sweep_word == gens[i])
+            return vo_fail(ctx, VO_E_SWEEP, "PnP step %d: the aggregation sweep of the pair in slot %d gave up a strip hand-off: its "
+                                            "disparity is undefined and no pose is derived from it", ticket, slots[i]);
+    }
+    return pnp_unpack(ctx, (const PnpRec*)p.result, p.want ? p.result + PNP_HDR : nullptr, p.nq, counts4, flags, Rt12, Rt12_refined, refine2,
+                      mask_out, q_idx, t_idx, "vo_pnp_pair_end");
 }

@@ -29,6 +29,8 @@ static void* arena_take(vo_ctx* ctx, size_t bytes)
     return p;
 }
 
+void* xfer_stage(vo_ctx* ctx, size_t bytes) { return arena_take(ctx, bytes); }
+
 int xfer_flush(vo_ctx* ctx)
 {
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -247,6 +249,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     if (const char* e26 = getenv("VO_DIAG_DEBUG")) ctx->tune_diag_dbg = atoi(e26);
     if (const char* e10 = getenv("VO_FAULT_PREFETCH")) ctx->fault_prefetch = atoi(e10);   // test-only build (libvo355_hooks.so)
     if (const char* e11 = getenv("VO_FAULT_SWEEP")) ctx->fault_sweep = atoi(e11);
+    if (const char* e12 = getenv("VO_FAULT_PNP_RANGE")) ctx->fault_pnp_range = atoi(e12);
 #endif
     if (const char* e6 = getenv("VO_SWEEP_TY")) { int v = atoi(e6); if (v >= 4 && v <= 4096) ctx->tune_sweep_ty = v; }
     *out = ctx;

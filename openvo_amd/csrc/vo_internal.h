@@ -222,7 +222,7 @@ struct vo_ctx {
     struct AsyncAlt {
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
-        uint8_t* result = nullptr;     // pinned record the step's last kernel writes (pose: PoseOut; monocular: see MONO_HDR)
+        uint8_t* result = nullptr;     // pinned record the step's last kernel writes (pose: PoseOut or PnpRec + arrays; monocular: see MONO_HDR)
         bool ready = false, busy = false;
         MatchWs mw;
     };
@@ -234,6 +234,8 @@ struct vo_ctx {
     struct PoseAlt : AsyncAlt {
         int slot_a = -1, slot_b = -1;
         int32_t gen_a = 0, gen_b = 0;      // disparity generations of the two slots when the step was begun (slot health at _end)
+        bool pnp = false, want = false;    // a vo_pnp_pair_begin step (its record is a PnpRec) / whose record carries mask, q, t
+        int nq = 0;                        // query keypoints of that step
     } pose_alt[N_POSE_ALT];
     static const int N_MONO_ALT = VO_NUM_MONO_ASYNC;
     struct MonoAlt : AsyncAlt {
@@ -277,6 +279,7 @@ struct vo_ctx {
     int tune_sweep_ty = 30;         // VO_SWEEP_TY: rows per tile of the cost sweep
     int mono_engine = 0;            // round robin of vo_prefetch_staged_mono
     int inflight = 0;               // look-ahead pairs submitted and not yet waited for (vo_lookahead_depth)
+    int fault_pnp_range = 0;        // VO_FAULT_PNP_RANGE=n (VO_TEST_HOOKS builds only): the n-th PnP pair step holds its match indices to a train set of ONE descriptor (flag bit 1, VO_E_STATE)
     int fault_prefetch = 0;         // VO_FAULT_PREFETCH=n (VO_TEST_HOOKS builds only): the n-th look-ahead submission fails inside its engine scope
 
     // timing
@@ -341,6 +344,24 @@ static inline hipError_t dev_zero(void* p, size_t bytes)
     return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }
 size_t pose_ws_bytes(int nq);
+// transfer-arena space the caller hands to a kernel that writes host memory itself; given back by xfer_flush like every staging
+// block (nullptr when the arena is full: flush first)
+void* xfer_stage(vo_ctx* ctx, size_t bytes);
+
+// float64 wave sum on DPP moves (two per step); every lane of the result is NOT valid -- lane 63 is, and it is broadcast
+__device__ __forceinline__ double wave_sum_f64_dpp(double v)
+{
+#define DPP_ADD64(ctrl, rmask)                                                                             \
+    {                                                                                                      \
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rmask, 0xf, false);         \
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, rmask, 0xf, false);         \
+        v += __hiloint2double(hi, lo);                                                                     \
+    }
+    DPP_ADD64(0x111, 0xf) DPP_ADD64(0x112, 0xf) DPP_ADD64(0x114, 0xf) DPP_ADD64(0x118, 0xf)
+    DPP_ADD64(0x142, 0xa) DPP_ADD64(0x143, 0xc)
+#undef DPP_ADD64
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
 // CROSS: a match must also pass the cross-check (knn_mutual on the column words of the same kNN launch)
 template <bool CROSS>
 __global__ void k_ratio_compact(const int32_t* idx, const int32_t* dist, int nq, double ratio, const float* xy_q, const float* xy_t,
@@ -412,6 +433,22 @@ int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt
 int points3d_launch(vo_ctx* ctx, const int16_t* d_disp16, int w, int h, const float* d_xy, int n,
                     float* d_xyz, uint8_t* d_status);
 void host_svd3(const double* A, double* U, double* w, double* Vt);
+
+// ---- stereo PnP pair step (vo_pnp_pair: k_pnp_prep in geom.hip, the rest in ransac.hip) ------------------------------------------
+// The record k_pnp_finish writes into pinned host memory; the optional arrays -- mask (1 byte), q, t (int32) for pnp_cap(kp_cap)
+// entries each -- lie PNP_HDR bytes behind it in a pose alternate's record, or in the transfer arena for the synchronous call.
+struct PnpRec {
+    int32_t M, n, best_iter, best_count;   // matches after ratio (+ cross-check), usable correspondences, winner, its inliers
+    int32_t flags;                         // bit 0: a 3-D lookup in slot a had no usable tap; bit 1: a match index outside [0, nt)
+    int32_t rstatus, rsteps, pad;          // refinement: 0 ok, 1 not requested / not attempted, -1 failed; steps run
+    double Rt[12], Rtr[12];                // the winner as vo_ransac_pnp returns it; the refined pose (valid for rstatus 0)
+};
+static const size_t PNP_HDR = 1024;
+static inline size_t pnp_cap(int kp_cap) { return ((size_t)kp_cap + 15) & ~(size_t)15; }
+// device scratch of one step behind the RANSAC arrays: hdr {M, n, flags}, the n usable correspondences in match order
+struct PnpDev { int32_t *hdr, *q, *t; float *X, *uv; };
+// kNN-2 is done (m_idx / m_dist of the current match scratch): ratio test (+ cross-check), 3-D lookup in slot a, compaction
+int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d);
 
 // ---- asynchronous steps (match.hip): see vo_ctx::AsyncAlt -------------------------------------------------------------------
 static const size_t MONO_HDR = 4096;             // monocular record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on

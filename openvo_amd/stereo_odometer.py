@@ -24,19 +24,27 @@ class StereoOdometer:
 
     def __init__(self, stereo_camera, nfeatures=500, match_threshold=0.8, rigidity_threshold=0,
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
-                 pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False):
+                 pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
         the rigidity / outlier stages are then not used, the motion gates still apply.
         cross_check=True is an extension too (the reference's "# TODO crosscheck", :21; cv2 itself refuses
         knnMatch(k=2) on a cross-checking matcher): a match must pass the ratio test AND its m[0] must be a mutual
-        nearest neighbour (include/vo355.h); every later decision is the reference's, on the smaller set."""
+        nearest neighbour (include/vo355.h); every later decision is the reference's, on the smaller set.
+        pnp_refine (0 .. 20, pose_method="pnp"): Gauss-Newton steps that refit the RANSAC winner -- the pose of a minimal
+        sample -- on its whole inlier set, as cv2.solvePnPRansac's final fit does; 0 (default) returns the winner itself, 3 is
+        the recommended value.  The refinement is part of the fused device step (vo_pnp_pair): where that step cannot run
+        (_pair_pnp: a replaced matcher or seam -- the context's point_clouds / ransac_pnp replaced on the object count as
+        seams of this mode --, more than 3800 keypoints) the winner is returned as it is."""
         if pose_method not in ("umeyama", "pnp"):
             raise ValueError("pose_method must be 'umeyama' or 'pnp'")
         if not isinstance(cross_check, (bool, np.bool_)):
             raise ValueError("cross_check must be True or False")
         self.cross_check = bool(cross_check)
+        if isinstance(pnp_refine, (bool, np.bool_)) or not isinstance(pnp_refine, (int, np.integer)) or not 0 <= pnp_refine <= 20:
+            raise ValueError("pnp_refine must be an int in 0 .. 20")
+        self.pnp_refine = int(pnp_refine)
         self.pose_method, self.pnp_iters, self.pnp_threshold, self.pnp_seed = pose_method, pnp_iters, pnp_threshold, pnp_seed
         self.stereo = stereo_camera
         self.current_img = self.current_disparity = self.current_3d = None
@@ -139,20 +147,51 @@ class StereoOdometer:
         self._start_next_pose()
         return True
 
+    _pnp_fused = True        # False: pose_method="pnp" takes the composed path (_pair_pnp) whatever the conditions
+    _PNP_CTX_SEAMS = ("point_clouds", "ransac_pnp")
+
+    def _pnp_fused_ok(self):
+        """The two native calls the composed PnP path is made of are seams too: replaced on the context object (instrumented,
+        say), they are what runs, so the fused step -- which would bypass them -- stands back."""
+        return self._pnp_fused and not any(n in getattr(self._ctx, "__dict__", {}) for n in self._PNP_CTX_SEAMS)
+
     def _pose_params(self):
+        """What a pose step begun ahead must have been begun with to be this odometer's step (part of its ticket's key)."""
+        if self.pose_method == "pnp":
+            Q = self.stereo.Q
+            return ("pnp", float(self.match_threshold), (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3])),
+                    int(self.pnp_iters), float(self.pnp_threshold), int(self.pnp_seed), int(self.pnp_refine), bool(self.cross_check))
         return (float(self.match_threshold), int(self.min_matches), float(max(self.rigidity_threshold, 0)),
                 float(max(self.outlier_threshold, 0)), bool(self.cross_check))
 
     def _fused_ok(self):
-        return (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and self.pose_method == "umeyama"
+        return (type(self) is StereoOdometer and type(self.matcher) is BFMatcher
+                and (self.pose_method == "umeyama" or self._pnp_fused_ok())
                 and not any(n in self.__dict__ for n in self._SEAMS))
+
+    @staticmethod
+    def _pnp_kwargs(params):
+        """_pose_params() of the PnP mode as the keyword arguments of Context.pnp_pair / pnp_pair_begin"""
+        _, ratio, K4, iters, thr, seed, refine, cross_check = params
+        return dict(ratio=ratio, K4=K4, iters=iters, thr=thr, seed=seed, refine=refine, want_matches=False, cross_check=cross_check)
+
+    def _step_begin(self, slot_a, slot_b, params):
+        if params[0] == "pnp":
+            return self._ctx.pnp_pair_begin(slot_a, slot_b, **self._pnp_kwargs(params))
+        return self._ctx.pose_pair_begin(slot_a, slot_b, *params)
+
+    def _step_end(self, params, ticket):
+        """Collect a step begun ahead with the _end of its kind."""
+        if params[0] == "pnp":
+            return self._ctx.pnp_pair_end(ticket)
+        return self._ctx.pose_pair_end(ticket)
 
     def _drop_specs(self, keep=()):
         """Collect and discard pose steps begun ahead.  A step's own error (e.g. VO_E_SWEEP on a pair it read) is discarded with
         it: it belongs to a result nobody asked for, and that pair's own update() reports what is wrong with it."""
         for key in [k for k in self._specs if k not in keep]:
             try:
-                self._ctx.pose_pair_end(self._specs[key])
+                self._step_end(key[2], self._specs[key])
             except _native.VoError:
                 pass
             finally:
@@ -208,7 +247,7 @@ class StereoOdometer:
         for key in wanted:
             if key not in self._specs and len(self._specs) < _native.VO_NUM_POSE_ASYNC:
                 try:
-                    self._specs[key] = self._ctx.pose_pair_begin(key[0][0], key[1][0], *params)
+                    self._specs[key] = self._step_begin(key[0][0], key[1][0], params)
                 except VoError:
                     break                    # nothing started: update() computes the step when it gets there
 
@@ -316,12 +355,15 @@ class StereoOdometer:
               "_estimate", "_gate")
 
     def _try_pair(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b):
-        if self.pose_method == "pnp":
-            return self._pair_pnp(kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b)
         # fused device path when nothing along the way was replaced by the user
-        if (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and 2 <= len(kps_b) and len(kps_a) <= 3800
-                and self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)
-                and not any(n in self.__dict__ for n in self._SEAMS)):
+        fused = (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and 2 <= len(kps_b) and len(kps_a) <= 3800
+                 and self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)
+                 and not any(n in self.__dict__ for n in self._SEAMS))
+        if self.pose_method == "pnp":
+            if fused and self._pnp_fused_ok():
+                return self._pair_pnp_fused(kps_a.frame.slot, kps_b.frame.slot)
+            return self._pair_pnp(kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b)
+        if fused:
             return self._pair_fused(kps_a.frame.slot, kps_b.frame.slot)
         pts_a, pts_b = self.point_clouds(kps_a, kps_b, desc_a, desc_b, im3d_a, im3d_b)
         if pts_a is None:
@@ -352,6 +394,29 @@ class StereoOdometer:
             self.skip_cause = "outlier"
             return None
         return self._gate(np.vstack([r["Rt"], [0, 0, 0, 1]]))
+
+    def _pair_pnp_fused(self, slot_a, slot_b):
+        """_pair_pnp in one native call (vo_pnp_pair: one device synchronisation, nothing but the record comes back): the same
+        decisions in the same order; with pnp_refine > 0 the gates see the refined pose when the refinement succeeded."""
+        params = self._pose_params()
+        ticket = self._specs.pop((self.stereo.slot_key(slot_a), self.stereo.slot_key(slot_b), params), None)
+        if ticket is not None:
+            r = self._ctx.pnp_pair_end(ticket)                           # started by an earlier update()
+        else:
+            r = self._ctx.pnp_pair(slot_a, slot_b, **self._pnp_kwargs(params))
+        if r["matches"] < self.min_matches:
+            self.skip_cause = "matches"
+            return None
+        if r["flags"] & 1:
+            raise ZeroDivisionError("division by zero")
+        if r["n"] < max(self.min_matches, 4):
+            self.skip_cause = "matches"
+            return None
+        if r["best_count"] < self.min_matches:
+            self.skip_cause = "outlier"
+            return None
+        Rt = r["Rt_refined"] if r["refine_status"] == 0 else r["Rt"]
+        return self._gate(np.vstack([Rt, [0, 0, 0, 1]]))
 
     def _pair_fused(self, slot_a, slot_b):
         """point_clouds + point_cloud_transform in one native call (one device synchronisation);
