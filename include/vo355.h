@@ -301,6 +301,59 @@ int vo_mono_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match
 int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
                           uint32_t seed, int solver, int want_matches, int* ticket_out);
 
+/* Monocular pose recovery on the device (NOT part of the reference) ------------------------------------------------------
+ * vo_recover_pose: essential matrix + correspondences -> (R, unit t) with x2 ~ R x1 + t, the depths of the inliers and the ratio
+ * of this pair's baseline to the previous pair's.  One launch of one block, host arrays in and out, one synchronisation.  Float64
+ * throughout, no FMA contraction, three-term sums left to right; tests/mono_pose_ref.py restates it in numpy.
+ *   E9 row-major; pts1 / pts2: n x 2 float32 pixels (1 <= n <= 65536); mask: n bytes (NULL: every point is an inlier); K4 = fx, fy,
+ *   cx, cy; q_idx / t_idx (both or neither; NULL: the identity, na = nb = n): keypoint index of correspondence i in frame a / b;
+ *   depth_a (may be NULL, na doubles): depth of frame a's keypoints in the PREVIOUS pair's units, a value that is not a positive
+ *   finite number means none; min_parallax_sin2 >= 0.
+ * Decomposition: E = U S Vt by one-sided Jacobi (signs flipped so that det U, det Vt > 0), R1 = U W Vt, R2 = U W^T Vt, t = U[:, 2].
+ * Per correspondence and rotation, with x = (u - cx) / fx, h1 = (x1, 1), h2 = (x2, 1), a = R h1: nvec = h2 x t, d = a x h2,
+ * dd = d.d, z1 = (nvec.d) / max(dd, 1e-300), z2 = ((z1 a + t).h2) / (h2.h2), sin2 = dd / ((a.a)(h2.h2)).
+ * Vote over EVERY inlier: votes4 = {#(z1 > 0 and z2 > 0) for R1, #(z1 < 0 and z2 < 0) for R1, the same two for R2}: candidates
+ * (R1, t), (R1, -t), (R2, t), (R2, -t).  The largest vote wins; on a tie the candidate whose R has the larger trace, then the
+ * lower index.  Correspondence i is VALID when it is an inlier, z1 > 0, z2 > 0 and sin2 >= min_parallax_sin2 under the winner.
+ * depth_b (may be NULL, nb doubles, written whole): z2 of the valid correspondence with the LOWEST i that names the keypoint,
+ * 0 elsewhere.  z1_out / z2_out (may be NULL, n doubles): the winner's depths of the inliers, 0 for the others.
+ * scale_rel: the lower median (rank (n_shared - 1) / 2, selected exactly) of depth_a[q_i] / z1_i over the n_shared valid
+ * correspondences whose keypoint has a depth: |t_this| / |t_previous|; 0 when n_shared = 0.
+ * out->flags  bit 0: no inlier, or a non-finite pose: R = I, t = 0, nothing but zeros written
+ *             bit 1: an index outside [0, na) / [0, nb): nothing is read or written through it, the call returns VO_E_STATE
+ *             bit 2: no scale: depth_a was NULL (vo_mono_pose_pair: the depths of slot a do not carry the serial asked for)
+ * out->M = n, best_iter = -1, best_count = the number of inliers, serial = 0. */
+typedef struct vo_mono_pose {
+    int32_t M, best_iter, best_count;      /* matches after the ratio test (+ cross-check), winning hypothesis, its inliers */
+    int32_t winner, n_depth, n_shared;     /* winning candidate 0 .. 3, valid correspondences, those with a depth in frame a */
+    int32_t flags;
+    uint32_t serial;                       /* of the step that wrote the record (and the depths of slot b) */
+    int32_t votes4[4];
+    double E[9], R[9], t[3], scale_rel;
+} vo_mono_pose;                            /* 224 bytes */
+int vo_recover_pose(vo_ctx* ctx, const double* E9, const float* pts1, const float* pts2, const uint8_t* mask, int n, const double* K4,
+                    const int32_t* q_idx, const int32_t* t_idx, int na, int nb, const double* depth_a, double min_parallax_sin2,
+                    vo_mono_pose* out, double* depth_b, double* z1_out, double* z2_out);
+/* The monocular pair step with that tail instead of the per-match record: kNN-2 -> ratio (-> cross-check) -> hypotheses -> scores
+ * as vo_mono_pair_ex, then ONE block: winner, its E and mask (as vo_mono_pair), vo_recover_pose on the surviving correspondences
+ * with slot_a's keypoint depths, the record (a vo_mono_pose, nothing per match) written straight into pinned host memory.  No
+ * further synchronisation and no copy command.  The depths land in slot_b (one double per keypoint) under the step's serial -- a
+ * per-context counter that is never 0.  prev_serial: the serial of the step whose depths of slot_a may be used (0: none); when
+ * slot_a's depths carry another serial, or the slot was refilled since, flag bit 2 is set and n_shared = 0, scale_rel = 0: never
+ * a scale from another frame's or another reference's depths.  slot_a != slot_b.
+ * _begin / _end: the same on a monocular alternate (tickets shared with vo_mono_pair_begin, VO_NUM_MONO_ASYNC in all; a ticket is
+ * ended by the _end of the kind that began it).  A step begun ahead on (b, c) runs its kNN and RANSAC beside the step (a, b) that
+ * writes b's depths and waits for it only before its own tail; a second writer of a slot's depths orders its tail behind the first. */
+int vo_mono_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                      uint32_t seed, int solver, uint32_t prev_serial, double min_parallax_sin2, vo_mono_pose* out);
+int vo_mono_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                            uint32_t seed, int solver, uint32_t prev_serial, double min_parallax_sin2, int* ticket_out,
+                            uint32_t* serial_out);
+int vo_mono_pose_pair_end(vo_ctx* ctx, int ticket, vo_mono_pose* out);
+/* the keypoint depths a slot holds (out: one double per keypoint of the slot, vo_slot_num_keypoints; may be NULL) and their
+ * serial (0: none, the depths then read 0); waits for the step that writes them */
+int vo_download_mono_depth(vo_ctx* ctx, int slot, double* out, uint32_t* serial_out);
+
 /* RANSAC solvePnP hypothesis scoring (north star; BASELINE config 2 names "ORB+SGBM+PnP") ----------
  * NOT part of the reference either (openVO fits 3-D/3-D, stereo_odometer.py:187-205): defined by this
  * build.  iters hypotheses; each draws 4 correspondences (same hash RNG), solves P3P on three of them in

@@ -39,6 +39,7 @@ SYMBOLS = [
     "vo_mono_pair_begin_ex", "vo_measure_knn_ex",
     "vo_set_sweep_group", "vo_lookahead_flush", "vo_sweep_group_stats",
     "vo_pnp_pair", "vo_pnp_pair_begin", "vo_pnp_pair_end",
+    "vo_recover_pose", "vo_mono_pose_pair", "vo_mono_pose_pair_begin", "vo_mono_pose_pair_end", "vo_download_mono_depth",
 ]
 
 
@@ -56,6 +57,20 @@ class SweepTimeout(VoError):
 
 
 VO_E_SWEEP = -6
+
+
+class MonoPose(ctypes.Structure):
+    """vo_mono_pose of include/vo355.h: the record of vo_recover_pose and of a monocular pose step."""
+    _fields_ = [("M", ctypes.c_int32), ("best_iter", ctypes.c_int32), ("best_count", ctypes.c_int32), ("winner", ctypes.c_int32),
+                ("n_depth", ctypes.c_int32), ("n_shared", ctypes.c_int32), ("flags", ctypes.c_int32), ("serial", ctypes.c_uint32),
+                ("votes4", ctypes.c_int32 * 4), ("E", ctypes.c_double * 9), ("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3),
+                ("scale_rel", ctypes.c_double)]
+
+    def as_dict(self):
+        return dict(matches=int(self.M), best_iter=int(self.best_iter), best_count=int(self.best_count), winner=int(self.winner),
+                    n_depth=int(self.n_depth), n_shared=int(self.n_shared), flags=int(self.flags), serial=int(self.serial),
+                    votes4=np.array(self.votes4[:], np.int32), E=np.array(self.E[:], np.float64).reshape(3, 3),
+                    R=np.array(self.R[:], np.float64).reshape(3, 3), t=np.array(self.t[:], np.float64), scale_rel=float(self.scale_rel))
 
 
 def _image(img):
@@ -192,6 +207,13 @@ def lib():
             L.vo_pnp_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
             L.vo_pnp_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
             L.vo_pnp_pair_end.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
+        if hasattr(L, "vo_recover_pose"):           # (likewise: an older build has no pose recovery on the device)
+            cu = ctypes.c_uint32
+            L.vo_recover_pose.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, cd, vp, vp, vp, vp]
+            L.vo_mono_pose_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, cu, ci, cu, cd, vp]
+            L.vo_mono_pose_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, cu, ci, cu, cd, vp, vp]
+            L.vo_mono_pose_pair_end.argtypes = [vp, ci, vp]
+            L.vo_download_mono_depth.argtypes = [vp, ci, vp, vp]
         if hasattr(L, "vo_lookahead_flush"):        # (an older build of the ABI loaded through VO355_LIB for an A/B run has no sweep groups)
             L.vo_set_sweep_group.argtypes = [vp, ci]
             L.vo_lookahead_flush.argtypes = [vp]
@@ -674,6 +696,77 @@ class Context:
         self._ck(self._lib.vo_mono_pair_end(self._h, int(ticket), _p(E), _p(c3), _p(arrays.get("mask")), _p(arrays.get("q")), _p(arrays.get("t")),
                                             _p(arrays.get("xy_b")), cap))
         return self._mono_result(E, c3, **arrays)
+
+    def recover_pose(self, E, pts1, pts2, K4, mask=None, q_idx=None, t_idx=None, na=None, nb=None, depth_a=None, min_parallax_sin2=0.0,
+                     want_depths=True):
+        """E + pixel correspondences -> (R, unit t), cheirality votes over every inlier, the inliers' depths and the ratio of this
+        pair's baseline to the previous one's (vo_recover_pose).  -> the record as a dict (MonoPose.as_dict) + depth_b, z1, z2."""
+        E = _c(np.asarray(E, np.float64).reshape(9), np.float64)
+        pts1, pts2 = _c(pts1, np.float32).reshape(-1, 2), _c(pts2, np.float32).reshape(-1, 2)
+        n = len(pts1)
+        if len(pts2) != n:
+            raise ValueError("point sets differ in length")
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        if mask is not None:
+            mask = _c(mask, np.uint8).reshape(-1)
+            if len(mask) != n:
+                raise ValueError("mask length differs from the point sets'")
+        if (q_idx is None) != (t_idx is None):
+            raise ValueError("q_idx and t_idx come together")
+        if q_idx is not None:
+            q_idx, t_idx = _c(q_idx, np.int32).reshape(-1), _c(t_idx, np.int32).reshape(-1)
+            if len(q_idx) != n or len(t_idx) != n or na is None or nb is None:
+                raise ValueError("q_idx / t_idx need one entry per correspondence, and na, nb")
+        else:
+            na = nb = n
+        if depth_a is not None:
+            depth_a = _c(depth_a, np.float64).reshape(-1)
+            if len(depth_a) != int(na):
+                raise ValueError("depth_a needs na entries")
+        rec = MonoPose()
+        depth_b = np.zeros(max(int(nb), 0), np.float64) if want_depths else None
+        z1 = np.zeros(n, np.float64) if want_depths else None
+        z2 = np.zeros(n, np.float64) if want_depths else None
+        self._ck(self._lib.vo_recover_pose(self._h, _p(E), _p(pts1), _p(pts2), _p(mask), n, _p(K4), _p(q_idx), _p(t_idx), int(na), int(nb),
+                                           _p(depth_a), float(min_parallax_sin2), ctypes.byref(rec), _p(depth_b), _p(z1), _p(z2)))
+        out = rec.as_dict()
+        out.update(depth_b=depth_b, z1=z1, z2=z2)
+        return out
+
+    def mono_pose_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, solver=8, cross_check=False, prev_serial=0,
+                       min_parallax_sin2=0.0):
+        """mono_pair with the pose recovered on the device (vo_mono_pose_pair): -> the record as a dict (MonoPose.as_dict); the
+        depths stay in slot_b under the record's serial."""
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        rec = MonoPose()
+        self._ck(self._lib.vo_mono_pose_pair(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+                                             int(seed) & 0xFFFFFFFF, int(solver), int(prev_serial), float(min_parallax_sin2), ctypes.byref(rec)))
+        return rec.as_dict()
+
+    def mono_pose_pair_begin(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, solver=8, cross_check=False, prev_serial=0,
+                             min_parallax_sin2=0.0):
+        """mono_pose_pair in two halves: -> (ticket for mono_pose_pair_end, the step's serial)."""
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        t, serial = ctypes.c_int(-1), ctypes.c_uint32(0)
+        self._ck(self._lib.vo_mono_pose_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters),
+                                                   float(thr), int(seed) & 0xFFFFFFFF, int(solver), int(prev_serial), float(min_parallax_sin2),
+                                                   ctypes.byref(t), ctypes.byref(serial)))
+        return t.value, serial.value
+
+    def mono_pose_pair_end(self, ticket):
+        rec = MonoPose()
+        self._ck(self._lib.vo_mono_pose_pair_end(self._h, int(ticket), ctypes.byref(rec)))
+        return rec.as_dict()
+
+    def download_mono_depth(self, slot):
+        """-> (depth of each keypoint of the slot in units of the baseline of the step that wrote them, that step's serial); serial
+        0: the slot holds none (zeros)."""
+        n = ctypes.c_int(0)
+        self._ck(self._lib.vo_slot_num_keypoints(self._h, int(slot), ctypes.byref(n)))
+        out = np.zeros(n.value, np.float64)
+        serial = ctypes.c_uint32(0)
+        self._ck(self._lib.vo_download_mono_depth(self._h, int(slot), _p(out), ctypes.byref(serial)))
+        return out, serial.value
 
     def ransac_pnp(self, pts3d, pts2d, K4, iters=5000, thr=2.0, seed=4321, want_counts=False):
         pts3d, pts2d = _c(pts3d, np.float32).reshape(-1, 3), _c(pts2d, np.float32).reshape(-1, 2)

@@ -60,21 +60,30 @@ __device__ void rs_svd3(const double* A, double* U, double* w, double* Vt)
             }
         if (!rotated) break;
     }
+    // (the order of the singular values is kept in three scalars and applied through selects: an index array read with a
+    // run-time index would put G, V and sv into scratch memory)
     double sv[3];
-    int ord[3] = { 0, 1, 2 };
     for (int j = 0; j < 3; j++) sv[j] = sqrt(G[j] * G[j] + G[3 + j] * G[3 + j] + G[6 + j] * G[6 + j]);
-    for (int i = 0; i < 2; i++)
-        for (int j = i + 1; j < 3; j++)
-            if (sv[ord[j]] > sv[ord[i]]) { int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
+#define RS_SEL3(a, b, c, o) ((o) == 0 ? (a) : (o) == 1 ? (b) : (c))
+#define RS_SV(o) RS_SEL3(sv[0], sv[1], sv[2], o)
+    int o0 = 0, o1 = 1, o2 = 2;
+    if (RS_SV(o1) > RS_SV(o0)) { const int t = o0; o0 = o1; o1 = t; }
+    if (RS_SV(o2) > RS_SV(o0)) { const int t = o0; o0 = o2; o2 = t; }
+    if (RS_SV(o2) > RS_SV(o1)) { const int t = o1; o1 = o2; o2 = t; }
     double Uc[3][3], Vc[3][3];
+#pragma unroll
     for (int j = 0; j < 3; j++) {
-        const int o = ord[j];
-        w[j] = sv[o];
+        const int o = j == 0 ? o0 : j == 1 ? o1 : o2;
+        const double so = RS_SV(o);
+        w[j] = so;
+#pragma unroll
         for (int i = 0; i < 3; i++) {
-            Vc[j][i] = V[i * 3 + o];
-            Uc[j][i] = sv[o] > 0 ? G[i * 3 + o] / sv[o] : 0.0;
+            Vc[j][i] = RS_SEL3(V[i * 3], V[i * 3 + 1], V[i * 3 + 2], o);
+            Uc[j][i] = so > 0 ? RS_SEL3(G[i * 3], G[i * 3 + 1], G[i * 3 + 2], o) / so : 0.0;
         }
     }
+#undef RS_SV
+#undef RS_SEL3
     const double tiny = w[0] * 1e-300 + 1e-300;
     if (w[1] <= tiny) {
         double a[3] = { 1, 0, 0 };
@@ -376,13 +385,14 @@ __global__ void __launch_bounds__(1024) k_mono_finish(const int32_t* __restrict_
     for (int i = threadIdx.x; i < nb; i += blockDim.x) ((float2*)(q + cap * 9))[i] = ((const float2*)xy_b)[i];
 }
 
-struct MonoTail { const int32_t* counts; const double* E; const float* F; float thr2; int min_n; };
+// (extra / scratch: `extra` more bytes of the workspace behind the mask, 256-byte aligned, for a tail that needs them)
+struct MonoTail { const int32_t* counts; const double* E; const float* F; float thr2; int min_n; uint8_t* scratch; };
 static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
-                        int solver, MonoDev& o, MonoTail* tail = nullptr)
+                        int solver, MonoDev& o, MonoTail* tail = nullptr, size_t extra = 0)
 {
     const int min_n = solver == 5 ? 6 : 8;
     const int nq = a.n_kp;
-    const size_t need = (size_t)iters * (72 + 36 + 4 + FP_REC_DOUBLES * 8) + (size_t)nq + 4096;
+    const size_t need = (size_t)iters * (72 + 36 + 4 + FP_REC_DOUBLES * 8) + (size_t)nq + 4096 + (extra ? extra + 256 : 0);
     if (ctx->mw->ransac_ws_bytes < need) {
         VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
@@ -421,6 +431,7 @@ static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
         hipLaunchKernelGGL(k_ransac_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, d_F, iters, thr2, d_counts, ctx->mw->m_count, min_n);
         if (tail) {                                  // the asynchronous step ends with k_mono_finish (one launch, record written in place)
             tail->counts = d_counts; tail->E = d_E; tail->F = d_F; tail->thr2 = thr2; tail->min_n = min_n;
+            tail->scratch = (uint8_t*)(((uintptr_t)(o.d_mask + nq) + 255) & ~(uintptr_t)255);
         } else {
             hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, d_counts, iters, o.d_best);
             hipLaunchKernelGGL(k_ransac_mask, dim3(div_up(nq, 256)), dim3(256), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, d_F, o.d_best, thr2, o.d_mask, ctx->mw->m_count, min_n);
@@ -499,7 +510,7 @@ extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     if ((rc = alt_open(ctx, vo_ctx::ALT_MONO, a, b, "vo_mono_pair_begin", &k))) return rc;
     vo_ctx::MonoAlt& p = ctx->mono_alt[k];
     memset(p.result, 0, MONO_HDR);
-    p.nq = a.n_kp; p.nb = b.n_kp; p.min_n = solver == 5 ? 6 : 8; p.want = want_matches != 0;
+    p.nq = a.n_kp; p.nb = b.n_kp; p.min_n = solver == 5 ? 6 : 8; p.want = want_matches != 0; p.pose = false;
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
         MonoDev o;
@@ -529,6 +540,7 @@ extern "C" int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t
     int rc = alt_ticket(ctx, vo_ctx::ALT_MONO, ticket, E9_out && counts3, "vo_mono_pair_end");
     if (rc) return rc;
     vo_ctx::MonoAlt& p = ctx->mono_alt[ticket];
+    if (p.pose) return vo_fail(ctx, VO_E_STATE, "vo_mono_pair_end: ticket %d belongs to vo_mono_pose_pair_begin (end it with vo_mono_pose_pair_end)", ticket);
     if ((mask_out || q_idx || t_idx) && (!p.want || cap < p.nq)) return vo_fail(ctx, VO_E_CAP, "vo_mono_pair_end: outputs hold %d entries, %d keypoints (or the step was begun without want_matches)", cap, p.nq);
     if (xy_b_out && (!p.want || cap < p.nb)) return vo_fail(ctx, VO_E_CAP, "vo_mono_pair_end: xy_b_out holds %d entries, %d keypoints", cap, p.nb);
     if ((rc = alt_wait(ctx, p))) return rc;
@@ -542,6 +554,523 @@ extern "C" int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t
     if (t_idx) memcpy(t_idx, q + kc * 5, (size_t)p.nq * 4);
     if (xy_b_out) memcpy(xy_b_out, q + kc * 9, (size_t)p.nb * 8);
     return VO_OK;
+}
+
+// =========================================================================================
+// Monocular pose recovery (vo_recover_pose, vo_mono_pose_pair / _begin / _end; no openVO counterpart): E -> (R, unit t) by the
+// four-fold decomposition and a cheirality vote over EVERY inlier, the inliers' depths kept with the second frame's keypoints,
+// and the ratio of this pair's baseline to the previous pair's from the keypoints the two pairs share.  One block (rp_tail)
+// behind the winner's mask -- of the stand-alone entry (k_recover_pose) or of the fused pair step (k_mono_pose_finish):
+//   pass 0   index check, inlier count (ballot + popcount), depth_b and the owner words cleared; one lane: 3x3 SVD, R1, R2, t
+//   pass 1   the vote: both rotations with +t per inlier, four ballots per wave
+//   pass 2   the winner's depths and parallax gate -> the valid set (ballot words in LDS), atomicMin of i on the owner word of
+//            keypoint t_i (several correspondences may name one keypoint: the lowest i wins, whatever the thread timing)
+//   pass 3   the owners write depth_b; depth_a[q_i] / z1_i of the shared keypoints as bit patterns
+//   select   the lower median of those patterns exactly: eight 256-bin LDS histogram passes from the top byte down (positive
+//            doubles order like their patterns)
+// Float64, three-term sums left to right, no contraction: tests/mono_pose_ref.py restates it value for value.
+// =========================================================================================
+struct RpArgs {
+    const float *p1, *p2;                 // n x 2 pixels
+    const int32_t *q, *t;                 // keypoint indices of the correspondences in frames a / b (both NULL: the identity)
+    int na, nb;
+    const double* depth_a;                // depths of frame a's keypoints in the previous pair's units (NULL: none)
+    const uint32_t* serial_a;             // the serial word that goes with depth_a (NULL: not checked) ...
+    uint32_t prev_serial;                 // ... and the serial it must hold
+    double gate;                          // min_parallax_sin2
+    K4 K;
+    double* depth_b;                      // nb, written whole
+    uint32_t* serial_b;                   // stamped with `serial` (NULL: no stamp)
+    uint32_t serial;
+    double *z1, *z2;                      // n each: the winner's depths of the inliers, 0 elsewhere
+    unsigned long long* ratio;            // n: scratch of the select
+    int32_t* owner;                       // nb: scratch of the scatter
+    vo_mono_pose* rec;                    // pinned host memory
+};
+
+struct RpZ { double z1, z2, sin2; };
+// depths along the two rays and the squared sine of the angle between them: z1 (R h1) + t = z2 h2
+__device__ __forceinline__ RpZ rp_depths(const double* R, double t0, double t1, double t2, double x1, double y1, double hx, double hy)
+{
+    const double ax = (R[0] * x1 + R[1] * y1) + R[2], ay = (R[3] * x1 + R[4] * y1) + R[5], az = (R[6] * x1 + R[7] * y1) + R[8];
+    const double nx = hy * t2 - t1, ny = t0 - hx * t2, nz = hx * t1 - hy * t0;          // h2 x t
+    const double dx = ay - az * hy, dy = az * hx - ax, dz = ax * hy - ay * hx;          // (R h1) x h2
+    const double dd = (dx * dx + dy * dy) + dz * dz;
+    const double hh = (hx * hx + hy * hy) + 1.0;
+    RpZ o;
+    o.z1 = ((nx * dx + ny * dy) + nz * dz) / (dd > 1e-300 ? dd : 1e-300);
+    o.z2 = (((o.z1 * ax + t0) * hx + (o.z1 * ay + t1) * hy) + (o.z1 * az + t2)) / hh;
+    o.sin2 = dd / (((ax * ax + ay * ay) + az * az) * hh);
+    return o;
+}
+
+__device__ __forceinline__ double rp_det3(const double* M)
+{
+    return (M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6])) + M[2] * (M[3] * M[7] - M[4] * M[6]);
+}
+
+// s_mask: the inliers of the n correspondences as ballot words (written and synchronised by the caller); s_valid: as many words.
+// M / best_iter go into the record as they come; best_count < 0: the number of inliers counted here.
+__device__ void rp_tail(const RpArgs& A, int n, const double* E9, int M, int best_iter, int best_count, const unsigned long long* s_mask,
+                        unsigned long long* s_valid)
+{
+    __shared__ double s_R[18], s_tw[3];
+    __shared__ int s_cnt[16][4], s_votes[4], s_flags, s_winner, s_k;
+    __shared__ unsigned int s_hist[256];
+    __shared__ unsigned long long s_prefix;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
+    const bool ident = A.q == nullptr;
+    const double fx = A.K.fx, fy = A.K.fy, cx = A.K.cx, cy = A.K.cy;
+
+    // ---- pass 0
+    int bad = 0, cnt = 0;
+    for (int i0 = wv * 64; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + lane;
+        bool in = false;
+        if (i < n) {
+            in = (s_mask[i >> 6] >> (i & 63)) & 1ull;
+            if (!ident) { const int qi = A.q[i], ti = A.t[i]; bad |= (qi < 0) | (qi >= A.na) | (ti < 0) | (ti >= A.nb); }
+        }
+        cnt += __popcll(__ballot(in));
+    }
+    for (int j = tid; j < A.nb; j += blockDim.x) { A.depth_b[j] = 0.0; A.owner[j] = 0x7fffffff; }
+    if (lane == 0) s_cnt[wv][0] = cnt;
+    bad = __syncthreads_or(bad);
+    if (tid == 0) {
+        int n_inl = 0;
+        for (int w = 0; w < nw; w++) n_inl += s_cnt[w][0];
+        double E[9], U[9], sv[3], Vt[9];
+        for (int k = 0; k < 9; k++) E[k] = E9[k];
+        rs_svd3(E, U, sv, Vt);
+        if (rp_det3(U) < 0.0) for (int k = 0; k < 9; k++) U[k] = -U[k];
+        if (rp_det3(Vt) < 0.0) for (int k = 0; k < 9; k++) Vt[k] = -Vt[k];
+        bool fin = true;
+        for (int r = 0; r < 3; r++) {
+            // U W = [u1, -u0, u2], U W^T = [-u1, u0, u2] (columns)
+            const double w0 = U[r * 3 + 1], w1 = -U[r * 3], w2 = U[r * 3 + 2];
+            for (int c = 0; c < 3; c++) {
+                const double r1 = (w0 * Vt[c] + w1 * Vt[3 + c]) + w2 * Vt[6 + c];
+                const double r2 = ((-w0) * Vt[c] + (-w1) * Vt[3 + c]) + w2 * Vt[6 + c];
+                s_R[r * 3 + c] = r1; s_R[9 + r * 3 + c] = r2;
+                fin = fin && isfinite(r1) && isfinite(r2);
+            }
+            fin = fin && isfinite(w2);
+            s_tw[r] = w2;
+        }
+        int flags = bad ? 2 : 0;
+        if (n_inl == 0 || !fin) flags |= 1;
+        if (!(A.depth_a && (!A.serial_a || (A.prev_serial != 0 && *A.serial_a == A.prev_serial)))) flags |= 4;
+        s_flags = flags;
+        s_k = n_inl;
+    }
+    __syncthreads();
+    const int flags = s_flags, n_inl = s_k;
+    if (best_count < 0) best_count = n_inl;
+    if (flags & 3) {                        // refused: nothing but zeros (depth_b is cleared already)
+        for (int i = tid; i < n; i += blockDim.x) { A.z1[i] = 0.0; A.z2[i] = 0.0; }
+        if (tid == 0) {
+            vo_mono_pose* r = A.rec;
+            r->M = M; r->best_iter = best_iter; r->best_count = best_count; r->winner = 0; r->n_depth = 0; r->n_shared = 0;
+            r->flags = flags; r->serial = A.serial;
+            for (int k = 0; k < 4; k++) r->votes4[k] = 0;
+            for (int k = 0; k < 9; k++) { r->E[k] = E9[k]; r->R[k] = (k & 3) == 0 ? 1.0 : 0.0; }
+            for (int k = 0; k < 3; k++) r->t[k] = 0.0;
+            r->scale_rel = 0.0;
+            if (A.serial_b) *A.serial_b = A.serial;
+        }
+        return;
+    }
+
+    // ---- pass 1: the vote
+    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    for (int i0 = wv * 64; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + lane;
+        bool p1 = false, m1 = false, p2 = false, m2 = false;
+        if (i < n && ((s_mask[i >> 6] >> (i & 63)) & 1ull)) {
+            const float2 a = ((const float2*)A.p1)[i], b = ((const float2*)A.p2)[i];
+            const double x1 = ((double)a.x - cx) / fx, y1 = ((double)a.y - cy) / fy, hx = ((double)b.x - cx) / fx, hy = ((double)b.y - cy) / fy;
+            const RpZ u = rp_depths(s_R, s_tw[0], s_tw[1], s_tw[2], x1, y1, hx, hy);
+            const RpZ v = rp_depths(s_R + 9, s_tw[0], s_tw[1], s_tw[2], x1, y1, hx, hy);
+            p1 = u.z1 > 0.0 && u.z2 > 0.0; m1 = u.z1 < 0.0 && u.z2 < 0.0;
+            p2 = v.z1 > 0.0 && v.z2 > 0.0; m2 = v.z1 < 0.0 && v.z2 < 0.0;
+        }
+        c0 += __popcll(__ballot(p1)); c1 += __popcll(__ballot(m1)); c2 += __popcll(__ballot(p2)); c3 += __popcll(__ballot(m2));
+    }
+    if (lane == 0) { s_cnt[wv][0] = c0; s_cnt[wv][1] = c1; s_cnt[wv][2] = c2; s_cnt[wv][3] = c3; }
+    __syncthreads();
+    if (tid == 0) {
+        int v0 = 0, v1 = 0, v2 = 0, v3 = 0;
+        for (int w = 0; w < nw; w++) { v0 += s_cnt[w][0]; v1 += s_cnt[w][1]; v2 += s_cnt[w][2]; v3 += s_cnt[w][3]; }
+        s_votes[0] = v0; s_votes[1] = v1; s_votes[2] = v2; s_votes[3] = v3;
+        const double tr1 = (s_R[0] + s_R[4]) + s_R[8], tr2 = (s_R[9] + s_R[13]) + s_R[17];
+        // the largest vote; on a tie the rotation with the larger trace; then the lower index
+        int best = 0, bv = v0;
+        double bt = tr1;
+        if (v1 > bv) { best = 1; bv = v1; }                                  // (same rotation as candidate 0: the trace cannot decide)
+        if (v2 > bv || (v2 == bv && tr2 > bt)) { best = 2; bv = v2; bt = tr2; }
+        if (v3 > bv || (v3 == bv && tr2 > bt)) { best = 3; bv = v3; bt = tr2; }
+        s_winner = best;
+        if (best & 1) for (int k = 0; k < 3; k++) s_tw[k] = -s_tw[k];
+    }
+    __syncthreads();
+    const int winner = s_winner;
+    const double* Rw = s_R + (winner >> 1) * 9;
+    const double t0 = s_tw[0], t1 = s_tw[1], t2 = s_tw[2];
+
+    // ---- pass 2: depths under the winner, the valid set, the owners
+    int nd = 0;
+    for (int i0 = wv * 64; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + lane;
+        bool val = false;
+        double z1 = 0.0, z2 = 0.0;
+        if (i < n && ((s_mask[i >> 6] >> (i & 63)) & 1ull)) {
+            const float2 a = ((const float2*)A.p1)[i], b = ((const float2*)A.p2)[i];
+            const double x1 = ((double)a.x - cx) / fx, y1 = ((double)a.y - cy) / fy, hx = ((double)b.x - cx) / fx, hy = ((double)b.y - cy) / fy;
+            const RpZ u = rp_depths(Rw, t0, t1, t2, x1, y1, hx, hy);
+            z1 = u.z1; z2 = u.z2;
+            val = z1 > 0.0 && z2 > 0.0 && u.sin2 >= A.gate;
+            if (val) atomicMin(&A.owner[ident ? i : A.t[i]], i);
+        }
+        if (i < n) { A.z1[i] = z1; A.z2[i] = z2; }
+        const unsigned long long bits = __ballot(val);
+        if (lane == 0) s_valid[i0 >> 6] = bits;
+        nd += __popcll(bits);
+    }
+    if (lane == 0) s_cnt[wv][0] = nd;
+    __syncthreads();
+
+    // ---- pass 3: the scatter, the ratios (thread tid has written z1 / z2 of the i it reads here)
+    const bool use = !(flags & 4);
+    int ns = 0;
+    for (int i0 = wv * 64; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + lane;
+        bool sh = false;
+        unsigned long long pat = ~0ull;
+        if (i < n && ((s_valid[i >> 6] >> (i & 63)) & 1ull)) {
+            const int ti = ident ? i : A.t[i];
+            if (__hip_atomic_load(&A.owner[ti], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i) A.depth_b[ti] = A.z2[i];
+            if (use) {
+                const double d = A.depth_a[ident ? i : A.q[i]];
+                if (d > 0.0 && d <= 1.7976931348623157e308) { sh = true; pat = (unsigned long long)__double_as_longlong(d / A.z1[i]); }
+            }
+        }
+        if (i < n) A.ratio[i] = pat;
+        ns += __popcll(__ballot(sh));
+    }
+    if (lane == 0) s_cnt[wv][1] = ns;
+    __syncthreads();
+    int n_depth = 0, n_shared = 0;
+    for (int w = 0; w < nw; w++) { n_depth += s_cnt[w][0]; n_shared += s_cnt[w][1]; }
+
+    // ---- the lower median of the ratios: radix select on the 64-bit patterns
+    if (tid == 0) { s_prefix = 0ull; s_k = (n_shared - 1) / 2; }
+    if (n_shared > 0) {
+        for (int pass = 0; pass < 8; pass++) {
+            const int shift = 56 - 8 * pass;
+            if (tid < 256) s_hist[tid] = 0u;
+            __syncthreads();
+            const unsigned long long prefix = s_prefix;
+            for (int i = tid; i < n; i += blockDim.x) {
+                const unsigned long long v = A.ratio[i];
+                if (v != ~0ull && (pass == 0 || (v >> (shift + 8)) == (prefix >> (shift + 8)))) atomicAdd(&s_hist[(unsigned)(v >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (wv == 0) {                  // the bin that holds rank k: lane l owns bins 4l .. 4l + 3
+                const unsigned h0 = s_hist[4 * lane], h1 = s_hist[4 * lane + 1], h2 = s_hist[4 * lane + 2], h3 = s_hist[4 * lane + 3];
+                const unsigned own = ((h0 + h1) + h2) + h3;
+                unsigned incl = own;
+                for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
+                const unsigned excl = incl - own, k = (unsigned)s_k;
+                if (k >= excl && k < incl) {
+                    unsigned r = k - excl, bin = 4u * lane;
+                    if (r >= h0) { r -= h0; bin++; if (r >= h1) { r -= h1; bin++; if (r >= h2) { r -= h2; bin++; } } }
+                    s_prefix = prefix | ((unsigned long long)bin << shift);
+                    s_k = (int)r;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        vo_mono_pose* r = A.rec;
+        r->M = M; r->best_iter = best_iter; r->best_count = best_count; r->winner = winner; r->n_depth = n_depth; r->n_shared = n_shared;
+        r->flags = flags; r->serial = A.serial;
+        for (int k = 0; k < 4; k++) r->votes4[k] = s_votes[k];
+        for (int k = 0; k < 9; k++) { r->E[k] = E9[k]; r->R[k] = Rw[k]; }
+        r->t[0] = t0; r->t[1] = t1; r->t[2] = t2;
+        r->scale_rel = n_shared > 0 ? __longlong_as_double((long long)s_prefix) : 0.0;
+        if (A.serial_b) *A.serial_b = A.serial;
+    }
+}
+
+static inline size_t rp_lds_bytes(int n) { return (size_t)((n + 63) >> 6) * 16; }
+// device scratch of one tail behind `base` (256-byte aligned): z1, z2, ratio (n x 8 B each), owner (nb x 4 B)
+static inline size_t rp_scratch_bytes(int n, int nb) { return (size_t)n * 24 + (size_t)nb * 4 + 256; }
+static void rp_scratch(RpArgs& A, uint8_t* base, int n)
+{
+    A.z1 = (double*)base; A.z2 = A.z1 + n;
+    A.ratio = (unsigned long long*)(A.z2 + n);
+    A.owner = (int32_t*)(A.ratio + n);
+}
+
+__global__ void __launch_bounds__(1024) k_recover_pose(RpArgs A, int n, const double* __restrict__ E9, const uint8_t* __restrict__ mask)
+{
+    extern __shared__ unsigned long long s_bits[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nwords = (n + 63) >> 6;
+    for (int i0 = wv * 64; i0 < n; i0 += blockDim.x) {
+        const int i = i0 + lane;
+        const unsigned long long bits = __ballot(i < n && (!mask || mask[i] != 0));
+        if (lane == 0) s_bits[i0 >> 6] = bits;
+    }
+    __syncthreads();
+    rp_tail(A, n, E9, n, -1, -1, s_bits, s_bits + nwords);
+}
+
+// The end of a monocular pose step as ONE launch: argmax of the hypotheses' inlier counts, the winner's E and its inlier mask
+// exactly as k_mono_finish computes them (the mask as ballot words in LDS instead of bytes in the record), then rp_tail on the
+// M surviving correspondences.  Nothing per match crosses the link: the record is a vo_mono_pose.
+__global__ void __launch_bounds__(1024) k_mono_pose_finish(const int32_t* __restrict__ counts, int iters, const double* __restrict__ E_all,
+                                                           const float* __restrict__ F_all, int nq, const int* __restrict__ n_dev, int min_n,
+                                                           float thr2, RpArgs A)
+{
+    extern __shared__ unsigned long long s_bits[];
+    __shared__ long long s_key[16];
+    __shared__ int s_best[2];
+    __shared__ double s_E[9];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long key = -1;
+    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
+        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);   // most inliers, then lowest index
+        key = k > key ? k : key;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
+    if (lane == 0) s_key[wv] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < (int)(blockDim.x >> 6); q++) key = s_key[q] > key ? s_key[q] : key;
+        s_best[0] = 0x7fffffff - (int)(key & 0x7fffffffLL);
+        s_best[1] = (int)(key >> 32);
+    }
+    __syncthreads();
+    const int best = s_best[0];
+    int m = *n_dev;
+    m = m < 0 ? 0 : (m > nq ? nq : m);      // (the LDS words and the scratch are sized for nq)
+    if (threadIdx.x < 9) s_E[threadIdx.x] = E_all[(size_t)best * 9 + threadIdx.x];
+    float Fl[9];
+    for (int k = 0; k < 9; k++) Fl[k] = F_all[(size_t)best * 9 + k];
+    const int live = m < min_n ? 0 : m;
+    for (int i0 = wv * 64; i0 < m; i0 += blockDim.x) {
+        const int i = i0 + lane;
+        bool in = false;
+        if (i < live) {
+            const float2 a = ((const float2*)A.p1)[i], b = ((const float2*)A.p2)[i];
+            in = sampson_inlier(Fl, a.x, a.y, b.x, b.y, thr2);
+        }
+        const unsigned long long bits = __ballot(in);
+        if (lane == 0) s_bits[i0 >> 6] = bits;
+    }
+    __syncthreads();
+    rp_tail(A, m, s_E, m, best, live ? s_best[1] : 0, s_bits, s_bits + ((nq + 63) >> 6));
+}
+
+static int rp_check_out(vo_ctx* ctx, const vo_mono_pose* r, const char* who)
+{
+    if (r->flags & 2) return vo_fail(ctx, VO_E_STATE, "%s: a keypoint index lies outside its frame: the step is refused", who);
+    return VO_OK;
+}
+
+static void rp_rec_clear(vo_mono_pose* r)
+{
+    memset(r, 0, sizeof(vo_mono_pose));
+    r->R[0] = r->R[4] = r->R[8] = 1.0;
+    r->flags = 1 | 4;
+}
+
+extern "C" int vo_recover_pose(vo_ctx* ctx, const double* E9, const float* pts1, const float* pts2, const uint8_t* mask, int n, const double* K4v,
+                               const int32_t* q_idx, const int32_t* t_idx, int na, int nb, const double* depth_a, double min_parallax_sin2,
+                               vo_mono_pose* out, double* depth_b, double* z1_out, double* z2_out)
+{
+    if (!ctx || !E9 || !pts1 || !pts2 || !K4v || !out || (q_idx == nullptr) != (t_idx == nullptr) || !(min_parallax_sin2 >= 0.0) ||
+        !(K4v[0] > 0.0) || !(K4v[1] > 0.0))
+        return vo_fail(ctx, VO_E_ARG, "vo_recover_pose: bad argument");
+    if (n < 1 || n > 65536) return vo_fail(ctx, VO_E_CAP, "vo_recover_pose: need 1 <= n <= 65536");
+    if (!q_idx) na = nb = n;
+    if (na < 1 || nb < 1 || na > (1 << 24) || nb > (1 << 24)) return vo_fail(ctx, VO_E_ARG, "vo_recover_pose: need 1 <= na, nb <= 16777216");
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    // workspace: E, the points, mask, indices, depth_a, depth_b, then the tail's scratch
+    const size_t need = 256 + (size_t)n * (8 + 8 + 1 + 4 + 4) + (size_t)(na + nb) * 8 + 2048 + rp_scratch_bytes(n, nb);
+    if (ctx->mw->ransac_ws_bytes < need) {
+        VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
+        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
+        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, need));
+        ctx->mw->ransac_ws_bytes = need;
+    }
+    auto align = [](uint8_t* p) { return (uint8_t*)(((uintptr_t)p + 255) & ~(uintptr_t)255); };
+    uint8_t* w = ctx->mw->ransac_ws;
+    double* d_E = (double*)w; w += 256;
+    float* d_p1 = (float*)w; w += (size_t)n * 8;
+    float* d_p2 = (float*)w; w += (size_t)n * 8;
+    int32_t* d_q = (int32_t*)w; w += (size_t)n * 4;
+    int32_t* d_t = (int32_t*)w; w += (size_t)n * 4;
+    double* d_da = (double*)align(w); w = (uint8_t*)(d_da + na);
+    double* d_db = (double*)w; w = (uint8_t*)(d_db + nb);
+    uint8_t* d_mask = w; w = align(w + n);
+    StageTimer t(ctx, VO_T_POSE);
+    int rc = xfer_h2d(ctx, d_E, E9, 72);
+    if (!rc) rc = xfer_h2d(ctx, d_p1, pts1, (size_t)n * 8);
+    if (!rc) rc = xfer_h2d(ctx, d_p2, pts2, (size_t)n * 8);
+    if (!rc && mask) rc = xfer_h2d(ctx, d_mask, mask, (size_t)n);
+    if (!rc && q_idx) rc = xfer_h2d(ctx, d_q, q_idx, (size_t)n * 4);
+    if (!rc && t_idx) rc = xfer_h2d(ctx, d_t, t_idx, (size_t)n * 4);
+    if (!rc && depth_a) rc = xfer_h2d(ctx, d_da, depth_a, (size_t)na * 8);
+    if (rc) return rc;
+    vo_mono_pose* rec = (vo_mono_pose*)ctx->pinned;
+    rp_rec_clear(rec);
+    RpArgs A{};
+    A.p1 = d_p1; A.p2 = d_p2; A.q = q_idx ? d_q : nullptr; A.t = t_idx ? d_t : nullptr; A.na = na; A.nb = nb;
+    A.depth_a = depth_a ? d_da : nullptr; A.serial_a = nullptr; A.prev_serial = 0; A.gate = min_parallax_sin2;
+    A.K = K4{ K4v[0], K4v[1], K4v[2], K4v[3] };
+    A.depth_b = d_db; A.serial_b = nullptr; A.serial = 0; A.rec = rec;
+    rp_scratch(A, w, n);
+    hipLaunchKernelGGL(k_recover_pose, dim3(1), dim3(1024), rp_lds_bytes(n), ctx->stream, A, n, d_E, mask ? d_mask : nullptr);
+    VO_CHECK_LAUNCH(ctx);
+    if (depth_b && (rc = xfer_d2h(ctx, depth_b, d_db, (size_t)nb * 8))) return rc;
+    if (z1_out && (rc = xfer_d2h(ctx, z1_out, A.z1, (size_t)n * 8))) return rc;
+    if (z2_out && (rc = xfer_d2h(ctx, z2_out, A.z2, (size_t)n * 8))) return rc;
+    if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
+    *out = *rec;
+    return rp_check_out(ctx, out, "vo_recover_pose");
+}
+
+// ---- the fused step --------------------------------------------------------------------------------------------------------
+static int mono_pose_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, int solver, double gate,
+                           const void* out, const char* who)
+{
+    if (ctx && (!out || (match_flags & ~VO_MATCH_CROSSCHECK) || !(gate >= 0.0) || slot_a == slot_b))
+        return vo_fail(ctx, VO_E_ARG, "%s: bad argument (two different slots, min_parallax_sin2 >= 0)", who);
+    int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, who);
+    if (rc) return rc;
+    if (!(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need positive focal lengths", who);
+    if (rp_lds_bytes(ctx->slots[slot_a].n_kp) > 48 * 1024) return vo_fail(ctx, VO_E_CAP, "%s: %d keypoints exceed the step's LDS", who, ctx->slots[slot_a].n_kp);
+    return VO_OK;
+}
+
+static uint32_t mono_next_serial(vo_ctx* ctx)
+{
+    if (++ctx->mono_serial_next == 0) ctx->mono_serial_next = 1;
+    return ctx->mono_serial_next;
+}
+
+// The chain of mono_enqueue on ctx->stream (the main one or an alternate's) with k_mono_pose_finish as its tail.  The tail alone
+// is ordered behind the step that writes slot a's depths, behind an earlier writer of slot b's and behind the steps still
+// reading slot b: the kNN and the RANSAC in front of it overlap them.  `rec`: pinned host memory.
+static int mono_pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
+                             int solver, uint32_t prev_serial, double gate, uint32_t serial, vo_mono_pose* rec)
+{
+    MonoDev o;
+    MonoTail tl;
+    int rc = mono_enqueue(ctx, a, b, ratio, cross, K4v, iters, thr, seed, solver, o, &tl, rp_scratch_bytes(a.n_kp, b.n_kp));
+    if (rc) return rc;
+    if (a.depth_writer) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, a.depth_writer, 0));
+    if (b.depth_writer) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, b.depth_writer, 0));
+    for (hipEvent_t r : b.readers) if (r) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, r, 0));
+    RpArgs A{};
+    A.p1 = ctx->mw->xy_a; A.p2 = ctx->mw->xy_b; A.q = ctx->mw->mq_idx; A.t = ctx->mw->mt_idx; A.na = a.n_kp; A.nb = b.n_kp;
+    // depths of slot a are offered only under the serial the HOST still holds for them (a refill clears it at once)
+    const bool offer = prev_serial != 0 && a.mono_serial == prev_serial;
+    A.depth_a = offer ? a.mono_depth : nullptr; A.serial_a = a.mono_serial_dev; A.prev_serial = prev_serial; A.gate = gate;
+    A.K = K4{ K4v[0], K4v[1], K4v[2], K4v[3] };
+    A.depth_b = b.mono_depth; A.serial_b = b.mono_serial_dev; A.serial = serial; A.rec = rec;
+    rp_scratch(A, tl.scratch, a.n_kp);
+    StageTimer t(ctx, VO_T_POSE);
+    hipLaunchKernelGGL(k_mono_pose_finish, dim3(1), dim3(1024), rp_lds_bytes(a.n_kp), ctx->stream, tl.counts, iters, tl.E, tl.F, a.n_kp,
+                       ctx->mw->m_count, tl.min_n, tl.thr2, A);
+    VO_CHECK_LAUNCH(ctx);
+    b.mono_serial = serial;
+    return VO_OK;
+}
+
+extern "C" int vo_mono_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                                 uint32_t seed, int solver, uint32_t prev_serial, double min_parallax_sin2, vo_mono_pose* out)
+{
+    int rc = mono_pose_check(ctx, slot_a, slot_b, match_flags, K4v, iters, solver, min_parallax_sin2, out, "vo_mono_pose_pair");
+    if (rc) return rc;
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    rp_rec_clear(out);
+    if (a.n_kp == 0) { b.mono_serial = 0; return VO_OK; }      // nothing to match: no step, no depths
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
+    vo_mono_pose* rec = (vo_mono_pose*)ctx->pinned;
+    rp_rec_clear(rec);
+    if ((rc = mono_pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, prev_serial, min_parallax_sin2,
+                                mono_next_serial(ctx), rec)))
+        return rc;
+    if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
+    b.depth_writer = nullptr;
+    *out = *rec;
+    return rp_check_out(ctx, out, "vo_mono_pose_pair");
+}
+
+extern "C" int vo_mono_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                                       uint32_t seed, int solver, uint32_t prev_serial, double min_parallax_sin2, int* ticket_out,
+                                       uint32_t* serial_out)
+{
+    int rc = mono_pose_check(ctx, slot_a, slot_b, match_flags, K4v, iters, solver, min_parallax_sin2, ticket_out, "vo_mono_pose_pair_begin");
+    if (rc) return rc;
+    if (!serial_out) return vo_fail(ctx, VO_E_ARG, "vo_mono_pose_pair_begin: bad argument");
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    int k;
+    if ((rc = alt_open(ctx, vo_ctx::ALT_MONO, a, b, "vo_mono_pose_pair_begin", &k))) return rc;
+    vo_ctx::MonoAlt& p = ctx->mono_alt[k];
+    rp_rec_clear((vo_mono_pose*)p.result);
+    p.nq = a.n_kp; p.nb = b.n_kp; p.min_n = solver == 5 ? 6 : 8; p.want = false; p.pose = true;
+    *serial_out = 0;
+    if (a.n_kp > 0) {
+        const uint32_t serial = mono_next_serial(ctx);
+        AltScope on_alt(ctx, p);
+        rc = mono_pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, prev_serial, min_parallax_sin2,
+                               serial, (vo_mono_pose*)p.result);
+        if (!rc) *serial_out = serial;
+    } else
+        b.mono_serial = 0;
+    if (rc) return rc;
+    if ((rc = alt_close(ctx, vo_ctx::ALT_MONO, k, a, b, ticket_out))) return rc;
+    if (a.n_kp > 0) b.depth_writer = p.done;
+    return VO_OK;
+}
+
+extern "C" int vo_mono_pose_pair_end(vo_ctx* ctx, int ticket, vo_mono_pose* out)
+{
+    int rc = alt_ticket(ctx, vo_ctx::ALT_MONO, ticket, out != nullptr, "vo_mono_pose_pair_end");
+    if (rc) return rc;
+    vo_ctx::MonoAlt& p = ctx->mono_alt[ticket];
+    if (!p.pose) return vo_fail(ctx, VO_E_STATE, "vo_mono_pose_pair_end: ticket %d belongs to vo_mono_pair_begin (end it with vo_mono_pair_end)", ticket);
+    if ((rc = alt_wait(ctx, p))) return rc;
+    *out = *(const vo_mono_pose*)p.result;
+    return rp_check_out(ctx, out, "vo_mono_pose_pair_end");
+}
+
+extern "C" int vo_download_mono_depth(vo_ctx* ctx, int slot, double* out, uint32_t* serial_out)
+{
+    if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS || !serial_out) return vo_fail(ctx, VO_E_ARG, "vo_download_mono_depth: bad argument");
+    FrameSlot& f = ctx->slots[slot];
+    if (!f.has_kp) return vo_fail(ctx, VO_E_STATE, "vo_download_mono_depth: the slot has no keypoints");
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    *serial_out = 0;
+    if (f.mono_serial == 0) {
+        if (out) memset(out, 0, (size_t)f.n_kp * 8);
+        return VO_OK;
+    }
+    if (f.depth_writer) { VO_HIP(ctx, hipEventSynchronize(f.depth_writer)); f.depth_writer = nullptr; }
+    int rc = xfer_d2h(ctx, serial_out, f.mono_serial_dev, 4);
+    if (!rc && out) rc = xfer_d2h(ctx, out, f.mono_depth, (size_t)f.n_kp * 8);
+    if (rc) return rc;
+    return xfer_flush(ctx);
 }
 
 // =========================================================================================

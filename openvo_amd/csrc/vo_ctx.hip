@@ -193,6 +193,8 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         (void)hipEventCreateWithFlags(&f.ready, hipEventDisableTiming);
         DALLOC(f.kp_xy, (size_t)ctx->kp_cap * 2); DALLOC(f.kp_size, ctx->kp_cap); DALLOC(f.kp_angle, ctx->kp_cap);
         DALLOC(f.kp_resp, ctx->kp_cap); DALLOC(f.kp_oct, ctx->kp_cap); DALLOC(f.desc, (size_t)ctx->kp_cap * 32);
+        DALLOC(f.mono_depth, ctx->kp_cap); DALLOC(f.mono_serial_dev, 16);
+        if (dev_zero(f.mono_serial_dev, 64) != hipSuccess) { g_create_err = "clearing a slot's depth serial failed"; vo_destroy(ctx); return VO_E_HIP; }
     }
     ctx->stage_bytes = npx * 3;
     DALLOC(ctx->stage_in, ctx->stage_bytes * 2);
@@ -271,7 +273,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (int s = 0; s <= VO_NUM_SLOTS; s++) {
         FrameSlot& f = ctx->slots[s];
-        void* ps[] = { f.left, f.right, f.disp16, f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc };
+        void* ps[] = { f.left, f.right, f.disp16, f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc, f.mono_depth, f.mono_serial_dev };
         for (void* p : ps) if (p) (void)hipFree(p);
         if (f.ready) (void)hipEventDestroy(f.ready);
     }
@@ -681,6 +683,9 @@ int slot_before_overwrite(vo_ctx* ctx, FrameSlot& f)
     if (f.pending) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, f.ready, 0));
     for (hipEvent_t& r : f.readers)
         if (r) { VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, r, 0)); r = nullptr; }
+    // ... and a monocular pose step may still be writing its depths; what the slot held is gone with the refill
+    if (f.depth_writer) { VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, f.depth_writer, 0)); f.depth_writer = nullptr; }
+    f.mono_serial = 0;
     return VO_OK;
 }
 

@@ -50,6 +50,15 @@ struct FrameSlot {
     // asynchronous pose steps still reading this slot on their own streams (vo_pose_pair_begin): whoever overwrites the slot
     // orders itself behind them (borrowed events: they belong to the pose alternates and live as long as the context)
     hipEvent_t readers[2] = {nullptr, nullptr};
+    // monocular pose steps (vo_mono_pose_pair): depth of each keypoint along the optical axis, in units of the baseline of the step
+    // that wrote it (0 = none), kp_cap doubles; [0] of mono_serial_dev is that step's serial, stamped by its last kernel.  mono_serial
+    // is the host's copy: set when the step is enqueued, cleared by whatever refills the slot or re-extracts its keypoints (the
+    // device word may then be stale: a step is only ever handed depths whose serial the HOST copy still confirms).  depth_writer: the
+    // `done` event of the asynchronous step that writes the array (borrowed like `readers`): a later step's tail waits for it.
+    double* mono_depth = nullptr;
+    uint32_t* mono_serial_dev = nullptr;
+    uint32_t mono_serial = 0;
+    hipEvent_t depth_writer = nullptr;
     // look-ahead ORB: keypoints were extracted behind the SGBM on the engine's stream; the count lands
     // in the slot's pinned word once `ready` has fired
     int32_t* n_kp_host = nullptr;
@@ -240,9 +249,11 @@ struct vo_ctx {
     static const int N_MONO_ALT = VO_NUM_MONO_ASYNC;
     struct MonoAlt : AsyncAlt {
         bool want = false;                 // the record carries mask / q / t / xy of the second frame behind its header
+        bool pose = false;                 // a vo_mono_pose_pair_begin step: the record is a vo_mono_pose (ended by vo_mono_pose_pair_end)
         int nq = 0, nb = 0, min_n = 0;
     } mono_alt[N_MONO_ALT];
     int alt_next[2] = {0, 0};              // round-robin position per kind
+    uint32_t mono_serial_next = 0;         // serials handed to monocular pose steps so far (never 0: FrameSlot::mono_serial)
     AsyncAlt& alt(int kind, int k) { return kind == ALT_POSE ? static_cast<AsyncAlt&>(pose_alt[k]) : mono_alt[k]; }
     static int alt_count(int kind) { return kind == ALT_POSE ? N_POSE_ALT : N_MONO_ALT; }
     std::vector<const void*> big_lds;      // kernels this context has allowed more than 64 KB of dynamic LDS (lds_allow_big)

@@ -10,6 +10,11 @@ The relative pose (R, unit-length t) comes from E by the usual four-fold decompo
 host (a dozen flops per inlier); the translation scale is unobservable, so the chained trajectory uses
 |t| = 1 per accepted pair unless `scale` is supplied.
 
+pose_on_device=True moves that last step to the device as well (vo_mono_pose_pair: decomposition, cheirality vote over EVERY
+inlier, triangulation; the record shrinks from 136 KB to 224 bytes and no worker thread is used), and propagate_scale=True chains
+a consistent RELATIVE scale: every step leaves the depths of its inliers with the second frame's keypoints, and the next step
+measures the ratio of its baseline to that one's from the keypoints the two pairs share (lower median of the depth ratios).
+
 Parity: every device stage equals the build's own CPU restatement bit for bit (tests/test_gpu_configs.py);
 there is no openVO oracle for this class.
 """
@@ -64,12 +69,29 @@ def recover_pose(E, x1, x2):
 
 class MonoOdometer:
     def __init__(self, K, img_size, nfeatures=8000, match_threshold=0.8, ransac_iters=5000, ransac_threshold=1.0,
-                 min_inliers=30, seed=4321, device=0, context=None, solver=5, cross_check=False):
+                 min_inliers=30, seed=4321, device=0, context=None, solver=5, cross_check=False, pose_on_device=False,
+                 propagate_scale=False, min_parallax_deg=0.5, min_scale_tracks=20):
         """K: 3x3 intrinsics; img_size = (width, height).  ransac_threshold is the Sampson distance in pixels.
         solver: 5 = five-point minimal solver (what cv2.findEssentialMat runs), 8 = eight-point.
-        cross_check: the matches of the ratio test must also be mutual nearest neighbours (include/vo355.h)."""
+        cross_check: the matches of the ratio test must also be mutual nearest neighbours (include/vo355.h).
+        pose_on_device: (R, t) comes from the device with the pair step's record (no worker thread, no per-match arrays).
+        propagate_scale (needs pose_on_device): self.scale, the |t| of the last accepted pair, follows the baseline ratios the
+        steps measure; a pair that shares fewer than min_scale_tracks triangulated keypoints with its predecessor (or none: the
+        first pair, the pair after restart()) holds the scale (scale_status "held", else "tracked"; "anchored" when update() was
+        given a scale).  min_parallax_deg: depths of inliers whose two rays meet under a smaller angle are not kept (near the
+        epipole they are noise: without the gate the baseline ratio of a forward motion is off by 6 % in the median, with it 1 %)."""
         if solver not in (5, 8):
             raise ValueError("solver is 5 or 8")
+        if propagate_scale and not pose_on_device:
+            raise ValueError("propagate_scale needs pose_on_device")
+        if not (0.0 <= float(min_parallax_deg) < 90.0) or int(min_scale_tracks) < 1:
+            raise ValueError("min_parallax_deg is 0 .. 90, min_scale_tracks >= 1")
+        self.pose_on_device, self.propagate_scale = bool(pose_on_device), bool(propagate_scale)
+        self.min_scale_tracks = int(min_scale_tracks)
+        self._gate = float(np.sin(np.deg2rad(float(min_parallax_deg))) ** 2)
+        self.scale, self.scale_status = 1.0, "held"
+        self._ref_serial = 0             # serial of the accepted step that left its depths in the reference slot (0: none)
+        self._serial = {}                # (slot_a, slot_b) -> serial of a step begun and not yet collected
         if not isinstance(cross_check, (bool, np.bool_)):
             raise ValueError("cross_check must be True or False")
         self.cross_check = bool(cross_check)
@@ -82,8 +104,10 @@ class MonoOdometer:
         self.nfeatures, self.match_threshold = int(nfeatures), float(match_threshold)
         self.ransac_iters, self.ransac_threshold, self.min_inliers, self.seed = int(ransac_iters), float(ransac_threshold), int(min_inliers), int(seed)
         self._c_T_w = np.eye(4)          # world (= first frame) expressed in the current camera frame, like StereoOdometer
-        from concurrent.futures import ThreadPoolExecutor
-        self._pool, self._pending = ThreadPoolExecutor(1), []      # accepted pairs' pose recoveries run beside the next pairs' GPU work
+        self._pool, self._pending = None, []
+        if not self.pose_on_device:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(1)                     # accepted pairs' pose recoveries run beside the next pairs' GPU work
         self.last = None                 # dict of the last pair step
         self.skip_cause = ""
         # staged streams run ahead: the ORB extraction of the next frames is enqueued on look-ahead engines
@@ -105,7 +129,7 @@ class MonoOdometer:
     def _void_open(self):
         """Collect and drop every begun step (their premise -- which frame is the reference -- fell)."""
         for key in list(self._open):
-            self._ctx.mono_pair_end(self._open.pop(key), want_matches=True)
+            self._end(key)
             self.speculation["void"] += 1
 
     def reset_lookahead(self):
@@ -119,6 +143,7 @@ class MonoOdometer:
         if self._ref is not None:
             self._free.append(self._ref[0])
             self._ref = None
+        self._ref_serial = 0
         self.last = None
 
     def _drop_ahead(self):
@@ -135,15 +160,31 @@ class MonoOdometer:
         self._ctx.stage_pairs([(f, f) for f in frames])
         self._n_staged = len(frames)
 
-    def _begin(self, a, b):
-        t = self._ctx.mono_pair_begin(a, b, self.match_threshold, self.K4, self.ransac_iters, self.ransac_threshold, self.seed,
-                                      want_matches=True, solver=self.solver, cross_check=self.cross_check)
+    def _begin(self, a, b, prev_serial=0):
+        """prev_serial (device pose only): the serial of the step whose depths of slot a this one may measure its baseline against"""
+        if self.pose_on_device:
+            t, serial = self._ctx.mono_pose_pair_begin(a, b, self.match_threshold, self.K4, self.ransac_iters, self.ransac_threshold, self.seed,
+                                                       solver=self.solver, cross_check=self.cross_check,
+                                                       prev_serial=prev_serial if self.propagate_scale else 0,
+                                                       min_parallax_sin2=self._gate)
+            self._serial[(a, b)] = serial
+        else:
+            t = self._ctx.mono_pair_begin(a, b, self.match_threshold, self.K4, self.ransac_iters, self.ransac_threshold, self.seed,
+                                          want_matches=True, solver=self.solver, cross_check=self.cross_check)
         self._open[(a, b)] = t
         return t
 
-    def update(self, img, scale=1.0):
+    def _end(self, key):
+        """collect the open step `key` -> its result"""
+        if self.pose_on_device:
+            self._serial.pop(key, None)
+            return self._ctx.mono_pose_pair_end(self._open.pop(key))
+        return self._ctx.mono_pair_end(self._open.pop(key), want_matches=True)
+
+    def update(self, img, scale=None):
         """One frame (an image, or the index of a staged one); True when a relative pose was accepted (always True
-        for the very first frame)."""
+        for the very first frame).  scale: the length of this pair's translation (None: 1, or with propagate_scale what the
+        chain of baseline ratios gives; a number anchors the chain at this pair)."""
         ctx = self._ctx
         staged = isinstance(img, (int, np.integer))
         if staged and int(img) in self._ahead:
@@ -173,7 +214,8 @@ class MonoOdometer:
             return False
         if self._ref is None:
             self._void_open()
-            self._ref = (cur, ctx.download_keypoints_xy(cur).astype(np.float64))
+            self._ref = (cur, None if self.pose_on_device else ctx.download_keypoints_xy(cur).astype(np.float64))
+            self._ref_serial = 0
             return True
         prev, xy_prev = self._ref
         key = (prev, cur)
@@ -186,12 +228,14 @@ class MonoOdometer:
                 chain.add((a, self._ahead[j]))
                 a = self._ahead[j]
         for k2 in [k2 for k2 in self._open if k2 not in chain]:
-            ctx.mono_pair_end(self._open.pop(k2), want_matches=True)
+            self._end(k2)
             self.speculation["void"] += 1
         if key in self._open:
             self.speculation["used"] += 1
         else:
-            self._begin(prev, cur)
+            self._begin(prev, cur, self._ref_serial)
+        track = self.propagate_scale                              # each step begun ahead gets the serial of the step it takes for accepted
+        serial = self._serial.get(key, 0) if track else 0
         # the later pairs, on the assumption that every frame up to them is accepted: only what is already extracted (no wait)
         if staged and self.speculate:
             a, na = cur, n
@@ -206,17 +250,25 @@ class MonoOdometer:
                 if na < 8 or self._count[b] < 8:
                     break
                 if (a, b) not in self._open:
-                    self._begin(a, b)
+                    self._begin(a, b, serial)
                     self.speculation["begun"] += 1
+                if track:
+                    serial = self._serial.get((a, b), 0)
                 a, na = b, self._count[b]
-        r = ctx.mono_pair_end(self._open.pop(key), want_matches=True)
+        r = self._end(key)
         self.last = r
         need = 6 if self.solver == 5 else 8
         if r["matches"] < need or r["best_count"] < self.min_inliers:
             self.skip_cause = "matches" if r["matches"] < need else "inliers"
             self._void_open()            # the steps begun ahead took this frame for the next reference
             self._free.append(cur)
-            return False                 # the previous frame stays the reference
+            return False                 # the previous frame stays the reference (and its depths: the next ratio is against them)
+        if self.pose_on_device:
+            self._accept_device(r, scale)
+            self._free.append(prev)
+            self._ref = (cur, None)
+            return True
+        scale = 1.0 if scale is None else scale
         inl = np.nonzero(r["mask"])[0][:512]                      # a few hundred inliers decide the cheirality vote
         xy_cur = r["xy_b"][:n].astype(np.float64)
         xa, xb = xy_prev[r["q"][inl]], xy_cur[r["t"][inl]]
@@ -229,6 +281,24 @@ class MonoOdometer:
         self._free.append(prev)          # the new frame becomes the reference; the old slot is reused
         self._ref = (cur, xy_cur)
         return True
+
+    def _accept_device(self, r, scale):
+        """an accepted step's record -> self.scale, c_T_w"""
+        if self.propagate_scale:
+            rel = r["scale_rel"]
+            if scale is not None:
+                self.scale, self.scale_status = float(scale), "anchored"
+            elif not (r["flags"] & 4) and r["n_shared"] >= self.min_scale_tracks and np.isfinite(rel) and rel > 0.0:
+                self.scale, self.scale_status = self.scale * rel, "tracked"
+            else:
+                self.scale_status = "held"
+            s = self.scale
+        else:
+            s = 1.0 if scale is None else float(scale)
+        self._ref_serial = r["serial"]
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = r["R"], r["t"] * s
+        self._c_T_w = T @ self._c_T_w
 
     def _collect_one(self):
         fut, scale = self._pending.pop(0)
@@ -255,7 +325,8 @@ class MonoOdometer:
         """Collect the pending pose, stop the worker thread and release the native context (if this object created it)."""
         self._void_open()
         self._flush()
-        self._pool.shutdown(wait=True)
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
         if self._own_ctx:
             self._ctx.close()
 
