@@ -755,13 +755,27 @@ __global__ void __launch_bounds__(256) k_sgbm_we(const int16_t* __restrict__ C, 
 // exchange through LDS behind the kernel's only barrier.  Phase 2: k_sgbm_we's second pass, outward from the middle.  The same
 // 3 path steps per cell and the same bytes; a wave's chain is 1.5 W1 dependent steps instead of 3 W1 and twice as many waves
 // share the work (360 at config 2).  Needs W1 % 16 == 0 (otherwise k_sgbm_we).
+// One launch serves up to VO_MAX_SWEEP_GROUP pairs of one geometry (the members of a sweep group; a pair on its own is a table
+// of one): blockIdx.x names the member -- the table index is uniform per workgroup, its three pointers are scalar loads from
+// the kernel-argument segment -- and blockIdx.y the pair of row groups.  Members vary fastest in dispatch order, so the first
+// workgroups to start cover every member and all of them finish together.
+struct WeJob {
+    const int16_t* C;
+    int16_t* Swe;
+    int16_t* ckpt;
+};
+struct WeJobs { WeJob j[VO_MAX_SWEEP_GROUP]; };
+
 template <int NP, bool PAD>
-__global__ void __launch_bounds__(256) k_sgbm_we2(const int16_t* __restrict__ C, int16_t* __restrict__ Swe, int16_t* __restrict__ ckpt,
-                                                 SgbmGeom g, int16_t* __restrict__ dump)
+__global__ void __launch_bounds__(256) k_sgbm_we2(WeJobs jobs, SgbmGeom g, int16_t* __restrict__ dump)
 {
     __shared__ uint32_t s_x[4][NP][64];
+    const WeJob& job = jobs.j[blockIdx.x];
+    const int16_t* __restrict__ const C = job.C;
+    int16_t* __restrict__ const Swe = job.Swe;
+    int16_t* __restrict__ const ckpt = job.ckpt;
     const int lane = threadIdx.x & 63, row = lane >> 4, l16 = lane & 15, wv = threadIdx.x >> 6;
-    const int group = blockIdx.x * 2 + (wv >> 1);          // four rows
+    const int group = blockIdx.y * 2 + (wv >> 1);          // four rows
     const bool right = (wv & 1) != 0;                      // this wave's half
     const int y = group * 4 + row;
     const bool live = y < g.H;                             // (a group past the image still runs: the barrier below wants every wave)
@@ -1246,13 +1260,37 @@ __global__ void k_lr_median3(const int16_t* __restrict__ disp1, const int* __res
 // applies the left-right check in place, writes the 3x3 medians of its RB rows to the disparity image and labels their runs
 // (one wave per row, wave-level prefix maximum instead of the block-wide scan).  The two halo rows are recomputed by the
 // neighbouring blocks (25 % at RB = 8); disp1 / disp2 never exist in HBM.  Also reports the run's health (see k_sgbm_planes).
-__global__ void __launch_bounds__(512) k_sgbm_post_rows(const int* __restrict__ aux0, const int* __restrict__ aux1, SgbmGeom g, int RB,
-                                                       int16_t* __restrict__ dst, int do_ccl, int maxDiff,
-                                                       int* __restrict__ L, int* __restrict__ runlen, int* __restrict__ size,
-                                                       const int* __restrict__ ctlA, const int* __restrict__ ctlB, int* sweep_word, int gen,
-                                                       int* __restrict__ sweep_errs)
+// Like the W + E kernel, this one and the three k_ccl_* kernels behind it serve up to VO_MAX_SWEEP_GROUP pairs of one geometry
+// per launch (PostJobs: what differs between the members of a sweep group; a pair on its own is a table of one).  The member is
+// blockIdx.y here and in k_ccl_apply, blockIdx.z in k_ccl_vmerge / k_ccl_sizes: uniform per workgroup, scalar loads.
+struct PostJob {
+    const int* aux0;       // the sweep's winner records
+    const int* aux1;
+    int16_t* dst;          // the slot's disparity image
+    int* L;                // ccl_label, ccl_runlen, ccl_size of the member's workspace
+    int* runlen;
+    int* size;
+    const int* ctlA;       // the member's own control blocks (word 1: its sweep gave up)
+    const int* ctlB;
+    int* sweep_word;       // FrameSlot::sweep_word / disp_gen
+    int gen;
+};
+struct PostJobs { PostJob j[VO_MAX_SWEEP_GROUP]; };
+
+__global__ void __launch_bounds__(512) k_sgbm_post_rows(PostJobs jobs, SgbmGeom g, int RB, int do_ccl, int maxDiff, int* __restrict__ sweep_errs)
 {
     extern __shared__ __attribute__((aligned(16))) int s_post[];
+    const PostJob& job = jobs.j[blockIdx.y];
+    const int* __restrict__ const aux0 = job.aux0;
+    const int* __restrict__ const aux1 = job.aux1;
+    int16_t* __restrict__ const dst = job.dst;
+    int* __restrict__ const L = job.L;
+    int* __restrict__ const runlen = job.runlen;
+    int* __restrict__ const size = job.size;
+    const int* const ctlA = job.ctlA;
+    const int* const ctlB = job.ctlB;
+    int* const sweep_word = job.sweep_word;
+    const int gen = job.gen;
     const int W = g.W, H = g.H, R = RB + 2;
     int* const d2 = s_post;                                   // [R][W] disp2 keys; later [RB][W] int16 medians
     int16_t* const d1 = (int16_t*)(s_post + (size_t)R * W);   // [R][W] disp1, then the left-right-checked values
@@ -1457,9 +1495,12 @@ __global__ void __launch_bounds__(256) k_ccl_rows(const int16_t* __restrict__ im
 // component with maxSize + 1).  The wide regions of a disparity map -- whose unions all fought over the same
 // few roots -- drop out; the union-find is left with the small runs.
 #define RUN_TOUCH (1 << 30)
-__global__ void k_ccl_vmerge(const int16_t* __restrict__ img, int W, int H, int newVal, int maxDiff, int maxSize, int* __restrict__ L,
-                             int* __restrict__ runlen)
+__global__ void k_ccl_vmerge(PostJobs jobs, int W, int H, int newVal, int maxDiff, int maxSize)
 {
+    const PostJob& job = jobs.j[blockIdx.z];
+    const int16_t* __restrict__ const img = job.dst;
+    int* __restrict__ const L = job.L;
+    int* __restrict__ const runlen = job.runlen;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= W) return;
     for (int y = blockIdx.y; y + 1 < H; y += gridDim.y) {
@@ -1491,9 +1532,13 @@ __global__ void k_ccl_vmerge(const int16_t* __restrict__ img, int W, int H, int 
 
 // component sizes: every run head (recognised geometrically -- after unions a head's label may
 // point elsewhere) adds its run length to the component root
-__global__ void k_ccl_sizes(const int16_t* __restrict__ img, int W, int H, int newVal, int maxDiff, int maxSize,
-                            int* __restrict__ L, const int* __restrict__ runlen, int* __restrict__ size)
+__global__ void k_ccl_sizes(PostJobs jobs, int W, int H, int newVal, int maxDiff, int maxSize)
 {
+    const PostJob& job = jobs.j[blockIdx.z];
+    const int16_t* __restrict__ const img = job.dst;
+    int* __restrict__ const L = job.L;
+    const int* __restrict__ const runlen = job.runlen;
+    int* __restrict__ const size = job.size;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= W) return;
     for (int y = blockIdx.y; y < H; y += gridDim.y) {
@@ -1512,9 +1557,12 @@ __global__ void k_ccl_sizes(const int16_t* __restrict__ img, int W, int H, int n
     }
 }
 
-__global__ void k_ccl_apply(int16_t* __restrict__ img, int n, int newVal, int maxSize, const int* __restrict__ L,
-                            const int* __restrict__ size)
+__global__ void k_ccl_apply(PostJobs jobs, int n, int newVal, int maxSize)
 {
+    const PostJob& job = jobs.j[blockIdx.y];
+    int16_t* __restrict__ const img = job.dst;
+    const int* __restrict__ const L = job.L;
+    const int* __restrict__ const size = job.size;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const int r = L[i];
         if (r >= 0 && size[uf_find(L, r)] <= maxSize) img[i] = (int16_t)newVal;
@@ -1557,18 +1605,24 @@ static int ensure_S(vo_ctx* ctx, int vols)
 // ---- diagonal sweep (sgbm_diag.inc) ------------------------------------------------------------------------------------
 // The open sweep group of a context (vo_internal.h): what each member contributes to the one launch (its DiagJob, complete
 // when the member's early stages are enqueued) and what its back part needs.  Members share the kernel instance (`launch`:
-// one function per <NP, PAD, NWC>), the strip count and the geometry -- one kernel argument each.
+// one function per <NP, PAD, NWC>), the strip count and the geometry -- one kernel argument each.  The stages on either side
+// of the sweep travel with it: the member's W + E (`we`; `we_launch` is null where the geometry takes k_sgbm_we / k_sgbm_pair,
+// whose W + E ran with the member's front) and its post filters (`post`).
 static_assert(VO_MAX_SWEEP_GROUP == DG_MAXJOBS, "include/vo355.h promises what one sweep launch carries");
 struct SweepGroup {
     typedef int (*Launch)(vo_ctx*, const DiagJobs&, const SgbmGeom&);
+    typedef int (*WeLaunch)(vo_ctx*, const WeJobs&, int, const SgbmGeom&);
     struct Member {
         int engine;
         FrameSlot* f;
         int w, h;
         SgbmGeom g;
         DiagJob job;
+        WeJob we;
+        PostJob post;
     };
     Launch launch = nullptr;
+    WeLaunch we_launch = nullptr;
     int nstrips = 0;
     int n = 0;
     Member m[DG_MAXJOBS];
@@ -1577,8 +1631,20 @@ struct SweepGroup {
     bool want_defer = false, did_defer = false;
     Member cand;
     Launch cand_launch = nullptr;
+    WeLaunch cand_we_launch = nullptr;
     int cand_nstrips = 0;
 };
+
+// W + E of n pairs of one geometry (rows cut at their middle: W1 % 16 == 0) in one launch on the current stream
+template <int NP>
+static int we2_launch_jobs(vo_ctx* ctx, const WeJobs& jobs, int n, const SgbmGeom& g)
+{
+    const dim3 grid(n, div_up(div_up(g.H, 4), 2));
+    if (g.D != g.Dp) hipLaunchKernelGGL((k_sgbm_we2<NP, true>), grid, dim3(256), 0, ctx->stream, jobs, g, ctx->dump);
+    else hipLaunchKernelGGL((k_sgbm_we2<NP, false>), grid, dim3(256), 0, ctx->stream, jobs, g, ctx->dump);
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
 
 // one launch for jobs.n pairs on the current stream; ticket counter and strip timeline in job 0's control block
 template <int NP, bool PAD, int NWC, bool REV, bool WTA>
@@ -1694,15 +1760,27 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
         int16_t* const ck = ctx->ws->S + 2 * vol;
         int* const ctlA = ctx->ws->sw_ctl;
         int* const ctlB = ctx->ws->sw_ctl + ctx->sw_ctl_words / 2;
+        // a row cut at its middle (k_sgbm_we2: two waves per four rows, half the chain each) is the W + E that a sweep group
+        // carries for all its members in one launch: a deferring run leaves it to sweep_group_close (and `mid` below then
+        // stands behind the cost volume)
+        const bool cut = g.W1 % 16 == 0 && g.W1 >= 32 && !(ctx->tune_diag_dbg & 8);
+        SweepGroup* const G = ctx->grp;
+        const bool defer_we = cut && G && G->want_defer && !hh && !(ctx->tune_diag_dbg & 16);
+        if (G) G->cand_we_launch = nullptr;
         {
-            StageTimer t(ctx, VO_T_SGBM_AGG);
+            StageTimer t(ctx, VO_T_SGBM_AGG, defer_we ? 0 : 1);
             if (ctx->tune_diag_dbg & 8) {
+            } else if (cut) {
+                WeJobs wj;
+                memset(&wj, 0, sizeof(wj));
+                wj.j[0].C = ctx->ws->C; wj.j[0].Swe = Swe; wj.j[0].ckpt = ck;
+                if (defer_we) {
+                    G->cand.we = wj.j[0];
+                    G->cand_we_launch = &we2_launch_jobs<NP>;
+                } else if ((rc = we2_launch_jobs<NP>(ctx, wj, 1, g))) return rc;
             } else if (g.W1 % 8 == 0 && g.W1 >= 16) {
                 const int nw = div_up(g.H, 4);
-                if (g.W1 % 16 == 0 && g.W1 >= 32) {               // a row cut at its middle: two waves per four rows, half the chain each
-                    if (pad) hipLaunchKernelGGL((k_sgbm_we2<NP, true>), dim3(div_up(nw, 2)), dim3(256), 0, ctx->stream, ctx->ws->C, Swe, ck, g, ctx->dump);
-                    else hipLaunchKernelGGL((k_sgbm_we2<NP, false>), dim3(div_up(nw, 2)), dim3(256), 0, ctx->stream, ctx->ws->C, Swe, ck, g, ctx->dump);
-                } else if (pad) hipLaunchKernelGGL((k_sgbm_we<NP, true>), dim3(div_up(nw, 4)), dim3(256), 0, ctx->stream, ctx->ws->C, Swe, ck, g, ctx->dump);
+                if (pad) hipLaunchKernelGGL((k_sgbm_we<NP, true>), dim3(div_up(nw, 4)), dim3(256), 0, ctx->stream, ctx->ws->C, Swe, ck, g, ctx->dump);
                 else hipLaunchKernelGGL((k_sgbm_we<NP, false>), dim3(div_up(nw, 4)), dim3(256), 0, ctx->stream, ctx->ws->C, Swe, ck, g, ctx->dump);
             } else {
                 PathPlan pp = plan;                                  // the W / E pair alone: one line per image row
@@ -1754,6 +1832,8 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
 
 static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const uint8_t* srcR);
 static int sgbm_post(vo_ctx* ctx, FrameSlot& f, int w, int h, const SgbmGeom& g);
+static PostJob post_job(const vo_ctx* ctx, const FrameSlot& f);
+static int sgbm_post_launch(vo_ctx* ctx, const PostJobs& jobs, int n, const SgbmGeom& g, bool rows);
 // rows per block of k_sgbm_post_rows: (RB + 2) rows of disp1 (2 bytes per pixel) and disp2 keys (4 bytes) must fit in LDS
 static uint32_t pk_rep_host(int v) { return (uint32_t)(v & 0xFFFF) * 0x00010001u; }
 static int post_rows_per_block(int w) { return std::min(6, (int)(150 * 1024 / ((size_t)w * 6)) - 2); }
@@ -1767,6 +1847,7 @@ static int sgbm_run_done(vo_ctx* ctx)
     if (ctx->ws == &ctx->main_ws && ctx->ws->done) {
         VO_HIP(ctx, hipEventRecord(ctx->ws->done, ctx->stream));
         ctx->ws->done_valid = true;
+        ctx->ws->done_on_engine0 = false;
     }
     return VO_OK;
 }
@@ -1774,7 +1855,8 @@ static int sgbm_run_done(vo_ctx* ctx)
 // A run is three parts on one stream.  Front: planes, cost volume, W + E (the engine's `mid` event behind them).  Sweep: the
 // forward diagonal launch.  Back: the post filters (sgbm_post).  A synchronous call and a look-ahead run with group size 1
 // enqueue them back to back.  A look-ahead run with a group size above 1 (MODE_SGBM, the fused schedule) stops behind its
-// front and becomes a member of the open group; sweep_group_close enqueues the rest.
+// front -- behind the cost volume where the geometry takes k_sgbm_we2, whose one launch then serves the whole group -- and
+// becomes a member of the open group; sweep_group_close enqueues the rest.
 int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const uint8_t* srcR, bool* deferred)
 {
     int rc;
@@ -1782,7 +1864,8 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
     // a run on the main stream works in the main workspace: engine 0's member of the open group still needs what is in there
     if (ctx->cur_engine < 0 && sweep_group_has_engine(ctx, 0) && (rc = sweep_group_close(ctx, VO_GRP_CONSUMER))) return rc;
     const bool shared = ctx->ws == &ctx->main_ws;
-    if (shared && ctx->ws->done_valid) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ws->done, 0));
+    // (a sweep group's record on its closing stream: engine 0's stream stands behind it through `swept` -- no second wait)
+    if (shared && ctx->ws->done_valid && !(ctx->cur_engine == 0 && ctx->ws->done_on_engine0)) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ws->done, 0));
     if (++ctx->sweep_gen_next <= 0) ctx->sweep_gen_next = 1;     // this run's generation: never 0 (FrameSlot::sweep_word)
     f.disp_gen = ctx->sweep_gen_next;
     const bool defer = deferred && ctx->cur_engine >= 0 && sweep_group_size(ctx) > 1 && ctx->sg.set && ctx->sg.ur < 100 && ctx->sg.mode == 0 &&
@@ -1799,13 +1882,15 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
         if (!rc && G->did_defer) {
             G->did_defer = false;
             // one launch = one kernel instance, one strip count, one geometry: a pair that differs starts a group of its own
-            if (G->n > 0 && (G->n >= DG_MAXJOBS || G->launch != G->cand_launch || G->nstrips != G->cand_nstrips || memcmp(&G->m[0].g, &G->cand.g, sizeof(SgbmGeom))) &&
+            if (G->n > 0 && (G->n >= DG_MAXJOBS || G->launch != G->cand_launch || G->we_launch != G->cand_we_launch || G->nstrips != G->cand_nstrips ||
+                             memcmp(&G->m[0].g, &G->cand.g, sizeof(SgbmGeom))) &&
                 (rc = sweep_group_close(ctx, VO_GRP_OTHER)))
                 return rc;
             SweepGroup::Member& m = G->m[G->n++];
             m = G->cand;
             m.engine = ctx->cur_engine; m.f = &f; m.w = w; m.h = h;
-            G->launch = G->cand_launch; G->nstrips = G->cand_nstrips;
+            m.post = post_job(ctx, f);
+            G->launch = G->cand_launch; G->we_launch = G->cand_we_launch; G->nstrips = G->cand_nstrips;
             f.in_group = true;
             *deferred = true;
             return VO_OK;
@@ -1841,12 +1926,16 @@ struct MemberScope {
     MemberScope& operator=(const MemberScope&) = delete;
 };
 
-// back part of one member on its engine's stream (the current one): post filters, the ORB chain, the slot's `ready` record
-static int sweep_member_back(vo_ctx* ctx, SweepGroup::Member& m)
+// back part of one member on its engine's stream (the current one): the post filters where the group's launches have not
+// carried them, the ORB chain, the slot's `ready` record
+static int sweep_member_back(vo_ctx* ctx, SweepGroup::Member& m, bool post_done)
 {
     FrameSlot& f = *m.f;
-    int rc = sgbm_post(ctx, f, m.w, m.h, m.g);
-    if (!rc) rc = sgbm_run_done(ctx);
+    int rc = VO_OK;
+    if (!post_done) {
+        rc = sgbm_post(ctx, f, m.w, m.h, m.g);
+        if (!rc) rc = sgbm_run_done(ctx);
+    }
     if (!rc && ctx->la_orb) {
         const int* q = ctx->la_orb_params;
         rc = orb_slot_enqueue(ctx, f, q[0], q[1], q[2], q[3]);
@@ -1868,32 +1957,59 @@ int sweep_group_close(vo_ctx* ctx, int why)
     int rc = VO_OK;
     {
         MemberScope scope(ctx);
-        // the member submitted last closes: its stream waits for the others' early stages, carries the launch (its control
-        // block holds the ticket counter: its next front, which clears the block, is ordered behind the launch there) ...
+        // the member submitted last closes: its stream waits for the others' early stages, carries the group's launches -- W + E
+        // (where the fronts left it to the group), the sweep, the post filters: one launch each for all members -- and its
+        // control block holds the sweep's ticket counter (its next front, which clears the block, is ordered behind the
+        // launch there) ...
         SweepGroup::Member& last = G->m[n - 1];
         scope.enter(last.engine);
         DiagJobs jobs;
+        WeJobs we;
+        PostJobs post;
         memset(&jobs, 0, sizeof(jobs));
+        memset(&we, 0, sizeof(we));
+        memset(&post, 0, sizeof(post));
         jobs.n = n; jobs.nstrips = G->nstrips;
-        jobs.j[0] = last.job;
+        jobs.j[0] = last.job; we.j[0] = last.we; post.j[0] = last.post;
+        bool main_member = last.engine == 0;         // engine 0's member works in the main workspace
         for (int i = 0; i + 1 < n && !rc; i++) {
-            jobs.j[i + 1] = G->m[i].job;
+            jobs.j[i + 1] = G->m[i].job; we.j[i + 1] = G->m[i].we; post.j[i + 1] = G->m[i].post;
+            main_member |= G->m[i].engine == 0;
             const vo_ctx::SgbmWs& a = ctx->ws_alt[G->m[i].engine];
             if (!a.mid_valid || hipStreamWaitEvent(ctx->stream, a.mid, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "sweep group: waiting for a member's early stages failed");
+        }
+        if (!rc && G->we_launch) {
+            StageTimer t(ctx, VO_T_SGBM_AGG, n);
+            rc = G->we_launch(ctx, we, n, last.g);
         }
         if (!rc) {
             StageTimer t(ctx, VO_T_SGBM_WTA, n);
             rc = G->launch(ctx, jobs, last.g);
         }
+        // (an image too wide for the LDS rows of k_sgbm_post_rows: the members' own streams carry their separate passes)
+        const bool post_here = post_rows_per_block(last.g.W) >= 1;
+        if (!rc && post_here) {
+            if (!(ctx->tune_diag_dbg & 32)) {
+                StageTimer t(ctx, VO_T_SGBM_POST, n);
+                rc = sgbm_post_launch(ctx, post, n, last.g, true);
+            }
+            // the main workspace's run ends here, on this stream: a synchronous run on the main stream waits for this record
+            if (!rc && main_member && ctx->main_ws.done) {
+                if (hipEventRecord(ctx->main_ws.done, ctx->stream) == hipSuccess) { ctx->main_ws.done_valid = true; ctx->main_ws.done_on_engine0 = false; }
+                else rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+            }
+        }
         hipEvent_t const swept = ctx->ws_alt[last.engine].swept;
         if (!rc && n > 1 && hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
-        // ... and every member finishes on its own engine's stream behind it
-        if (!rc) rc = sweep_member_back(ctx, last);
+        // ... and every member finishes on its own engine's stream behind them
+        if (!rc) rc = sweep_member_back(ctx, last, post_here);
         for (int i = 0; i + 1 < n && !rc; i++) {
             scope.enter(G->m[i].engine);
             if (hipStreamWaitEvent(ctx->stream, swept, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed");
-            if (!rc) rc = sweep_member_back(ctx, G->m[i]);
+            if (!rc) rc = sweep_member_back(ctx, G->m[i], post_here);
         }
+        // (engine 0's stream now stands behind `swept`, or is the one that carried the record)
+        if (!rc && post_here && main_member) ctx->main_ws.done_on_engine0 = true;
     }
     if (rc) {
         // no member's slot may hand anything out (some of them may even be complete: the caller cannot tell which)
@@ -1991,28 +2107,58 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
     return sgbm_post(ctx, f, w, h, g);
 }
 
+// what the post filters of a run in the current workspace into slot `f` work on
+static PostJob post_job(const vo_ctx* ctx, const FrameSlot& f)
+{
+    PostJob j;
+    j.aux0 = ctx->ws->rec; j.aux1 = ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64;
+    j.dst = f.disp16;
+    j.L = ctx->ws->ccl_label; j.runlen = ctx->ws->ccl_runlen; j.size = ctx->ws->ccl_size;
+    j.ctlA = ctx->ws->sw_ctl; j.ctlB = ctx->ws->sw_ctl + ctx->sw_ctl_words / 2;
+    j.sweep_word = f.sweep_word; j.gen = f.disp_gen;
+    return j;
+}
+
+// post filters of n pairs of one geometry on the current stream, one launch per kernel.  rows: from the diagonal sweep's records
+// (sub-pixel disp1 + disp2 -> left-right check -> medianBlur(3) -> labelled runs: k_sgbm_post_rows); otherwise the disparity
+// images and their labelled runs exist already and only the three filterSpeckles launches follow.
+static int sgbm_post_launch(vo_ctx* ctx, const PostJobs& jobs, int n, const SgbmGeom& g, bool rows)
+{
+    const SgbmEff& e = ctx->sg;
+    const int w = g.W, h = g.H, npix = w * h;
+    const int newVal = g.invalid16, maxDiff = 16 * e.speckleRange;
+    const bool speckle = e.speckleWindow > 0;
+    if (rows) {
+        // rows per block: (RB + 2) rows of disp1 (2 bytes) and disp2 keys (4 bytes) must fit in LDS
+        const int rb = post_rows_per_block(w);
+        if (int rca = lds_allow_big(ctx, (const void*)k_sgbm_post_rows)) return rca;
+        hipLaunchKernelGGL(k_sgbm_post_rows, dim3(div_up(h, rb), n), dim3(512), (size_t)(rb + 2) * w * 6, ctx->stream, jobs, g, rb, speckle ? 1 : 0, maxDiff,
+                           ctx->d_sweep_errs);
+    }
+    if (speckle) {
+        hipLaunchKernelGGL(k_ccl_vmerge, dim3(div_up(w, 256), std::min(h, 128), n), dim3(256), 0, ctx->stream, jobs, w, h, newVal, maxDiff, e.speckleWindow);
+        hipLaunchKernelGGL(k_ccl_sizes, dim3(div_up(w, 256), std::min(h, 128), n), dim3(256), 0, ctx->stream, jobs, w, h, newVal, maxDiff, e.speckleWindow);
+        hipLaunchKernelGGL(k_ccl_apply, dim3(std::min(div_up(npix, 256), 1024), n), dim3(256), 0, ctx->stream, jobs, npix, newVal, e.speckleWindow);
+    }
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
 // back part of a run: the sweep's records (or the unfused schedule's disp_tmp) -> f.disp16
 static int sgbm_post(vo_ctx* ctx, FrameSlot& f, int w, int h, const SgbmGeom& g)
 {
     const SgbmEff& e = ctx->sg;
     int16_t* const d_disp = f.disp16;
-    const int n = w * h;
     const bool fused = g.ur < 100;               // the schedule follows from the parameters alone (launch_agg)
     if (!(ctx->tune_diag_dbg & 32)) {
         StageTimer t(ctx, VO_T_SGBM_POST);
         const int newVal = g.invalid16, maxDiff = 16 * e.speckleRange;
         const bool speckle = e.speckleWindow > 0;
-        // rows per block of the fused kernel: (RB + 2) rows of disp1 (2 bytes) and disp2 keys (4 bytes) must fit in LDS
-        const int rb = post_rows_per_block(w);
-        if (fused && rb >= 1) {
-            // records of the diagonal sweep -> sub-pixel disp1 + disp2 -> left-right check -> medianBlur(3) -> labelled runs: one launch
-            if (int rca = lds_allow_big(ctx, (const void*)k_sgbm_post_rows)) return rca;
-            const int* const ctlA = ctx->ws->sw_ctl;
-            const int* const ctlB = ctx->ws->sw_ctl + ctx->sw_ctl_words / 2;
-            hipLaunchKernelGGL(k_sgbm_post_rows, dim3(div_up(h, rb)), dim3(512), (size_t)(rb + 2) * w * 6, ctx->stream, ctx->ws->rec,
-                               ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64, g, rb, d_disp, speckle ? 1 : 0, maxDiff, ctx->ws->ccl_label,
-                               ctx->ws->ccl_runlen, ctx->ws->ccl_size, ctlA, ctlB, f.sweep_word, f.disp_gen, ctx->d_sweep_errs);
-        } else {
+        PostJobs jobs;
+        memset(&jobs, 0, sizeof(jobs));
+        jobs.j[0] = post_job(ctx, f);
+        const bool rows = fused && post_rows_per_block(w) >= 1;
+        if (!rows) {
             if (fused) {
                 // (an image too wide for the fused kernel's LDS rows: the same steps as separate passes over HBM)
                 hipLaunchKernelGGL(k_sgbm_fin, dim3(div_up(g.W1, 256), g.H), dim3(256), 0, ctx->stream, ctx->ws->rec, ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64,
@@ -2021,13 +2167,9 @@ static int sgbm_post(vo_ctx* ctx, FrameSlot& f, int w, int h, const SgbmGeom& g)
             hipLaunchKernelGGL(k_lr_median3, dim3(div_up(w, 256), h), dim3(256), 0, ctx->stream, ctx->ws->disp_tmp, ctx->ws->ccl_size, g, d_disp);
             if (speckle)
                 hipLaunchKernelGGL(k_ccl_rows, dim3(h), dim3(256), 0, ctx->stream, d_disp, w, newVal, maxDiff, ctx->ws->ccl_label, ctx->ws->ccl_runlen, ctx->ws->ccl_size);
+            VO_CHECK_LAUNCH(ctx);
         }
-        if (speckle) {
-            hipLaunchKernelGGL(k_ccl_vmerge, dim3(div_up(w, 256), std::min(h, 128)), dim3(256), 0, ctx->stream, d_disp, w, h, newVal, maxDiff, e.speckleWindow, ctx->ws->ccl_label, ctx->ws->ccl_runlen);
-            hipLaunchKernelGGL(k_ccl_sizes, dim3(div_up(w, 256), std::min(h, 128)), dim3(256), 0, ctx->stream, d_disp, w, h, newVal, maxDiff, e.speckleWindow, ctx->ws->ccl_label, ctx->ws->ccl_runlen, ctx->ws->ccl_size);
-            hipLaunchKernelGGL(k_ccl_apply, dim3(std::min(div_up(n, 256), 1024)), dim3(256), 0, ctx->stream, d_disp, n, newVal, e.speckleWindow, ctx->ws->ccl_label, ctx->ws->ccl_size);
-        }
-        VO_CHECK_LAUNCH(ctx);
+        return sgbm_post_launch(ctx, jobs, 1, g, rows);
     }
     return VO_OK;
 }

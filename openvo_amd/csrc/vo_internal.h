@@ -116,12 +116,14 @@ struct vo_ctx {
         uint32_t sw_tag = 0;
         hipEvent_t done = nullptr;       // end of the latest SGBM run in this workspace (any stream)
         bool done_valid = false;
+        bool done_on_engine0 = false;    // ... and look-ahead engine 0's stream is already ordered behind that record
         bool ready = false;
         OrbWs orb;
         uint8_t* pinned = nullptr;       // host staging of vo_prefetch_pair (two raw images)
         hipEvent_t h2d_done = nullptr;   // the copies out of `pinned` have finished
         bool h2d_valid = false;
-        hipEvent_t mid = nullptr;        // the early stages (cost volume, W + E) of the engine's latest pair have finished
+        hipEvent_t mid = nullptr;        // the early stages of the engine's latest pair have finished: cost volume and W + E, or -- a member
+                                         // of a sweep group whose W + E travels with the group's launches -- the cost volume
         bool mid_valid = false;
         hipEvent_t swept = nullptr;      // the sweep launch of the latest group this engine closed has finished
     } ws_alt[MAX_ENGINES];           // [0]: only its ORB scratch / staging / events are used (engine 0 works in main_ws)
@@ -141,7 +143,8 @@ struct vo_ctx {
     int next_engine = 0;
     // Sweep groups (sgbm.hip): with fewer hardware queues than streams a pair's kernels queue up behind other pairs' on the same
     // queue, and the diagonal sweep -- a latency chain that keeps ~28 CUs busy for a millisecond -- is the longest of them.  The
-    // look-ahead path then collects up to B pairs whose early stages are enqueued (the open group) and sweeps them in ONE launch.
+    // look-ahead path then collects up to B pairs whose early stages are enqueued (the open group) and sweeps them in ONE launch,
+    // with one launch of W + E before it and one of each post filter behind it for all of them.
     // hw_queues: GPU_MAX_HW_QUEUES as the process sees it (unset: HIP's 4).  sweep_group_req: VO_SWEEP_GROUP / vo_set_sweep_group,
     // 0 = follow the queue budget (sweep_group_size).  grp_closed: groups closed so far, by cause (VO_GRP_*).
     int hw_queues = 4;
