@@ -491,6 +491,11 @@ class Context:
             self._ck(self._lib.vo_set_lookahead_orb(self._h, 1, *key))
             self._la_orb = key
 
+    def lookahead_orb_off(self):
+        """The look-ahead engines stop extracting keypoints behind each prefetched SGBM."""
+        self._ck(self._lib.vo_set_lookahead_orb(self._h, 0, 0, 0, 0, 0))
+        self._la_orb = None
+
     def orb_slot(self, slot, nfeatures, mask_mode, min_d16=0, max_d16=0):
         cap = self.kp_cap
         b = self._kp_buffers(cap)

@@ -7,30 +7,11 @@ import numpy as np
 import pytest
 
 from openvo_amd import _native
+from tests.group_inputs import Refs, check, pair, params
 
 pytestmark = pytest.mark.gpu
 
 SLOT0 = 2
-
-
-def _params(ndisp=64, speckle=100):
-    return dict(minDisparity=0, numDisparities=ndisp, blockSize=5, P1=200, P2=800, disp12MaxDiff=1, preFilterCap=63,
-                uniquenessRatio=10, speckleWindowSize=speckle, speckleRange=2)
-
-
-def _pair(w, h, k):
-    """textured pair number k of a shape: noise over a smooth ramp, the right image shifted by a disparity that differs from
-    pair to pair and steps in mid-image (two surfaces: the speckle filter and the left-right check have something to remove)"""
-    rng = np.random.default_rng(1000 * w + 10 * h + k)
-    base = rng.integers(0, 256, (h, w + 64), dtype=np.uint8)
-    base = ((base.astype(np.int32) + np.arange(w + 64)[None, :] * 3 + np.arange(h)[:, None] * 5) & 255).astype(np.uint8)
-    d_near, d_far = 5 + 2 * k, 3 + k
-    L = base[:, 32:32 + w].copy()
-    R = np.empty_like(L)
-    R[:h // 2] = base[:h // 2, 32 + d_near:32 + d_near + w]
-    R[h // 2:] = base[h // 2:, 32 + d_far:32 + d_far + w]
-    R[(k * 7) % h, ::3] ^= 0x55                     # a few mismatching pixels
-    return L, R
 
 
 @pytest.fixture(scope="module")
@@ -40,45 +21,17 @@ def ctx():
     c.close()
 
 
-class _Refs:
-    """oracle disparity and the disparity of the pair swept alone, computed once per (shape, parameters, pair)"""
-
-    def __init__(self, oracle):
-        self.oracle, self.memo = oracle, {}
-
-    def get(self, ctx, w, h, k, p):
-        key = (w, h, k, p["numDisparities"], p["speckleWindowSize"])
-        if key not in self.memo:
-            L, R = _pair(w, h, k)
-            ref = self.oracle.sgbm_compute(L, R, p, 0)
-            assert (ref >= 0).mean() > 0.2                             # the pair really produces disparities
-            ctx.set_sgbm(p)
-            assert ctx.set_sweep_group(1) == 1
-            ctx.prefetch_pair(SLOT0, L, R, True)
-            assert ctx.sweep_group_stats()["open"] == 0                # group size 1 never defers
-            self.memo[key] = (ref, _disp16(ctx, SLOT0, w, h))
-        return self.memo[key]
-
-
 @pytest.fixture(scope="module")
 def refs(oracle):
-    return _Refs(oracle)
-
-
-def _disp16(ctx, slot, w, h):
-    return np.rint(ctx.download_disparity_f32(slot, (h, w)) * 16).astype(np.int16)
-
-
-def _check(ctx, want, slot, w, h, what):
-    ref, alone = want
-    got = _disp16(ctx, slot, w, h)
-    assert np.array_equal(alone, ref), (what, "alone vs oracle", int((alone != ref).sum()))
-    assert np.array_equal(got, ref), (what, "group vs oracle", int((got != ref).sum()))
-    assert np.array_equal(got, alone), (what, "group vs alone")
+    """oracle disparity and the disparity of the pair swept alone, once per (shape, parameters, pair); the oracle's output must
+    show that the pair is mostly valid and that both post filters removed pixels (group_inputs.Coverage)"""
+    return Refs(oracle)
 
 
 def _prepare(ctx, refs, jobs, p):
     """references first (they change the group size), then the parameters and the group size of the run under test"""
+    for (w, h) in dict.fromkeys((w, h) for (w, h, _) in jobs):       # (what holds per group: for the members of each shape)
+        refs.cov.group(w, h, [k for (jw, jh, k) in jobs if (jw, jh) == (w, h)], p)
     want = [refs.get(ctx, w, h, k, p) for (w, h, k) in jobs]
     ctx.set_sgbm(p)
     return want
@@ -91,59 +44,59 @@ def _run_group(ctx, refs, w, h, p, B, first=0):
     assert ctx.set_sweep_group(B) == B
     before = ctx.sweep_group_stats()
     for i, (_, _, k) in enumerate(jobs):
-        ctx.prefetch_pair(SLOT0 + i, *_pair(w, h, k), True)
+        ctx.prefetch_pair(SLOT0 + i, *pair(w, h, k, p["numDisparities"]), True)
         assert ctx.sweep_group_stats()["open"] == (i + 1 if B > 1 and i + 1 < B else 0)
     after = ctx.sweep_group_stats()
     assert after["full"] - before["full"] == (1 if B > 1 else 0) and after["open"] == 0
     for i in reversed(range(B)):                                       # (read in another order than submitted)
-        _check(ctx, want[i], SLOT0 + i, w, h, (w, h, B, i))
+        check(ctx, want[i], SLOT0 + i, w, h, (w, h, B, i))
     assert ctx.sgbm_sweep_status() == 0
 
 
-@pytest.mark.parametrize("speckle", [100, 0])
+@pytest.mark.parametrize("speckle", [150, 0])
 @pytest.mark.parametrize("B", [1, 2, 3, 5, 12])
 def test_cut_row_geometry_every_group_size(ctx, refs, B, speckle):
     """160 x 50, D = 64: W1 = 96 takes k_sgbm_we2; 50 rows are 13 row groups -- the last workgroup of W + E holds a dead group
     behind its barrier -- and a ragged last block of post rows.  With and without the speckle filter's three launches."""
-    _run_group(ctx, refs, 160, 50, _params(64, speckle), B)
+    _run_group(ctx, refs, 160, 50, params(64, speckle), B)
 
 
 def test_padded_disparity_range(ctx, refs):
     """144 x 50, D = 48: Dp = 64, the padded instantiation; W1 = 96"""
-    _run_group(ctx, refs, 144, 50, _params(48), 3)
+    _run_group(ctx, refs, 144, 50, params(48), 3)
 
 
 @pytest.mark.parametrize("w", [168, 164])
 def test_widths_whose_w_plus_e_stays_with_the_member(ctx, refs, w):
     """W1 = 104 (k_sgbm_we) and W1 = 100 (k_sgbm_pair): W + E runs per member with its front; the post filters still batch"""
-    _run_group(ctx, refs, w, 40, _params(64), 3)
+    _run_group(ctx, refs, w, 40, params(64), 3)
 
 
 def test_groups_closed_by_a_consumer_by_a_flush_and_by_a_geometry_change(ctx, refs):
-    p = _params(64)
+    p = params(64)
     w, h = 160, 50
     # a consumer after 2 of 4 members
     want = _prepare(ctx, refs, [(w, h, 3), (w, h, 4)], p)
     assert ctx.set_sweep_group(4) == 4
     s0 = ctx.sweep_group_stats()
-    ctx.prefetch_pair(SLOT0, *_pair(w, h, 3), True)
-    ctx.prefetch_pair(SLOT0 + 1, *_pair(w, h, 4), True)
+    ctx.prefetch_pair(SLOT0, *pair(w, h, 3), True)
+    ctx.prefetch_pair(SLOT0 + 1, *pair(w, h, 4), True)
     assert ctx.sweep_group_stats()["open"] == 2
-    _check(ctx, want[0], SLOT0, w, h, "consumer 0")
+    check(ctx, want[0], SLOT0, w, h, "consumer 0")
     s1 = ctx.sweep_group_stats()
     assert s1["consumer"] - s0["consumer"] == 1 and s1["open"] == 0
-    _check(ctx, want[1], SLOT0 + 1, w, h, "consumer 1")
+    check(ctx, want[1], SLOT0 + 1, w, h, "consumer 1")
     # lookahead_flush after 3 of 4
     want = _prepare(ctx, refs, [(w, h, k) for k in (5, 6, 7)], p)
     assert ctx.set_sweep_group(4) == 4
     for i, k in enumerate((5, 6, 7)):
-        ctx.prefetch_pair(SLOT0 + i, *_pair(w, h, k), True)
+        ctx.prefetch_pair(SLOT0 + i, *pair(w, h, k), True)
     assert ctx.sweep_group_stats()["open"] == 3
     ctx.lookahead_flush()
     s2 = ctx.sweep_group_stats()
     assert s2["flush"] - s1["flush"] == 1 and s2["open"] == 0
     for i, k in enumerate((5, 6, 7)):
-        _check(ctx, want[i], SLOT0 + i, w, h, ("flush", i))
+        check(ctx, want[i], SLOT0 + i, w, h, ("flush", i))
     # the geometry changes in mid-stream: two pairs of 160 x 50, then two of 176 x 50 (W1 = 112, k_sgbm_we2 as well) --
     # the third submission closes the first group, the two geometries never share a launch
     jobs = [(160, 50, 8), (160, 50, 9), (176, 50, 0), (176, 50, 1)]
@@ -151,14 +104,14 @@ def test_groups_closed_by_a_consumer_by_a_flush_and_by_a_geometry_change(ctx, re
     assert ctx.set_sweep_group(4) == 4
     s3 = ctx.sweep_group_stats()
     for i, (jw, jh, k) in enumerate(jobs):
-        ctx.prefetch_pair(SLOT0 + i, *_pair(jw, jh, k), True)
+        ctx.prefetch_pair(SLOT0 + i, *pair(jw, jh, k), True)
         assert ctx.sweep_group_stats()["open"] == (1, 2, 1, 2)[i]
     s4 = ctx.sweep_group_stats()
     assert s4["other"] - s3["other"] == 1 and s4["full"] == s3["full"]
     ctx.lookahead_flush()
     assert ctx.sweep_group_stats()["open"] == 0
     for i, (jw, jh, k) in enumerate(jobs):
-        _check(ctx, want[i], SLOT0 + i, jw, jh, ("geometry", i))
+        check(ctx, want[i], SLOT0 + i, jw, jh, ("geometry", i))
     assert ctx.sgbm_sweep_status() == 0
 
 
@@ -166,27 +119,27 @@ def test_main_workspace_member_then_a_synchronous_run_at_once(oracle, ctx, refs)
     """Look-ahead engine 0 works in the main workspace.  Its member's run ends with the group's post launches on the closing
     member's stream; a synchronous run on the main stream, started right behind the close, must wait for exactly that -- with
     engine 0's member a non-closing one (engines 0, 1) and the closing one (engines 2, 0)."""
-    p = _params(64)
+    p = params(64)
     w, h = 160, 50
     c = _native.Context(0, 192, 64, 64, 500, engines=3)                # a fresh context: its first pair goes to engine 0
     try:
         want = _prepare(ctx, refs, [(w, h, k) for k in (0, 1, 2, 3)], p)     # (references on the module's context)
-        sync = [_pair(w, h, 10), _pair(w, h, 11)]
+        sync = [pair(w, h, 10), pair(w, h, 11)]
         sync_ref = [oracle.sgbm_compute(L, R, p, 0) for (L, R) in sync]
         c.set_sgbm(p)
         assert c.set_sweep_group(2) == 2
-        c.prefetch_pair(SLOT0, *_pair(w, h, 0), True)                  # engine 0
-        c.prefetch_pair(SLOT0 + 1, *_pair(w, h, 1), True)              # engine 1 closes
+        c.prefetch_pair(SLOT0, *pair(w, h, 0), True)                  # engine 0
+        c.prefetch_pair(SLOT0 + 1, *pair(w, h, 1), True)              # engine 1 closes
         assert c.sweep_group_stats()["open"] == 0
         got_sync0 = c.sgbm_compute_host(*sync[0])
-        c.prefetch_pair(SLOT0 + 2, *_pair(w, h, 2), True)              # engine 2
-        c.prefetch_pair(SLOT0 + 3, *_pair(w, h, 3), True)              # engine 0 closes
+        c.prefetch_pair(SLOT0 + 2, *pair(w, h, 2), True)              # engine 2
+        c.prefetch_pair(SLOT0 + 3, *pair(w, h, 3), True)              # engine 0 closes
         assert c.sweep_group_stats()["open"] == 0
         got_sync1 = c.sgbm_compute_host(*sync[1])
         assert c.sweep_group_stats()["full"] == 2
         assert np.array_equal(got_sync0, sync_ref[0]) and np.array_equal(got_sync1, sync_ref[1])
         for i in range(4):
-            _check(c, want[i], SLOT0 + i, w, h, ("engine 0", i))
+            check(c, want[i], SLOT0 + i, w, h, ("engine 0", i))
         assert c.sgbm_sweep_status() == 0
     finally:
         c.close()
