@@ -183,9 +183,31 @@ int vo_bf_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, 
  * parity unpinned (no OpenCV to compare against where this was written; tests/test_crosscheck_host.py pins it wherever a cv2
  * is importable).  a(j) comes out of the SAME kernel launch as the kNN-2 (column minima of the distance tiles): the matcher
  * runs once, not twice.  Cross-check needs nq <= 65535 (VO_E_CAP otherwise).
- * match_flags of the _ex entries below: bit 0 = VO_MATCH_CROSSCHECK; every other bit must be 0.  The entries without _ex are
- * the same calls with match_flags = 0, unchanged. */
+ * match_flags of the _ex entries below: bit 0 = VO_MATCH_CROSSCHECK, bit 1 = VO_MATCH_WINDOW; every other bit must be 0.  The
+ * entries without _ex are the same calls with match_flags = 0, unchanged.
+ * Window (VO_MATCH_WINDOW), a second EXTENSION of the matcher [stereo_odometer.py:165 "# TODO config" at the match step]: train j
+ * is a candidate of query i only if |xq_i - xt_j| <= rx and |yq_i - yt_j| <= ry, evaluated in float32 on the keypoint positions the
+ * two slots hold (ROI-cropped pixels); a NaN coordinate is in no window.  idx / dist are the two lexicographically smallest
+ * (distance, train index) AMONG THE CANDIDATES, {-1, INT32_MAX} where there are fewer than two -- a query with fewer than two
+ * candidates gives no match in any consumer (the ratio test needs both).  With VO_MATCH_CROSSCHECK as well, a(j) is taken over the
+ * queries that have j in their window (the test is symmetric): a match must be mutual within the window.  rx = ry = 0 is legal
+ * (equal positions only); a window larger than the image gives the plain kernel's result bit for bit.  The same launch as the
+ * plain kNN-2: the window is a mask on its keys, and tiles of 16 trains whose bounding box is out of reach of a wave's 64 queries
+ * are skipped (keypoints are stored in (octave, y, x) order, so most are).
+ * The radii are context state (vo_set_match_window), read when a step is ENQUEUED: a step begun ahead keeps the window it was
+ * begun with.  VO_MATCH_WINDOW without a window set is VO_E_ARG.  The ratio test inside a window is laxer than over the whole
+ * image (the runner-up is the best of fewer candidates). */
 #define VO_MATCH_CROSSCHECK 1
+#define VO_MATCH_WINDOW 2
+/* finite radii >= 0 (VO_E_ARG otherwise: negative, NaN, inf) */
+int vo_set_match_window(vo_ctx* ctx, float rx, float ry);
+/* back to no window; VO_E_STATE when none is set (like every call made out of order) */
+int vo_clear_match_window(vo_ctx* ctx);
+/* the windowed kNN-2 on host arrays: xy_q / xy_t are nq / nt (x, y) float pairs, the radii are arguments (the context's window is
+ * neither read nor changed); match_flags may add VO_MATCH_CROSSCHECK, and only then are mutual (nq bytes, required) and t_best
+ * (nt x 2, may be NULL) written, as by vo_bf_knn2_hamming_mutual */
+int vo_bf_knn2_hamming_window(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, const float* xy_q, const float* xy_t,
+                              float rx, float ry, int match_flags, int32_t* idx, int32_t* dist, uint8_t* mutual, int32_t* t_best);
 /* vo_bf_knn2_hamming's idx / dist of the same launch, plus mutual (nq bytes: 1 = query i passes the cross-check) and, when
  * t_best is not NULL, t_best (nt x 2 int32): {a(j), its distance}, {-1, INT32_MAX} when there is no query */
 int vo_bf_knn2_hamming_mutual(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx, int32_t* dist,
@@ -423,7 +445,8 @@ int vo_measure_copy(vo_ctx* ctx, int64_t bytes, int reps, int nontemporal, doubl
  * arrays are the context's match scratch; nothing the caller holds changes.  Semantics of the kernel: stereo_odometer.py:163. */
 int vo_measure_knn(vo_ctx* ctx, int slot_a, int slot_b, int reps, double* us_per_launch);
 /* the same for either form of the kernel: match_flags 0 = the plain kNN-2, VO_MATCH_CROSSCHECK = kNN-2 + column minima (and the
- * reset of the column words on the stream in front of each launch, which is part of what a cross-check launch costs) */
+ * reset of the column words on the stream in front of each launch, which is part of what a cross-check launch costs),
+ * VO_MATCH_WINDOW = inside the context's window around the two slots' keypoint positions */
 int vo_measure_knn_ex(vo_ctx* ctx, int slot_a, int slot_b, int reps, int match_flags, double* us_per_launch);
 /* the shader clock the GPU holds right now (MHz): one wave counts its cycles (s_memtime) against the 100 MHz wall counter
  * (s_memrealtime) for `micros` microseconds on the context's main stream; synchronous.  Measurement aid (bench.py records it

@@ -40,6 +40,7 @@ SYMBOLS = [
     "vo_set_sweep_group", "vo_lookahead_flush", "vo_sweep_group_stats",
     "vo_pnp_pair", "vo_pnp_pair_begin", "vo_pnp_pair_end",
     "vo_recover_pose", "vo_mono_pose_pair", "vo_mono_pose_pair_begin", "vo_mono_pose_pair_end", "vo_download_mono_depth",
+    "vo_set_match_window", "vo_clear_match_window", "vo_bf_knn2_hamming_window",
 ]
 
 
@@ -203,6 +204,9 @@ def lib():
         L.vo_mono_pair_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, ci]
         L.vo_mono_pair_begin_ex.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
         L.vo_measure_knn_ex.argtypes = [vp, ci, ci, ci, ci, vp]
+        L.vo_set_match_window.argtypes = [vp, ctypes.c_float, ctypes.c_float]
+        L.vo_clear_match_window.argtypes = [vp]
+        L.vo_bf_knn2_hamming_window.argtypes = [vp, vp, ci, vp, ci, vp, vp, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
         if hasattr(L, "vo_pnp_pair"):               # (likewise: an older build has no fused PnP step)
             L.vo_pnp_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
             L.vo_pnp_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
@@ -233,11 +237,32 @@ def lib():
 
 
 VO_MATCH_CROSSCHECK = 1
+VO_MATCH_WINDOW = 2
 
 
 def _flags(cross_check):
     """match_flags of the _ex entries"""
     return VO_MATCH_CROSSCHECK if cross_check else 0
+
+
+def window_radii(window, what="window"):
+    """None | number (both radii) | (rx, ry) -> None | (rx, ry) as the float32 values the kernel compares with; ValueError for
+    anything else, negative or non-finite"""
+    if window is None:
+        return None
+    try:
+        if isinstance(window, (bool, str, bytes)):
+            raise TypeError
+        w = (window, window) if np.ndim(window) == 0 else tuple(window)
+        if len(w) != 2:
+            raise TypeError
+        with np.errstate(over="ignore"):              # (too large for float32: inf, refused below)
+            rx, ry = float(np.float32(w[0])), float(np.float32(w[1]))
+    except (TypeError, ValueError):
+        raise ValueError("%s is None, a radius or a pair (rx, ry) of pixels, not %r" % (what, window))
+    if not (np.isfinite(rx) and np.isfinite(ry) and rx >= 0 and ry >= 0):
+        raise ValueError("%s: the radii must be finite and >= 0, not %r" % (what, window))
+    return rx, ry
 
 
 def _p(a):
@@ -266,6 +291,7 @@ class Context:
                 raise ValueError("engines must be >= 1")
             self.set_engines(engines)
         self._la_orb = None
+        self._window = None          # the match window this wrapper last set in the context
         self.device, self.max_w, self.max_h, self.max_disp, self.max_kp = device, max_w, max_h, max_disp, max_kp
         self.kp_cap = max_kp * 2 + 1024
 
@@ -556,6 +582,36 @@ class Context:
         self._ck(self._lib.vo_bf_knn2_hamming(self._h, _p(q), len(q), _p(t), len(t), _p(idx), _p(dist)))
         return idx, dist
 
+    def _mflags(self, cross_check, window):
+        """match_flags of the _ex entries; a window goes into the context first (only when it differs from the last one set)"""
+        f = _flags(cross_check)
+        w = window_radii(window)
+        if w is not None:
+            if w != self._window:
+                self._ck(self._lib.vo_set_match_window(self._h, w[0], w[1]))
+                self._window = w
+            f |= VO_MATCH_WINDOW
+        return f
+
+    def bf_knn2_window(self, q, t, xy_q, xy_t, window, cross_check=False):
+        """kNN-2 among the trains inside the window (rx, ry) around each query's position: |xq - xt| <= rx and |yq - yt| <= ry in
+        float32, a NaN coordinate in no window -> (idx, dist), {-1, INT32_MAX} where a query has fewer than two candidates; with
+        cross_check (idx, dist, mutual, t_best) as bf_knn2_mutual, mutual within the window."""
+        w = window_radii(window)
+        if w is None:
+            raise ValueError("bf_knn2_window needs a window")
+        q, t = _c(q, np.uint8).reshape(-1, 32), _c(t, np.uint8).reshape(-1, 32)
+        xy_q, xy_t = _c(xy_q, np.float32).reshape(-1, 2), _c(xy_t, np.float32).reshape(-1, 2)
+        if len(xy_q) != len(q) or len(xy_t) != len(t):
+            raise ValueError("one position per descriptor")
+        idx = np.empty((len(q), 2), np.int32)
+        dist = np.empty((len(q), 2), np.int32)
+        mutual = np.empty(len(q), np.uint8) if cross_check else None
+        t_best = np.empty((len(t), 2), np.int32) if cross_check else None
+        self._ck(self._lib.vo_bf_knn2_hamming_window(self._h, _p(q), len(q), _p(t), len(t), _p(xy_q), _p(xy_t), w[0], w[1],
+                                                     VO_MATCH_WINDOW | _flags(cross_check), _p(idx), _p(dist), _p(mutual), _p(t_best)))
+        return (idx, dist, mutual, t_best) if cross_check else (idx, dist)
+
     def bf_knn2_mutual(self, q, t):
         """bf_knn2 plus the cross-check of the same launch -> (idx, dist, mutual, t_best): mutual[i] = 1 when the nearest train of
         query i has query i as ITS nearest query (ties -> lower index both ways); t_best (nt x 2) = that nearest query of every
@@ -592,13 +648,13 @@ class Context:
         self._ck(self._lib.vo_bilinear_at(self._h, _p(img3d), w, h, _p(xy), len(xy), _p(out), _p(st)))
         return out, st
 
-    def point_clouds(self, slot_a, slot_b, ratio, cross_check=False):
+    def point_clouds(self, slot_a, slot_b, ratio, cross_check=False, window=None):
         cap = self.kp_cap
         q, t = np.empty(cap, np.int32), np.empty(cap, np.int32)
         pa, pb = np.empty((cap, 3), np.float32), np.empty((cap, 3), np.float32)
         sa, sb = np.empty(cap, np.uint8), np.empty(cap, np.uint8)
         m = ctypes.c_int(0)
-        self._ck(self._lib.vo_point_clouds_ex(self._h, slot_a, slot_b, float(ratio), _flags(cross_check), _p(q), _p(t), _p(pa), _p(pb),
+        self._ck(self._lib.vo_point_clouds_ex(self._h, slot_a, slot_b, float(ratio), self._mflags(cross_check, window), _p(q), _p(t), _p(pa), _p(pb),
                                               _p(sa), _p(sb), cap, ctypes.byref(m)))
         m = m.value
         return q[:m], t[:m], pa[:m], pb[:m], sa[:m], sb[:m]
@@ -608,17 +664,17 @@ class Context:
         """(counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4) as the pose entries expect them on entry"""
         return np.zeros(4, np.int32), np.ones(2, np.int32), np.full((3, 4), np.nan), np.full((3, 4), np.nan)
 
-    def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False):
+    def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False, window=None):
         """Fused match + ratio + 3-D lookup + clique filter + outlier pass + Umeyama for two slots.
         Returns (counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4)."""
         out = self._pose_out()
-        self._ck(self._lib.vo_pose_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), int(min_matches),
+        self._ck(self._lib.vo_pose_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), int(min_matches),
                                            float(rigidity_thr), float(outlier_thr), *[_p(a) for a in out]))
         return out
 
-    def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False):
+    def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False, window=None):
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_pose_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), int(min_matches),
+        self._ck(self._lib.vo_pose_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), int(min_matches),
                                                  float(rigidity_thr), float(outlier_thr), ctypes.byref(t)))
         return t.value
 
@@ -660,7 +716,7 @@ class Context:
         out.update((k, (v if k == "xy_b" else v[:int(c3[0])]).copy()) for k, v in arrays.items())
         return out
 
-    def mono_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False):
+    def mono_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False, window=None):
         """kNN-2 + ratio + essential-matrix RANSAC between two slots' keypoints, all on the device, one sync.
         -> dict(E 3x3, matches M, best_iter, best_count[, mask, q, t of length M])."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
@@ -668,7 +724,7 @@ class Context:
         c3 = np.zeros(3, np.int32)
         cap = self.kp_cap
         arrays = dict(mask=np.zeros(cap, np.uint8), q=np.zeros(cap, np.int32), t=np.zeros(cap, np.int32)) if want_matches else {}
-        self._ck(self._lib.vo_mono_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_mono_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
                                            int(seed) & 0xFFFFFFFF, int(solver), _p(E), _p(c3), _p(arrays.get("mask")), _p(arrays.get("q")),
                                            _p(arrays.get("t")), cap))
         return self._mono_result(E, c3, **arrays)
@@ -678,11 +734,11 @@ class Context:
         self._ck(self._lib.vo_slot_ready(self._h, int(slot), ctypes.byref(r)))
         return bool(r.value)
 
-    def mono_pair_begin(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False):
+    def mono_pair_begin(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, want_matches=False, solver=8, cross_check=False, window=None):
         """mono_pair in two halves (several pairs in flight): -> ticket for mono_pair_end."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_mono_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_mono_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
                                               int(seed) & 0xFFFFFFFF, int(solver), int(bool(want_matches)), ctypes.byref(t)))
         return t.value
 
@@ -739,21 +795,21 @@ class Context:
         return out
 
     def mono_pose_pair(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, solver=8, cross_check=False, prev_serial=0,
-                       min_parallax_sin2=0.0):
+                       min_parallax_sin2=0.0, window=None):
         """mono_pair with the pose recovered on the device (vo_mono_pose_pair): -> the record as a dict (MonoPose.as_dict); the
         depths stay in slot_b under the record's serial."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         rec = MonoPose()
-        self._ck(self._lib.vo_mono_pose_pair(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_mono_pose_pair(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
                                              int(seed) & 0xFFFFFFFF, int(solver), int(prev_serial), float(min_parallax_sin2), ctypes.byref(rec)))
         return rec.as_dict()
 
     def mono_pose_pair_begin(self, slot_a, slot_b, ratio, K4, iters=5000, thr=1.0, seed=4321, solver=8, cross_check=False, prev_serial=0,
-                             min_parallax_sin2=0.0):
+                             min_parallax_sin2=0.0, window=None):
         """mono_pose_pair in two halves: -> (ticket for mono_pose_pair_end, the step's serial)."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         t, serial = ctypes.c_int(-1), ctypes.c_uint32(0)
-        self._ck(self._lib.vo_mono_pose_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters),
+        self._ck(self._lib.vo_mono_pose_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters),
                                                    float(thr), int(seed) & 0xFFFFFFFF, int(solver), int(prev_serial), float(min_parallax_sin2),
                                                    ctypes.byref(t), ctypes.byref(serial)))
         return t.value, serial.value
@@ -812,17 +868,27 @@ class Context:
         for two slots, all on the device, one synchronisation (vo_pnp_pair).  -> dict(matches M, n usable correspondences,
         best_iter, best_count, flags, Rt 3x4, Rt_refined 3x4 (valid when refine_status == 0), refine_status, refine_steps
         [, mask, q, t of length n])."""
+        return self.pnp_pair_window(slot_a, slot_b, ratio, K4, None, iters, thr, seed, refine, want_matches, cross_check)
+
+    def pnp_pair_window(self, slot_a, slot_b, ratio, K4, window, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False, cross_check=False):
+        """pnp_pair with the kNN-2 inside the match window (None | (rx, ry), see bf_knn2_window).  A method of its own: the
+        signature of pnp_pair is pinned by the callers that bind against it."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         head, arrays = self._pnp_out(want_matches)
-        self._ck(self._lib.vo_pnp_pair(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_pnp_pair(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
                                        int(seed) & 0xFFFFFFFF, int(refine), *[_p(a) for a in head + arrays], self.kp_cap))
         return self._pnp_result(head, arrays)
 
     def pnp_pair_begin(self, slot_a, slot_b, ratio, K4, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False, cross_check=False):
         """pnp_pair in two halves -> a ticket for pnp_pair_end (a pose ticket: VO_NUM_POSE_ASYNC bounds both kinds together)."""
+        return self.pnp_pair_begin_window(slot_a, slot_b, ratio, K4, None, iters, thr, seed, refine, want_matches, cross_check)
+
+    def pnp_pair_begin_window(self, slot_a, slot_b, ratio, K4, window, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False,
+                              cross_check=False):
+        """pnp_pair_window in two halves -> a ticket for pnp_pair_end"""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_pnp_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), _flags(cross_check), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_pnp_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
                                              int(seed) & 0xFFFFFFFF, int(refine), int(bool(want_matches)), ctypes.byref(t)))
         return t.value
 
@@ -887,11 +953,11 @@ class Context:
         self._ck(self._lib.vo_measure_copy(self._h, int(nbytes), int(reps), 1 if nontemporal else 0, ctypes.byref(g)))
         return g.value
 
-    def measure_knn(self, slot_a, slot_b, reps=20, cross_check=False):
+    def measure_knn(self, slot_a, slot_b, reps=20, cross_check=False, window=None):
         """microseconds per launch of the Hamming kNN-2 kernel on two slots' descriptors (`reps` launches between two events);
         cross_check=True times the cross-check form of the kernel (with the reset of its column words)."""
         g = ctypes.c_double(0.0)
-        self._ck(self._lib.vo_measure_knn_ex(self._h, int(slot_a), int(slot_b), int(reps), _flags(cross_check), ctypes.byref(g)))
+        self._ck(self._lib.vo_measure_knn_ex(self._h, int(slot_a), int(slot_b), int(reps), self._mflags(cross_check, window), ctypes.byref(g)))
         return g.value
 
     def shader_clock(self, micros=200):

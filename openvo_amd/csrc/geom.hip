@@ -322,8 +322,9 @@ template __global__ void k_ratio_compact<true>(const int32_t*, const int32_t*, i
 extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int32_t* q_idx, int32_t* t_idx,
                                   float* pts_a, float* pts_b, uint8_t* status_a, uint8_t* status_b, int cap, int* m_out)
 {
-    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !m_out || (match_flags & ~VO_MATCH_CROSSCHECK))
+    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !m_out)
         return vo_fail(ctx, VO_E_ARG, "vo_point_clouds: bad argument");
+    if (int rcf = match_flags_check(ctx, match_flags, "vo_point_clouds")) return rcf;
     const int cross = match_flags & VO_MATCH_CROSSCHECK;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
@@ -336,7 +337,7 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
+        rc = match_knn2_slots(ctx, a, b, match_flags);
         if (rc) return rc;
         auto kern = cross ? k_ratio_compact<true> : k_ratio_compact<false>;
         hipLaunchKernelGGL(kern, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
@@ -1316,10 +1317,10 @@ size_t pose_ws_bytes(int nq)
 
 // k_pose_solve writes the finished PoseOut record into host_out (pinned host memory the device can address) itself.  No host
 // synchronisation, no copy command.
-static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, int min_matches, double rigidity_thr,
+static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, int min_matches, double rigidity_thr,
                         double outlier_thr, void* host_out)
 {
-    const int nq = a.n_kp;
+    const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     // workspace: bit matrix + ncons + filtered point sets + residuals + result.  match_ws_alloc sizes it
     // for kp_cap query keypoints, so the branch below (a device-wide synchronisation) is never taken on the hot path
     const int words = (nq + 63) / 64;
@@ -1346,7 +1347,7 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
+        rc = match_knn2_slots(ctx, a, b, match_flags);
         if (rc) return rc;
     }
     {
@@ -1407,8 +1408,9 @@ extern "C" int vo_pose_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio
                                double outlier_thr, int32_t* counts4 /*M,n1,n2,flags*/, int32_t* rc2 /*first,final*/,
                                double* T1_12, double* T2_12)
 {
-    if (!counts4 || !rc2 || !T2_12 || (match_flags & ~VO_MATCH_CROSSCHECK)) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair: bad argument");
+    if (!counts4 || !rc2 || !T2_12) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair: bad argument");
     int rc = pose_check(ctx, slot_a, slot_b);
+    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_pose_pair");
     if (rc) return rc;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
@@ -1417,7 +1419,7 @@ extern "C" int vo_pose_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio
     counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
     rc2[0] = rc2[1] = 1;
     if (a.n_kp == 0) return VO_OK;
-    if ((rc = pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, min_matches, rigidity_thr, outlier_thr, ctx->pinned))) return rc;
+    if ((rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, ctx->pinned))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;
     if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // never a pose from an undefined disparity
     pose_unpack(ctx->pinned, counts4, rc2, T1_12, T2_12);
@@ -1433,8 +1435,9 @@ extern "C" int vo_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, i
 extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int min_matches, double rigidity_thr,
                                      double outlier_thr, int* ticket_out)
 {
-    if (!ticket_out || (match_flags & ~VO_MATCH_CROSSCHECK)) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair_begin: bad argument");
+    if (!ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair_begin: bad argument");
     int rc = pose_check(ctx, slot_a, slot_b);
+    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_pose_pair_begin");
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     FrameSlot& a = ctx->slots[slot_a];
@@ -1447,7 +1450,7 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     rec->rc1 = rec->rc2 = 1;
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
-        rc = pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, min_matches, rigidity_thr, outlier_thr, rec);
+        rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, rec);
     }
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;

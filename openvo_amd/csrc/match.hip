@@ -58,10 +58,15 @@ __device__ __forceinline__ void merge2(uint32_t& a0, uint32_t& a1, uint32_t b0, 
 
 #define KNN_WAVES 8              // waves (= groups of 64 queries) per workgroup: they share one slice of the train set in LDS
 #define KNN_CHUNK 32            // tiles of 16 train descriptors expanded into LDS at a time: 32 x 4 KB + their bit counts = 130 KB
-template <bool CROSS>
+// WINDOW (DESIGN 4d''): train j is a candidate of query i only if |xq_i - xt_j| <= rx and |yq_i - yt_j| <= ry (float32, NaN in no
+// window); every other element's key is 0xFFFFFFFF, in the row state and in the column minimum alike.  A tile of 16 trains whose
+// bounding box cannot reach the bounding box of the wave's 64 queries is skipped before its LDS reads and MFMAs.
+#define ROW_ROR_F(v, c) __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x120 + (c), 0xf, 0xf, false))
+template <bool CROSS, bool WINDOW>
 __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __restrict__ q, int nq, const uint8_t* __restrict__ t, int nt, int splits,
                                                int tiles_per_split, int ngroups, unsigned long long* __restrict__ part, int* __restrict__ tickets,
-                                               int32_t* __restrict__ idx, int32_t* __restrict__ dist, uint32_t* __restrict__ colmin)
+                                               int32_t* __restrict__ idx, int32_t* __restrict__ dist, uint32_t* __restrict__ colmin,
+                                               const float2* __restrict__ xy_q, const float2* __restrict__ xy_t, float rx, float ry)
 {
     const int lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
     const int gblock = blockIdx.x / splits, split = blockIdx.x - gblock * splits;
@@ -81,6 +86,8 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
     uint4* const s_B = s_lds4;                                           // [chunk_tiles][4][64]
     int* const s_tn = (int*)(s_lds4 + (size_t)chunk_tiles * 256);        // [chunk_tiles * 16]: |t| + 256, or 0x7FFF past the end
     uint32_t* const s_col = (uint32_t*)(s_tn + chunk_tiles * 16);         // CROSS: [chunk_tiles * 16] column minima of the chunk
+    float2* const s_txy = (float2*)(s_col + (CROSS ? chunk_tiles * 16 : 0));   // WINDOW: [chunk_tiles * 16] train positions (NaN past the end)
+    float4* const s_box = (float4*)(s_txy + chunk_tiles * 16);            // WINDOW: [chunk_tiles] {min x, max x, min y, max y} of a tile's trains
 
     v4i A[4][4];
 #pragma unroll
@@ -112,6 +119,26 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
     for (int s = 0; s < 4; s++)
 #pragma unroll
         for (int r = 0; r < 4; r++) k0[s][r] = k1[s][r] = 0xFFFFFFFFu;
+    // WINDOW: the position of query 16 s + 4 g + r, the row that k0[s][r] belongs to (rows past nq repeat query nq - 1 with ITS
+    // position), and the bounding box of the wave's 64 queries (a NaN coordinate is in no window and in no box)
+    float2 pq[4][4];
+    float qx0 = __builtin_inff(), qx1 = -__builtin_inff(), qy0 = __builtin_inff(), qy1 = -__builtin_inff();
+    if constexpr (WINDOW) {
+#pragma unroll
+        for (int s = 0; s < 4; s++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float2 p = xy_q[max(0, min(q0 + 16 * s + 4 * g + r, nq - 1))];
+                pq[s][r] = p;
+                if (p.x == p.x) { qx0 = fminf(qx0, p.x); qx1 = fmaxf(qx1, p.x); }
+                if (p.y == p.y) { qy0 = fminf(qy0, p.y); qy1 = fmaxf(qy1, p.y); }
+            }
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {               // the four lane groups hold 16 queries each
+            qx0 = fminf(qx0, __shfl_xor(qx0, o, 64)); qx1 = fmaxf(qx1, __shfl_xor(qx1, o, 64));
+            qy0 = fminf(qy0, __shfl_xor(qy0, o, 64)); qy1 = fmaxf(qy1, __shfl_xor(qy1, o, 64));
+        }
+    }
 
     for (int c0 = t0; c0 < t1; c0 += KNN_CHUNK) {
         const int c1 = min(t1, c0 + KNN_CHUNK);
@@ -143,11 +170,67 @@ __global__ void __launch_bounds__(KNN_WAVES * 64) k_bf_knn2(const uint8_t* __res
                 for (int m = 0; m < 4; m++) dst[m * 64 + gg * 16] = make_uint4((uint32_t)e[m].x, (uint32_t)e[m].y, (uint32_t)e[m].z, (uint32_t)e[m].w);
             }
             s_tn[i] = j < nt ? __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w) + 256 : 0x7FFF;
+            if constexpr (WINDOW) {
+                // the 16 trains of a tile sit in one DPP row (i and the trip count are multiples of 16 apart: a row is whole or idle)
+                const float nan = __builtin_nanf("");
+                const float2 p = j < nt ? xy_t[j] : make_float2(nan, nan);
+                s_txy[i] = p;
+                float x0 = p.x == p.x ? p.x : __builtin_inff(), x1 = p.x == p.x ? p.x : -__builtin_inff();
+                float y0 = p.y == p.y ? p.y : __builtin_inff(), y1 = p.y == p.y ? p.y : -__builtin_inff();
+#define ROW_BOX(c) x0 = fminf(x0, ROW_ROR_F(x0, c)); x1 = fmaxf(x1, ROW_ROR_F(x1, c)); y0 = fminf(y0, ROW_ROR_F(y0, c)); y1 = fmaxf(y1, ROW_ROR_F(y1, c));
+                ROW_BOX(8) ROW_BOX(4) ROW_BOX(2) ROW_BOX(1)
+#undef ROW_BOX
+                if ((i & 15) == 0) s_box[i >> 4] = make_float4(x0, x1, y0, y1);
+            }
         }
         __syncthreads();
         if (!active) continue;
         const uint4* const s_w = s_B + lane;
         const int* const s_n = s_tn + col;
+        if constexpr (WINDOW) {
+            // One bit per tile of the chunk whose box can reach the wave's box (lane L tests tile c0 + L; a ballot is wave-uniform).
+            // Conservative under rounding: float subtraction is monotone, so fl(min - max) > r implies |xq - xt| > r for every
+            // pair drawn from the two boxes.  An empty box is (+inf, -inf): unreachable.
+            bool reach = false;
+            if (lane < c1 - c0) {
+                const float4 bx = s_box[lane];
+                reach = !(bx.x - qx1 > rx || qx0 - bx.y > rx || bx.z - qy1 > ry || qy0 - bx.w > ry);
+            }
+            uint32_t todo = (uint32_t)__ballot(reach);
+            while (todo) {
+                const int tl = __builtin_ctz(todo);          // tile c0 + tl
+                todo &= todo - 1;
+                v4i B[4];
+#pragma unroll
+                for (int m = 0; m < 4; m++) { const uint4 u = s_w[tl * 256 + m * 64]; B[m] = (v4i){ (int)u.x, (int)u.y, (int)u.z, (int)u.w }; }
+                const int tn = s_n[tl * 16];                 // |t| + 256, or 0x7FFF past the end of the train set (its position is NaN)
+                const float2 pt = s_txy[tl * 16 + col];
+                const uint32_t base = ((uint32_t)tn << 16) | (uint32_t)(((c0 + tl) * 16 + col) & 0xFFFF);
+                uint32_t cm = 0xFFFFFFFFu;
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+                    v4i acc = { 0, 0, 0, 0 };
+#pragma unroll
+                    for (int m = 0; m < 4; m++) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[s][m], B[m], acc, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const bool in = fabsf(pq[s][r].x - pt.x) <= rx && fabsf(pq[s][r].y - pt.y) <= ry;
+                        const uint32_t key = in ? base + ((uint32_t)acc[r] << 17) : 0xFFFFFFFFu;
+                        k1[s][r] = med3_u32(k0[s][r], k1[s][r], key);
+                        k0[s][r] = min(k0[s][r], key);
+                        if constexpr (CROSS) cm = min(cm, in ? cb[s][r] + ((uint32_t)acc[r] << 17) : 0xFFFFFFFFu);
+                    }
+                }
+                if constexpr (CROSS) {
+                    const auto x = __builtin_amdgcn_permlane32_swap(cm, cm, false, false);
+                    cm = min(x[0], x[1]);
+                    const auto y = __builtin_amdgcn_permlane16_swap(cm, cm, false, false);
+                    cm = min(y[0], y[1]);
+                    if (lane < 16) atomicMin(s_col + tl * 16 + col, cm);
+                }
+            }
+            continue;
+        }
         v4i Bn[4];
 #pragma unroll
         for (int m = 0; m < 4; m++) { const uint4 u = s_w[m * 64]; Bn[m] = (v4i){ (int)u.x, (int)u.y, (int)u.z, (int)u.w }; }
@@ -281,8 +364,14 @@ void match_ws_free(vo_ctx::MatchWs& m)
 // (zeroed once by match_ws_alloc; every launch leaves them zero), then the per-train column words of the cross-check.
 // cross != 0: the same launch also leaves, for every train descriptor j, the key of its nearest query in match_colmin(d_dist)
 // (reset on the launching stream first; read by the consumers of the next launches, never inside this one)
-int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx, int32_t* d_dist, int cross)
+// xy_q / xy_t (both or neither; nullptr = no window): the keypoint positions behind the descriptors, nq and nt float pairs in
+// device memory; the windowed kernel then takes the radii by value (a launch keeps the window it was enqueued with)
+int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx, int32_t* d_dist, int cross, const float* xy_q,
+               const float* xy_t, float rx, float ry)
 {
+    const bool window = xy_q != nullptr;
+    if (window && (!xy_t || !(rx >= 0.f) || !(ry >= 0.f) || rx > 3.4028234e38f || ry > 3.4028234e38f))
+        return vo_fail(ctx, VO_E_ARG, "windowed kNN: needs both position arrays and finite radii >= 0");
     if (nt > 65535) return vo_fail(ctx, VO_E_CAP, "train set of %d descriptors exceeds 65535", nt);
     if (cross && nq > 65535) return vo_fail(ctx, VO_E_CAP, "cross-check: query set of %d descriptors exceeds 65535", nq);
     if (cross && nt > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "cross-check: train set of %d descriptors exceeds capacity %d", nt, ctx->kp_cap);
@@ -297,8 +386,9 @@ int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt
     unsigned long long* part = (unsigned long long*)(d_dist + 2 * capq);
     int* tickets = (int*)(part + (size_t)VO_KNN_SPLITS * capq);
     uint32_t* colmin = cross ? match_colmin(d_dist, ctx->kp_cap) : nullptr;
-    const size_t lds = (size_t)std::min(per, KNN_CHUNK) * 16 * (256 + 4 + (cross ? 4 : 0));
-    auto kern = cross ? k_bf_knn2<true> : k_bf_knn2<false>;
+    // per train: the expanded descriptor, its bit count (+ a column word) (+ its position); WINDOW: one box per tile behind them
+    const size_t lds = (size_t)std::min(per, KNN_CHUNK) * (16 * (256 + 4 + (cross ? 4 : 0) + (window ? 8 : 0)) + (window ? 16 : 0));
+    auto kern = window ? (cross ? k_bf_knn2<true, true> : k_bf_knn2<false, true>) : (cross ? k_bf_knn2<true, false> : k_bf_knn2<false, false>);
     if (lds > 64 * 1024)
         if (int rca = lds_allow_big(ctx, (const void*)kern)) return rca;
     // (the column words are reset on the stream that launches: a null-stream memset does not order itself against the
@@ -306,17 +396,49 @@ int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt
     if (cross && nt > 0) VO_HIP(ctx, hipMemsetAsync(colmin, 0xFF, (size_t)nt * 4, ctx->stream));
     StageTimer tk(ctx, VO_T_KNN);
     hipLaunchKernelGGL(kern, dim3(gblocks * splits), dim3(KNN_WAVES * 64), lds, ctx->stream, dq, nq, dt, nt, splits, per, groups, part, tickets, d_idx,
-                       d_dist, colmin);
+                       d_dist, colmin, (const float2*)xy_q, (const float2*)xy_t, rx, ry);
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }
 
+extern "C" int vo_set_match_window(vo_ctx* ctx, float rx, float ry)
+{
+    if (!ctx) return VO_E_ARG;
+    if (!(rx >= 0.f) || !(ry >= 0.f) || rx > 3.4028234e38f || ry > 3.4028234e38f)
+        return vo_fail(ctx, VO_E_ARG, "vo_set_match_window: the radii must be finite and >= 0");
+    ctx->has_win = true; ctx->win_rx = rx; ctx->win_ry = ry;
+    return VO_OK;
+}
+
+extern "C" int vo_clear_match_window(vo_ctx* ctx)
+{
+    if (!ctx) return VO_E_ARG;
+    if (!ctx->has_win) return vo_fail(ctx, VO_E_STATE, "vo_clear_match_window: no window is set");
+    ctx->has_win = false; ctx->win_rx = ctx->win_ry = 0.f;
+    return VO_OK;
+}
+
+int match_flags_check(vo_ctx* ctx, int match_flags, const char* who)
+{
+    if (match_flags & ~(VO_MATCH_CROSSCHECK | VO_MATCH_WINDOW)) return vo_fail(ctx, VO_E_ARG, "%s: bad argument (unknown match_flags bits)", who);
+    if ((match_flags & VO_MATCH_WINDOW) && !ctx->has_win)
+        return vo_fail(ctx, VO_E_ARG, "%s: VO_MATCH_WINDOW without a window (call vo_set_match_window first)", who);
+    return VO_OK;
+}
+
+int match_knn2_slots(vo_ctx* ctx, const FrameSlot& a, const FrameSlot& b, int match_flags)
+{
+    if (int rc = match_flags_check(ctx, match_flags, "kNN of two slots")) return rc;
+    const bool window = (match_flags & VO_MATCH_WINDOW) != 0;
+    return match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, match_flags & VO_MATCH_CROSSCHECK,
+                      window ? a.kp_xy : nullptr, window ? b.kp_xy : nullptr, ctx->win_rx, ctx->win_ry);
+}
+
 extern "C" int vo_measure_knn_ex(vo_ctx* ctx, int slot_a, int slot_b, int reps, int match_flags, double* us_per_launch)
 {
-    if (!ctx || !us_per_launch || reps <= 0 || reps > 10000 || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS ||
-        (match_flags & ~VO_MATCH_CROSSCHECK))
+    if (!ctx || !us_per_launch || reps <= 0 || reps > 10000 || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS)
         return vo_fail(ctx, VO_E_ARG, "vo_measure_knn: bad argument");
-    const int cross = match_flags & VO_MATCH_CROSSCHECK;
+    if (int rcf = match_flags_check(ctx, match_flags, "vo_measure_knn")) return rcf;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
     if (!a.has_kp || !b.has_kp || a.n_kp <= 0) return vo_fail(ctx, VO_E_STATE, "vo_measure_knn: both slots need keypoints");
@@ -325,9 +447,9 @@ extern "C" int vo_measure_knn_ex(vo_ctx* ctx, int slot_a, int slot_b, int reps, 
     hipEvent_t e0, e1;
     VO_HIP(ctx, hipEventCreate(&e0));
     VO_HIP(ctx, hipEventCreate(&e1));
-    int rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);      // warm-up (LDS attribute, caches)
+    int rc = match_knn2_slots(ctx, a, b, match_flags);      // warm-up (LDS attribute, caches)
     if (!rc && hipEventRecord(e0, ctx->stream) != hipSuccess) rc = VO_E_HIP;
-    for (int r = 0; r < reps && !rc; r++) rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross);
+    for (int r = 0; r < reps && !rc; r++) rc = match_knn2_slots(ctx, a, b, match_flags);
     if (!rc && hipEventRecord(e1, ctx->stream) != hipSuccess) rc = VO_E_HIP;
     float ms = 0.f;
     if (!rc && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) rc = VO_E_HIP;
@@ -404,6 +526,44 @@ extern "C" int vo_bf_knn2_hamming_mutual(vo_ctx* ctx, const uint8_t* q, int nq, 
     if (!rc) rc = xfer_d2h(ctx, dist, ctx->mw->m_dist, (size_t)nq * 8);
     if (!rc) rc = xfer_d2h(ctx, mutual, ctx->mw->st_a, (size_t)nq);
     if (!rc && t_best && nt) rc = xfer_d2h(ctx, t_best, d_tbest, (size_t)nt * 8);
+    if (rc) return rc;
+    return xfer_flush(ctx);
+}
+
+// kNN-2 inside a window of the keypoint positions on host arrays (the radii are arguments here: the context's window is neither read
+// nor changed); with VO_MATCH_CROSSCHECK also mutual / t_best as vo_bf_knn2_hamming_mutual gives them, mutual within the window
+extern "C" int vo_bf_knn2_hamming_window(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, const float* xy_q, const float* xy_t, float rx,
+                                         float ry, int match_flags, int32_t* idx, int32_t* dist, uint8_t* mutual, int32_t* t_best)
+{
+    const int cross = match_flags & VO_MATCH_CROSSCHECK;
+    if (!ctx || nq < 0 || nt < 0 || (nq && (!q || !xy_q || !idx || !dist || (cross && !mutual))) || (nt && (!t || !xy_t)) ||
+        (match_flags & ~(VO_MATCH_CROSSCHECK | VO_MATCH_WINDOW)))
+        return vo_fail(ctx, VO_E_ARG, "vo_bf_knn2_hamming_window: bad argument");
+    if (!(rx >= 0.f) || !(ry >= 0.f) || rx > 3.4028234e38f || ry > 3.4028234e38f)
+        return vo_fail(ctx, VO_E_ARG, "vo_bf_knn2_hamming_window: the radii must be finite and >= 0");
+    if (nq > ctx->kp_cap || nt > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "descriptor count exceeds capacity %d", ctx->kp_cap);
+    if (cross && nq > 65535) return vo_fail(ctx, VO_E_CAP, "cross-check: query set of %d descriptors exceeds 65535", nq);
+    if (cross && t_best)
+        for (int j = 0; j < nt; j++) { t_best[2 * j] = -1; t_best[2 * j + 1] = 0x7FFFFFFF; }
+    if (nq == 0) return VO_OK;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    StageTimer tm(ctx, VO_T_MATCH);
+    int rc = xfer_h2d(ctx, ctx->mq, q, (size_t)nq * 32);
+    if (!rc) rc = xfer_h2d(ctx, ctx->mw->xy_a, xy_q, (size_t)nq * 8);
+    if (!rc && nt) rc = xfer_h2d(ctx, ctx->mt, t, (size_t)nt * 32);
+    if (!rc && nt) rc = xfer_h2d(ctx, ctx->mw->xy_b, xy_t, (size_t)nt * 8);
+    if (rc) return rc;
+    if ((rc = match_knn2(ctx, ctx->mq, nq, ctx->mt, nt, ctx->mw->m_idx, ctx->mw->m_dist, cross, ctx->mw->xy_a, ctx->mw->xy_b, rx, ry))) return rc;
+    int32_t* d_tbest = (int32_t*)ctx->mw->pts_a;     // (kp_cap x 12 bytes: the positions occupy xy_a / xy_b here)
+    if (cross) {
+        hipLaunchKernelGGL(k_mutual_decode, dim3(div_up(std::max(nq, std::max(nt, 1)), 256)), dim3(256), 0, ctx->stream, ctx->mw->m_idx, nq,
+                           match_colmin(ctx->mw->m_dist, ctx->kp_cap), ctx->mt, nt, ctx->mw->st_a, d_tbest);
+        VO_CHECK_LAUNCH(ctx);
+    }
+    rc = xfer_d2h(ctx, idx, ctx->mw->m_idx, (size_t)nq * 8);
+    if (!rc) rc = xfer_d2h(ctx, dist, ctx->mw->m_dist, (size_t)nq * 8);
+    if (!rc && cross) rc = xfer_d2h(ctx, mutual, ctx->mw->st_a, (size_t)nq);
+    if (!rc && cross && t_best && nt) rc = xfer_d2h(ctx, t_best, d_tbest, (size_t)nt * 8);
     if (rc) return rc;
     return xfer_flush(ctx);
 }

@@ -387,11 +387,11 @@ __global__ void __launch_bounds__(1024) k_mono_finish(const int32_t* __restrict_
 
 // (extra / scratch: `extra` more bytes of the workspace behind the mask, 256-byte aligned, for a tail that needs them)
 struct MonoTail { const int32_t* counts; const double* E; const float* F; float thr2; int min_n; uint8_t* scratch; };
-static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
+static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
                         int solver, MonoDev& o, MonoTail* tail = nullptr, size_t extra = 0)
 {
     const int min_n = solver == 5 ? 6 : 8;
-    const int nq = a.n_kp;
+    const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     const size_t need = (size_t)iters * (72 + 36 + 4 + FP_REC_DOUBLES * 8) + (size_t)nq + 4096 + (extra ? extra + 256 : 0);
     if (ctx->mw->ransac_ws_bytes < need) {
         VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -411,7 +411,7 @@ static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        if ((rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross))) return rc;
+        if ((rc = match_knn2_slots(ctx, a, b, match_flags))) return rc;
         auto kern = cross ? k_ratio_compact<true> : k_ratio_compact<false>;
         hipLaunchKernelGGL(kern, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy, b.kp_xy,
                            ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
@@ -458,8 +458,9 @@ static int mono_check(vo_ctx* ctx, int slot_a, int slot_b, const double* K4v, in
 extern "C" int vo_mono_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
                                uint32_t seed, int solver, double* E9_out, int32_t* counts3, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
 {
-    if (ctx && (!E9_out || !counts3 || (match_flags & ~VO_MATCH_CROSSCHECK))) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair: bad argument");
+    if (ctx && (!E9_out || !counts3)) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair: bad argument");
     int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, "vo_mono_pair");
+    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_mono_pair");
     if (rc) return rc;
     const int min_n = solver == 5 ? 6 : 8;
     FrameSlot& a = ctx->slots[slot_a];
@@ -472,7 +473,7 @@ extern "C" int vo_mono_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     const int nq = a.n_kp;
     MonoDev o;
-    if ((rc = mono_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, o))) return rc;
+    if ((rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o))) return rc;
     int32_t* h = (int32_t*)ctx->pinned;         // [0] M, [1..2] best, then E9 at byte 64
     VO_HIP(ctx, hipMemcpyAsync(h, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     VO_HIP(ctx, hipMemcpyAsync(h + 1, o.d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -500,8 +501,9 @@ extern "C" int vo_mono_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, c
 extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
                                      uint32_t seed, int solver, int want_matches, int* ticket_out)
 {
-    if (ctx && (!ticket_out || (match_flags & ~VO_MATCH_CROSSCHECK))) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair_begin: bad argument");
+    if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_mono_pair_begin: bad argument");
     int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, "vo_mono_pair_begin");
+    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_mono_pair_begin");
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     FrameSlot& a = ctx->slots[slot_a];
@@ -515,7 +517,7 @@ extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
         AltScope on_alt(ctx, p);
         MonoDev o;
         MonoTail tl;
-        rc = mono_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, o, &tl);
+        rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o, &tl);
         if (!rc) {
             // (p.result is pinned host memory: the kernel writes the record across the link itself -- no copy command)
             hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(1024), 0, ctx->stream, tl.counts, iters, tl.E, tl.F, ctx->mw->xy_a, ctx->mw->xy_b, a.n_kp,
@@ -948,9 +950,10 @@ extern "C" int vo_recover_pose(vo_ctx* ctx, const double* E9, const float* pts1,
 static int mono_pose_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, int solver, double gate,
                            const void* out, const char* who)
 {
-    if (ctx && (!out || (match_flags & ~VO_MATCH_CROSSCHECK) || !(gate >= 0.0) || slot_a == slot_b))
+    if (ctx && (!out || !(gate >= 0.0) || slot_a == slot_b))
         return vo_fail(ctx, VO_E_ARG, "%s: bad argument (two different slots, min_parallax_sin2 >= 0)", who);
     int rc = mono_check(ctx, slot_a, slot_b, K4v, iters, solver, who);
+    if (!rc) rc = match_flags_check(ctx, match_flags, who);
     if (rc) return rc;
     if (!(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need positive focal lengths", who);
     if (rp_lds_bytes(ctx->slots[slot_a].n_kp) > 48 * 1024) return vo_fail(ctx, VO_E_CAP, "%s: %d keypoints exceed the step's LDS", who, ctx->slots[slot_a].n_kp);
@@ -966,12 +969,12 @@ static uint32_t mono_next_serial(vo_ctx* ctx)
 // The chain of mono_enqueue on ctx->stream (the main one or an alternate's) with k_mono_pose_finish as its tail.  The tail alone
 // is ordered behind the step that writes slot a's depths, behind an earlier writer of slot b's and behind the steps still
 // reading slot b: the kNN and the RANSAC in front of it overlap them.  `rec`: pinned host memory.
-static int mono_pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
+static int mono_pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
                              int solver, uint32_t prev_serial, double gate, uint32_t serial, vo_mono_pose* rec)
 {
     MonoDev o;
     MonoTail tl;
-    int rc = mono_enqueue(ctx, a, b, ratio, cross, K4v, iters, thr, seed, solver, o, &tl, rp_scratch_bytes(a.n_kp, b.n_kp));
+    int rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o, &tl, rp_scratch_bytes(a.n_kp, b.n_kp));
     if (rc) return rc;
     if (a.depth_writer) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, a.depth_writer, 0));
     if (b.depth_writer) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, b.depth_writer, 0));
@@ -1005,7 +1008,7 @@ extern "C" int vo_mono_pose_pair(vo_ctx* ctx, int slot_a, int slot_b, double rat
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     vo_mono_pose* rec = (vo_mono_pose*)ctx->pinned;
     rp_rec_clear(rec);
-    if ((rc = mono_pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, prev_serial, min_parallax_sin2,
+    if ((rc = mono_pose_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, prev_serial, min_parallax_sin2,
                                 mono_next_serial(ctx), rec)))
         return rc;
     if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
@@ -1033,7 +1036,7 @@ extern "C" int vo_mono_pose_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, doub
     if (a.n_kp > 0) {
         const uint32_t serial = mono_next_serial(ctx);
         AltScope on_alt(ctx, p);
-        rc = mono_pose_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, solver, prev_serial, min_parallax_sin2,
+        rc = mono_pose_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, prev_serial, min_parallax_sin2,
                                serial, (vo_mono_pose*)p.result);
         if (!rc) *serial_out = serial;
     } else
@@ -1602,8 +1605,9 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
 
 static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who)
 {
-    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v || (match_flags & ~VO_MATCH_CROSSCHECK))
+    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v)
         return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
+    if (int rcf = match_flags_check(ctx, match_flags, who)) return rcf;
     if (iters <= 0 || iters > (1 << 22)) return vo_fail(ctx, VO_E_ARG, "%s: need 0 < iters <= 4194304", who);
     if (refine_iters < 0 || refine_iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: refine_iters is 0 .. 20", who);
     if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
@@ -1617,10 +1621,10 @@ static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const
 
 // the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
 // pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
-static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const double* K4v, int iters, float thr, uint32_t seed,
+static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
                        int refine_iters, PnpRec* rec, uint8_t* arr)
 {
-    const int nq = a.n_kp;
+    const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
     const size_t need = (size_t)iters * (96 + 48 + 4) + (size_t)nq * (12 + 8 + 4 + 4 + 1) + 4096;
     if (ctx->mw->ransac_ws_bytes < need) {       // first use of this workspace (or a larger step than any before): never on the steady path
@@ -1646,7 +1650,7 @@ static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, in
     int rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
-        if ((rc = match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, cross))) return rc;
+        if ((rc = match_knn2_slots(ctx, a, b, match_flags))) return rc;
     }
     {
         StageTimer t(ctx, VO_T_POSE);
@@ -1709,7 +1713,7 @@ extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, in
             if ((rc = xfer_flush(ctx))) return rc;
             if (!(arr = (uint8_t*)xfer_stage(ctx, bytes))) return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair: the transfer arena cannot hold %d keypoints", a.n_kp);
         }
-        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, refine_iters, rec, arr))) return rc;
+        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, rec, arr))) return rc;
         if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
         if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // never a pose from an undefined disparity
     }
@@ -1733,7 +1737,7 @@ extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double rat
     pnp_rec_clear((PnpRec*)p.result);
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
-        rc = pnp_enqueue(ctx, a, b, ratio, match_flags & VO_MATCH_CROSSCHECK, K4v, iters, thr, seed, refine_iters, (PnpRec*)p.result,
+        rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, (PnpRec*)p.result,
                          want_matches ? p.result + PNP_HDR : nullptr);
     }
     if (rc) return rc;

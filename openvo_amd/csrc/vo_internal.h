@@ -218,6 +218,9 @@ struct vo_ctx {
     };
     MatchWs main_mw;
     MatchWs* mw = &main_mw;
+    // the match window of VO_MATCH_WINDOW (vo_set_match_window): read when a step is ENQUEUED and handed to the kernel by value
+    bool has_win = false;
+    float win_rx = 0.f, win_ry = 0.f;
     uint8_t* mq = nullptr;
     uint8_t* mt = nullptr;
     double* red = nullptr;         // reduction scratch
@@ -443,7 +446,12 @@ enum { MATCH_WS_POSE = 1 };
 hipError_t match_ws_alloc(vo_ctx* ctx, vo_ctx::MatchWs& m, int what);
 void match_ws_free(vo_ctx::MatchWs& m);
 int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx,
-               int32_t* d_dist, int cross = 0);
+               int32_t* d_dist, int cross = 0, const float* xy_q = nullptr, const float* xy_t = nullptr, float rx = 0.f, float ry = 0.f);
+// match_flags of an _ex / fused entry: VO_E_ARG for an unknown bit, and for VO_MATCH_WINDOW while the context has no window
+int match_flags_check(vo_ctx* ctx, int match_flags, const char* who);
+// the kNN-2 of a pair step into the current match scratch: slot a's descriptors against slot b's; with VO_MATCH_WINDOW inside
+// the context's window around the two slots' keypoint positions
+int match_knn2_slots(vo_ctx* ctx, const FrameSlot& a, const FrameSlot& b, int match_flags);
 int points3d_launch(vo_ctx* ctx, const int16_t* d_disp16, int w, int h, const float* d_xy, int n,
                     float* d_xyz, uint8_t* d_status);
 void host_svd3(const double* A, double* U, double* w, double* Vt);

@@ -389,6 +389,36 @@ class BFMatcher:
             out.append(tuple(DMatch(i, idx[i, j], dist[i, j]) for j in range(2) if idx[i, j] >= 0))
         return tuple(out)
 
+    @staticmethod
+    def _positions(kps, n):
+        """keypoints (a KeyPointList, a sequence of objects with .pt, or an n x 2 array) -> n x 2 float32"""
+        xy = getattr(kps, "xy", None)
+        if xy is None:
+            xy = [k.pt for k in kps] if len(kps) and hasattr(kps[0], "pt") else kps
+        xy = np.asarray(xy, np.float32).reshape(-1, 2)
+        if len(xy) != n:
+            raise ValueError("%d keypoints for %d descriptors" % (len(xy), n))
+        return xy
+
+    def knnMatchWindow(self, queryDescriptors, trainDescriptors, queryKeypoints, trainKeypoints, window, k=2):
+        """knnMatch among the train descriptors whose keypoint lies inside the window (rx, ry) around the query's keypoint
+        (include/vo355.h: |dx| <= rx and |dy| <= ry in float32) -> per query a tuple of 0, 1 or 2 DMatch (k = 2), of 0 or 1
+        (k = 1).  An extension: cv2 has no such call.  A crossCheck=True matcher takes k = 1 only, as in knnMatch, and a match
+        must then be mutual within the window."""
+        if k not in (1, 2):
+            raise NotImplementedError("only k=1 and k=2 are implemented (the reference uses k=2)")
+        if k == 2 and self.crossCheck:
+            raise ValueError("knnMatchWindow with crossCheck=True needs k=1 (as knnMatch does)")
+        q, t = self._arrays(queryDescriptors, trainDescriptors)
+        xy_q, xy_t = self._positions(queryKeypoints, len(q)), self._positions(trainKeypoints, len(t))
+        if self.crossCheck:
+            idx, dist, mutual, _ = self._ctx.bf_knn2_window(q, t, xy_q, xy_t, window, cross_check=True)
+        else:
+            idx, dist = self._ctx.bf_knn2_window(q, t, xy_q, xy_t, window)
+            mutual = np.ones(len(q), bool)
+        return tuple(tuple(DMatch(i, idx[i, j], dist[i, j]) for j in range(k) if idx[i, j] >= 0) if mutual[i] else ()
+                     for i in range(len(q)))
+
 
 class StereoSGBM:
     """cv2.StereoSGBM_create(...) stand-in: compute(left, right) -> int16 disparity x16."""

@@ -70,10 +70,13 @@ def recover_pose(E, x1, x2):
 class MonoOdometer:
     def __init__(self, K, img_size, nfeatures=8000, match_threshold=0.8, ransac_iters=5000, ransac_threshold=1.0,
                  min_inliers=30, seed=4321, device=0, context=None, solver=5, cross_check=False, pose_on_device=False,
-                 propagate_scale=False, min_parallax_deg=0.5, min_scale_tracks=20):
+                 propagate_scale=False, min_parallax_deg=0.5, min_scale_tracks=20, match_window=None):
         """K: 3x3 intrinsics; img_size = (width, height).  ransac_threshold is the Sampson distance in pixels.
         solver: 5 = five-point minimal solver (what cv2.findEssentialMat runs), 8 = eight-point.
         cross_check: the matches of the ratio test must also be mutual nearest neighbours (include/vo355.h).
+        match_window (None, a radius, or (rx, ry) in pixels): a keypoint of the reference frame is matched only against
+        keypoints of the new frame no farther than rx in x and ry in y (include/vo355.h); used as given, whatever lies between
+        the two frames.
         pose_on_device: (R, t) comes from the device with the pair step's record (no worker thread, no per-match arrays).
         propagate_scale (needs pose_on_device): self.scale, the |t| of the last accepted pair, follows the baseline ratios the
         steps measure; a pair that shares fewer than min_scale_tracks triangulated keypoints with its predecessor (or none: the
@@ -95,6 +98,8 @@ class MonoOdometer:
         if not isinstance(cross_check, (bool, np.bool_)):
             raise ValueError("cross_check must be True or False")
         self.cross_check = bool(cross_check)
+        self.match_window = _native.window_radii(match_window, "match_window")
+        self._window_kw = {} if self.match_window is None else {"window": self.match_window}
         self.solver = int(solver)
         K = np.asarray(K, np.float64)
         self.K, self.K4 = K, [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
@@ -166,11 +171,11 @@ class MonoOdometer:
             t, serial = self._ctx.mono_pose_pair_begin(a, b, self.match_threshold, self.K4, self.ransac_iters, self.ransac_threshold, self.seed,
                                                        solver=self.solver, cross_check=self.cross_check,
                                                        prev_serial=prev_serial if self.propagate_scale else 0,
-                                                       min_parallax_sin2=self._gate)
+                                                       min_parallax_sin2=self._gate, **self._window_kw)
             self._serial[(a, b)] = serial
         else:
             t = self._ctx.mono_pair_begin(a, b, self.match_threshold, self.K4, self.ransac_iters, self.ransac_threshold, self.seed,
-                                          want_matches=True, solver=self.solver, cross_check=self.cross_check)
+                                          want_matches=True, solver=self.solver, cross_check=self.cross_check, **self._window_kw)
         self._open[(a, b)] = t
         return t
 

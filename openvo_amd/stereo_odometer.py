@@ -24,7 +24,8 @@ class StereoOdometer:
 
     def __init__(self, stereo_camera, nfeatures=500, match_threshold=0.8, rigidity_threshold=0,
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
-                 pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0):
+                 pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
+                 match_window=None):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -36,12 +37,20 @@ class StereoOdometer:
         sample -- on its whole inlier set, as cv2.solvePnPRansac's final fit does; 0 (default) returns the winner itself, 3 is
         the recommended value.  The refinement is part of the fused device step (vo_pnp_pair): where that step cannot run
         (_pair_pnp: a replaced matcher or seam -- the context's point_clouds / ransac_pnp replaced on the object count as
-        seams of this mode --, more than 3800 keypoints) the winner is returned as it is."""
+        seams of this mode --, more than 3800 keypoints) the winner is returned as it is.
+        match_window (None, a radius, or (rx, ry) in pixels; an extension, the reference's "# TODO config" at its match step,
+        :165): a keypoint of the older frame is matched only against keypoints of the newer one no farther than rx in x and ry
+        in y (include/vo355.h).  The radii are per frame: like the motion gates they are multiplied by the frames the pair
+        spans -- skipped_frames + 1 for (current, next), skipped_frames + 2 for the one-frame-back fallback.  A keypoint with
+        fewer than two candidates in its window gives no match, and the ratio test inside a window is laxer than over the
+        whole image: the window replaces the clique filter on the default odometer, it does not add to it (README)."""
         if pose_method not in ("umeyama", "pnp"):
             raise ValueError("pose_method must be 'umeyama' or 'pnp'")
         if not isinstance(cross_check, (bool, np.bool_)):
             raise ValueError("cross_check must be True or False")
         self.cross_check = bool(cross_check)
+        self.match_window = _native.window_radii(match_window, "match_window")
+        self._pair_span = None       # frames the pair being tried spans (_try_pair); None: skipped_frames + 1
         if isinstance(pnp_refine, (bool, np.bool_)) or not isinstance(pnp_refine, (int, np.integer)) or not 0 <= pnp_refine <= 20:
             raise ValueError("pnp_refine must be an int in 0 .. 20")
         self.pnp_refine = int(pnp_refine)
@@ -127,13 +136,16 @@ class StereoOdometer:
             self.save_frame_update(next_img, next_disp, next_3d, next_kps, next_desc)
             return True
 
-        T = self._try_pair(self.current_kps, self.current_desc, self.current_3d, next_kps, next_desc, next_3d)
+        # (the span is passed only where a window needs it: a subclass that replaces _try_pair keeps the signature it has)
+        span = {} if self.match_window is None else {"span": self.skipped_frames + 1}
+        T = self._try_pair(self.current_kps, self.current_desc, self.current_3d, next_kps, next_desc, next_3d, **span)
         if T is not None:
             self.c_T_w_prev = self.c_T_w
             self.c_T_w = T @ self.c_T_w
         elif self.prev_img is not None:
             # one-frame-back fallback: pair the new frame with the frame before `current`
-            T = self._try_pair(self.prev_kps, self.prev_desc, self.prev_3d, next_kps, next_desc, next_3d)
+            span = {} if self.match_window is None else {"span": self.skipped_frames + 2}
+            T = self._try_pair(self.prev_kps, self.prev_desc, self.prev_3d, next_kps, next_desc, next_3d, **span)
             if T is not None:
                 base = self.c_T_w_prev
                 self.c_T_w_prev = self.c_T_w
@@ -155,14 +167,25 @@ class StereoOdometer:
         say), they are what runs, so the fused step -- which would bypass them -- stands back."""
         return self._pnp_fused and not any(n in getattr(self._ctx, "__dict__", {}) for n in self._PNP_CTX_SEAMS)
 
+    def _window(self, span=None):
+        """The match window of a pair that spans `span` frames (None: the pair being tried, else skipped_frames + 1): the radii
+        as the float32 values the kernel compares with, or None without a window."""
+        if self.match_window is None:
+            return None
+        if span is None:
+            span = self._pair_span if self._pair_span is not None else self.skipped_frames + 1
+        return tuple(float(np.float32(r * span)) for r in self.match_window)
+
     def _pose_params(self):
-        """What a pose step begun ahead must have been begun with to be this odometer's step (part of its ticket's key)."""
+        """What a pose step begun ahead must have been begun with to be this odometer's step (part of its ticket's key).  With a
+        match window its effective radii are the last entry: a step begun with another window (another span) is never reused."""
+        tail = () if self.match_window is None else (self._window(),)
         if self.pose_method == "pnp":
             Q = self.stereo.Q
             return ("pnp", float(self.match_threshold), (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3])),
-                    int(self.pnp_iters), float(self.pnp_threshold), int(self.pnp_seed), int(self.pnp_refine), bool(self.cross_check))
+                    int(self.pnp_iters), float(self.pnp_threshold), int(self.pnp_seed), int(self.pnp_refine), bool(self.cross_check)) + tail
         return (float(self.match_threshold), int(self.min_matches), float(max(self.rigidity_threshold, 0)),
-                float(max(self.outlier_threshold, 0)), bool(self.cross_check))
+                float(max(self.outlier_threshold, 0)), bool(self.cross_check)) + tail
 
     def _fused_ok(self):
         return (type(self) is StereoOdometer and type(self.matcher) is BFMatcher
@@ -171,13 +194,18 @@ class StereoOdometer:
 
     @staticmethod
     def _pnp_kwargs(params):
-        """_pose_params() of the PnP mode as the keyword arguments of Context.pnp_pair / pnp_pair_begin"""
-        _, ratio, K4, iters, thr, seed, refine, cross_check = params
-        return dict(ratio=ratio, K4=K4, iters=iters, thr=thr, seed=seed, refine=refine, want_matches=False, cross_check=cross_check)
+        """_pose_params() of the PnP mode as the keyword arguments of Context.pnp_pair / pnp_pair_begin (with a match window: of
+        pnp_pair_window / pnp_pair_begin_window)"""
+        _, ratio, K4, iters, thr, seed, refine, cross_check = params[:8]
+        kw = dict(ratio=ratio, K4=K4, iters=iters, thr=thr, seed=seed, refine=refine, want_matches=False, cross_check=cross_check)
+        if len(params) > 8:
+            kw["window"] = params[8]
+        return kw
 
     def _step_begin(self, slot_a, slot_b, params):
         if params[0] == "pnp":
-            return self._ctx.pnp_pair_begin(slot_a, slot_b, **self._pnp_kwargs(params))
+            kw = self._pnp_kwargs(params)
+            return (self._ctx.pnp_pair_begin_window if "window" in kw else self._ctx.pnp_pair_begin)(slot_a, slot_b, **kw)
         return self._ctx.pose_pair_begin(slot_a, slot_b, *params)
 
     def _step_end(self, params, ticket):
@@ -354,7 +382,15 @@ class StereoOdometer:
     _SEAMS = ("point_clouds", "point_cloud_transform", "rigid_body_filter", "bilinear_interpolate_pixels",
               "_estimate", "_gate")
 
-    def _try_pair(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b):
+    def _try_pair(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b, span=None):
+        """span: the frames between a and b (None: skipped_frames + 1); it scales the match window."""
+        self._pair_span = span
+        try:
+            return self._try_pair_span(kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b)
+        finally:
+            self._pair_span = None
+
+    def _try_pair_span(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b):
         # fused device path when nothing along the way was replaced by the user
         fused = (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and 2 <= len(kps_b) and len(kps_a) <= 3800
                  and self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)
@@ -375,7 +411,8 @@ class StereoOdometer:
         """Extension: pose of the pair by RANSAC solvePnP (3-D of frame a, pixels of frame b)."""
         if not (self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b) and len(kps_b) >= 2):
             raise ValueError("pose_method='pnp' needs the device-resident frames compute_3d returns")
-        q, t, pts_a, _, st_a, _ = self._ctx.point_clouds(kps_a.frame.slot, kps_b.frame.slot, self.match_threshold, self.cross_check)
+        q, t, pts_a, _, st_a, _ = self._ctx.point_clouds(kps_a.frame.slot, kps_b.frame.slot, self.match_threshold, self.cross_check,
+                                                         **self._window_kw())
         if len(q) < self.min_matches:
             self.skip_cause = "matches"
             return None
@@ -403,7 +440,8 @@ class StereoOdometer:
         if ticket is not None:
             r = self._ctx.pnp_pair_end(ticket)                           # started by an earlier update()
         else:
-            r = self._ctx.pnp_pair(slot_a, slot_b, **self._pnp_kwargs(params))
+            kw = self._pnp_kwargs(params)
+            r = (self._ctx.pnp_pair_window if "window" in kw else self._ctx.pnp_pair)(slot_a, slot_b, **kw)
         if r["matches"] < self.min_matches:
             self.skip_cause = "matches"
             return None
@@ -454,24 +492,42 @@ class StereoOdometer:
                  and self._on_device(kps2, desc2, im3d2) and len(kps2) >= 2)
         if fused:
             q, t, pts1, pts2, st1, st2 = self._ctx.point_clouds(kps1.frame.slot, kps2.frame.slot,
-                                                                self.match_threshold, self.cross_check)
+                                                                self.match_threshold, self.cross_check, **self._window_kw())
             if len(q) < self.min_matches:
                 return None, None
             if (st1 == 2).any() or (st2 == 2).any():
                 raise ZeroDivisionError("division by zero")
             return pts1, pts2
         # generic path: the same steps through the public seams (any matcher / arrays)
-        matches = self.matcher.knnMatch(desc1, desc2, k=2)
+        window = self._window()
+        if window is None:
+            knn = self.matcher.knnMatch
+        else:
+            if not hasattr(self.matcher, "knnMatchWindow"):
+                raise ValueError("match_window needs a matcher with knnMatchWindow(query, train, queryKeypoints, trainKeypoints, window, k)")
+
+            def knn(d1, d2, k):
+                k1, k2 = (kps1, kps2) if d1 is desc1 else (kps2, kps1)
+                return self.matcher.knnMatchWindow(d1, d2, k1, k2, window, k=k)
+        matches = knn(desc1, desc2, k=2)
+        if window is not None:
+            matches = [m for m in matches if len(m) == 2]    # fewer than two candidates in the window: no ratio test, no match
         matches = [m[0] for m in matches if m[0].distance < self.match_threshold * m[1].distance]
         if self.cross_check:
             # a(j), the nearest query of every train descriptor: the matcher with the roles swapped (k = 1, ties -> lower index)
-            back = self.matcher.knnMatch(desc2, desc1, k=1)
+            back = knn(desc2, desc1, k=1)
             matches = [m for m in matches if len(back[m.trainIdx]) and back[m.trainIdx][0].trainIdx == m.queryIdx]
         if len(matches) < self.min_matches:
             return None, None
         pts1 = [self.bilinear_interpolate_pixels(im3d1, *kps1[m.queryIdx].pt) for m in matches]
         pts2 = [self.bilinear_interpolate_pixels(im3d2, *kps2[m.trainIdx].pt) for m in matches]
         return np.array(pts1), np.array(pts2)
+
+    def _window_kw(self):
+        """the window of the pair being tried as the keyword of the context's calls (none without a window: a replaced
+        point_clouds keeps the signature it has)"""
+        w = self._window()
+        return {} if w is None else {"window": w}
 
     @staticmethod
     def _on_device(kps, desc, im3d):
