@@ -418,6 +418,41 @@ int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int mat
 int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
                     uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
 
+/* Sparse stereo depth (NOT part of the reference, which reads a dense disparity at its keypoints, stereo_odometer.py:50-79,117):
+ * per-keypoint 3-D from ORB on BOTH rectified images of a slot, without any SGBM run.  Defined by this build; tests/sparse_stereo_ref.py
+ * restates steps b - e in numpy.  Needs a pair in the slot (vo_upload_pair / vo_load_staged_pair) and vo_set_Q; one host synchronisation.
+ *   a. KL = ORB(left crop), KR = ORB(right crop): the crop rectangle of vo_orb_detect_and_compute (from the LEFT ROI) on both images,
+ *      no mask, canonical order, nfeatures each.
+ *   b. association of left keypoint i: right keypoint j is a candidate when |oct_i - oct_j| <= 1, fabsf(y_i - y_j) <= row_tol * sc[oct_i]
+ *      (sc[o] = (float)pow((double)1.2f, o)) and d0 = x_i - x_j (float32) lies in [min_disp, max_disp]; the winner is the
+ *      lexicographically smallest (Hamming distance, j), accepted when its distance <= max_hamming.
+ *   c. refinement in crop pixels: x0 = rint(x_i), y0 = rint(y_i), xr = rint(x_j) (half to even); rejected when the 11 x 11 window at
+ *      (x0, y0) or the 11 x 21 strip around (xr, y0) leaves the crop; SAD(s) = sum |L[y0+dy, x0+dx] - R[y0+dy, xr+s+dx]| for s = -5 .. 5
+ *      in integers; s* = the first minimum, rejected at s* = +-5; den = SAD(s*-1) + SAD(s*+1) - 2 SAD(s*), rejected when den <= 0;
+ *      delta = (float)(SAD(s*-1) - SAD(s*+1)) / (float)(2 den); d = (float)(x0 - xr - s*) - delta; kept iff d > 0 and
+ *      min_disp <= d <= max_disp.
+ *   d. 3-D: cv2.reprojectImageTo3D's arithmetic (as vo_download_xyz) on v = {(double)(x_i + (float)roi_x0), (double)(y_i + (float)roi_y0),
+ *      (double)d, 1}, the additions in float32.
+ *   e. the surviving LEFT keypoints, in their order, become the slot's keypoints (all six arrays and the descriptors) together with
+ *      their 3-D point and disparity; the slot's keypoints then CARRY DEPTH until the next ORB extraction into the slot or its refill.
+ * 0 <= min_disp < max_disp, row_tol >= 0 (finite float32), max_hamming 0 .. 256, VO_E_ARG otherwise; more than 65535 right keypoints:
+ * VO_E_CAP.  counts3 = {left keypoints, accepted associations, kept}. */
+int vo_sparse_stereo(vo_ctx* ctx, int slot, int nfeatures, float min_disp, float max_disp, float row_tol, int max_hamming,
+                     int32_t* counts3);
+/* the 3-D points (n x 3) and disparities (n) of a slot's keypoints, in keypoint order; either output may be NULL.  VO_E_STATE when the
+ * slot's keypoints carry no depth. */
+int vo_download_keypoint_depth(vo_ctx* ctx, int slot, float* xyz /*cap*3*/, float* disp /*cap*/, int cap, int* n_out);
+/* steps b and c on host arrays, no ORB involved (the seam the kernel tests use): two w x h images (the crop is the whole image),
+ * nl / nr keypoints (x, y pairs, octaves 0 .. 7, 32-byte descriptors).  match_out[i] = the accepted right keypoint or -1;
+ * disp_out[i] = d, NaN where keypoint i was not accepted or was rejected by the refinement. */
+int vo_sparse_match_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l, const int32_t* oct_l,
+                         const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r, const uint8_t* desc_r, int nr,
+                         float min_disp, float max_disp, float row_tol, int max_hamming, int32_t* match_out /*nl*/, float* disp_out /*nl*/);
+/* The pair steps read their depth source from the slots: when BOTH slots' keypoints carry depth, vo_point_clouds(_ex),
+ * vo_pose_pair(_ex / _begin / _begin_ex / _end) and vo_pnp_pair(_begin / _end) take the 3-D point of keypoint k from the slot's
+ * per-keypoint array instead of the bilinear lookup in the reprojected disparity (status 0; the slots need no disparity and its
+ * health is not consulted); when neither does, nothing changes; when exactly one does, VO_E_STATE. */
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */

@@ -41,6 +41,7 @@ SYMBOLS = [
     "vo_pnp_pair", "vo_pnp_pair_begin", "vo_pnp_pair_end",
     "vo_recover_pose", "vo_mono_pose_pair", "vo_mono_pose_pair_begin", "vo_mono_pose_pair_end", "vo_download_mono_depth",
     "vo_set_match_window", "vo_clear_match_window", "vo_bf_knn2_hamming_window",
+    "vo_sparse_stereo", "vo_download_keypoint_depth", "vo_sparse_match_host",
 ]
 
 
@@ -207,6 +208,12 @@ def lib():
         L.vo_set_match_window.argtypes = [vp, ctypes.c_float, ctypes.c_float]
         L.vo_clear_match_window.argtypes = [vp]
         L.vo_bf_knn2_hamming_window.argtypes = [vp, vp, ci, vp, ci, vp, vp, ctypes.c_float, ctypes.c_float, ci, vp, vp, vp, vp]
+        if hasattr(L, "vo_sparse_stereo"):          # (an older build has no sparse stereo depth)
+            cf = ctypes.c_float
+            for name, proto in (("vo_sparse_stereo", [vp, ci, ci, cf, cf, cf, ci, vp]),
+                                ("vo_download_keypoint_depth", [vp, ci, vp, vp, ci, vp]),
+                                ("vo_sparse_match_host", [vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, ci, vp, vp])):
+                getattr(L, name).argtypes = proto
         if hasattr(L, "vo_pnp_pair"):               # (likewise: an older build has no fused PnP step)
             L.vo_pnp_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
             L.vo_pnp_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
@@ -573,6 +580,42 @@ class Context:
         self._ck(self._lib.vo_orb_detect_and_compute_host(self._h, _p(img), w, h, img.strides[0], _p(mask), mstride,
                                                           int(nfeatures), *self._kp_args(b), cap, ctypes.byref(n)))
         return self._trim(b, n.value)
+
+    # ---- sparse stereo depth
+    def sparse_stereo(self, slot, nfeatures, min_disp, max_disp, row_tol=2.0, max_hamming=75):
+        """ORB on both images of the slot's pair, association along the row, sub-pixel refinement, 3-D (vo_sparse_stereo): the slot
+        then holds the left keypoints that have a depth, and they carry it.  -> counts3 = [left keypoints, accepted, kept]."""
+        c3 = np.zeros(3, np.int32)
+        self._ck(self._lib.vo_sparse_stereo(self._h, int(slot), int(nfeatures), float(min_disp), float(max_disp), float(row_tol),
+                                            int(max_hamming), _p(c3)))
+        return c3
+
+    def download_keypoint_depth(self, slot):
+        """-> (xyz (n, 3) float32, disparity (n,) float32) of a slot whose keypoints carry depth (VoError otherwise)."""
+        cap = self.kp_cap
+        xyz, disp = np.empty((cap, 3), np.float32), np.empty(cap, np.float32)
+        n = ctypes.c_int(0)
+        self._ck(self._lib.vo_download_keypoint_depth(self._h, int(slot), _p(xyz), _p(disp), cap, ctypes.byref(n)))
+        return xyz[:n.value].copy(), disp[:n.value].copy()
+
+    def sparse_match_host(self, left, right, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, min_disp, max_disp, row_tol=2.0, max_hamming=75):
+        """Association + refinement of vo_sparse_stereo on host arrays -> (match (nl,) int32, -1 = none; disparity (nl,) float32,
+        NaN = rejected)."""
+        left, right = _c(left, np.uint8), _c(right, np.uint8)
+        if left.ndim != 2 or left.shape != right.shape:
+            raise ValueError("two 2-D uint8 images of one shape")
+        h, w = left.shape
+        xy_l, xy_r = _c(xy_l, np.float32).reshape(-1, 2), _c(xy_r, np.float32).reshape(-1, 2)
+        oct_l, oct_r = _c(oct_l, np.int32).reshape(-1), _c(oct_r, np.int32).reshape(-1)
+        desc_l, desc_r = _c(desc_l, np.uint8).reshape(-1, 32), _c(desc_r, np.uint8).reshape(-1, 32)
+        nl, nr = len(xy_l), len(xy_r)
+        if len(oct_l) != nl or len(desc_l) != nl or len(oct_r) != nr or len(desc_r) != nr:
+            raise ValueError("one octave and one descriptor per keypoint")
+        match, disp = np.full(nl, -1, np.int32), np.full(nl, np.nan, np.float32)
+        self._ck(self._lib.vo_sparse_match_host(self._h, _p(left), _p(right), w, h, _p(xy_l), _p(oct_l), _p(desc_l), nl, _p(xy_r), _p(oct_r),
+                                                _p(desc_r), nr, float(min_disp), float(max_disp), float(row_tol), int(max_hamming),
+                                                _p(match), _p(disp)))
+        return match, disp
 
     # ---- matching / 3-D / pose
     def bf_knn2(self, q, t):

@@ -319,6 +319,18 @@ template __global__ void k_ratio_compact<false>(const int32_t*, const int32_t*, 
 template __global__ void k_ratio_compact<true>(const int32_t*, const int32_t*, int, double, const float*, const float*, int32_t*, int32_t*, float*,
                                                float*, int32_t*, const uint32_t*, int);
 
+// the matched keypoints' 3-D points of two slots whose keypoints carry depth (vo_sparse_stereo)
+__global__ void k_gather_xyz(const float* __restrict__ xyz_a, const float* __restrict__ xyz_b, const int32_t* __restrict__ q, const int32_t* __restrict__ t,
+                             int m, float* __restrict__ pts_a, float* __restrict__ pts_b, uint8_t* __restrict__ st_a, uint8_t* __restrict__ st_b)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int qi = q[i], ti = t[i];
+#pragma unroll
+    for (int c = 0; c < 3; c++) { pts_a[3 * (size_t)i + c] = xyz_a[3 * (size_t)qi + c]; pts_b[3 * (size_t)i + c] = xyz_b[3 * (size_t)ti + c]; }
+    st_a[i] = 0; st_b[i] = 0;
+}
+
 extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, int32_t* q_idx, int32_t* t_idx,
                                   float* pts_a, float* pts_b, uint8_t* status_a, uint8_t* status_b, int cap, int* m_out)
 {
@@ -328,7 +340,10 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
     const int cross = match_flags & VO_MATCH_CROSSCHECK;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
-    if (!a.has_kp || !b.has_kp || !a.has_disp || !b.has_disp) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
+    if (!a.has_kp || !b.has_kp) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
+    const bool sparse = slot_sparse(a);
+    if (sparse != slot_sparse(b)) return vo_fail(ctx, VO_E_STATE, "vo_point_clouds: one slot's keypoints carry depth, the other's do not");
+    if (!sparse && (!a.has_disp || !b.has_disp)) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     *m_out = 0;
     if (a.n_kp == 0) return VO_OK;
@@ -348,11 +363,17 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
         VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
         VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // (both slots' producers are behind that synchronisation)
+    if (!sparse && ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b)))) return rc;   // (both slots' producers are behind that synchronisation)
     const int m = *(int32_t*)ctx->pinned;
     *m_out = m;
     if (m == 0) return VO_OK;
-    {
+    if (sparse) {
+        // the keypoints carry their 3-D points: gathered by match index, status 0
+        StageTimer t(ctx, VO_T_POSE);
+        hipLaunchKernelGGL(k_gather_xyz, dim3(div_up(m, 256)), dim3(256), 0, ctx->stream, a.kp_xyz, b.kp_xyz, ctx->mw->mq_idx, ctx->mw->mt_idx, m,
+                           ctx->mw->pts_a, ctx->mw->pts_b, ctx->mw->st_a, ctx->mw->st_b);
+        VO_CHECK_LAUNCH(ctx);
+    } else {
         StageTimer t(ctx, VO_T_POSE);
         rc = points3d_launch(ctx, a.disp16, a.w, a.h, ctx->mw->xy_a, m, ctx->mw->pts_a, ctx->mw->st_a);
         if (rc) return rc;
@@ -1189,8 +1210,10 @@ __global__ void __launch_bounds__(256) k_pose_prep(const int32_t* __restrict__ i
                                                    float* __restrict__ xyt_out, int32_t* __restrict__ m_out, PoseOut* __restrict__ out,
                                                    int* __restrict__ flags_dev, TapDisp ta, TapDisp tb, int cw, int ch,
                                                    float* __restrict__ pts_a, float* __restrict__ pts_b, uint8_t* __restrict__ st_a,
-                                                   uint8_t* __restrict__ st_b, int* __restrict__ ncons, const uint32_t* __restrict__ colmin, int nt_c)
+                                                   uint8_t* __restrict__ st_b, int* __restrict__ ncons, const uint32_t* __restrict__ colmin, int nt_c,
+                                                   const float* __restrict__ xyz_a, const float* __restrict__ xyz_b)
 {
+    // xyz_a / xyz_b (both or neither): the two slots' keypoints carry depth -- the points are kp_xyz[q] / kp_xyz[t], status 0
     __shared__ int s_m;
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
@@ -1225,6 +1248,13 @@ __global__ void __launch_bounds__(256) k_pose_prep(const int32_t* __restrict__ i
     const int m = s_m;
     int bad = 0;
     for (int i = threadIdx.x; i < m; i += blockDim.x) {
+        if (xyz_a) {
+            const int q = q_out[i], t = t_out[i];
+#pragma unroll
+            for (int c = 0; c < 3; c++) { pts_a[3 * (size_t)i + c] = xyz_a[3 * (size_t)q + c]; pts_b[3 * (size_t)i + c] = xyz_b[3 * (size_t)t + c]; }
+            st_a[i] = 0; st_b[i] = 0;
+            continue;
+        }
         bilinear_one(ta, cw, ch, xyq_out[2 * i], xyq_out[2 * i + 1], pts_a + 3 * (size_t)i, st_a + i);
         bilinear_one(tb, cw, ch, xyt_out[2 * i], xyt_out[2 * i + 1], pts_b + 3 * (size_t)i, st_b + i);
         bad |= st_a[i] == 2 || st_b[i] == 2;
@@ -1321,6 +1351,7 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
                         double outlier_thr, void* host_out)
 {
     const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
+    const bool sparse = slot_sparse(a);      // (pose_check: then b's keypoints carry depth too)
     // workspace: bit matrix + ncons + filtered point sets + residuals + result.  match_ws_alloc sizes it
     // for kp_cap query keypoints, so the branch below (a device-wide synchronisation) is never taken on the hot path
     const int words = (nq + 63) / 64;
@@ -1360,7 +1391,7 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
         hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, ctx->mw->mq_idx,
                            ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a, ctx->mw->pts_b,
                            ctx->mw->st_a, ctx->mw->st_b, d_ncons, cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr,
-                           cross ? b.n_kp : 0);
+                           cross ? b.n_kp : 0, sparse ? (const float*)a.kp_xyz : nullptr, sparse ? (const float*)b.kp_xyz : nullptr);
         const int use_filter = rigidity_thr > 0;
         // LDS: 4 int arrays of nq (rounded to even so the bit matrix stays 8-byte aligned) + bit matrix if <= 48 KB
         const int m_cap = (nq + 1) & ~1;
@@ -1388,7 +1419,9 @@ static int pose_check(vo_ctx* ctx, int slot_a, int slot_b)
     if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair: bad argument");
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
-    if (!a.has_kp || !b.has_kp || !a.has_disp || !b.has_disp) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
+    if (!a.has_kp || !b.has_kp) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
+    if (slot_sparse(a) != slot_sparse(b)) return vo_fail(ctx, VO_E_STATE, "vo_pose_pair: one slot's keypoints carry depth, the other's do not");
+    if (!slot_sparse(a) && (!a.has_disp || !b.has_disp)) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
     if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
     if (a.n_kp > 0 && b.n_kp < 2) return vo_fail(ctx, VO_E_ARG, "train set has fewer than 2 descriptors (reference raises IndexError)");
     if (a.n_kp >= 32768 || (size_t)a.n_kp * 16 > 60 * 1024) return vo_fail(ctx, VO_E_CAP, "%d query keypoints exceed the fused pose path", a.n_kp);
@@ -1421,7 +1454,7 @@ extern "C" int vo_pose_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio
     if (a.n_kp == 0) return VO_OK;
     if ((rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, ctx->pinned))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;
-    if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // never a pose from an undefined disparity
+    if (!slot_sparse(a) && ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b)))) return rc;   // never a pose from an undefined disparity
     pose_unpack(ctx->pinned, counts4, rc2, T1_12, T2_12);
     return VO_OK;
 }
@@ -1455,6 +1488,7 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
+    if (slot_sparse(a)) p.gen_a = p.gen_b = 0;       // the step read no disparity: nothing to check at _end
     p.pnp = false;
     return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }
@@ -1498,8 +1532,9 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
                                                   int32_t* __restrict__ mq, int32_t* __restrict__ mt, TapDisp ta, int cw, int ch, float x0f,
                                                   float y0f, int32_t* __restrict__ q2, int32_t* __restrict__ t2, float* __restrict__ X,
                                                   float* __restrict__ uv, int32_t* __restrict__ hdr, const uint32_t* __restrict__ colmin,
-                                                  int nt_range)
+                                                  int nt_range, const float* __restrict__ xyz_a)
 {
+    // xyz_a: slot a's keypoints carry depth -- the 3-D point of match (q, t) is kp_xyz[q], status 0
     __shared__ int s_m, s_flags, s_cnt[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (wv == 0) {
@@ -1534,8 +1569,9 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
         float p[3] = { 0.f, 0.f, 0.f };
         if (i < m) {
             q = mq[i]; t = mt[i];
-            uint8_t st;
-            bilinear_one(ta, cw, ch, xy_q[2 * q], xy_q[2 * q + 1], p, &st);
+            uint8_t st = 0;
+            if (xyz_a) { p[0] = xyz_a[3 * (size_t)q]; p[1] = xyz_a[3 * (size_t)q + 1]; p[2] = xyz_a[3 * (size_t)q + 2]; }
+            else bilinear_one(ta, cw, ch, xy_q[2 * q], xy_q[2 * q + 1], p, &st);
             bad |= st == 2;
             use = st == 0 && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && t >= 0 && t < nt_range;
         }
@@ -1568,7 +1604,8 @@ int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int c
     if (ctx->fault_pnp_range > 0 && --ctx->fault_pnp_range == 0) nt_range = 1;   // (only the test-hooks build ever sets it)
     hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, b.n_kp,
                        ctx->mw->mq_idx, ctx->mw->mt_idx, ta, x1 - x0, y1 - y0, (float)x0, (float)y0, d.q, d.t, d.X, d.uv, d.hdr,
-                       cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, nt_range);
+                       cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, nt_range,
+                       slot_sparse(a) ? (const float*)a.kp_xyz : nullptr);
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }

@@ -1005,10 +1005,11 @@ __global__ void __launch_bounds__(256) k_orb_describe(const LevelsDev L, const u
 // ---------------------------------------------------------------------------------------
 // Enqueue one extraction on ctx->stream (scratch: (*ctx->orbws)).  The keypoint count lands in the slot's
 // pinned word; orb_finish() reads it once the stream (or the slot's `ready` event) has been waited for.
-static int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
-                       const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride)
+int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
+                const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride)
 {
     fs->has_kp = false;
+    fs->kp_depth = false;           // ... and so do the depths of vo_sparse_stereo
     fs->mono_serial = 0;            // depths of a monocular pose step belong to the keypoints this run replaces
     if (w <= 2 * EDGE || h <= 2 * EDGE) {
         // level 0 has no pixel inside the border, and no smaller level has one: runByImageBorder clears every level
@@ -1099,7 +1100,7 @@ int orb_slot_enqueue(vo_ctx* ctx, FrameSlot& f, int nfeatures, int mask_mode, in
     int x0 = 0, y0 = 0, x1 = f.w, y1 = f.h;
     if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < f.w ? ctx->roi[2] : f.w; y1 = ctx->roi[3] < f.h ? ctx->roi[3] : f.h; }
     const int cw = x1 - x0, ch = y1 - y0;
-    if (cw <= 0 || ch <= 0) { f.has_kp = false; *f.n_kp_host = 0; return VO_OK; }
+    if (cw <= 0 || ch <= 0) { f.has_kp = false; f.kp_depth = false; *f.n_kp_host = 0; return VO_OK; }
     return orb_enqueue(ctx, &f, f.left + (size_t)y0 * f.w + x0, f.w, cw, ch, nfeatures, mask_mode,
                        f.disp16 + (size_t)y0 * f.w + x0, f.w, min_disp16, max_disp16, nullptr, 0);
 }

@@ -1613,7 +1613,9 @@ static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const
     if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
-    if (!a.has_kp || !b.has_kp || !a.has_disp || !b.has_disp) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
+    if (!a.has_kp || !b.has_kp) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
+    if (slot_sparse(a) != slot_sparse(b)) return vo_fail(ctx, VO_E_STATE, "%s: one slot's keypoints carry depth, the other's do not", who);
+    if (!slot_sparse(a) && (!a.has_disp || !b.has_disp)) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
     if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
     if (a.n_kp > 0 && b.n_kp < 2) return vo_fail(ctx, VO_E_ARG, "train set has fewer than 2 descriptors");
     return VO_OK;
@@ -1715,7 +1717,7 @@ extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, in
         }
         if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, rec, arr))) return rc;
         if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
-        if ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b))) return rc;   // never a pose from an undefined disparity
+        if (!slot_sparse(a) && ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b)))) return rc;   // never a pose from an undefined disparity
     }
     return pnp_unpack(ctx, rec, arr, a.n_kp, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, t_idx, "vo_pnp_pair");
 }
@@ -1743,6 +1745,7 @@ extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double rat
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
+    if (slot_sparse(a)) p.gen_a = p.gen_b = 0;       // the step read no disparity: nothing to check at _end
     p.pnp = true; p.want = want_matches != 0 && a.n_kp > 0; p.nq = a.n_kp;
     return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }

@@ -194,7 +194,14 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         DALLOC(f.kp_xy, (size_t)ctx->kp_cap * 2); DALLOC(f.kp_size, ctx->kp_cap); DALLOC(f.kp_angle, ctx->kp_cap);
         DALLOC(f.kp_resp, ctx->kp_cap); DALLOC(f.kp_oct, ctx->kp_cap); DALLOC(f.desc, (size_t)ctx->kp_cap * 32);
         DALLOC(f.mono_depth, ctx->kp_cap); DALLOC(f.mono_serial_dev, 16);
+        DALLOC(f.kp_xyz, (size_t)ctx->kp_cap * 3); DALLOC(f.kp_disp, ctx->kp_cap);
         if (dev_zero(f.mono_serial_dev, 64) != hipSuccess) { g_create_err = "clearing a slot's depth serial failed"; vo_destroy(ctx); return VO_E_HIP; }
+    }
+    {
+        FrameSlot& r = ctx->sparse_r;      // the second scratch keypoint set of vo_sparse_stereo
+        DALLOC(r.kp_xy, (size_t)ctx->kp_cap * 2); DALLOC(r.kp_size, ctx->kp_cap); DALLOC(r.kp_angle, ctx->kp_cap);
+        DALLOC(r.kp_resp, ctx->kp_cap); DALLOC(r.kp_oct, ctx->kp_cap); DALLOC(r.desc, (size_t)ctx->kp_cap * 32);
+        DALLOC(ctx->sp_match, ctx->kp_cap); DALLOC(ctx->sp_disp, ctx->kp_cap); DALLOC(ctx->sp_xyz, (size_t)ctx->kp_cap * 3);
     }
     ctx->stage_bytes = npx * 3;
     DALLOC(ctx->stage_in, ctx->stage_bytes * 2);
@@ -223,6 +230,8 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     }
     memset(ctx->slot_words, 0, 128 * sizeof(int32_t));
     for (int s = 0; s <= VO_NUM_SLOTS; s++) { ctx->slots[s].n_kp_host = ctx->slot_words + s; ctx->slots[s].sweep_word = ctx->slot_words + 64 + s; }
+    ctx->sparse_r.n_kp_host = ctx->slot_words + 32;      // (words 29 .. 63 belong to no slot)
+    ctx->sp_rec = ctx->slot_words + 40;
     DALLOC(ctx->d_sweep_errs, 64);
     if (dev_zero(ctx->d_sweep_errs, 64 * sizeof(int)) != hipSuccess) { g_create_err = "clearing the sweep error counter failed"; vo_destroy(ctx); return VO_E_HIP; }
     if (const char* e8 = getenv("VO_ENGINES")) { int v = atoi(e8); if (v >= 1 && v <= vo_ctx::MAX_ENGINES) ctx->n_engines = v; }
@@ -273,12 +282,14 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (int s = 0; s <= VO_NUM_SLOTS; s++) {
         FrameSlot& f = ctx->slots[s];
-        void* ps[] = { f.left, f.right, f.disp16, f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc, f.mono_depth, f.mono_serial_dev };
+        void* ps[] = { f.left, f.right, f.disp16, f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc, f.mono_depth, f.mono_serial_dev,
+                       f.kp_xyz, f.kp_disp };
         for (void* p : ps) if (p) (void)hipFree(p);
         if (f.ready) (void)hipEventDestroy(f.ready);
     }
     void* ps[] = { ctx->stage_in, ctx->map1[0], ctx->map1[1], ctx->map2[0], ctx->map2[1], ctx->dump, ctx->rs_ofs, ctx->rs_coef, ctx->pyr_rects,
-                   ctx->host_mask_dev, ctx->mq, ctx->mt, ctx->red, ctx->img3_ws, ctx->d_sweep_errs };
+                   ctx->host_mask_dev, ctx->mq, ctx->mt, ctx->red, ctx->img3_ws, ctx->d_sweep_errs, ctx->sparse_r.kp_xy, ctx->sparse_r.kp_size,
+                   ctx->sparse_r.kp_angle, ctx->sparse_r.kp_resp, ctx->sparse_r.kp_oct, ctx->sparse_r.desc, ctx->sp_match, ctx->sp_disp, ctx->sp_xyz };
     for (void* p : ps) if (p) (void)hipFree(p);
     alt_free(ctx);
     match_ws_free(ctx->main_mw);
@@ -542,7 +553,7 @@ extern "C" int vo_upload_pair(vo_ctx* ctx, int slot, const uint8_t* left, const 
     // the second ingest reuses the staging area: order on the stream makes that safe
     rc = ingest(ctx, 1, right, w, h, channels, preprocessed, f.right, ctx->stage_in);
     if (rc) return rc;
-    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
     return VO_OK;
 }
 
@@ -558,7 +569,7 @@ extern "C" int vo_upload_mono(vo_ctx* ctx, int slot, const uint8_t* img, int w, 
     if ((rc = slot_wait(ctx, f)) || (rc = slot_before_overwrite(ctx, f))) return rc;
     StageTimer t(ctx, VO_T_UPLOAD);
     if ((rc = ingest(ctx, 0, img, w, h, channels, 1, f.left, ctx->stage_in))) return rc;
-    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
     return VO_OK;
 }
 
@@ -602,7 +613,7 @@ extern "C" int vo_load_staged_pair(vo_ctx* ctx, int slot, int index, int preproc
     if (rc) return rc;
     rc = ingest(ctx, 1, ctx->staged + per * (2 * index + 1), w, h, ctx->staged_ch, preprocessed, f.right, ctx->stage_in, hipMemcpyDeviceToDevice);
     if (rc) return rc;
-    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
     return VO_OK;
 }
 
@@ -735,7 +746,7 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
         kind = hipMemcpyHostToDevice;
     }
     ctx->next_engine = (engine + 1) % ctx->n_engines;
-    f.w = w; f.h = h; f.has_kp = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
     {
         EngineScope on_engine(ctx, engine);          // ctx->stream / staging / SGBM + ORB workspaces are the engine's in here
         const int stagger = ctx->tune_stagger >= 0 ? ctx->tune_stagger : (7 * ctx->n_engines + 8) / 16;
@@ -822,7 +833,7 @@ extern "C" int vo_prefetch_staged_mono(vo_ctx* ctx, int slot, int index, int nfe
     ctx->mono_engine = (engine + 1) % span;
     const size_t per = (size_t)ctx->staged_w * ctx->staged_h * ctx->staged_ch;
     const int w = ctx->staged_w, h = ctx->staged_h;
-    f.w = w; f.h = h; f.has_kp = false; f.n_kp = 0; f.kp_pending = false; f.has_disp = false;
+    f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false; f.has_disp = false;
     {
         EngineScope on_engine(ctx, engine);
         rc = slot_before_overwrite(ctx, f);
@@ -1017,7 +1028,7 @@ extern "C" int vo_sgbm_compute(vo_ctx* ctx, int slot, int16_t* disp16_out)
     if ((rc = slot_wait(ctx, f))) return rc;
     rc = sgbm_run(ctx, f, f.w, f.h);
     if (rc) return rc;
-    f.has_disp = true; f.kp_pending = false; f.has_kp = false;
+    f.has_disp = true; f.kp_pending = false; f.has_kp = false; f.kp_depth = false;
     if (disp16_out) {
         VO_HIP(ctx, hipMemcpyAsync(disp16_out, f.disp16, (size_t)f.w * f.h * 2, hipMemcpyDeviceToHost, ctx->stream));
         VO_HIP(ctx, hipStreamSynchronize(ctx->stream));

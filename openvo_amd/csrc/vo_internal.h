@@ -70,6 +70,12 @@ struct FrameSlot {
     int32_t* sweep_word = nullptr;
     int32_t disp_gen = 0;
     int kp_params[4] = {0, 0, 0, 0};   // nfeatures, mask_mode, min_disp16, max_disp16 of the pending run
+    // sparse stereo depth (vo_sparse_stereo): 3-D position (3 floats) and disparity of each keypoint, kp_cap entries.  kp_depth: the
+    // keypoints the slot holds carry them (and are only the keypoints that have a depth); cleared by every ORB extraction into the
+    // slot and by every refill.  The pose steps read their points from kp_xyz when BOTH slots' keypoints carry depth.
+    float* kp_xyz = nullptr;
+    float* kp_disp = nullptr;
+    bool kp_depth = false;
     // the slot's look-ahead run is a member of the context's open sweep group: its diagonal sweep, post filters and ORB chain are
     // not enqueued and `ready` is NOT recorded for this run yet -- whoever is about to wait on, read, refill or drop the slot
     // closes the group first (sweep_group_close_for)
@@ -168,6 +174,13 @@ struct vo_ctx {
     bool has_map[2] = {false, false};
 
     FrameSlot slots[VO_NUM_SLOTS + 1];  // last slot = scratch for the *_host seams
+    // vo_sparse_stereo: the left keypoints are extracted into the scratch slot above, the right ones into this second scratch set
+    // (keypoint arrays and pinned count word only); sp_match / sp_disp / sp_xyz: per left keypoint the associated right keypoint
+    // (-1: none), the refined disparity (NaN: rejected) and its 3-D position; sp_rec (pinned): {left keypoints, accepted, kept}
+    FrameSlot sparse_r;
+    int32_t* sp_match = nullptr;
+    float *sp_disp = nullptr, *sp_xyz = nullptr;
+    int32_t* sp_rec = nullptr;
 
     // staging
     uint8_t* stage_in = nullptr;   // raw upload (max_w*max_h*3)
@@ -350,6 +363,11 @@ int slot_before_overwrite(vo_ctx* ctx, FrameSlot& f);
 // `done` marks the end of an asynchronous step that reads the slot: whoever overwrites the slot waits for it first
 void slot_add_reader(FrameSlot& f, hipEvent_t done);
 int orb_slot_enqueue(vo_ctx* ctx, FrameSlot& f, int nfeatures, int mask_mode, int min_disp16, int max_disp16);
+// one extraction on ctx->stream into the keypoint arrays of *fs (enqueue only: the count lands in fs->n_kp_host)
+int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
+                const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride);
+// the slot's keypoints carry depth (vo_sparse_stereo): the pose steps take their 3-D points from kp_xyz
+static inline bool slot_sparse(const FrameSlot& f) { return f.has_kp && f.kp_depth; }
 // kernel `fn` may use up to 160 KB of dynamic LDS: set once per context, before its first launch that needs more than 64 KB
 int lds_allow_big(vo_ctx* ctx, const void* fn);
 // Device memory that must read zero before its first use on WHATEVER stream: the context's streams are non-blocking, they do

@@ -123,6 +123,7 @@ class FrameHandle:
         self.roi = roi                      # (x0, y0, x1, y1) numpy-slice bounds, already clipped
         self._cache = {}
         self._lazy_kps = []                 # weak refs of KeyPointLists still living only in the slot
+        self.sparse = False                 # a frame of StereoCamera.compute_sparse: keypoints with depth, no disparity image
 
     @property
     def live(self):
@@ -142,6 +143,8 @@ class FrameHandle:
                 self._cache[kind] = self.ctx.download_xyz(self.slot, (self.h, self.w))
             elif kind == "left":
                 self._cache[kind] = self.ctx.download_left(self.slot, (self.h, self.w))
+            elif kind in ("kp_xyz", "kp_disp"):
+                self._cache["kp_xyz"], self._cache["kp_disp"] = self.ctx.download_keypoint_depth(self.slot)
         return self._cache[kind]
 
     def materialize_keypoints(self):
@@ -151,12 +154,14 @@ class FrameHandle:
             if k is not None:
                 k._load()
         self._lazy_kps = []
+        if self.sparse and self.live:
+            self.full("kp_xyz")             # the depths belong to the keypoints: they go when the keypoints go
 
     def evict(self):
         """Detach from the device slot, keeping host copies of everything."""
         if self.live:
             self.materialize_keypoints()
-            for kind in ("disp", "xyz", "left"):
+            for kind in (("kp_xyz", "left") if self.sparse else ("disp", "xyz", "left")):
                 self.full(kind)
             self.slot = None
 
@@ -227,7 +232,7 @@ class DeviceImage:
 
     def __getattr__(self, name):
         # only reached for names the class does not define: forward to the materialised array
-        if name.startswith("__") or name in ("frame", "kind"):
+        if name.startswith("__") or name in ("frame", "kind", "_n"):
             raise AttributeError(name)
         return getattr(self.numpy(), name)
 
@@ -281,6 +286,27 @@ def _forward_operators():
 
 
 _forward_operators()
+
+
+class KeypointDepth(DeviceImage):
+    """Per-keypoint array of a frame whose keypoints carry depth (StereoCamera.compute_sparse): kind "kp_xyz" (n, 3) or "kp_disp"
+    (n,), float32, in keypoint order; downloaded on first numpy use like every DeviceImage."""
+
+    _dt = {"kp_xyz": np.float32, "kp_disp": np.float32}
+
+    def __init__(self, frame, kind, n):
+        super().__init__(frame, kind)
+        self._n = int(n)
+
+    @property
+    def shape(self):
+        return (self._n, 3) if self.kind == "kp_xyz" else (self._n,)
+
+    def numpy(self):
+        return self.frame.full(self.kind)
+
+    def __repr__(self):
+        return "KeypointDepth(%s, shape=%s)" % (self.kind, self.shape)
 
 
 class DisparityMask(DeviceImage):

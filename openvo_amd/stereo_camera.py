@@ -11,7 +11,7 @@ import pickle
 import numpy as np
 
 from . import _native, calib
-from .features import DeviceImage, FrameHandle, StereoSGBM
+from .features import DeviceDescriptors, DeviceImage, FrameHandle, KeyPointList, KeypointDepth, StereoSGBM
 
 
 class StagedPair:
@@ -294,6 +294,40 @@ class StereoCamera:
     def crop_to_valid_region_right(self, img):
         vr = self.valid_region_right
         return img[vr[1]: vr[3], vr[0]: vr[2]]
+
+    def compute_sparse(self, img_left, img_right, nfeatures, preprocessed=False, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75):
+        """Sparse stereo depth (not in the reference): ORB on both rectified images, association along the row, sub-pixel
+        refinement -- no disparity image (include/vo355.h, vo_sparse_stereo).  -> (keypoints, descriptors, xyz (n, 3),
+        disparity (n,), img_left): the left keypoints that have a depth, device-resident and lazy like compute_3d's results.
+        Takes host arrays or a StagedPair; a SubmittedPair has SGBM work in flight and is refused.  Starts no look-ahead."""
+        if isinstance(img_left, SubmittedPair):
+            raise ValueError("compute_sparse takes host arrays or a StagedPair: a SubmittedPair's disparity is already in flight")
+        staged = isinstance(img_left, StagedPair)
+        if not staged:
+            img_left, img_right = np.asarray(img_left), np.asarray(img_right)
+            if img_left.ndim != img_right.ndim:
+                if img_left.ndim == 3:
+                    img_left = self._ctx.cvt_bgr2gray(img_left)
+                if img_right.ndim == 3:
+                    img_right = self._ctx.cvt_bgr2gray(img_right)
+        import weakref
+        slot, _ = self._acquire_slot()
+        self._slot_gen[slot] += 1
+        if staged:
+            w, h = self._ctx.load_staged_pair(slot, img_left.index, preprocessed)
+        else:
+            w, h = self._ctx.upload_pair(slot, img_left, img_right, preprocessed)
+        n = int(self._ctx.sparse_stereo(slot, nfeatures, min_disp, max_disp, row_tol, max_hamming)[2])
+        vr = self.valid_region_left
+        y0, y1, _ = slice(vr[1], vr[3]).indices(h)
+        x0, x1, _ = slice(vr[0], vr[2]).indices(w)
+        frame = FrameHandle(self, slot, w, h, (x0, y0, max(x1, x0), max(y1, y0)))
+        frame.sparse = True
+        self._slot_owner[slot] = weakref.ref(frame)
+        kps = KeyPointList(None, frame, n)
+        kps.desc = DeviceDescriptors(kps)
+        frame._lazy_kps += [weakref.ref(kps), weakref.ref(kps.desc)]
+        return kps, kps.desc, KeypointDepth(frame, "kp_xyz", n), KeypointDepth(frame, "kp_disp", n), DeviceImage(frame, "left")
 
     def compute_3d(self, img_left, img_right, preprocessed=False):
         """-> (img_3d float32 HcxWcx3, disparity float32 HcxWc, img_left uint8 HcxWc), cropped;

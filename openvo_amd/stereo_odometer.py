@@ -25,7 +25,7 @@ class StereoOdometer:
     def __init__(self, stereo_camera, nfeatures=500, match_threshold=0.8, rigidity_threshold=0,
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
-                 match_window=None):
+                 match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -43,7 +43,22 @@ class StereoOdometer:
         in y (include/vo355.h).  The radii are per frame: like the motion gates they are multiplied by the frames the pair
         spans -- skipped_frames + 1 for (current, next), skipped_frames + 2 for the one-frame-back fallback.  A keypoint with
         fewer than two candidates in its window gives no match, and the ratio test inside a window is laxer than over the
-        whole image: the window replaces the clique filter on the default odometer, it does not add to it (README)."""
+        whole image: the window replaces the clique filter on the default odometer, it does not add to it (README).
+        depth="sparse" (an extension; default "dense" = the reference's path): no disparity image is computed.  ORB runs on both
+        rectified images, left and right keypoints are associated along the row (at most sparse_row_tol pixels apart in y at
+        the keypoint's scale, Hamming distance at most sparse_max_hamming) and refined to sub-pixel (StereoCamera.compute_sparse,
+        include/vo355.h); a frame's keypoints are then the left keypoints that have a depth, current_3d / prev_3d are their (n, 3)
+        points and current_disparity their (n,) disparities.  The state machine, both pose methods, cross_check and match_window
+        are unchanged; feature_mask is not used.  Sparse pairs are processed synchronously (run() submits nothing ahead)."""
+        if not isinstance(depth, str) or depth not in ("dense", "sparse"):
+            raise ValueError("depth must be 'dense' or 'sparse'")
+        if (isinstance(sparse_row_tol, (bool, np.bool_)) or not isinstance(sparse_row_tol, (int, float, np.integer, np.floating))
+                or not np.isfinite(sparse_row_tol) or sparse_row_tol < 0):
+            raise ValueError("sparse_row_tol must be a finite number >= 0")
+        if (isinstance(sparse_max_hamming, (bool, np.bool_)) or not isinstance(sparse_max_hamming, (int, np.integer))
+                or not 0 <= sparse_max_hamming <= 256):
+            raise ValueError("sparse_max_hamming must be an int in 0 .. 256")
+        self.depth, self.sparse_row_tol, self.sparse_max_hamming = depth, float(sparse_row_tol), int(sparse_max_hamming)
         if pose_method not in ("umeyama", "pnp"):
             raise ValueError("pose_method must be 'umeyama' or 'pnp'")
         if not isinstance(cross_check, (bool, np.bool_)):
@@ -125,9 +140,14 @@ class StereoOdometer:
         hand-off inside its aggregation sweep gave up waiting on an oversubscribed GPU: no pose is ever derived from such a
         pair.  The odometer's state is that of before the call (the frame is neither saved nor counted as skipped); the same
         pair may be passed again, or the next one."""
-        next_3d, next_disp, next_img = self.stereo.compute_3d(img_left, img_right,
-                                                              preprocessed=self.preprocessed_frames)
-        next_kps, next_desc = self.orb.detectAndCompute(next_img, self.feature_mask(next_disp))
+        if self.depth == "sparse":
+            next_kps, next_desc, next_3d, next_disp, next_img = self.stereo.compute_sparse(
+                img_left, img_right, self.orb.nfeatures, preprocessed=self.preprocessed_frames, min_disp=self.MIN_VALID_DISPARITY,
+                max_disp=self.MAX_VALID_DISPARITY, row_tol=self.sparse_row_tol, max_hamming=self.sparse_max_hamming)
+        else:
+            next_3d, next_disp, next_img = self.stereo.compute_3d(img_left, img_right,
+                                                                  preprocessed=self.preprocessed_frames)
+            next_kps, next_desc = self.orb.detectAndCompute(next_img, self.feature_mask(next_disp))
         if len(next_kps) < self.min_matches:
             self.skipped_frames += 1
             self.skip_cause = "keypoints"
@@ -242,8 +262,8 @@ class StereoOdometer:
         results arrive in a burst (a cold start: every pair in flight finishes at about the same time) the short kernel
         chains of many pairs run side by side instead of one after the other behind the host.  Purely an ordering change:
         _pair_fused looks a step up by its slots and parameters and computes on the spot when the guess was wrong."""
-        if not self._fused_ok() or self.orb.last_slot_args is None:
-            return self._drop_specs()
+        if self.depth == "sparse" or not self._fused_ok() or self.orb.last_slot_args is None:
+            return self._drop_specs()           # (sparse pairs are never on the device ahead of their update())
         kps = self.current_kps
         if not self._on_device(kps, self.current_desc, self.current_3d):
             return self._drop_specs()
@@ -300,6 +320,11 @@ class StereoOdometer:
         from collections import deque
         if on_sweep_timeout not in ("raise", "skip"):
             raise ValueError("on_sweep_timeout must be 'raise' or 'skip'")
+        if self.depth == "sparse":
+            # no look-ahead for sparse pairs: update() pair by pair, nothing submitted and no sweep to time out
+            for L, R in pairs:
+                yield self.update(L, R)
+            return
         cam, ctx = self.stereo, self.stereo._ctx
         depth = int(cam.lookahead if depth is None else depth)
         nbuf = _native.VO_NUM_HOST_STAGE
@@ -519,6 +544,9 @@ class StereoOdometer:
             matches = [m for m in matches if len(back[m.trainIdx]) and back[m.trainIdx][0].trainIdx == m.queryIdx]
         if len(matches) < self.min_matches:
             return None, None
+        if self.depth == "sparse":
+            # the clouds are per keypoint: indexed by the matches
+            return (np.asarray(im3d1, np.float32)[[m.queryIdx for m in matches]], np.asarray(im3d2, np.float32)[[m.trainIdx for m in matches]])
         pts1 = [self.bilinear_interpolate_pixels(im3d1, *kps1[m.queryIdx].pt) for m in matches]
         pts2 = [self.bilinear_interpolate_pixels(im3d2, *kps2[m.trainIdx].pt) for m in matches]
         return np.array(pts1), np.array(pts2)
