@@ -462,6 +462,12 @@ enum { VO_T_UPLOAD = 0, VO_T_SGBM_COST, VO_T_SGBM_AGG, VO_T_SGBM_WTA, VO_T_SGBM_
 int vo_enable_timing(vo_ctx* ctx, int on);
 /* accumulated milliseconds and launch counts per stage since the last reset */
 int vo_get_timings(vo_ctx* ctx, double* ms_out /*VO_T_NSTAGES*/, int64_t* launches_out, int reset);
+/* Development aid: the brackets recorded since vo_get_timings last resolved them, one by one and in the order they were opened
+ * -- stage id, entries (pairs a sweep group's launch carries), begin and end in milliseconds relative to the begin of the first
+ * of them (brackets lie on different streams: a begin may be negative).  Waits for every stream of the context, writes at most
+ * `cap` brackets, *n_out = how many there are; a bracket whose events cannot be resolved is left out.  Consumes nothing (a
+ * following vo_get_timings accumulates the same brackets); *n_out = 0 while timing is off. */
+int vo_get_stage_timeline(vo_ctx* ctx, int cap, int32_t* stage_out, int32_t* entries_out, double* begin_ms_out, double* end_ms_out, int* n_out);
 /* algorithmic cost-volume cells (width1*H*D) of the last vo_sgbm_compute, and the number of path directions its dominant
  * aggregation kernel covers (3: NW / N / NE inside k_sgbm_diag; all of them for uniquenessRatio >= 100) */
 int vo_sgbm_last_geometry(vo_ctx* ctx, int64_t* cells, int* n_paths);

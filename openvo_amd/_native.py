@@ -42,6 +42,7 @@ SYMBOLS = [
     "vo_recover_pose", "vo_mono_pose_pair", "vo_mono_pose_pair_begin", "vo_mono_pose_pair_end", "vo_download_mono_depth",
     "vo_set_match_window", "vo_clear_match_window", "vo_bf_knn2_hamming_window",
     "vo_sparse_stereo", "vo_download_keypoint_depth", "vo_sparse_match_host",
+    "vo_get_stage_timeline",
 ]
 
 
@@ -225,6 +226,8 @@ def lib():
             L.vo_mono_pose_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, cu, ci, cu, cd, vp, vp]
             L.vo_mono_pose_pair_end.argtypes = [vp, ci, vp]
             L.vo_download_mono_depth.argtypes = [vp, ci, vp, vp]
+        if hasattr(L, "vo_get_stage_timeline"):     # (likewise: an older build has no stage timeline)
+            L.vo_get_stage_timeline.argtypes = [vp, ci, vp, vp, vp, vp, vp]
         if hasattr(L, "vo_lookahead_flush"):        # (an older build of the ABI loaded through VO355_LIB for an A/B run has no sweep groups)
             L.vo_set_sweep_group.argtypes = [vp, ci]
             L.vo_lookahead_flush.argtypes = [vp]
@@ -976,6 +979,16 @@ class Context:
         n = np.zeros(len(T_STAGES), np.int64)
         self._ck(self._lib.vo_get_timings(self._h, _p(ms), _p(n), int(reset)))
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(T_STAGES)}
+
+    def stage_timeline(self, cap=65536):
+        """Development aid: the stage brackets recorded since timings() last resolved them, in the order they were opened, as
+        (stage name, entries, begin ms, end ms) relative to the begin of the first (vo_get_stage_timeline).  Consumes nothing;
+        empty while timing is off."""
+        st, en = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        b, e = np.zeros(cap, np.float64), np.zeros(cap, np.float64)
+        n = ctypes.c_int(0)
+        self._ck(self._lib.vo_get_stage_timeline(self._h, cap, _p(st), _p(en), _p(b), _p(e), ctypes.byref(n)))
+        return [(T_STAGES[st[i]], int(en[i]), float(b[i]), float(e[i])) for i in range(min(n.value, cap))]
 
     def sgbm_sweep_status(self):
         """Number of SGBM runs of this context whose diagonal sweep gave up a strip hand-off (0 = healthy; sticky).  Results that

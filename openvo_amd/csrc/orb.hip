@@ -204,16 +204,39 @@ int orb_prepare_tables(vo_ctx* ctx, int w, int h)
 // columns / rows (v < min, v >= max: the clamped taps of the exact-bilinear table) become taps with weights (256, 0).
 // The mask pyramid (feature_mask of stereo_odometer.py:38-41 at level 0, or an explicit mask) is resized the same way and
 // then thresholded (threshold(254, THRESH_TOZERO)), as orb.cpp does.
-struct PyrArgs {
+struct PyrArgs { int mask_mode, min_d16, max_d16, nbx, nby, bufA, bufB, tab; };
+
+// Every kernel of the <= 2000-feature chain serves up to VO_MAX_SWEEP_GROUP extractions of ONE geometry and ONE request
+// (nfeatures, mask mode, disparity range: `L` and PyrArgs travel once per launch) in one launch: the member is a block index of
+// its own grid dimension -- uniform per workgroup, so its entry of the table in the kernel arguments is read with scalar loads
+// -- and names the member's source images, its ORB scratch (an OrbWs) and the keypoint arrays of its slot.  A pair on its own
+// is a table of one.  (The table is 2016 bytes: with LevelsDev well inside the 4 KB of a kernel-argument segment.)
+struct OrbJob {
     const uint8_t* img; const int16_t* disp16; const uint8_t* mask;
-    int img_stride, disp_stride, mask_stride, mask_mode, min_d16, max_d16, nbx, nby, bufA, bufB, tab;
+    uint8_t *pyr_img, *pyr_mask;
+    int32_t *cand_pos, *candA_pos, *candB_pos, *counters;
+    float *cand_resp, *candA_resp, *candB_resp;
+    float *kp_xy, *kp_size, *kp_resp, *kp_angle;
+    int32_t* kp_oct;
+    uint8_t* desc;
+    int32_t* n_kp_host;
+    int img_stride, disp_stride, mask_stride, pad;
 };
+struct OrbJobs { OrbJob j[VO_MAX_SWEEP_GROUP]; };
+static_assert(sizeof(LevelsDev) + sizeof(PyrArgs) + sizeof(OrbJobs) + 64 <= 4096, "the ORB kernels' arguments must fit one kernel-argument segment");
 
 template <bool MASK>
-__global__ void __launch_bounds__(256) k_orb_pyramid(const LevelsDev L, const PyrArgs A, const int32_t* __restrict__ rects,
-                                                     const int32_t* __restrict__ ofs, const uint16_t* __restrict__ coef,
-                                                     uint8_t* __restrict__ pimg, uint8_t* __restrict__ pmask, int32_t* __restrict__ cnt)
+__global__ void __launch_bounds__(256) k_orb_pyramid(const LevelsDev L, const PyrArgs A, const OrbJobs jobs, const int32_t* __restrict__ rects,
+                                                     const int32_t* __restrict__ ofs, const uint16_t* __restrict__ coef)
 {
+    const OrbJob& job = jobs.j[blockIdx.z];
+    const uint8_t* __restrict__ const src_img = job.img;
+    const int16_t* __restrict__ const src_disp = job.disp16;
+    const uint8_t* __restrict__ const src_mask = job.mask;
+    const int img_stride = job.img_stride, disp_stride = job.disp_stride, mask_stride = job.mask_stride;
+    uint8_t* __restrict__ const pimg = job.pyr_img;
+    uint8_t* __restrict__ const pmask = job.pyr_mask;
+    int32_t* __restrict__ const cnt = job.counters;
     extern __shared__ __attribute__((aligned(16))) uint8_t s_pyr_generic[];
     // (explicit LDS address space: a pointer picked from an array by a run-time index is a generic pointer to the compiler, and
     // every access through it a flat_load / flat_store)
@@ -288,13 +311,13 @@ __global__ void __launch_bounds__(256) k_orb_pyramid(const LevelsDev L, const Py
 #pragma unroll
                 for (int u = 0; u < RB0; u++) {
                     const int yy = min(yb + 4 * u, nh - 1), y = y0 + yy;
-                    v[u] = A.img[(size_t)y * A.img_stride + x];
+                    v[u] = src_img[(size_t)y * img_stride + x];
                     if (MASK) {
                         if (A.mask_mode == 1) {
-                            const int dd = A.disp16[(size_t)y * A.disp_stride + x];
+                            const int dd = src_disp[(size_t)y * disp_stride + x];
                             m[u] = (dd >= A.min_d16 && dd <= A.max_d16) ? 255 : 0;
                         } else
-                            m[u] = A.mask[(size_t)y * A.mask_stride + x];
+                            m[u] = src_mask[(size_t)y * mask_stride + x];
                     }
                 }
 #pragma unroll
@@ -408,10 +431,14 @@ __device__ __forceinline__ int fast_corner_score(const int* d)
 //   B  the listed pixels, densely packed over the lanes: the ring's dark / bright masks and the run-of-9 test; survivors listed
 //   C  the few real corners: cornerScore
 // The tile's pixels (+ the ring's reach) are staged in LDS once: a ring read is one ds_read_u8 at a constant offset.
-__global__ void __launch_bounds__(256) k_orb_fast_nms(const LevelsDev L, const uint8_t* __restrict__ pimg,
-                                                      const uint8_t* __restrict__ pmask, int with_mask, int32_t* __restrict__ cand_pos,
-                                                      float* __restrict__ cand_resp, int32_t* __restrict__ cnt)
+__global__ void __launch_bounds__(256) k_orb_fast_nms(const LevelsDev L, const OrbJobs jobs, int with_mask)
 {
+    const OrbJob& job = jobs.j[blockIdx.y];
+    const uint8_t* __restrict__ const pimg = job.pyr_img;
+    const uint8_t* __restrict__ const pmask = job.pyr_mask;
+    int32_t* __restrict__ const cand_pos = job.cand_pos;
+    float* __restrict__ const cand_resp = job.cand_resp;
+    int32_t* __restrict__ const cnt = job.counters;
     constexpr int TW = 64, TH = ORB_FAST_TH, RW = TH / 4, SW = TW + 2, SH = TH + 2, SP = SW + 2;   // padded LDS row
     constexpr int IW = SW + 6, IH = SH + 6, IP = IW + 4;                    // staged pixels: the scored region + 3 on each side
     constexpr int NPX = SW * SH;
@@ -812,10 +839,20 @@ __global__ void __launch_bounds__(1024) k_orb_select_harris(const LevelsDev L, c
 // (35 + 7 + 42 us at config 2).  A level whose survivors do not fit the LDS lists (ORB_SEL_CAP: a flood of score ties) falls
 // back to the global scratch arrays, inside the same launch.
 #define ORB_SEL_CAP 2048
-__global__ void __launch_bounds__(1024) k_orb_select(const LevelsDev L, const uint8_t* __restrict__ pimg, const int32_t* cand_pos, const float* cand_resp,
-                                                     int32_t* candA_pos, float* candA_resp, int32_t* fin_pos, float* fin_resp,
-                                                     int32_t* tmp_pos, float* tmp_resp, int32_t* cnt)
+__global__ void __launch_bounds__(1024) k_orb_select(const LevelsDev L, const OrbJobs jobs)
 {
+    // (the final lists replace the NMS lists, which are dead by then: fin_* alias cand_*, candB_* are scratch)
+    const OrbJob& job = jobs.j[blockIdx.y];
+    const uint8_t* __restrict__ const pimg = job.pyr_img;
+    const int32_t* const cand_pos = job.cand_pos;
+    const float* const cand_resp = job.cand_resp;
+    int32_t* const candA_pos = job.candA_pos;
+    float* const candA_resp = job.candA_resp;
+    int32_t* const fin_pos = job.cand_pos;
+    float* const fin_resp = job.cand_resp;
+    int32_t* const tmp_pos = job.candB_pos;
+    float* const tmp_resp = job.candB_resp;
+    int32_t* const cnt = job.counters;
     __shared__ int s_hist[256];
     __shared__ int s_thr, s_n, s_inlds, s_remaining, s_nf;
     __shared__ unsigned s_prefix, s_mask;
@@ -903,13 +940,20 @@ __device__ __forceinline__ int wave_sum_i32(int v)
 #define DESC_W (2 * DESC_R + 1)        // 39
 #define DESC_HR (DESC_W + 6)           // 45 rows after the row pass
 #define DESC_LD 40
-__global__ void __launch_bounds__(256) k_orb_describe(const LevelsDev L, const uint8_t* __restrict__ pimg,
-                                                     const int32_t* __restrict__ fin_pos, const float* __restrict__ fin_resp,
-                                                     int32_t* __restrict__ cnt, int cap, float* __restrict__ kp_xy,
-                                                     float* __restrict__ kp_size, float* __restrict__ kp_resp,
-                                                     int32_t* __restrict__ kp_oct, float* __restrict__ kp_angle,
-                                                     uint8_t* __restrict__ desc, int32_t* n_kp_host)
+__global__ void __launch_bounds__(256) k_orb_describe(const LevelsDev L, const OrbJobs jobs, int cap)
 {
+    const OrbJob& job = jobs.j[blockIdx.y];
+    const uint8_t* __restrict__ const pimg = job.pyr_img;
+    const int32_t* __restrict__ const fin_pos = job.cand_pos;
+    const float* __restrict__ const fin_resp = job.cand_resp;
+    int32_t* __restrict__ const cnt = job.counters;
+    float* __restrict__ const kp_xy = job.kp_xy;
+    float* __restrict__ const kp_size = job.kp_size;
+    float* __restrict__ const kp_resp = job.kp_resp;
+    int32_t* __restrict__ const kp_oct = job.kp_oct;
+    float* __restrict__ const kp_angle = job.kp_angle;
+    uint8_t* __restrict__ const desc = job.desc;
+    int32_t* const n_kp_host = job.n_kp_host;
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     // the levels' final lists are concatenated in level order: find this wave's keypoint
@@ -1003,17 +1047,72 @@ __global__ void __launch_bounds__(256) k_orb_describe(const LevelsDev L, const u
 // ---------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------
-// Enqueue one extraction on ctx->stream (scratch: (*ctx->orbws)).  The keypoint count lands in the slot's
-// pinned word; orb_finish() reads it once the stream (or the slot's `ready` event) has been waited for.
-int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
-                const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride)
+// The launches of n extractions of one geometry and one request on ctx->stream: one launch per kernel for all of them (a
+// StageTimer bracket of n entries).  nfeatures > 2000 (three selection launches whose Harris step is sized for ONE list of
+// ~16000 candidates) is only ever handed one member at a time.
+static int orb_launch(vo_ctx* ctx, const LevelsDev& dL, const OrbIn* in, int n, int w, int h, int nfeatures, int mask_mode, int min_d16, int max_d16)
 {
-    fs->has_kp = false;
-    fs->kp_depth = false;           // ... and so do the depths of vo_sparse_stereo
-    fs->mono_serial = 0;            // depths of a monocular pose step belong to the keypoints this run replaces
+    const int with_mask = mask_mode != 0;
+    OrbJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    for (int i = 0; i < n; i++) {
+        OrbJob& j = jobs.j[i];
+        const OrbWs& o = *in[i].ws;
+        const FrameSlot& fs = *in[i].fs;
+        j.img = in[i].img; j.disp16 = in[i].disp16; j.mask = in[i].mask;
+        j.img_stride = in[i].img_stride; j.disp_stride = in[i].disp_stride; j.mask_stride = in[i].mask_stride;
+        j.pyr_img = o.pyr_img; j.pyr_mask = o.pyr_mask;
+        j.cand_pos = o.cand_pos; j.candA_pos = o.candA_pos; j.candB_pos = o.candB_pos; j.counters = o.counters;
+        j.cand_resp = o.cand_resp; j.candA_resp = o.candA_resp; j.candB_resp = o.candB_resp;
+        j.kp_xy = fs.kp_xy; j.kp_size = fs.kp_size; j.kp_resp = fs.kp_resp; j.kp_angle = fs.kp_angle; j.kp_oct = fs.kp_oct;
+        j.desc = fs.desc; j.n_kp_host = fs.n_kp_host;
+    }
+    StageTimer t(ctx, VO_T_ORB, n);
+    {
+        PyrArgs pa;
+        pa.mask_mode = mask_mode;
+        pa.min_d16 = min_d16; pa.max_d16 = max_d16; pa.nbx = ctx->pyr_nbx; pa.nby = ctx->pyr_nby;
+        pa.bufA = ctx->pyr_buf[0]; pa.bufB = ctx->pyr_buf[1]; pa.tab = ctx->pyr_tab;
+        const size_t lds = (size_t)(with_mask ? 2 : 1) * (pa.bufA + pa.bufB) + (size_t)(NL - 1) * 2 * pa.tab * 8 + NL * 16;
+        if (lds > 150 * 1024) return vo_fail(ctx, VO_E_CAP, "pyramid cones of %dx%d need %zu bytes of LDS", w, h, lds);
+        auto kp = with_mask ? k_orb_pyramid<true> : k_orb_pyramid<false>;
+        if (int rca = lds_allow_big(ctx, (const void*)kp)) return rca;
+        hipLaunchKernelGGL(kp, dim3(pa.nbx, pa.nby, n), dim3(256), lds, ctx->stream, dL, pa, jobs, ctx->pyr_rects, ctx->rs_ofs, ctx->rs_coef);
+    }
+    int fast_tiles = 0;
+    for (int l = 0; l < NL; l++)
+        if (dL.l[l].w > 2 * EDGE && dL.l[l].h > 2 * EDGE) fast_tiles += div_up(dL.l[l].w - 2 * EDGE, 64) * div_up(dL.l[l].h - 2 * EDGE, ORB_FAST_TH);
+    hipLaunchKernelGGL(k_orb_fast_nms, dim3(std::max(1, std::min(fast_tiles, ORB_FAST_GRID_CAP)), n), dim3(256), 0, ctx->stream, dL, jobs, with_mask);
+    // after the select, cand_* hold the per-level final lists; candB_* are scratch
+    if (nfeatures <= 2000) {
+        hipLaunchKernelGGL(k_orb_select, dim3(NL, n), dim3(1024), 0, ctx->stream, dL, jobs);
+    } else {
+        const OrbWs& o = *in[0].ws;
+        hipLaunchKernelGGL(k_orb_select_fast, dim3(NL), dim3(1024), 0, ctx->stream, dL, o.cand_pos, o.cand_resp, o.candA_pos, o.counters);
+        hipLaunchKernelGGL(k_orb_harris, dim3(256, NL), dim3(256), 0, ctx->stream, dL, o.pyr_img, o.candA_pos, o.candA_resp, o.counters);
+        hipLaunchKernelGGL(k_orb_select_harris, dim3(NL), dim3(1024), (size_t)ORB_RANK_LDS * 4, ctx->stream, dL, o.candA_pos, o.candA_resp,
+                           o.cand_pos, o.cand_resp, o.candB_pos, o.candB_resp, o.counters);
+    }
+    hipLaunchKernelGGL(k_orb_describe, dim3(div_up(ctx->kp_cap, 4), n), dim3(256), 0, ctx->stream, dL, jobs, ctx->kp_cap);
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
+// Enqueue n extractions of one geometry (w x h) and one request on ctx->stream, each from its own source into its own slot's
+// keypoint arrays and through its own scratch.  The keypoint counts land in the slots' pinned words; orb_finish() reads one
+// once the stream (or the slot's `ready` event) has been waited for.
+int orb_enqueue_jobs(vo_ctx* ctx, const OrbIn* in, int n, int w, int h, int nfeatures, int mask_mode, int min_d16, int max_d16)
+{
+    if (n < 1 || n > VO_MAX_SWEEP_GROUP) return vo_fail(ctx, VO_E_ARG, "orb_enqueue_jobs: %d extractions in one batch", n);
+    for (int i = 0; i < n; i++) {
+        FrameSlot* const fs = in[i].fs;
+        fs->has_kp = false;
+        fs->kp_depth = false;           // ... and so do the depths of vo_sparse_stereo
+        fs->mono_serial = 0;            // depths of a monocular pose step belong to the keypoints this run replaces
+    }
     if (w <= 2 * EDGE || h <= 2 * EDGE) {
         // level 0 has no pixel inside the border, and no smaller level has one: runByImageBorder clears every level
-        *fs->n_kp_host = 0;
+        for (int i = 0; i < n; i++) *in[i].fs->n_kp_host = 0;
         return VO_OK;
     }
     int rc = orb_prepare_tables(ctx, w, h);
@@ -1034,44 +1133,18 @@ int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride
     // The level table (geometry + this call's quotas, 452 bytes) travels BY VALUE in every launch: extractions
     // queued on other engines' streams with other nfeatures keep the quotas they were enqueued with.
     const LevelsDev dL = *Lh;
-    const int with_mask = mask_mode != 0;
-    StageTimer t(ctx, VO_T_ORB);
-    {
-        PyrArgs pa;
-        pa.img = d_img; pa.disp16 = d_disp16; pa.mask = d_mask;
-        pa.img_stride = img_stride; pa.disp_stride = disp_stride; pa.mask_stride = mask_stride; pa.mask_mode = mask_mode;
-        pa.min_d16 = min_d16; pa.max_d16 = max_d16; pa.nbx = ctx->pyr_nbx; pa.nby = ctx->pyr_nby;
-        pa.bufA = ctx->pyr_buf[0]; pa.bufB = ctx->pyr_buf[1]; pa.tab = ctx->pyr_tab;
-        const size_t lds = (size_t)(with_mask ? 2 : 1) * (pa.bufA + pa.bufB) + (size_t)(NL - 1) * 2 * pa.tab * 8 + NL * 16;
-        if (lds > 150 * 1024) return vo_fail(ctx, VO_E_CAP, "pyramid cones of %dx%d need %zu bytes of LDS", w, h, lds);
-        auto kp = with_mask ? k_orb_pyramid<true> : k_orb_pyramid<false>;
-        if (int rca = lds_allow_big(ctx, (const void*)kp)) return rca;
-        hipLaunchKernelGGL(kp, dim3(pa.nbx, pa.nby), dim3(256), lds, ctx->stream, dL, pa, ctx->pyr_rects, ctx->rs_ofs, ctx->rs_coef,
-                           ctx->orbws->pyr_img, ctx->orbws->pyr_mask, ctx->orbws->counters);
-    }
-    int fast_tiles = 0;
-    for (int l = 0; l < NL; l++)
-        if (Lh->l[l].w > 2 * EDGE && Lh->l[l].h > 2 * EDGE) fast_tiles += div_up(Lh->l[l].w - 2 * EDGE, 64) * div_up(Lh->l[l].h - 2 * EDGE, ORB_FAST_TH);
-    hipLaunchKernelGGL(k_orb_fast_nms, dim3(std::max(1, std::min(fast_tiles, ORB_FAST_GRID_CAP))), dim3(256), 0, ctx->stream, dL,
-                       ctx->orbws->pyr_img, ctx->orbws->pyr_mask, with_mask, ctx->orbws->cand_pos, ctx->orbws->cand_resp, ctx->orbws->counters);
-    // after the select, cand_* hold the per-level final lists; candB_* are scratch
-    if (nfeatures <= 2000) {
-        hipLaunchKernelGGL(k_orb_select, dim3(NL), dim3(1024), 0, ctx->stream, dL, ctx->orbws->pyr_img, ctx->orbws->cand_pos, ctx->orbws->cand_resp,
-                           ctx->orbws->candA_pos, ctx->orbws->candA_resp, ctx->orbws->cand_pos, ctx->orbws->cand_resp, ctx->orbws->candB_pos,
-                           ctx->orbws->candB_resp, ctx->orbws->counters);
-    } else {
-        hipLaunchKernelGGL(k_orb_select_fast, dim3(NL), dim3(1024), 0, ctx->stream, dL, ctx->orbws->cand_pos, ctx->orbws->cand_resp, ctx->orbws->candA_pos,
-                           ctx->orbws->counters);
-        hipLaunchKernelGGL(k_orb_harris, dim3(256, NL), dim3(256), 0, ctx->stream, dL, ctx->orbws->pyr_img, ctx->orbws->candA_pos,
-                           ctx->orbws->candA_resp, ctx->orbws->counters);
-        hipLaunchKernelGGL(k_orb_select_harris, dim3(NL), dim3(1024), (size_t)ORB_RANK_LDS * 4, ctx->stream, dL, ctx->orbws->candA_pos, ctx->orbws->candA_resp,
-                           ctx->orbws->cand_pos, ctx->orbws->cand_resp, ctx->orbws->candB_pos, ctx->orbws->candB_resp, ctx->orbws->counters);
-    }
-    hipLaunchKernelGGL(k_orb_describe, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, dL, ctx->orbws->pyr_img, ctx->orbws->cand_pos,
-                       ctx->orbws->cand_resp, ctx->orbws->counters, ctx->kp_cap, fs->kp_xy, fs->kp_size, fs->kp_resp, fs->kp_oct, fs->kp_angle,
-                       fs->desc, fs->n_kp_host);
-    VO_CHECK_LAUNCH(ctx);
+    if (nfeatures <= 2000) return orb_launch(ctx, dL, in, n, w, h, nfeatures, mask_mode, min_d16, max_d16);
+    for (int i = 0; i < n; i++)
+        if ((rc = orb_launch(ctx, dL, in + i, 1, w, h, nfeatures, mask_mode, min_d16, max_d16))) return rc;
     return VO_OK;
+}
+
+// one extraction on ctx->stream through the current scratch (*ctx->orbws): a batch of one
+int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
+                const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride)
+{
+    const OrbIn in = { fs, ctx->orbws, d_img, d_disp16, d_mask, img_stride, disp_stride, mask_stride };
+    return orb_enqueue_jobs(ctx, &in, 1, w, h, nfeatures, mask_mode, min_d16, max_d16);
 }
 
 static int orb_finish(vo_ctx* ctx, FrameSlot* fs)
@@ -1093,16 +1166,30 @@ int orb_run(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, in
     return orb_finish(ctx, fs);
 }
 
-// extraction on a slot's left image inside the valid ROI with the fused disparity mask (mask_mode 1) or
-// none (0); enqueue only
+// extraction on the left images of n slots of one size inside the valid ROI with the fused disparity mask (mask_mode 1) or
+// none (0), member i through the scratch ws[i]; enqueue only
+int orb_slots_enqueue(vo_ctx* ctx, FrameSlot* const* f, OrbWs* const* ws, int n, int nfeatures, int mask_mode, int min_disp16, int max_disp16)
+{
+    if (n < 1 || n > VO_MAX_SWEEP_GROUP) return vo_fail(ctx, VO_E_ARG, "orb_slots_enqueue: %d extractions in one batch", n);
+    const int fw = f[0]->w, fh = f[0]->h;
+    int x0 = 0, y0 = 0, x1 = fw, y1 = fh;
+    if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < fw ? ctx->roi[2] : fw; y1 = ctx->roi[3] < fh ? ctx->roi[3] : fh; }
+    const int cw = x1 - x0, ch = y1 - y0;
+    OrbIn in[VO_MAX_SWEEP_GROUP];
+    for (int i = 0; i < n; i++) {
+        FrameSlot& s = *f[i];
+        if (s.w != fw || s.h != fh) return vo_fail(ctx, VO_E_STATE, "orb_slots_enqueue: slots of different sizes in one batch");
+        if (cw <= 0 || ch <= 0) { s.has_kp = false; s.kp_depth = false; *s.n_kp_host = 0; continue; }
+        in[i] = { &s, ws[i], s.left + (size_t)y0 * fw + x0, s.disp16 + (size_t)y0 * fw + x0, nullptr, fw, fw, 0 };
+    }
+    if (cw <= 0 || ch <= 0) return VO_OK;
+    return orb_enqueue_jobs(ctx, in, n, cw, ch, nfeatures, mask_mode, min_disp16, max_disp16);
+}
+
 int orb_slot_enqueue(vo_ctx* ctx, FrameSlot& f, int nfeatures, int mask_mode, int min_disp16, int max_disp16)
 {
-    int x0 = 0, y0 = 0, x1 = f.w, y1 = f.h;
-    if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < f.w ? ctx->roi[2] : f.w; y1 = ctx->roi[3] < f.h ? ctx->roi[3] : f.h; }
-    const int cw = x1 - x0, ch = y1 - y0;
-    if (cw <= 0 || ch <= 0) { f.has_kp = false; f.kp_depth = false; *f.n_kp_host = 0; return VO_OK; }
-    return orb_enqueue(ctx, &f, f.left + (size_t)y0 * f.w + x0, f.w, cw, ch, nfeatures, mask_mode,
-                       f.disp16 + (size_t)y0 * f.w + x0, f.w, min_disp16, max_disp16, nullptr, 0);
+    FrameSlot* const fp = &f;
+    return orb_slots_enqueue(ctx, &fp, &ctx->orbws, 1, nfeatures, mask_mode, min_disp16, max_disp16);
 }
 
 static int download_kps(vo_ctx* ctx, FrameSlot& f, float* kp_xy, float* kp_size, float* kp_angle, float* kp_response,

@@ -1926,16 +1926,13 @@ struct MemberScope {
     MemberScope& operator=(const MemberScope&) = delete;
 };
 
-// back part of one member on its engine's stream (the current one): the post filters where the group's launches have not
-// carried them, the ORB chain, the slot's `ready` record
-static int sweep_member_back(vo_ctx* ctx, SweepGroup::Member& m, bool post_done)
+// back part of one member on its engine's stream (the current one) where the group's launches cannot carry the post filters
+// (an image too wide for k_sgbm_post_rows): the post filters, the ORB chain, the slot's `ready` record
+static int sweep_member_back(vo_ctx* ctx, SweepGroup::Member& m)
 {
     FrameSlot& f = *m.f;
-    int rc = VO_OK;
-    if (!post_done) {
-        rc = sgbm_post(ctx, f, m.w, m.h, m.g);
-        if (!rc) rc = sgbm_run_done(ctx);
-    }
+    int rc = sgbm_post(ctx, f, m.w, m.h, m.g);
+    if (!rc) rc = sgbm_run_done(ctx);
     if (!rc && ctx->la_orb) {
         const int* q = ctx->la_orb_params;
         rc = orb_slot_enqueue(ctx, f, q[0], q[1], q[2], q[3]);
@@ -1943,6 +1940,21 @@ static int sweep_member_back(vo_ctx* ctx, SweepGroup::Member& m, bool post_done)
     }
     if (!rc && hipEventRecord(f.ready, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
     return rc;
+}
+
+// The engine is about to be given work: its stream first stands behind the launches of the group it was last a non-closing
+// member of -- they run on the closing member's stream and use this engine's workspaces and ORB scratch.  Asked of the host
+// first: a chain that is over (the usual case once the pipeline is full) costs the stream no wait.
+int engine_behind_chain(vo_ctx* ctx, int engine)
+{
+    vo_ctx::SgbmWs& a = ctx->ws_alt[engine];
+    if (!a.chain) return VO_OK;
+    if (hipEventQuery(a.chain) != hipSuccess) {
+        (void)hipGetLastError();                     // (not ready: no error of ours)
+        VO_HIP(ctx, hipStreamWaitEvent(ctx->la_stream[engine], a.chain, 0));
+    }
+    a.chain = nullptr;
+    return VO_OK;
 }
 
 int sweep_group_close(vo_ctx* ctx, int why)
@@ -2000,16 +2012,38 @@ int sweep_group_close(vo_ctx* ctx, int why)
             }
         }
         hipEvent_t const swept = ctx->ws_alt[last.engine].swept;
-        if (!rc && n > 1 && hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
-        // ... and every member finishes on its own engine's stream behind them
-        if (!rc) rc = sweep_member_back(ctx, last, post_here);
-        for (int i = 0; i + 1 < n && !rc; i++) {
-            scope.enter(G->m[i].engine);
-            if (hipStreamWaitEvent(ctx->stream, swept, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed");
-            if (!rc) rc = sweep_member_back(ctx, G->m[i], post_here);
+        if (!rc && post_here) {
+            // ... and so does the members' ORB chain (one launch per kernel for all of them), every member's `ready` record and
+            // one record behind the last launch that touches any member's workspace or ORB scratch.  Nothing lands on another
+            // member's stream: a wait for this chain at the head of each of them would sit in the few hardware queues the streams
+            // share and hold back whatever is enqueued behind it -- the next group's fronts -- until the chain is over.  An
+            // engine's stream orders itself behind the chain when the engine is next given work (engine_behind_chain).
+            if (ctx->la_orb) {
+                const int* q = ctx->la_orb_params;
+                FrameSlot* fs[DG_MAXJOBS];
+                OrbWs* ows[DG_MAXJOBS];
+                for (int i = 0; i < n; i++) { fs[i] = G->m[i].f; ows[i] = &ctx->ws_alt[G->m[i].engine].orb; }
+                rc = orb_slots_enqueue(ctx, fs, ows, n, q[0], q[1], q[2], q[3]);
+                for (int i = 0; i < n && !rc; i++) { memcpy(fs[i]->kp_params, q, sizeof(fs[i]->kp_params)); fs[i]->kp_pending = true; }
+            }
+            for (int i = 0; i < n && !rc; i++)
+                if (hipEventRecord(G->m[i].f->ready, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+            if (!rc && n > 1) {
+                if (hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+                for (int i = 0; i + 1 < n && !rc; i++) ctx->ws_alt[G->m[i].engine].chain = swept;
+            }
+            // (engine 0's stream stands behind the main workspace's record only where it carried it)
+            if (!rc && main_member) ctx->main_ws.done_on_engine0 = last.engine == 0;
+        } else if (!rc) {
+            // (the members' post passes are per member by construction: each finishes on its own engine's stream behind the sweep)
+            if (n > 1 && hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+            if (!rc) rc = sweep_member_back(ctx, last);
+            for (int i = 0; i + 1 < n && !rc; i++) {
+                scope.enter(G->m[i].engine);
+                if (hipStreamWaitEvent(ctx->stream, swept, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed");
+                if (!rc) rc = sweep_member_back(ctx, G->m[i]);
+            }
         }
-        // (engine 0's stream now stands behind `swept`, or is the one that carried the record)
-        if (!rc && post_here && main_member) ctx->main_ws.done_on_engine0 = true;
     }
     if (rc) {
         // no member's slot may hand anything out (some of them may even be complete: the caller cannot tell which)

@@ -749,12 +749,13 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
     f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
     {
         EngineScope on_engine(ctx, engine);          // ctx->stream / staging / SGBM + ORB workspaces are the engine's in here
+        rc = engine_behind_chain(ctx, engine);
         const int stagger = ctx->tune_stagger >= 0 ? ctx->tune_stagger : (7 * ctx->n_engines + 8) / 16;
         if (stagger > 0 && stagger < ctx->n_engines) {
             vo_ctx::SgbmWs& p = ctx->ws_alt[(engine - stagger + ctx->n_engines) % ctx->n_engines];
             if (p.mid_valid) (void)hipStreamWaitEvent(ctx->stream, p.mid, 0);
         }
-        rc = slot_before_overwrite(ctx, f);
+        if (!rc) rc = slot_before_overwrite(ctx, f);
         // a rectified gray pair that already lies in HBM needs no ingest step of its own: the SGBM run's first kernel reads it
         // where it lies and leaves the slot's copy behind (two copy commands less per pair on the engine's queue)
         const bool in_place = kind == hipMemcpyDeviceToDevice && preprocessed && channels == 1;
@@ -836,7 +837,8 @@ extern "C" int vo_prefetch_staged_mono(vo_ctx* ctx, int slot, int index, int nfe
     f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false; f.has_disp = false;
     {
         EngineScope on_engine(ctx, engine);
-        rc = slot_before_overwrite(ctx, f);
+        rc = engine_behind_chain(ctx, engine);       // (the engine's ORB scratch may still serve the group it was last a member of)
+        if (!rc) rc = slot_before_overwrite(ctx, f);
         if (!rc) {
             StageTimer t(ctx, VO_T_UPLOAD);
             rc = ingest(ctx, 0, ctx->staged + per * 2 * index, w, h, ctx->staged_ch, 1, f.left, ctx->stage_in, hipMemcpyDeviceToDevice);
@@ -1205,6 +1207,36 @@ extern "C" int vo_get_timings(vo_ctx* ctx, double* ms_out, int64_t* launches_out
         if (launches_out) launches_out[i] = ctx->t_n[i];
         if (reset) { ctx->t_ms[i] = 0; ctx->t_n[i] = 0; }
     }
+    return VO_OK;
+}
+
+extern "C" int vo_get_stage_timeline(vo_ctx* ctx, int cap, int32_t* stage_out, int32_t* entries_out, double* begin_ms_out, double* end_ms_out, int* n_out)
+{
+    if (!ctx || !n_out || cap < 0 || (cap > 0 && (!stage_out || !entries_out || !begin_ms_out || !end_ms_out)))
+        return vo_fail(ctx, VO_E_ARG, "vo_get_stage_timeline: bad argument");
+    *n_out = 0;
+    if (ctx->ev_used == 0) return VO_OK;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    // brackets lie on the engines' and the pose steps' streams as well (the open sweep group, if any, stays open: its
+    // members' fronts are complete brackets, the rest has not been recorded yet)
+    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
+        if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
+    for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
+        for (int k = 0; k < vo_ctx::alt_count(kind); k++)
+            if (ctx->alt(kind, k).stream) VO_HIP(ctx, hipStreamSynchronize(ctx->alt(kind, k).stream));
+    VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int n = 0;
+    for (size_t i = 0; i < ctx->ev_used; i++) {
+        float t0 = 0, dt = 0;
+        if (hipEventElapsedTime(&t0, ctx->ev_pool[0], ctx->ev_pool[2 * i]) != hipSuccess ||
+            hipEventElapsedTime(&dt, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
+        if (n < cap) { stage_out[n] = ctx->ev_stage[i]; entries_out[n] = ctx->ev_entries[i]; begin_ms_out[n] = t0; end_ms_out[n] = (double)t0 + (double)dt; }
+        n++;
+    }
+    *n_out = n;
     return VO_OK;
 }
 

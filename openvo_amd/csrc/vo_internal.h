@@ -131,7 +131,10 @@ struct vo_ctx {
         hipEvent_t mid = nullptr;        // the early stages of the engine's latest pair have finished: cost volume and W + E, or -- a member
                                          // of a sweep group whose W + E travels with the group's launches -- the cost volume
         bool mid_valid = false;
-        hipEvent_t swept = nullptr;      // the sweep launch of the latest group this engine closed has finished
+        hipEvent_t swept = nullptr;      // the launches of the latest group this engine closed have finished (recorded behind the last of them)
+        hipEvent_t chain = nullptr;      // borrowed: `swept` of the engine that closed the group this engine was last a non-closing member of,
+                                         // until this engine's stream has been ordered behind it (engine_behind_chain); a later close on that
+                                         // engine's stream re-records it later on the same stream, which only orders more
     } ws_alt[MAX_ENGINES];           // [0]: only its ORB scratch / staging / events are used (engine 0 works in main_ws)
     SgbmWs main_ws;
     SgbmWs* ws = &main_ws;
@@ -150,7 +153,8 @@ struct vo_ctx {
     // Sweep groups (sgbm.hip): with fewer hardware queues than streams a pair's kernels queue up behind other pairs' on the same
     // queue, and the diagonal sweep -- a latency chain that keeps ~28 CUs busy for a millisecond -- is the longest of them.  The
     // look-ahead path then collects up to B pairs whose early stages are enqueued (the open group) and sweeps them in ONE launch,
-    // with one launch of W + E before it and one of each post filter behind it for all of them.
+    // with one launch of W + E before it and one of each post filter and of each kernel of the look-ahead ORB chain behind it
+    // for all of them.
     // hw_queues: GPU_MAX_HW_QUEUES as the process sees it (unset: HIP's 4).  sweep_group_req: VO_SWEEP_GROUP / vo_set_sweep_group,
     // 0 = follow the queue budget (sweep_group_size).  grp_closed: groups closed so far, by cause (VO_GRP_*).
     int hw_queues = 4;
@@ -363,6 +367,16 @@ int slot_before_overwrite(vo_ctx* ctx, FrameSlot& f);
 // `done` marks the end of an asynchronous step that reads the slot: whoever overwrites the slot waits for it first
 void slot_add_reader(FrameSlot& f, hipEvent_t done);
 int orb_slot_enqueue(vo_ctx* ctx, FrameSlot& f, int nfeatures, int mask_mode, int min_disp16, int max_disp16);
+// the same for n slots of one size (a sweep group's members) in ONE launch per kernel on ctx->stream, slot i through scratch ws[i]
+int orb_slots_enqueue(vo_ctx* ctx, FrameSlot* const* f, OrbWs* const* ws, int n, int nfeatures, int mask_mode, int min_disp16, int max_disp16);
+// one member of a batched extraction (orb_enqueue_jobs): where its keypoints go, its scratch, its source image and mask
+struct OrbIn {
+    FrameSlot* fs; OrbWs* ws;
+    const uint8_t* img; const int16_t* disp16; const uint8_t* mask;
+    int img_stride, disp_stride, mask_stride;
+};
+// n extractions of one geometry and one request on ctx->stream, one launch per kernel (enqueue only: the counts land in n_kp_host)
+int orb_enqueue_jobs(vo_ctx* ctx, const OrbIn* in, int n, int w, int h, int nfeatures, int mask_mode, int min_d16, int max_d16);
 // one extraction on ctx->stream into the keypoint arrays of *fs (enqueue only: the count lands in fs->n_kp_host)
 int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
                 const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride);
@@ -420,9 +434,12 @@ static inline int sweep_group_size(const vo_ctx* ctx)
     int b = ctx->sweep_group_req > 0 ? ctx->sweep_group_req : (ctx->hw_queues >= ctx->n_engines + 4 ? 1 : VO_SWEEP_GROUP_FEW_QUEUES);
     return b < ctx->n_engines ? b : ctx->n_engines;
 }
-// One sweep launch for the open group's members, then each member's post filters, ORB chain and `ready` record on its own
-// engine's stream.  Nothing to do without an open group.  On failure every member's slot is left holding nothing.
+// The open group's members finish on the closing member's stream: W + E, the sweep, the post filters and the ORB chain as one
+// launch per kernel for all of them, then every member's `ready` record.  No other member's stream receives anything: an engine
+// orders itself behind the chain when it is next given work (engine_behind_chain).  Nothing to do without an open group.  On
+// failure every member's slot is left holding nothing.
 int sweep_group_close(vo_ctx* ctx, int why);
+int engine_behind_chain(vo_ctx* ctx, int engine);
 bool sweep_group_has_engine(const vo_ctx* ctx, int engine);
 int sweep_group_members(const vo_ctx* ctx);
 void sweep_group_free(vo_ctx* ctx);
