@@ -420,7 +420,8 @@ int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, d
 
 /* Sparse stereo depth (NOT part of the reference, which reads a dense disparity at its keypoints, stereo_odometer.py:50-79,117):
  * per-keypoint 3-D from ORB on BOTH rectified images of a slot, without any SGBM run.  Defined by this build; tests/sparse_stereo_ref.py
- * restates steps b - e in numpy.  Needs a pair in the slot (vo_upload_pair / vo_load_staged_pair) and vo_set_Q; one host synchronisation.
+ * restates steps b - e in numpy.  Needs a pair in the slot (vo_upload_pair / vo_load_staged_pair) and vo_set_Q; one host synchronisation
+ * (a slot filled by a vo_prefetch_*_sparse entry: see there).
  *   a. KL = ORB(left crop), KR = ORB(right crop): the crop rectangle of vo_orb_detect_and_compute (from the LEFT ROI) on both images,
  *      no mask, canonical order, nfeatures each.
  *   b. association of left keypoint i: right keypoint j is a candidate when |oct_i - oct_j| <= 1, fabsf(y_i - y_j) <= row_tol * sc[oct_i]
@@ -448,6 +449,36 @@ int vo_download_keypoint_depth(vo_ctx* ctx, int slot, float* xyz /*cap*3*/, floa
 int vo_sparse_match_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l, const int32_t* oct_l,
                          const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r, const uint8_t* desc_r, int nr,
                          float min_disp, float max_disp, float row_tol, int max_hamming, int32_t* match_out /*nl*/, float* disp_out /*nl*/);
+/* steps b - e on host arrays in ONE launch (k_sparse_pair: association and refinement, then the compaction in the workgroup that
+ * arrives last; the seam that kernel's tests use): vo_sparse_match_host's inputs plus Q and the ROI origin of step d.  match_out /
+ * disp_out as there; the survivors, in their order, come back as kp_xy / kp_octave / desc / kp_disp / kp_xyz (nl entries of room each),
+ * compacted into a destination that is not the scratch set they are read from.  counts3 as vo_sparse_stereo. */
+int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l, const int32_t* oct_l,
+                        const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r, const uint8_t* desc_r, int nr,
+                        float min_disp, float max_disp, float row_tol, int max_hamming, const double* Q16, int roi_x0, int roi_y0,
+                        int32_t* match_out /*nl*/, float* disp_out /*nl*/, float* kp_xy /*nl*2*/, int32_t* kp_octave /*nl*/,
+                        uint8_t* desc /*nl*32*/, float* kp_disp /*nl*/, float* kp_xyz /*nl*3*/, int32_t* counts3);
+/* Sparse stereo begun ahead (NOT part of the reference either).  The three entries are vo_prefetch_pair / vo_prefetch_host_staged /
+ * vo_prefetch_staged_pair with the sparse stereo chain in place of the SGBM: on the next look-ahead engine's stream the pair is
+ * ingested into the slot, both extractions run as one batch, and one launch associates, refines and compacts; the slot's `ready` is
+ * recorded behind it and the slot counts towards vo_lookahead_depth.  The request (the five trailing arguments, as vo_sparse_stereo)
+ * is checked before anything is enqueued; vo_set_Q is needed, vo_set_sgbm is not, and an engine that only ever sees sparse pairs
+ * never allocates an SGBM workspace.  The slot then holds the pair, no disparity and -- until collected -- no keypoints:
+ *   vo_sparse_stereo(slot, the same request) launches nothing: it waits for the slot (a host wait on its event, as
+ *     vo_orb_detect_and_compute does for keypoints extracted ahead), reads the slot's own record, applies vo_sparse_stereo's capacity
+ *     checks and returns counts3; the results are bit for bit those of the synchronous call.  With another request it waits and
+ *     recomputes synchronously from the slot's pair.  On a slot begun ahead that has already been collected with the same request it
+ *     returns the counts again without recomputing; nothing else is ever reused: a result computed synchronously is recomputed by
+ *     the next call, as before, and vo_set_Q / vo_set_roi void both a pending chain and a collected one (the next call computes
+ *     with the Q and ROI in force).
+ *   An ORB extraction into the slot or a refill before that voids the chain's result, like the depth mark itself.
+ *   The pair steps (vo_pose_pair_begin, vo_pnp_pair_begin, ...) need COLLECTED slots: VO_E_STATE otherwise. */
+int vo_prefetch_pair_sparse(vo_ctx* ctx, int slot, const uint8_t* left, const uint8_t* right, int w, int h, int channels, int preprocessed,
+                            int nfeatures, float min_disp, float max_disp, float row_tol, int max_hamming);
+int vo_prefetch_host_staged_sparse(vo_ctx* ctx, int slot, int buf, int w, int h, int channels, int preprocessed, int nfeatures,
+                                   float min_disp, float max_disp, float row_tol, int max_hamming);
+int vo_prefetch_staged_pair_sparse(vo_ctx* ctx, int slot, int index, int preprocessed, int nfeatures, float min_disp, float max_disp,
+                                   float row_tol, int max_hamming);
 /* The pair steps read their depth source from the slots: when BOTH slots' keypoints carry depth, vo_point_clouds(_ex),
  * vo_pose_pair(_ex / _begin / _begin_ex / _end) and vo_pnp_pair(_begin / _end) take the 3-D point of keypoint k from the slot's
  * per-keypoint array instead of the bilinear lookup in the reprojected disparity (status 0; the slots need no disparity and its

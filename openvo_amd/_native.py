@@ -42,6 +42,7 @@ SYMBOLS = [
     "vo_recover_pose", "vo_mono_pose_pair", "vo_mono_pose_pair_begin", "vo_mono_pose_pair_end", "vo_download_mono_depth",
     "vo_set_match_window", "vo_clear_match_window", "vo_bf_knn2_hamming_window",
     "vo_sparse_stereo", "vo_download_keypoint_depth", "vo_sparse_match_host",
+    "vo_sparse_pair_host", "vo_prefetch_pair_sparse", "vo_prefetch_host_staged_sparse", "vo_prefetch_staged_pair_sparse",
     "vo_get_stage_timeline",
 ]
 
@@ -214,6 +215,14 @@ def lib():
             for name, proto in (("vo_sparse_stereo", [vp, ci, ci, cf, cf, cf, ci, vp]),
                                 ("vo_download_keypoint_depth", [vp, ci, vp, vp, ci, vp]),
                                 ("vo_sparse_match_host", [vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, ci, vp, vp])):
+                getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_prefetch_pair_sparse"):   # (likewise: an older build starts no sparse pair ahead)
+            cf = ctypes.c_float
+            req = [ci, cf, cf, cf, ci]
+            for name, proto in (("vo_prefetch_pair_sparse", [vp, ci, vp, vp, ci, ci, ci, ci] + req),
+                                ("vo_prefetch_host_staged_sparse", [vp, ci, ci, ci, ci, ci, ci] + req),
+                                ("vo_prefetch_staged_pair_sparse", [vp, ci, ci, ci] + req),
+                                ("vo_sparse_pair_host", [vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, ci, vp, ci, ci] + [vp] * 8)):
                 getattr(L, name).argtypes = proto
         if hasattr(L, "vo_pnp_pair"):               # (likewise: an older build has no fused PnP step)
             L.vo_pnp_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
@@ -391,6 +400,30 @@ class Context:
         h, w = left.shape[:2]
         self._ck(self._lib.vo_prefetch_pair(self._h, slot, _p(left), _p(right), w, h, ch, int(bool(preprocessed))))
         return w, h
+
+    @staticmethod
+    def _sparse_req(nfeatures, min_disp, max_disp, row_tol, max_hamming):
+        """the five trailing arguments of the vo_prefetch_*_sparse entries (vo_sparse_stereo's request)"""
+        return int(nfeatures), float(min_disp), float(max_disp), float(row_tol), int(max_hamming)
+
+    def prefetch_pair_sparse(self, slot, left, right, preprocessed, nfeatures, min_disp, max_disp, row_tol=2.0, max_hamming=75):
+        """Look-ahead from host images with the sparse stereo chain in place of the SGBM: sparse_stereo(slot, the same request)
+        then only waits and collects."""
+        left, right, ch = _image_pair(left, right)
+        h, w = left.shape[:2]
+        self._ck(self._lib.vo_prefetch_pair_sparse(self._h, int(slot), _p(left), _p(right), w, h, ch, int(bool(preprocessed)),
+                                                   *self._sparse_req(nfeatures, min_disp, max_disp, row_tol, max_hamming)))
+        return w, h
+
+    def prefetch_host_staged_sparse(self, slot, buf, w, h, ch, preprocessed, nfeatures, min_disp, max_disp, row_tol=2.0, max_hamming=75):
+        self._ck(self._lib.vo_prefetch_host_staged_sparse(self._h, int(slot), int(buf), w, h, ch, int(bool(preprocessed)),
+                                                          *self._sparse_req(nfeatures, min_disp, max_disp, row_tol, max_hamming)))
+        return w, h
+
+    def prefetch_staged_pair_sparse(self, slot, index, preprocessed, nfeatures, min_disp, max_disp, row_tol=2.0, max_hamming=75):
+        self._ck(self._lib.vo_prefetch_staged_pair_sparse(self._h, int(slot), int(index), int(bool(preprocessed)),
+                                                          *self._sparse_req(nfeatures, min_disp, max_disp, row_tol, max_hamming)))
+        return self.staged_shape
 
     def host_stage_pair(self, buf, left, right):
         """Copy a host pair into pinned staging buffer `buf` (waits for that buffer's previous upload).  The one call that
@@ -619,6 +652,30 @@ class Context:
                                                 _p(desc_r), nr, float(min_disp), float(max_disp), float(row_tol), int(max_hamming),
                                                 _p(match), _p(disp)))
         return match, disp
+
+    def sparse_pair_host(self, left, right, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, Q, roi_xy, min_disp, max_disp, row_tol=2.0, max_hamming=75):
+        """Association, refinement AND compaction of vo_sparse_stereo on host arrays in one launch (vo_sparse_pair_host) -> dict:
+        match (nl,), disp (nl,) as sparse_match_host; xy, octave, desc, kp_disp, xyz of the survivors in their order; counts3."""
+        left, right = _c(left, np.uint8), _c(right, np.uint8)
+        if left.ndim != 2 or left.shape != right.shape:
+            raise ValueError("two 2-D uint8 images of one shape")
+        h, w = left.shape
+        xy_l, xy_r = _c(xy_l, np.float32).reshape(-1, 2), _c(xy_r, np.float32).reshape(-1, 2)
+        oct_l, oct_r = _c(oct_l, np.int32).reshape(-1), _c(oct_r, np.int32).reshape(-1)
+        desc_l, desc_r = _c(desc_l, np.uint8).reshape(-1, 32), _c(desc_r, np.uint8).reshape(-1, 32)
+        nl, nr = len(xy_l), len(xy_r)
+        if len(oct_l) != nl or len(desc_l) != nl or len(oct_r) != nr or len(desc_r) != nr:
+            raise ValueError("one octave and one descriptor per keypoint")
+        Q = _c(Q, np.float64).reshape(16)
+        match, disp = np.full(nl, -1, np.int32), np.full(nl, np.nan, np.float32)
+        xy, octave, desc = np.zeros((nl, 2), np.float32), np.zeros(nl, np.int32), np.zeros((nl, 32), np.uint8)
+        kp_disp, xyz, c3 = np.zeros(nl, np.float32), np.zeros((nl, 3), np.float32), np.zeros(3, np.int32)
+        self._ck(self._lib.vo_sparse_pair_host(self._h, _p(left), _p(right), w, h, _p(xy_l), _p(oct_l), _p(desc_l), nl, _p(xy_r), _p(oct_r),
+                                               _p(desc_r), nr, float(min_disp), float(max_disp), float(row_tol), int(max_hamming), _p(Q),
+                                               int(roi_xy[0]), int(roi_xy[1]), _p(match), _p(disp), _p(xy), _p(octave), _p(desc), _p(kp_disp),
+                                               _p(xyz), _p(c3)))
+        n = int(c3[2])
+        return dict(match=match, disp=disp, xy=xy[:n], octave=octave[:n], desc=desc[:n], kp_disp=kp_disp[:n], xyz=xyz[:n], counts3=c3)
 
     # ---- matching / 3-D / pose
     def bf_knn2(self, q, t):

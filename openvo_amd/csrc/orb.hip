@@ -1108,10 +1108,14 @@ int orb_enqueue_jobs(vo_ctx* ctx, const OrbIn* in, int n, int w, int h, int nfea
         FrameSlot* const fs = in[i].fs;
         fs->has_kp = false;
         fs->kp_depth = false;           // ... and so do the depths of vo_sparse_stereo
+        fs->sp_pending = false;         // (a sparse chain begun ahead into the slot is no longer what the slot will hold)
         fs->mono_serial = 0;            // depths of a monocular pose step belong to the keypoints this run replaces
     }
     if (w <= 2 * EDGE || h <= 2 * EDGE) {
         // level 0 has no pixel inside the border, and no smaller level has one: runByImageBorder clears every level
+        // (a host write into the pinned count words: safe for a SLOT's word, which nothing in flight reads -- the caller has ordered
+        // itself behind the slot's earlier work; sparse_enqueue, whose scratch sets' words an engine's earlier pair may still be
+        // reading, never comes here: it handles this geometry itself)
         for (int i = 0; i < n; i++) *in[i].fs->n_kp_host = 0;
         return VO_OK;
     }
@@ -1179,7 +1183,7 @@ int orb_slots_enqueue(vo_ctx* ctx, FrameSlot* const* f, OrbWs* const* ws, int n,
     for (int i = 0; i < n; i++) {
         FrameSlot& s = *f[i];
         if (s.w != fw || s.h != fh) return vo_fail(ctx, VO_E_STATE, "orb_slots_enqueue: slots of different sizes in one batch");
-        if (cw <= 0 || ch <= 0) { s.has_kp = false; s.kp_depth = false; *s.n_kp_host = 0; continue; }
+        if (cw <= 0 || ch <= 0) { s.has_kp = false; s.kp_depth = false; s.sp_pending = false; *s.n_kp_host = 0; continue; }
         in[i] = { &s, ws[i], s.left + (size_t)y0 * fw + x0, s.disp16 + (size_t)y0 * fw + x0, nullptr, fw, fw, 0 };
     }
     if (cw <= 0 || ch <= 0) return VO_OK;

@@ -3,7 +3,10 @@
 // build, see include/vo355.h (vo_sparse_stereo) and tests/sparse_stereo_ref.py, which restates it in numpy.
 //   k_sparse_match     one wave per left keypoint: association along the epipolar row (lanes over right keypoints, wave argmin
 //                      on (distance << 16 | j)), then the sub-pixel refinement by 11 x 11 SAD over 11 shifts and the 3-D point
-//   k_sparse_compact   ordered compaction (ballot prefix) of the surviving left keypoints from the scratch set into the slot
+//   k_sparse_pair      the same association and refinement, and behind it -- in the workgroup that arrives last at a ticket -- the
+//                      ordered compaction (ballot prefix) of the surviving left keypoints from the scratch set into the slot: ONE
+//                      launch per pair (a queue entry behind other engines' kernels costs more than the two kernels it replaces)
+//   k_sparse_compact   that compaction as a launch of its own (VO_SPARSE_TWO_LAUNCHES builds only: the form k_sparse_pair is measured against)
 // Compiled with -ffp-contract=off like the rest of the library: the float32 / float64 arithmetic below is the definition.
 #include <math.h>
 #include "vo_internal.h"
@@ -50,17 +53,14 @@ __device__ __forceinline__ int sp_lower_bound(const int32_t* __restrict__ oct, i
 // nl_p / nr_p: the keypoint counts as the two extractions left them (pinned host words; clamped to cap).  sorted_r: the right
 // octaves are non-decreasing (ORB's canonical order), so the candidates lie in one index range found by two binary searches.
 // imgL / imgR: the two crops (cw x ch, `stride` bytes per row).  xyz may be NULL (host seam: no 3-D point).
-__global__ void __launch_bounds__(256) k_sparse_match(const int32_t* nl_p, const int32_t* nr_p, int cap,
-                                                      const float* __restrict__ xy_l, const int32_t* __restrict__ oct_l, const uint8_t* __restrict__ desc_l,
-                                                      const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
-                                                      int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
-                                                      int cw, int ch, const SparseP P, int32_t* __restrict__ match, float* __restrict__ disp,
-                                                      float* __restrict__ xyz)
+// One wave: left keypoint i (< nl) of the keypoint sets below.  match / disp / xyz are plain pointers: k_sparse_pair reads them back
+// in the same launch behind an agent-scope acquire, and bytes handed over that way must stay off the scalar path.
+__device__ __forceinline__ void sparse_match_one(int i, int lane, int nr,
+                                                 const float* __restrict__ xy_l, const int32_t* __restrict__ oct_l, const uint8_t* __restrict__ desc_l,
+                                                 const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
+                                                 int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
+                                                 int cw, int ch, const SparseP& P, int32_t* match, float* disp, float* xyz)
 {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int nl = min(*nl_p, cap), nr = min(*nr_p, cap);
-    if (i >= nl) return;
     const float nanf_ = __builtin_nanf("");
     const float xi = xy_l[2 * i], yi = xy_l[2 * i + 1];
     const int oi = oct_l[i];
@@ -152,18 +152,31 @@ __global__ void __launch_bounds__(256) k_sparse_match(const int32_t* nl_p, const
     }
 }
 
+__global__ void __launch_bounds__(256) k_sparse_match(const int32_t* nl_p, const int32_t* nr_p, int cap,
+                                                      const float* __restrict__ xy_l, const int32_t* __restrict__ oct_l, const uint8_t* __restrict__ desc_l,
+                                                      const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
+                                                      int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
+                                                      int cw, int ch, const SparseP P, int32_t* __restrict__ match, float* __restrict__ disp,
+                                                      float* __restrict__ xyz)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int nl = min(*nl_p, cap), nr = min(*nr_p, cap);
+    if (i >= nl) return;
+    sparse_match_one(i, lane, nr, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, sorted_r, imgL, imgR, stride, cw, ch, P, match, disp, xyz);
+}
+
 struct KpSet { float *xy, *size, *angle, *resp; int32_t* oct; uint8_t* desc; };
 
-// One block: the left keypoints whose disparity is a number move, in their order, from the scratch set into the slot (six keypoint
-// arrays, descriptors, kp_xyz, kp_disp).  rec (pinned) = {left keypoints, accepted associations, kept}; n_kp_host = kept.
-__global__ void __launch_bounds__(256) k_sparse_compact(const int32_t* nl_p, int cap, const KpSet src, const int32_t* __restrict__ match,
-                                                        const float* __restrict__ disp, const float* __restrict__ xyz, const KpSet dst,
-                                                        float* __restrict__ dst_xyz, float* __restrict__ dst_disp, int32_t* rec,
-                                                        int32_t* n_kp_host)
+// One workgroup of 256: the left keypoints whose disparity is a number move, in their order, from the scratch set into the slot (six
+// keypoint arrays, descriptors, kp_xyz, kp_disp).  rec (pinned, the slot's) = {left keypoints, accepted associations, kept, right
+// keypoints} -- the two counts as the extractions left them, so that the host can hold them against the capacity --; n_kp_host = kept.
+__device__ __forceinline__ void sparse_compact_block(int nl_raw, int nr_raw, int cap, const KpSet& src, const int32_t* match, const float* disp,
+                                                     const float* xyz, const KpSet& dst, float* dst_xyz, float* dst_disp, int32_t* rec,
+                                                     int32_t* n_kp_host, int* s_keep, int* s_acc)
 {
-    __shared__ int s_keep[4], s_acc[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nl = min(*nl_p, cap);
+    const int nl = min(nl_raw, cap);
     int base = 0, acc = 0;
     for (int i0 = 0; i0 < nl; i0 += 256) {
         const int i = i0 + threadIdx.x;
@@ -190,11 +203,60 @@ __global__ void __launch_bounds__(256) k_sparse_compact(const int32_t* nl_p, int
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        __hip_atomic_store(rec + 0, nl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(rec + 0, nl_raw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(rec + 1, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(rec + 2, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(rec + 3, nr_raw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(n_kp_host, base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+#ifdef VO_SPARSE_TWO_LAUNCHES
+__global__ void __launch_bounds__(256) k_sparse_compact(const int32_t* nl_p, const int32_t* nr_p, int cap, const KpSet src, const int32_t* match,
+                                                        const float* disp, const float* xyz, const KpSet dst, float* dst_xyz, float* dst_disp,
+                                                        int32_t* rec, int32_t* n_kp_host)
+{
+    __shared__ int s_lds[8];
+    sparse_compact_block(*nl_p, *nr_p, cap, src, match, disp, xyz, dst, dst_xyz, dst_disp, rec, n_kp_host, s_lds, s_lds + 4);
+}
+#endif
+
+// Association + refinement (one wave per left keypoint, four to a workgroup) and the compaction in ONE launch.  Every workgroup --
+// those whose four keypoints lie beyond nl too -- draws a number at `ticket`; the one that draws the last has seen every other
+// arrive and compacts.  Nothing waits and nothing polls.  The hand-off is agent-scope release / acquire in its counter form: every
+// wave drains its stores, the workgroup meets, lane 0 releases (fence, then the wait the fence may not carry itself) and adds to the
+// ticket; the last arriver acquires, waits, the workgroup meets again and reads match / disp / xyz with plain vector loads.  The
+// ticket reads zero before the first launch (sparse_ws_prepare) and the last arriver puts it back.
+__global__ void __launch_bounds__(256) k_sparse_pair(const int32_t* nl_p, const int32_t* nr_p, int cap, const KpSet src,
+                                                     const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
+                                                     int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
+                                                     int cw, int ch, const SparseP P, int32_t* match, float* disp, float* xyz, const KpSet dst,
+                                                     float* dst_xyz, float* dst_disp, int32_t* rec, int32_t* n_kp_host, int32_t* ticket)
+{
+    __shared__ int s_lds[12];           // ONE LDS object: the compaction's per-wave counts [0 .. 7] and "I am last" [8]
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int nl_raw = *nl_p, nr_raw = *nr_p;
+    const int nl = min(nl_raw, cap), nr = min(nr_raw, cap);
+    if (i < nl)
+        sparse_match_one(i, lane, nr, src.xy, src.oct, src.desc, xy_r, oct_r, desc_r, sorted_r, imgL, imgR, stride, cw, ch, P, match, disp, xyz);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = t == (int)gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        s_lds[8] = last;
+    }
+    __syncthreads();
+    if (!s_lds[8]) return;
+    sparse_compact_block(nl_raw, nr_raw, cap, src, match, disp, xyz, dst, dst_xyz, dst_disp, rec, n_kp_host, s_lds, s_lds + 4);
+    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -215,55 +277,167 @@ static int sparse_params(vo_ctx* ctx, float min_disp, float max_disp, float row_
 
 static KpSet kp_set(const FrameSlot& f) { return KpSet{ f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc }; }
 
+int sparse_req_check(vo_ctx* ctx, const SparseReq& q, const char* who)
+{
+    if (q.nfeatures < 0 || q.nfeatures > ctx->max_kp) return vo_fail(ctx, VO_E_CAP, "nfeatures %d exceeds max_kp %d", q.nfeatures, ctx->max_kp);
+    SparseP P;
+    return sparse_params(ctx, q.min_disp, q.max_disp, q.row_tol, q.max_hamming, who, &P);
+}
+
+static bool sparse_req_same(const SparseReq& a, const SparseReq& b)
+{
+    // (bit patterns: -0.f and 0.f are two requests, which only costs a recomputation)
+    return a.nfeatures == b.nfeatures && a.max_hamming == b.max_hamming && !memcmp(&a.min_disp, &b.min_disp, sizeof(float)) &&
+           !memcmp(&a.max_disp, &b.max_disp, sizeof(float)) && !memcmp(&a.row_tol, &b.row_tol, sizeof(float));
+}
+
+void sparse_ws_free(SparseWs& ws)
+{
+    void* ps[] = { ws.match, ws.disp, ws.xyz, ws.ticket };
+    for (void* p : ps) if (p) (void)hipFree(p);
+    orb_ws_free(ws.orb_r);
+    if (ws.own) {
+        for (int k = 0; k < 2; k++) {
+            void* ks[] = { ws.own[k].kp_xy, ws.own[k].kp_size, ws.own[k].kp_angle, ws.own[k].kp_resp, ws.own[k].kp_oct, ws.own[k].desc };
+            for (void* p : ks) if (p) (void)hipFree(p);
+        }
+        delete[] ws.own;
+    }
+    if (ws.own_words) (void)hipHostFree(ws.own_words);
+    ws = SparseWs();
+}
+
+int sparse_ws_prepare(vo_ctx* ctx, SparseWs& ws, hipStream_t stream, bool own_sets, bool with_orb)
+{
+    if (ws.ready && (ws.orb_ready || !with_orb)) return VO_OK;
+    const size_t cap = (size_t)ctx->kp_cap;
+    hipError_t e = hipSuccess;
+    auto take = [&](void** p, size_t bytes) { if (e == hipSuccess && !*p) e = hipMalloc(p, bytes + 256); };
+    if (own_sets && !ws.own) {
+        ws.own = new FrameSlot[2];
+        if (hipHostMalloc((void**)&ws.own_words, 64, hipHostMallocDefault) != hipSuccess) e = hipErrorOutOfMemory;
+        else memset(ws.own_words, 0, 64);
+        for (int k = 0; k < 2 && e == hipSuccess; k++) {
+            FrameSlot& s = ws.own[k];
+            take((void**)&s.kp_xy, cap * 8); take((void**)&s.kp_size, cap * 4); take((void**)&s.kp_angle, cap * 4);
+            take((void**)&s.kp_resp, cap * 4); take((void**)&s.kp_oct, cap * 4); take((void**)&s.desc, cap * 32);
+            s.n_kp_host = ws.own_words + 8 * k;
+        }
+        ws.l = &ws.own[0]; ws.r = &ws.own[1];
+    }
+    if (e == hipSuccess && with_orb && !ws.orb_ready && orb_ws_alloc(ctx, ws.orb_r)) e = hipErrorOutOfMemory;
+    take((void**)&ws.match, cap * 4); take((void**)&ws.disp, cap * 4); take((void**)&ws.xyz, cap * 12);
+    take((void**)&ws.ticket, 64);
+    // the ticket must read zero before the first launch on WHATEVER stream that is: cleared on that stream, and waited for
+    if (e == hipSuccess && !ws.ready) {
+        e = hipMemsetAsync(ws.ticket, 0, 64, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    }
+    if (e != hipSuccess) {
+        FrameSlot *l = ws.l, *r = ws.r;
+        const bool borrowed = !ws.own;
+        sparse_ws_free(ws);
+        if (borrowed) { ws.l = l; ws.r = r; }
+        return vo_fail(ctx, VO_E_HIP, "sparse stereo scratch: allocation failed: %s", hipGetErrorString(e));
+    }
+    ws.ready = true;
+    if (with_orb) ws.orb_ready = true;
+    return VO_OK;
+}
+
+int sparse_enqueue(vo_ctx* ctx, FrameSlot& f, SparseWs& ws, const SparseReq& q)
+{
+    SparseP P;
+    if (int rcp = sparse_params(ctx, q.min_disp, q.max_disp, q.row_tol, q.max_hamming, "sparse stereo", &P)) return rcp;
+    int x0 = 0, y0 = 0, x1 = f.w, y1 = f.h;
+    if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < f.w ? ctx->roi[2] : f.w; y1 = ctx->roi[3] < f.h ? ctx->roi[3] : f.h; }
+    const int cw = x1 - x0, ch = y1 - y0;
+    if (cw <= 2 * VO_ORB_EDGE || ch <= 2 * VO_ORB_EDGE || x0 < 0 || y0 < 0) {
+        // No pixel inside ORB's border: no keypoint on either side, nothing to launch.  The one place this function waits: a voided
+        // earlier run into the slot (the stream is ordered behind it) may still be writing the record the host clears here.  The
+        // scratch sets' count words are left alone (an engine's earlier pair may still be reading them).
+        VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f.sp_rec[0] = f.sp_rec[1] = f.sp_rec[2] = f.sp_rec[3] = 0;
+        *f.n_kp_host = 0;
+        return VO_OK;
+    }
+    FrameSlot &sl = *ws.l, &sr = *ws.r;
+    const size_t off = (size_t)y0 * f.w + x0;
+    // the left crop rectangle on BOTH images (columns compare directly), the two extractions as one batch: one launch per kernel
+    const OrbIn in[2] = { { &sl, ctx->orbws, f.left + off, nullptr, nullptr, f.w, 0, 0 }, { &sr, &ws.orb_r, f.right + off, nullptr, nullptr, f.w, 0, 0 } };
+    if (int rc = orb_enqueue_jobs(ctx, in, 2, cw, ch, q.nfeatures, 0, 0, 0)) return rc;
+    memcpy(P.Q, ctx->Q, sizeof(P.Q));
+    P.x0f = (float)x0; P.y0f = (float)y0;
+    StageTimer t(ctx, VO_T_MATCH);
+#ifdef VO_SPARSE_TWO_LAUNCHES
+    hipLaunchKernelGGL(k_sparse_match, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap,
+                       sl.kp_xy, sl.kp_oct, sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, 1, f.left + off, f.right + off, f.w, cw, ch, P,
+                       ws.match, ws.disp, ws.xyz);
+    VO_CHECK_LAUNCH(ctx);
+    hipLaunchKernelGGL(k_sparse_compact, dim3(1), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl), ws.match, ws.disp,
+                       ws.xyz, kp_set(f), f.kp_xyz, f.kp_disp, f.sp_rec, f.n_kp_host);
+#else
+    hipLaunchKernelGGL(k_sparse_pair, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl),
+                       sr.kp_xy, sr.kp_oct, sr.desc, 1, f.left + off, f.right + off, f.w, cw, ch, P, ws.match, ws.disp, ws.xyz, kp_set(f),
+                       f.kp_xyz, f.kp_disp, f.sp_rec, f.n_kp_host, ws.ticket);
+#endif
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
+// the chain into the slot has finished and the host has waited for it: today's checks from the slot's record, then the slot's state
+static int sparse_collect(vo_ctx* ctx, FrameSlot& f, int32_t* counts3)
+{
+    const volatile int32_t* rec = f.sp_rec;
+    const int nl = rec[0], nr = rec[3];
+    if (nl > ctx->kp_cap || nr > ctx->kp_cap)
+        return vo_fail(ctx, VO_E_CAP, "%d / %d keypoints (response ties included) exceed capacity %d; raise max_kp", nl, nr, ctx->kp_cap);
+    if (nr > 65535) return vo_fail(ctx, VO_E_CAP, "vo_sparse_stereo: %d right keypoints (at most 65535)", nr);
+    counts3[0] = rec[0]; counts3[1] = rec[1]; counts3[2] = rec[2];
+    f.n_kp = rec[2];
+    f.has_kp = true; f.kp_depth = true;
+    return VO_OK;
+}
+
 extern "C" int vo_sparse_stereo(vo_ctx* ctx, int slot, int nfeatures, float min_disp, float max_disp, float row_tol, int max_hamming,
                                 int32_t* counts3)
 {
     if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS || !counts3) return vo_fail(ctx, VO_E_ARG, "vo_sparse_stereo: bad argument");
-    if (nfeatures < 0 || nfeatures > ctx->max_kp) return vo_fail(ctx, VO_E_CAP, "nfeatures %d exceeds max_kp %d", nfeatures, ctx->max_kp);
-    SparseP P;
-    if (int rcp = sparse_params(ctx, min_disp, max_disp, row_tol, max_hamming, "vo_sparse_stereo", &P)) return rcp;
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    if (int rcq = sparse_req_check(ctx, q, "vo_sparse_stereo")) return rcq;
     FrameSlot& f = ctx->slots[slot];
     if (!f.has_pair) return vo_fail(ctx, VO_E_STATE, "slot %d holds no image pair", slot);
     if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
     VO_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
+    const bool same = sparse_req_same(q, f.sp_req);
+    if (f.sp_pending && same) {
+        // a look-ahead engine ran the whole chain: wait for it, nothing to launch
+        f.sp_pending = false;
+        VO_HIP(ctx, hipEventSynchronize(f.ready));
+        if (f.pending && f.counted && ctx->inflight > 0) ctx->inflight--;
+        f.pending = false; f.counted = false;
+        if ((rc = sparse_collect(ctx, f, counts3))) return rc;
+        f.sp_ahead = true;
+        return VO_OK;
+    }
+    if (slot_sparse(f) && f.sp_ahead && same) {
+        // a slot begun ahead and already collected with this request (e.g. ahead of a pose step): its counts again.  A result
+        // computed synchronously is never reused: the synchronous call recomputes, as it always has
+        if ((rc = slot_wait(ctx, f))) return rc;
+        counts3[0] = f.sp_rec[0]; counts3[1] = f.sp_rec[1]; counts3[2] = f.sp_rec[2];
+        return VO_OK;
+    }
     if ((rc = slot_wait(ctx, f)) || (rc = slot_before_overwrite(ctx, f))) return rc;     // (steps begun ahead may still read the slot's keypoints)
-    f.has_kp = false; f.kp_depth = false; f.kp_pending = false;
+    f.has_kp = false; f.kp_depth = false; f.kp_pending = false; f.sp_pending = false; f.sp_ahead = false;
     f.mono_serial = 0;              // depths of a monocular pose step belong to the keypoints this call replaces (as orb_enqueue)
     f.kp_params[0] = f.kp_params[1] = f.kp_params[2] = f.kp_params[3] = -1;     // no ORB extraction ever asks for these: the next one recomputes
     counts3[0] = counts3[1] = counts3[2] = 0;
-    int x0 = 0, y0 = 0, x1 = f.w, y1 = f.h;
-    if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < f.w ? ctx->roi[2] : f.w; y1 = ctx->roi[3] < f.h ? ctx->roi[3] : f.h; }
-    const int cw = x1 - x0, ch = y1 - y0;
-    if (cw <= 0 || ch <= 0 || x0 < 0 || y0 < 0) { *f.n_kp_host = 0; f.n_kp = 0; f.has_kp = true; f.kp_depth = true; return VO_OK; }
-    FrameSlot& sl = ctx->slots[VO_NUM_SLOTS];
-    FrameSlot& sr = ctx->sparse_r;
-    const size_t off = (size_t)y0 * f.w + x0;
-    // the left crop rectangle on BOTH images: columns compare directly
-    if ((rc = orb_enqueue(ctx, &sl, f.left + off, f.w, cw, ch, nfeatures, 0, nullptr, 0, 0, 0, nullptr, 0))) return rc;
-    if ((rc = orb_enqueue(ctx, &sr, f.right + off, f.w, cw, ch, nfeatures, 0, nullptr, 0, 0, 0, nullptr, 0))) return rc;
-    memcpy(P.Q, ctx->Q, sizeof(P.Q));
-    P.x0f = (float)x0; P.y0f = (float)y0;
-    {
-        StageTimer t(ctx, VO_T_MATCH);
-        hipLaunchKernelGGL(k_sparse_match, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap,
-                           sl.kp_xy, sl.kp_oct, sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, 1, f.left + off, f.right + off, f.w, cw, ch, P,
-                           ctx->sp_match, ctx->sp_disp, ctx->sp_xyz);
-        VO_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_sparse_compact, dim3(1), dim3(256), 0, ctx->stream, sl.n_kp_host, ctx->kp_cap, kp_set(sl), ctx->sp_match, ctx->sp_disp,
-                           ctx->sp_xyz, kp_set(f), f.kp_xyz, f.kp_disp, ctx->sp_rec, f.n_kp_host);
-        VO_CHECK_LAUNCH(ctx);
-    }
+    if ((rc = sparse_ws_prepare(ctx, ctx->sp_main, ctx->stream, false))) return rc;
+    if ((rc = sparse_enqueue(ctx, f, ctx->sp_main, q))) return rc;
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the one synchronisation
-    const int nl = *(volatile int32_t*)sl.n_kp_host, nr = *(volatile int32_t*)sr.n_kp_host;
-    if (nl > ctx->kp_cap || nr > ctx->kp_cap)
-        return vo_fail(ctx, VO_E_CAP, "%d / %d keypoints (response ties included) exceed capacity %d; raise max_kp", nl, nr, ctx->kp_cap);
-    if (nr > 65535) return vo_fail(ctx, VO_E_CAP, "vo_sparse_stereo: %d right keypoints (at most 65535)", nr);
-    const volatile int32_t* rec = ctx->sp_rec;
-    counts3[0] = rec[0]; counts3[1] = rec[1]; counts3[2] = rec[2];
-    f.n_kp = rec[2];
-    f.has_kp = true; f.kp_depth = true;
-    return VO_OK;
+    f.sp_req = q;
+    return sparse_collect(ctx, f, counts3);
 }
 
 extern "C" int vo_download_keypoint_depth(vo_ctx* ctx, int slot, float* xyz, float* disp, int cap, int* n_out)
@@ -305,6 +479,7 @@ extern "C" int vo_sparse_match_host(vo_ctx* ctx, const uint8_t* left, const uint
     }
     if (nl == 0) return VO_OK;
     VO_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcw = sparse_ws_prepare(ctx, ctx->sp_main, ctx->stream, false, false)) return rcw;
     FrameSlot& sl = ctx->slots[VO_NUM_SLOTS];
     FrameSlot& sr = ctx->sparse_r;
     const size_t npx = (size_t)w * h;
@@ -320,10 +495,87 @@ extern "C" int vo_sparse_match_host(vo_ctx* ctx, const uint8_t* left, const uint
     sl.has_kp = false; sl.kp_depth = false;
     *sl.n_kp_host = nl; *sr.n_kp_host = nr;
     hipLaunchKernelGGL(k_sparse_match, dim3(div_up(nl, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, sl.kp_xy, sl.kp_oct,
-                       sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, sorted_r, sl.left, sl.right, w, w, h, P, ctx->sp_match, ctx->sp_disp, (float*)nullptr);
+                       sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, sorted_r, sl.left, sl.right, w, w, h, P, ctx->sp_main.match, ctx->sp_main.disp, (float*)nullptr);
     VO_CHECK_LAUNCH(ctx);
-    rc = xfer_d2h(ctx, match_out, ctx->sp_match, (size_t)nl * 4);
-    if (!rc) rc = xfer_d2h(ctx, disp_out, ctx->sp_disp, (size_t)nl * 4);
+    rc = xfer_d2h(ctx, match_out, ctx->sp_main.match, (size_t)nl * 4);
+    if (!rc) rc = xfer_d2h(ctx, disp_out, ctx->sp_main.disp, (size_t)nl * 4);
     if (rc) return rc;
     return xfer_flush(ctx);
+}
+
+// k_sparse_pair alone on host arrays (the seam its tests use): vo_sparse_match_host's inputs plus Q and the ROI origin; the survivors
+// are compacted from the scratch set into a destination of their own (never the source) and come back with their disparity and 3-D
+// point.  The scratch set's size / angle / response are whatever an earlier call left there: they travel, nobody reads them.
+extern "C" int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l,
+                                   const int32_t* oct_l, const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r,
+                                   const uint8_t* desc_r, int nr, float min_disp, float max_disp, float row_tol, int max_hamming,
+                                   const double* Q16, int roi_x0, int roi_y0, int32_t* match_out, float* disp_out, float* kp_xy,
+                                   int32_t* kp_octave, uint8_t* desc, float* kp_disp, float* kp_xyz, int32_t* counts3)
+{
+    if (!ctx || !left || !right || w <= 0 || h <= 0 || nl < 0 || nr < 0 || !Q16 || !counts3) return vo_fail(ctx, VO_E_ARG, "vo_sparse_pair_host: bad argument");
+    if (w > ctx->max_w || h > ctx->max_h) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context", w, h);
+    if (nr > 65535) return vo_fail(ctx, VO_E_CAP, "vo_sparse_pair_host: %d right keypoints (at most 65535)", nr);
+    if (nl > ctx->kp_cap || nr > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "%d / %d keypoints exceed capacity %d", nl, nr, ctx->kp_cap);
+    if ((nl > 0 && (!xy_l || !oct_l || !desc_l || !match_out || !disp_out || !kp_xy || !kp_octave || !desc || !kp_disp || !kp_xyz)) ||
+        (nr > 0 && (!xy_r || !oct_r || !desc_r)))
+        return vo_fail(ctx, VO_E_ARG, "vo_sparse_pair_host: null pointer");
+    SparseP P;
+    if (int rcp = sparse_params(ctx, min_disp, max_disp, row_tol, max_hamming, "vo_sparse_pair_host", &P)) return rcp;
+    for (int i = 0; i < nl; i++) if (oct_l[i] < 0 || oct_l[i] >= VO_ORB_LEVELS) return vo_fail(ctx, VO_E_ARG, "vo_sparse_pair_host: octave %d", oct_l[i]);
+    int sorted_r = 1;
+    for (int j = 0; j < nr; j++) {
+        if (oct_r[j] < 0 || oct_r[j] >= VO_ORB_LEVELS) return vo_fail(ctx, VO_E_ARG, "vo_sparse_pair_host: octave %d", oct_r[j]);
+        if (j && oct_r[j] < oct_r[j - 1]) sorted_r = 0;
+    }
+    memcpy(P.Q, Q16, sizeof(P.Q));
+    P.x0f = (float)roi_x0; P.y0f = (float)roi_y0;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rcw = sparse_ws_prepare(ctx, ctx->sp_main, ctx->stream, false, false)) return rcw;
+    SparseWs& ws = ctx->sp_main;
+    FrameSlot& sl = ctx->slots[VO_NUM_SLOTS];
+    FrameSlot& sr = ctx->sparse_r;
+    // the destination: one allocation cut into the keypoint arrays (a test seam: allocated and freed per call)
+    const size_t cap = ((size_t)ctx->kp_cap + 63) & ~(size_t)63;
+    uint8_t* d = nullptr;
+    VO_HIP(ctx, hipMalloc((void**)&d, cap * (8 + 4 + 4 + 4 + 4 + 32 + 12 + 4) + 256));
+    KpSet dst;
+    dst.xy = (float*)d; dst.size = (float*)(d + cap * 8); dst.angle = (float*)(d + cap * 12); dst.resp = (float*)(d + cap * 16);
+    dst.oct = (int32_t*)(d + cap * 20); dst.desc = d + cap * 24;
+    float* const dst_xyz = (float*)(d + cap * 56);
+    float* const dst_disp = (float*)(d + cap * 68);
+    const size_t npx = (size_t)w * h;
+    int rc = VO_OK;
+    do {
+        if (hipMemcpyAsync(sl.left, left, npx, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(sl.right, right, npx, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = vo_fail(ctx, VO_E_HIP, "vo_sparse_pair_host: upload failed"); break; }
+        if ((rc = xfer_h2d(ctx, sl.kp_xy, xy_l, (size_t)nl * 8))) break;
+        if ((rc = xfer_h2d(ctx, sl.kp_oct, oct_l, (size_t)nl * 4))) break;
+        if ((rc = xfer_h2d(ctx, sl.desc, desc_l, (size_t)nl * 32))) break;
+        if ((rc = xfer_h2d(ctx, sr.kp_xy, xy_r, (size_t)nr * 8))) break;
+        if ((rc = xfer_h2d(ctx, sr.kp_oct, oct_r, (size_t)nr * 4))) break;
+        if ((rc = xfer_h2d(ctx, sr.desc, desc_r, (size_t)nr * 32))) break;
+        sl.has_kp = false; sl.kp_depth = false;
+        *sl.n_kp_host = nl; *sr.n_kp_host = nr;
+        // (the product's grid: every workgroup draws a ticket, most of them with no keypoint of their own)
+        hipLaunchKernelGGL(k_sparse_pair, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl),
+                           sr.kp_xy, sr.kp_oct, sr.desc, sorted_r, sl.left, sl.right, w, w, h, P, ws.match, ws.disp, ws.xyz, dst, dst_xyz, dst_disp,
+                           sl.sp_rec, sl.n_kp_host, ws.ticket);
+        if (hipGetLastError() != hipSuccess) { rc = vo_fail(ctx, VO_E_HIP, "vo_sparse_pair_host: launch failed"); break; }
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = vo_fail(ctx, VO_E_HIP, "vo_sparse_pair_host: the launch failed"); break; }
+        const volatile int32_t* rec = sl.sp_rec;
+        counts3[0] = rec[0]; counts3[1] = rec[1]; counts3[2] = rec[2];
+        const int n = rec[2];
+        if (n < 0 || n > nl) { rc = vo_fail(ctx, VO_E_STATE, "vo_sparse_pair_host: %d survivors of %d keypoints", n, nl); break; }
+        if ((rc = xfer_d2h(ctx, match_out, ws.match, (size_t)nl * 4))) break;
+        if ((rc = xfer_d2h(ctx, disp_out, ws.disp, (size_t)nl * 4))) break;
+        if ((rc = xfer_d2h(ctx, kp_xy, dst.xy, (size_t)n * 8))) break;
+        if ((rc = xfer_d2h(ctx, kp_octave, dst.oct, (size_t)n * 4))) break;
+        if ((rc = xfer_d2h(ctx, desc, dst.desc, (size_t)n * 32))) break;
+        if ((rc = xfer_d2h(ctx, kp_disp, dst_disp, (size_t)n * 4))) break;
+        if ((rc = xfer_d2h(ctx, kp_xyz, dst_xyz, (size_t)n * 12))) break;
+        rc = xfer_flush(ctx);
+    } while (0);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return rc;
 }

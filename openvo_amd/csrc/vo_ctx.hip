@@ -93,7 +93,7 @@ extern "C" const char* vo_last_error(const vo_ctx* ctx)
     return ctx ? ctx->err.c_str() : g_create_err.c_str();
 }
 
-static int orb_ws_alloc(vo_ctx* ctx, OrbWs& o)
+int orb_ws_alloc(vo_ctx* ctx, OrbWs& o)
 {
     const size_t cand = (size_t)ctx->cand_cap * 4 * sizeof(int32_t);   // 8 levels together: < 3.2x level 0
     void** ps[] = { (void**)&o.pyr_img, (void**)&o.pyr_mask,
@@ -106,7 +106,7 @@ static int orb_ws_alloc(vo_ctx* ctx, OrbWs& o)
     return VO_OK;
 }
 
-static void orb_ws_free(OrbWs& o)
+void orb_ws_free(OrbWs& o)
 {
     void* ps[] = { o.pyr_img, o.pyr_mask, o.cand_pos, o.cand_resp, o.candA_pos, o.candA_resp,
                    o.candB_pos, o.candB_resp, o.counters };
@@ -201,7 +201,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         FrameSlot& r = ctx->sparse_r;      // the second scratch keypoint set of vo_sparse_stereo
         DALLOC(r.kp_xy, (size_t)ctx->kp_cap * 2); DALLOC(r.kp_size, ctx->kp_cap); DALLOC(r.kp_angle, ctx->kp_cap);
         DALLOC(r.kp_resp, ctx->kp_cap); DALLOC(r.kp_oct, ctx->kp_cap); DALLOC(r.desc, (size_t)ctx->kp_cap * 32);
-        DALLOC(ctx->sp_match, ctx->kp_cap); DALLOC(ctx->sp_disp, ctx->kp_cap); DALLOC(ctx->sp_xyz, (size_t)ctx->kp_cap * 3);
+        ctx->sp_main.l = &ctx->slots[VO_NUM_SLOTS]; ctx->sp_main.r = &r;      // (the rest of it comes with the first sparse call: sparse_ws_prepare)
     }
     ctx->stage_bytes = npx * 3;
     DALLOC(ctx->stage_in, ctx->stage_bytes * 2);
@@ -225,13 +225,17 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     DALLOC(ctx->red, 4096);
     ctx->pinned_bytes = 8 << 20;
     if (hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void**)&ctx->slot_words, 128 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+        hipHostMalloc((void**)&ctx->slot_words, 256 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
         g_create_err = "hipHostMalloc failed"; vo_destroy(ctx); return VO_E_HIP;
     }
-    memset(ctx->slot_words, 0, 128 * sizeof(int32_t));
-    for (int s = 0; s <= VO_NUM_SLOTS; s++) { ctx->slots[s].n_kp_host = ctx->slot_words + s; ctx->slots[s].sweep_word = ctx->slot_words + 64 + s; }
+    memset(ctx->slot_words, 0, 256 * sizeof(int32_t));
+    // one count word per slot, then one sweep word per slot from word 64 on, then four words of sparse record per slot from word 128 on
+    static_assert(128 + 4 * (VO_NUM_SLOTS + 1) <= 256 && VO_NUM_SLOTS + 1 <= 32, "slot_words layout");
+    for (int s = 0; s <= VO_NUM_SLOTS; s++) {
+        ctx->slots[s].n_kp_host = ctx->slot_words + s; ctx->slots[s].sweep_word = ctx->slot_words + 64 + s;
+        ctx->slots[s].sp_rec = ctx->slot_words + 128 + 4 * s;
+    }
     ctx->sparse_r.n_kp_host = ctx->slot_words + 32;      // (words 29 .. 63 belong to no slot)
-    ctx->sp_rec = ctx->slot_words + 40;
     DALLOC(ctx->d_sweep_errs, 64);
     if (dev_zero(ctx->d_sweep_errs, 64 * sizeof(int)) != hipSuccess) { g_create_err = "clearing the sweep error counter failed"; vo_destroy(ctx); return VO_E_HIP; }
     if (const char* e8 = getenv("VO_ENGINES")) { int v = atoi(e8); if (v >= 1 && v <= vo_ctx::MAX_ENGINES) ctx->n_engines = v; }
@@ -289,9 +293,11 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     }
     void* ps[] = { ctx->stage_in, ctx->map1[0], ctx->map1[1], ctx->map2[0], ctx->map2[1], ctx->dump, ctx->rs_ofs, ctx->rs_coef, ctx->pyr_rects,
                    ctx->host_mask_dev, ctx->mq, ctx->mt, ctx->red, ctx->img3_ws, ctx->d_sweep_errs, ctx->sparse_r.kp_xy, ctx->sparse_r.kp_size,
-                   ctx->sparse_r.kp_angle, ctx->sparse_r.kp_resp, ctx->sparse_r.kp_oct, ctx->sparse_r.desc, ctx->sp_match, ctx->sp_disp, ctx->sp_xyz };
+                   ctx->sparse_r.kp_angle, ctx->sparse_r.kp_resp, ctx->sparse_r.kp_oct, ctx->sparse_r.desc };
     for (void* p : ps) if (p) (void)hipFree(p);
     alt_free(ctx);
+    sparse_ws_free(ctx->sp_main);
+    for (SparseWs& w : ctx->sp_alt) sparse_ws_free(w);
     match_ws_free(ctx->main_mw);
     sgbm_ws_free(ctx->main_ws);
     orb_ws_free(ctx->main_ws.orb);
@@ -431,11 +437,19 @@ extern "C" int vo_set_sgbm(vo_ctx* ctx, int minDisparity, int numDisparities, in
     return VO_OK;
 }
 
+// Q or the ROI changes: a sparse chain begun ahead ran with the old one.  Its result is no longer what vo_sparse_stereo would
+// compute: the next call on such a slot recomputes (the chain itself finishes; the slot's `ready` still orders its consumers).
+static void sparse_void_ahead(vo_ctx* ctx)
+{
+    for (int s = 0; s < VO_NUM_SLOTS; s++) { ctx->slots[s].sp_pending = false; ctx->slots[s].sp_ahead = false; }
+}
+
 extern "C" int vo_set_Q(vo_ctx* ctx, const double* Q16)
 {
     if (!ctx || !Q16) return VO_E_ARG;
     memcpy(ctx->Q, Q16, sizeof(ctx->Q));
     ctx->has_Q = true;
+    sparse_void_ahead(ctx);
     return VO_OK;
 }
 
@@ -446,6 +460,7 @@ extern "C" int vo_set_roi(vo_ctx* ctx, int x0, int y0, int x1, int y1)
     if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;
     ctx->roi[0] = x0; ctx->roi[1] = y0; ctx->roi[2] = x1; ctx->roi[3] = y1;
     ctx->has_roi = true;
+    sparse_void_ahead(ctx);
     return VO_OK;
 }
 
@@ -553,7 +568,7 @@ extern "C" int vo_upload_pair(vo_ctx* ctx, int slot, const uint8_t* left, const 
     // the second ingest reuses the staging area: order on the stream makes that safe
     rc = ingest(ctx, 1, right, w, h, channels, preprocessed, f.right, ctx->stage_in);
     if (rc) return rc;
-    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.sp_pending = false; f.n_kp = 0; f.kp_pending = false;
     return VO_OK;
 }
 
@@ -569,7 +584,7 @@ extern "C" int vo_upload_mono(vo_ctx* ctx, int slot, const uint8_t* img, int w, 
     if ((rc = slot_wait(ctx, f)) || (rc = slot_before_overwrite(ctx, f))) return rc;
     StageTimer t(ctx, VO_T_UPLOAD);
     if ((rc = ingest(ctx, 0, img, w, h, channels, 1, f.left, ctx->stage_in))) return rc;
-    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.sp_pending = false; f.n_kp = 0; f.kp_pending = false;
     return VO_OK;
 }
 
@@ -613,7 +628,7 @@ extern "C" int vo_load_staged_pair(vo_ctx* ctx, int slot, int index, int preproc
     if (rc) return rc;
     rc = ingest(ctx, 1, ctx->staged + per * (2 * index + 1), w, h, ctx->staged_ch, preprocessed, f.right, ctx->stage_in, hipMemcpyDeviceToDevice);
     if (rc) return rc;
-    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_pair = true; f.has_disp = false; f.has_kp = false; f.kp_depth = false; f.sp_pending = false; f.n_kp = 0; f.kp_pending = false;
     return VO_OK;
 }
 
@@ -645,7 +660,10 @@ struct EngineScope {
     EngineScope& operator=(const EngineScope&) = delete;
 };
 
-static int engine_prepare(vo_ctx* ctx, int engine)
+// an engine's stream, events, staging and ORB scratch at its first use; its SGBM workspace (engines 1 ..: about 0.95 GB at 1280 x 720,
+// D = 128) with them unless the caller is a SPARSE submission (want_sgbm = false): it then comes when the first dense pair or
+// monocular extraction lands on the engine
+static int engine_prepare(vo_ctx* ctx, int engine, bool want_sgbm)
 {
     if (!ctx->la_stream[engine]) VO_HIP(ctx, hipStreamCreateWithFlags(&ctx->la_stream[engine], hipStreamNonBlocking));
     if (!ctx->ws_alt[engine].mid) {
@@ -656,7 +674,7 @@ static int engine_prepare(vo_ctx* ctx, int engine)
         VO_HIP(ctx, hipMalloc((void**)&ctx->la_stage[engine], ctx->stage_bytes * 2 + 256));
         if (orb_ws_alloc(ctx, ctx->ws_alt[engine].orb)) return vo_fail(ctx, VO_E_HIP, "hipMalloc failed (look-ahead ORB workspace)");
     }
-    if (engine == 0 || ctx->ws_alt[engine].ready) return VO_OK;
+    if (!want_sgbm || engine == 0 || ctx->ws_alt[engine].ready) return VO_OK;
     const hipError_t e = sgbm_ws_alloc(ctx, ctx->ws_alt[engine]);
     if (e != hipSuccess) return vo_fail(ctx, VO_E_HIP, "look-ahead engine %d: workspace allocation failed: %s", engine, hipGetErrorString(e));
     return VO_OK;
@@ -715,14 +733,17 @@ void slot_add_reader(FrameSlot& f, hipEvent_t done)
 }
 
 // common tail of the look-ahead entry points: ingest (device or pinned-host source) + SGBM (+ ORB) of one
-// pair on the next engine's stream, `ready` recorded at the end
+// pair on the next engine's stream, `ready` recorded at the end.  sp (the *_sparse entries): no SGBM -- behind the ingest the whole
+// sparse stereo chain with that request, in the engine's own SparseWs (the engine's next pair reuses it before the host has read
+// anything: what the host reads lies in the slot)
 static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8_t* srcR, bool from_host, int w, int h,
-                         int channels, int preprocessed, vo_ctx::HostStage* hs = nullptr)
+                         int channels, int preprocessed, vo_ctx::HostStage* hs = nullptr, const SparseReq* sp = nullptr)
 {
     int rc;
     FrameSlot& f = ctx->slots[slot];
     const int engine = ctx->next_engine;
-    if ((rc = engine_prepare(ctx, engine))) return rc;
+    if ((rc = engine_prepare(ctx, engine, sp == nullptr))) return rc;
+    if (sp && (rc = sparse_ws_prepare(ctx, ctx->sp_alt[engine], ctx->la_stream[engine], true))) return rc;
     // an engine holds one member of the open group at a time (this pair's front would land on its stream ahead of that member's
     // back part and reuse its workspace), and a slot that is a member is not refilled before its run is complete
     if ((f.in_group || sweep_group_has_engine(ctx, engine)) && (rc = sweep_group_close(ctx, f.in_group ? VO_GRP_CONSUMER : VO_GRP_OTHER))) return rc;
@@ -746,19 +767,20 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
         kind = hipMemcpyHostToDevice;
     }
     ctx->next_engine = (engine + 1) % ctx->n_engines;
-    f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false;
+    f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.sp_pending = false; f.sp_ahead = false; f.n_kp = 0; f.kp_pending = false;
+    if (sp) { f.mono_serial = 0; f.kp_params[0] = f.kp_params[1] = f.kp_params[2] = f.kp_params[3] = -1; }   // (as vo_sparse_stereo)
     {
         EngineScope on_engine(ctx, engine);          // ctx->stream / staging / SGBM + ORB workspaces are the engine's in here
         rc = engine_behind_chain(ctx, engine);
         const int stagger = ctx->tune_stagger >= 0 ? ctx->tune_stagger : (7 * ctx->n_engines + 8) / 16;
-        if (stagger > 0 && stagger < ctx->n_engines) {
+        if (!sp && stagger > 0 && stagger < ctx->n_engines) {          // (the stagger spreads SGBM stages: a sparse pair has none)
             vo_ctx::SgbmWs& p = ctx->ws_alt[(engine - stagger + ctx->n_engines) % ctx->n_engines];
             if (p.mid_valid) (void)hipStreamWaitEvent(ctx->stream, p.mid, 0);
         }
         if (!rc) rc = slot_before_overwrite(ctx, f);
         // a rectified gray pair that already lies in HBM needs no ingest step of its own: the SGBM run's first kernel reads it
         // where it lies and leaves the slot's copy behind (two copy commands less per pair on the engine's queue)
-        const bool in_place = kind == hipMemcpyDeviceToDevice && preprocessed && channels == 1;
+        const bool in_place = !sp && kind == hipMemcpyDeviceToDevice && preprocessed && channels == 1;
         if (!rc && !in_place) {
             StageTimer t(ctx, VO_T_UPLOAD);
             const bool pinned_src = hs != nullptr || from_host;   // (the library's own pinned staging either way)
@@ -778,8 +800,9 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
         if (!rc && ctx->fault_prefetch > 0 && --ctx->fault_prefetch == 0)
             rc = vo_fail(ctx, VO_E_STATE, "injected failure (VO_FAULT_PREFETCH) inside the engine scope");
 #endif
-        if (!rc) rc = in_place ? sgbm_run(ctx, f, w, h, srcL, srcR, &deferred) : sgbm_run(ctx, f, w, h, nullptr, nullptr, &deferred);
-        if (!rc && !deferred && ctx->la_orb) {
+        if (!rc && sp) rc = sparse_enqueue(ctx, f, ctx->sp_alt[engine], *sp);
+        else if (!rc) rc = in_place ? sgbm_run(ctx, f, w, h, srcL, srcR, &deferred) : sgbm_run(ctx, f, w, h, nullptr, nullptr, &deferred);
+        if (!rc && !sp && !deferred && ctx->la_orb) {
             const int* q = ctx->la_orb_params;
             rc = orb_slot_enqueue(ctx, f, q[0], q[1], q[2], q[3]);
             if (!rc) { memcpy(f.kp_params, q, sizeof(f.kp_params)); f.kp_pending = true; }
@@ -793,7 +816,8 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
         f.counted = false;                               // (`pending` stays: an earlier run into this slot may still be in flight)
         return rc;
     }
-    f.has_pair = true; f.has_disp = true;
+    f.has_pair = true; f.has_disp = sp == nullptr;
+    if (sp) { f.sp_req = *sp; f.sp_pending = true; }
     if (!f.counted) ctx->inflight++;
     f.pending = true; f.counted = true;
     // (a member of the open group: the sweep, the post filters, the ORB chain and `ready` follow when the group closes)
@@ -815,6 +839,60 @@ extern "C" int vo_prefetch_staged_pair(vo_ctx* ctx, int slot, int index, int pre
                          ctx->staged_h, ctx->staged_ch, preprocessed);
 }
 
+// The three look-ahead entries with the sparse stereo chain in place of the SGBM (include/vo355.h): the request is checked before
+// anything is enqueued; vo_set_Q is needed, vo_set_sgbm is not
+static int host_stage_wait(vo_ctx* ctx, int buf);
+static int sparse_entry_check(vo_ctx* ctx, const SparseReq& q, const char* who)
+{
+    if (int rc = sparse_req_check(ctx, q, who)) return rc;
+    if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
+    return VO_OK;
+}
+
+extern "C" int vo_prefetch_staged_pair_sparse(vo_ctx* ctx, int slot, int index, int preprocessed, int nfeatures, float min_disp, float max_disp,
+                                              float row_tol, int max_hamming)
+{
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (index < 0 || index >= ctx->staged_n) return vo_fail(ctx, VO_E_ARG, "vo_prefetch_staged_pair_sparse: bad index");
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    if ((rc = sparse_entry_check(ctx, q, "vo_prefetch_staged_pair_sparse"))) return rc;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t per = (size_t)ctx->staged_w * ctx->staged_h * ctx->staged_ch;
+    return prefetch_pair(ctx, slot, ctx->staged + per * 2 * index, ctx->staged + per * (2 * index + 1), false, ctx->staged_w,
+                         ctx->staged_h, ctx->staged_ch, preprocessed, nullptr, &q);
+}
+
+extern "C" int vo_prefetch_pair_sparse(vo_ctx* ctx, int slot, const uint8_t* left, const uint8_t* right, int w, int h, int channels,
+                                       int preprocessed, int nfeatures, float min_disp, float max_disp, float row_tol, int max_hamming)
+{
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!left || !right || (channels != 1 && channels != 3)) return vo_fail(ctx, VO_E_ARG, "vo_prefetch_pair_sparse: bad argument");
+    if (w > ctx->max_w || h > ctx->max_h || w < 16 || h < 16) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context %dx%d", w, h, ctx->max_w, ctx->max_h);
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    if ((rc = sparse_entry_check(ctx, q, "vo_prefetch_pair_sparse"))) return rc;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    return prefetch_pair(ctx, slot, left, right, true, w, h, channels, preprocessed, nullptr, &q);
+}
+
+extern "C" int vo_prefetch_host_staged_sparse(vo_ctx* ctx, int slot, int buf, int w, int h, int channels, int preprocessed, int nfeatures,
+                                              float min_disp, float max_disp, float row_tol, int max_hamming)
+{
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (buf < 0 || buf >= vo_ctx::N_HOST_STAGE || (channels != 1 && channels != 3)) return vo_fail(ctx, VO_E_ARG, "vo_prefetch_host_staged_sparse: bad argument");
+    if (w > ctx->max_w || h > ctx->max_h || w < 16 || h < 16) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context %dx%d", w, h, ctx->max_w, ctx->max_h);
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    if ((rc = sparse_entry_check(ctx, q, "vo_prefetch_host_staged_sparse"))) return rc;
+    vo_ctx::HostStage& hs = ctx->host_stage[buf];
+    if (!hs.pinned) return vo_fail(ctx, VO_E_STATE, "staging buffer %d has not been filled (vo_host_stage_pair / vo_host_stage_begin)", buf);
+    if ((rc = host_stage_wait(ctx, buf))) return vo_fail(ctx, rc, "the copy into staging buffer %d failed", buf);
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t per = (size_t)w * h * channels;
+    return prefetch_pair(ctx, slot, hs.pinned, hs.pinned + per, true, w, h, channels, preprocessed, &hs, &q);
+}
+
 // monocular look-ahead (config 5): the left image of a staged pair into a slot and its ORB extraction (no disparity
 // mask), all on a look-ahead engine's stream; vo_orb_detect_and_compute with the same nfeatures / mask_mode 0 then only
 // waits.  The main stream keeps matching and scoring the previous pair meanwhile.
@@ -829,12 +907,12 @@ extern "C" int vo_prefetch_staged_mono(vo_ctx* ctx, int slot, int index, int nfe
     // a monocular extraction is short: four engines cover any useful look-ahead (an engine's first use allocates its workspaces)
     const int span = ctx->n_engines < 4 ? ctx->n_engines : 4;
     const int engine = ctx->mono_engine % span;
-    if ((rc = engine_prepare(ctx, engine))) return rc;
+    if ((rc = engine_prepare(ctx, engine, true))) return rc;      // (as ever on this path: the engine's workspaces all come with its first use)
     if ((f.in_group || sweep_group_has_engine(ctx, engine)) && (rc = sweep_group_close(ctx, f.in_group ? VO_GRP_CONSUMER : VO_GRP_OTHER))) return rc;
     ctx->mono_engine = (engine + 1) % span;
     const size_t per = (size_t)ctx->staged_w * ctx->staged_h * ctx->staged_ch;
     const int w = ctx->staged_w, h = ctx->staged_h;
-    f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.n_kp = 0; f.kp_pending = false; f.has_disp = false;
+    f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.sp_pending = false; f.n_kp = 0; f.kp_pending = false; f.has_disp = false;
     {
         EngineScope on_engine(ctx, engine);
         rc = engine_behind_chain(ctx, engine);       // (the engine's ORB scratch may still serve the group it was last a member of)
@@ -1030,7 +1108,7 @@ extern "C" int vo_sgbm_compute(vo_ctx* ctx, int slot, int16_t* disp16_out)
     if ((rc = slot_wait(ctx, f))) return rc;
     rc = sgbm_run(ctx, f, f.w, f.h);
     if (rc) return rc;
-    f.has_disp = true; f.kp_pending = false; f.has_kp = false; f.kp_depth = false;
+    f.has_disp = true; f.kp_pending = false; f.has_kp = false; f.kp_depth = false; f.sp_pending = false;
     if (disp16_out) {
         VO_HIP(ctx, hipMemcpyAsync(disp16_out, f.disp16, (size_t)f.w * f.h * 2, hipMemcpyDeviceToHost, ctx->stream));
         VO_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -76,6 +76,16 @@ struct FrameSlot {
     float* kp_xyz = nullptr;
     float* kp_disp = nullptr;
     bool kp_depth = false;
+    // sparse stereo begun ahead (vo_prefetch_*_sparse): the whole chain was enqueued on a look-ahead engine's stream with the request
+    // sp_req, and the slot's pinned record sp_rec = {left keypoints, accepted, kept, right keypoints} (the two extractions' counts as
+    // they left them, unclamped) is written by its last kernel; vo_sparse_stereo with the same request only waits for `ready` and
+    // reads the record.  sp_pending is cleared like kp_depth: by every ORB extraction into the slot and by every refill.  sp_req
+    // stays that of the result the slot holds while kp_depth is set (a repeated call returns the record's counts again).
+    int32_t* sp_rec = nullptr;
+    bool sp_pending = false;
+    bool sp_ahead = false;       // the sparse result the slot holds was begun ahead and has been collected: the same request again returns its counts
+                                 // (never set by a synchronous computation, which always recomputes; voided by vo_set_Q / vo_set_roi)
+    struct SparseReq { int nfeatures; float min_disp, max_disp, row_tol; int max_hamming; } sp_req = {-1, 0.f, 0.f, 0.f, 0};
     // the slot's look-ahead run is a member of the context's open sweep group: its diagonal sweep, post filters and ORB chain are
     // not enqueued and `ready` is NOT recorded for this run yet -- whoever is about to wait on, read, refill or drop the slot
     // closes the group first (sweep_group_close_for)
@@ -90,6 +100,24 @@ struct OrbWs {
     hipEvent_t done = nullptr;   // end of the latest run in this workspace (any stream)
     bool done_valid = false;
 };
+
+// Scratch of one sparse stereo chain (sparse.hip): the two extractions' keypoint sets, each with its pinned count word (keypoint
+// arrays and n_kp_host of a FrameSlot, nothing else), the ORB scratch of the second extraction (the first runs in the scratch the
+// context works in: *ctx->orbws), per left keypoint the associated right keypoint (-1: none), the refined disparity (NaN: rejected)
+// and its 3-D position, and the ticket word of k_sparse_pair (zero between launches).  The context owns one for its main stream
+// (l / r: the scratch slot of the *_host seams and sparse_r) and one per look-ahead engine, each completed at its first sparse use
+// (sparse_ws_prepare) and freed by vo_destroy.
+struct SparseWs {
+    FrameSlot *l = nullptr, *r = nullptr;
+    OrbWs orb_r;
+    int32_t* match = nullptr;
+    float *disp = nullptr, *xyz = nullptr;
+    int32_t* ticket = nullptr;
+    FrameSlot* own = nullptr;        // an engine's two sets (the main one borrows the context's)
+    int32_t* own_words = nullptr;    // ... and their pinned count words
+    bool ready = false, orb_ready = false;
+};
+typedef FrameSlot::SparseReq SparseReq;
 
 struct vo_ctx {
     int device = 0;
@@ -179,12 +207,11 @@ struct vo_ctx {
 
     FrameSlot slots[VO_NUM_SLOTS + 1];  // last slot = scratch for the *_host seams
     // vo_sparse_stereo: the left keypoints are extracted into the scratch slot above, the right ones into this second scratch set
-    // (keypoint arrays and pinned count word only); sp_match / sp_disp / sp_xyz: per left keypoint the associated right keypoint
-    // (-1: none), the refined disparity (NaN: rejected) and its 3-D position; sp_rec (pinned): {left keypoints, accepted, kept}
+    // (keypoint arrays and pinned count word only); sp_main: the SparseWs of the main stream built on the two, sp_alt[k]: look-ahead
+    // engine k's own
     FrameSlot sparse_r;
-    int32_t* sp_match = nullptr;
-    float *sp_disp = nullptr, *sp_xyz = nullptr;
-    int32_t* sp_rec = nullptr;
+    SparseWs sp_main;
+    SparseWs sp_alt[MAX_ENGINES];
 
     // staging
     uint8_t* stage_in = nullptr;   // raw upload (max_w*max_h*3)
@@ -380,6 +407,23 @@ int orb_enqueue_jobs(vo_ctx* ctx, const OrbIn* in, int n, int w, int h, int nfea
 // one extraction on ctx->stream into the keypoint arrays of *fs (enqueue only: the count lands in fs->n_kp_host)
 int orb_enqueue(vo_ctx* ctx, FrameSlot* fs, const uint8_t* d_img, int img_stride, int w, int h, int nfeatures, int mask_mode,
                 const int16_t* d_disp16, int disp_stride, int min_d16, int max_d16, const uint8_t* d_mask, int mask_stride);
+// ---- sparse stereo (sparse.hip) ----
+// VO_E_ARG / VO_E_CAP for a request no sparse entry accepts (nothing is enqueued before this has passed)
+int sparse_req_check(vo_ctx* ctx, const SparseReq& q, const char* who);
+// completes a SparseWs at its first use: the second ORB scratch, the per-keypoint arrays, an engine's keypoint sets, and the ticket,
+// cleared on `stream` -- the stream that will use it -- and waited for
+// with_orb = false: the host seam of the association alone (no extraction: no second ORB scratch)
+int sparse_ws_prepare(vo_ctx* ctx, SparseWs& ws, hipStream_t stream, bool own_sets, bool with_orb = true);
+// the one allocator of an ORB scratch (vo_ctx.hip)
+int orb_ws_alloc(vo_ctx* ctx, OrbWs& o);
+void orb_ws_free(OrbWs& o);
+void sparse_ws_free(SparseWs& ws);
+// ENQUEUES on ctx->stream: both extractions of the slot's pair as one batch of two, association + refinement + compaction into the
+// slot's keypoint arrays, kp_xyz, kp_disp; the slot's record and n_kp_host are written by the last kernel.  No synchronisation
+// -- with one exception: a crop with no pixel inside ORB's border (empty, or at most 62 pixels in either direction) has no keypoint;
+// nothing is launched, the stream is WAITED for (an earlier run into the slot may still be writing the record) and the host clears
+// the slot's record.  No scratch count word is ever written from the host: an engine's earlier pair may still be reading them.
+int sparse_enqueue(vo_ctx* ctx, FrameSlot& f, SparseWs& ws, const SparseReq& q);
 // the slot's keypoints carry depth (vo_sparse_stereo): the pose steps take their 3-D points from kp_xyz
 static inline bool slot_sparse(const FrameSlot& f) { return f.has_kp && f.kp_depth; }
 // kernel `fn` may use up to 160 KB of dynamic LDS: set once per context, before its first launch that needs more than 64 KB

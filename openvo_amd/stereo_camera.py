@@ -25,10 +25,30 @@ class StagedPair:
 class SubmittedPair:
     """Handle of a host pair handed to StereoCamera.submit(): its upload, disparity (and, once the
     odometer has announced its ORB settings, keypoints) already run on a look-ahead engine.  Pass it
-    as `img_left` (with img_right=None) to compute_3d / StereoOdometer.update."""
+    as `img_left` (with img_right=None) to compute_3d / StereoOdometer.update.
+    A pair from StereoCamera.submit_sparse() is of the sparse kind: `sparse` = (nfeatures, min_disp, max_disp, row_tol,
+    max_hamming), the request its sparse stereo chain was begun with; it goes to compute_sparse / a depth="sparse" odometer."""
 
-    def __init__(self, slot, shape, preprocessed, images=None):
+    def __init__(self, slot, shape, preprocessed, images=None, sparse=None):
         self.slot, self.shape, self.preprocessed, self.images = slot, shape, bool(preprocessed), images
+        self.sparse = None if sparse is None else tuple(sparse)
+
+
+def sparse_request(nfeatures, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75):
+    """The request of a sparse stereo chain as the tuple a SubmittedPair remembers, held to the rules the library applies
+    (ValueError here, before a slot is taken or anything is submitted)."""
+    def number(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and np.isfinite(v)
+    if isinstance(nfeatures, (bool, np.bool_)) or not isinstance(nfeatures, (int, np.integer)) or nfeatures < 0:
+        raise ValueError("nfeatures must be an int >= 0")
+    if not (number(min_disp) and number(max_disp) and 0 <= min_disp < max_disp):
+        raise ValueError("need finite 0 <= min_disp < max_disp")
+    if not (number(row_tol) and row_tol >= 0):
+        raise ValueError("row_tol must be a finite number >= 0")
+    if isinstance(max_hamming, (bool, np.bool_)) or not isinstance(max_hamming, (int, np.integer)) or not 0 <= max_hamming <= 256:
+        raise ValueError("max_hamming must be an int in 0 .. 256")
+    # (the float32 values the library compares with: two requests that differ only beyond them are one request)
+    return (int(nfeatures), float(np.float32(min_disp)), float(np.float32(max_disp)), float(np.float32(row_tol)), int(max_hamming))
 
 
 def _RESERVED():
@@ -231,19 +251,47 @@ class StereoCamera:
         self._slot_owner[slot] = _RESERVED
         return SubmittedPair(slot, shape, preprocessed)
 
-    def submit_staged(self, buf, w, h, ch, preprocessed):
-        """Second half of submit() for a pair that a helper thread has already copied into pinned staging buffer `buf`
-        (Context.host_stage_pair): upload + disparity (+ keypoints) start on a look-ahead engine, nothing is copied on
-        this thread.  With no free slot the pair is taken back out of the staging buffer and processed synchronously when
-        consumed, like submit() (the caller's own arrays may have been reused by then)."""
+    def submit_sparse(self, img_left, img_right, nfeatures, preprocessed=False, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75):
+        """submit() for the sparse stereo depth: upload, ORB on both images, association, refinement and compaction of a host
+        pair start on a look-ahead engine (no disparity image); the SubmittedPair remembers that it is sparse and with which
+        request, and goes to compute_sparse -- with the same request it only collects -- or to a depth="sparse" odometer's
+        update(), in submission order.  Not in the reference.  With no free slot the pair is kept on the host and processed
+        synchronously when consumed, like submit()."""
+        req = sparse_request(nfeatures, min_disp, max_disp, row_tol, max_hamming)
+        img_left, img_right = np.asarray(img_left), np.asarray(img_right)
+        if img_left.ndim != img_right.ndim:
+            if img_left.ndim == 3:
+                img_left = self._ctx.cvt_bgr2gray(img_left)
+            if img_right.ndim == 3:
+                img_right = self._ctx.cvt_bgr2gray(img_right)
         held = sum(1 for o in self._slot_owner if o is _RESERVED)
         slot = self._free_slot() if held < _native.VO_NUM_SLOTS - 3 else None
         if slot is None:
-            return SubmittedPair(None, None, preprocessed, self._ctx.host_stage_fetch(buf, w, h, ch))
-        shape = self._ctx.prefetch_host_staged(slot, buf, w, h, ch, preprocessed)
+            return SubmittedPair(None, None, preprocessed, (img_left.copy(), img_right.copy()), sparse=req)
+        shape = self._ctx.prefetch_pair_sparse(slot, img_left, img_right, preprocessed, *req)
         self._slot_gen[slot] += 1
         self._slot_owner[slot] = _RESERVED
-        return SubmittedPair(slot, shape, preprocessed)
+        return SubmittedPair(slot, shape, preprocessed, sparse=req)
+
+    def submit_staged(self, buf, w, h, ch, preprocessed, sparse=None):
+        """Second half of submit() for a pair that a helper thread has already copied into pinned staging buffer `buf`
+        (Context.host_stage_pair): upload + disparity (+ keypoints) start on a look-ahead engine, nothing is copied on
+        this thread.  With no free slot the pair is taken back out of the staging buffer and processed synchronously when
+        consumed, like submit() (the caller's own arrays may have been reused by then).
+        sparse = (nfeatures, min_disp, max_disp, row_tol, max_hamming): the second half of submit_sparse() instead."""
+        if sparse is not None:
+            sparse = sparse_request(*sparse)
+        held = sum(1 for o in self._slot_owner if o is _RESERVED)
+        slot = self._free_slot() if held < _native.VO_NUM_SLOTS - 3 else None
+        if slot is None:
+            return SubmittedPair(None, None, preprocessed, self._ctx.host_stage_fetch(buf, w, h, ch), sparse=sparse)
+        if sparse is not None:
+            shape = self._ctx.prefetch_host_staged_sparse(slot, buf, w, h, ch, preprocessed, *sparse)
+        else:
+            shape = self._ctx.prefetch_host_staged(slot, buf, w, h, ch, preprocessed)
+        self._slot_gen[slot] += 1
+        self._slot_owner[slot] = _RESERVED
+        return SubmittedPair(slot, shape, preprocessed, sparse=sparse)
 
     def _drop(self, slot):
         """Give back the slot of a look-ahead pair nobody will consume (the native side stops counting it as in flight;
@@ -299,11 +347,25 @@ class StereoCamera:
         """Sparse stereo depth (not in the reference): ORB on both rectified images, association along the row, sub-pixel
         refinement -- no disparity image (include/vo355.h, vo_sparse_stereo).  -> (keypoints, descriptors, xyz (n, 3),
         disparity (n,), img_left): the left keypoints that have a depth, device-resident and lazy like compute_3d's results.
-        Takes host arrays or a StagedPair; a SubmittedPair has SGBM work in flight and is refused.  Starts no look-ahead."""
+        Takes host arrays, a StagedPair, or a SubmittedPair from submit_sparse() (with the request it was submitted under the call
+        only collects what the look-ahead engine computed; with another it recomputes from the slot's pair; `preprocessed` is
+        then the pair's own); a dense SubmittedPair has SGBM work in flight and is refused.  Starts no look-ahead itself."""
+        submitted = None
         if isinstance(img_left, SubmittedPair):
-            raise ValueError("compute_sparse takes host arrays or a StagedPair: a SubmittedPair's disparity is already in flight")
+            if img_left.sparse is None:
+                raise ValueError("compute_sparse takes host arrays, a StagedPair or a pair from submit_sparse(): this SubmittedPair's disparity is already in flight")
+            submitted = img_left
+            if submitted.slot is None:                       # no slot was free at submit_sparse(): host copy
+                if submitted.images is None:
+                    raise ValueError("this SubmittedPair has already been consumed")
+                img_left, img_right = submitted.images
+                preprocessed = submitted.preprocessed
+                submitted.images = None
+                submitted = None
+            elif self._slot_owner[submitted.slot] is not _RESERVED:
+                raise ValueError("this SubmittedPair has already been consumed")
         staged = isinstance(img_left, StagedPair)
-        if not staged:
+        if not staged and submitted is None:
             img_left, img_right = np.asarray(img_left), np.asarray(img_right)
             if img_left.ndim != img_right.ndim:
                 if img_left.ndim == 3:
@@ -311,13 +373,22 @@ class StereoCamera:
                 if img_right.ndim == 3:
                     img_right = self._ctx.cvt_bgr2gray(img_right)
         import weakref
-        slot, _ = self._acquire_slot()
-        self._slot_gen[slot] += 1
-        if staged:
-            w, h = self._ctx.load_staged_pair(slot, img_left.index, preprocessed)
+        if submitted is not None:
+            slot, (w, h) = submitted.slot, submitted.shape
+            submitted.slot = None
         else:
-            w, h = self._ctx.upload_pair(slot, img_left, img_right, preprocessed)
-        n = int(self._ctx.sparse_stereo(slot, nfeatures, min_disp, max_disp, row_tol, max_hamming)[2])
+            slot, _ = self._acquire_slot()
+            self._slot_gen[slot] += 1
+            if staged:
+                w, h = self._ctx.load_staged_pair(slot, img_left.index, preprocessed)
+            else:
+                w, h = self._ctx.upload_pair(slot, img_left, img_right, preprocessed)
+        try:
+            n = int(self._ctx.sparse_stereo(slot, nfeatures, min_disp, max_disp, row_tol, max_hamming)[2])
+        except Exception:
+            if submitted is not None:
+                self._drop(slot)                             # (consumed all the same: the slot goes back, nothing stays counted in flight)
+            raise
         vr = self.valid_region_left
         y0, y1, _ = slice(vr[1], vr[3]).indices(h)
         x0, x1, _ = slice(vr[0], vr[2]).indices(w)
@@ -334,6 +405,8 @@ class StereoCamera:
         each is a DeviceImage (np.asarray(x) or x[...] materialises it)."""
         submitted = None
         if isinstance(img_left, SubmittedPair):
+            if img_left.sparse is not None:
+                raise ValueError("compute_3d takes a pair from submit(): this SubmittedPair carries sparse stereo depth, no disparity (compute_sparse)")
             submitted = img_left
             if submitted.slot is None:                       # no slot was free at submit(): host copy
                 if submitted.images is None:

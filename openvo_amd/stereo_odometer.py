@@ -49,7 +49,8 @@ class StereoOdometer:
         the keypoint's scale, Hamming distance at most sparse_max_hamming) and refined to sub-pixel (StereoCamera.compute_sparse,
         include/vo355.h); a frame's keypoints are then the left keypoints that have a depth, current_3d / prev_3d are their (n, 3)
         points and current_disparity their (n,) disparities.  The state machine, both pose methods, cross_check and match_window
-        are unchanged; feature_mask is not used.  Sparse pairs are processed synchronously (run() submits nothing ahead)."""
+        are unchanged; feature_mask is not used.  run() submits sparse pairs ahead like dense ones (StereoCamera.submit_sparse): their
+        upload, both extractions, association and compaction run on the look-ahead engines, update() collects."""
         if not isinstance(depth, str) or depth not in ("dense", "sparse"):
             raise ValueError("depth must be 'dense' or 'sparse'")
         if (isinstance(sparse_row_tol, (bool, np.bool_)) or not isinstance(sparse_row_tol, (int, float, np.integer, np.floating))
@@ -254,6 +255,11 @@ class StereoOdometer:
         if hasattr(self.stereo, "reset_lookahead"):
             self.stereo.reset_lookahead()
 
+    def _sparse_req(self):
+        """the request of this odometer's sparse stereo chain, as StereoCamera.submit_sparse / SubmittedPair.sparse hold it"""
+        from .stereo_camera import sparse_request
+        return sparse_request(self.orb.nfeatures, self.MIN_VALID_DISPARITY, self.MAX_VALID_DISPARITY, self.sparse_row_tol, self.sparse_max_hamming)
+
     def _start_next_pose(self):
         """The frame just accepted is the new `current`.  The pairs that will come next may already be on the device
         (look-ahead / submitted ahead): for as many of them as have FINISHED their disparity and keypoints (never waiting for
@@ -262,24 +268,34 @@ class StereoOdometer:
         results arrive in a burst (a cold start: every pair in flight finishes at about the same time) the short kernel
         chains of many pairs run side by side instead of one after the other behind the host.  Purely an ordering change:
         _pair_fused looks a step up by its slots and parameters and computes on the spot when the guess was wrong."""
-        if self.depth == "sparse" or not self._fused_ok() or self.orb.last_slot_args is None:
-            return self._drop_specs()           # (sparse pairs are never on the device ahead of their update())
+        sparse = self.depth == "sparse"
+        if not self._fused_ok() or (not sparse and self.orb.last_slot_args is None):
+            return self._drop_specs()
+        # what identifies the keypoints a pair begun ahead will hold: the ORB arguments, or the sparse request (collected by the
+        # waiting form of sparse_stereo: the slot is ready, so it only reads the slot's record)
+        req = ("sparse",) + self._sparse_req() if sparse else self.orb.last_slot_args
         kps = self.current_kps
         if not self._on_device(kps, self.current_desc, self.current_3d):
             return self._drop_specs()
         depth = self.pose_ahead
-        nxt = [h.slot for h in self._next_hint] if self._next_hint else self.stereo.next_lookahead_slots(depth)
+        if sparse:      # (only pairs submitted under this very request: another one would be recomputed, which is update()'s business)
+            nxt = [h.slot if h.sparse == req[1:] else None for h in self._next_hint]
+        else:
+            nxt = [h.slot for h in self._next_hint] if self._next_hint else self.stereo.next_lookahead_slots(depth)
         chain, counts = [kps.frame.slot], [len(kps)]
         for s in nxt[:depth]:
             if s is None or not self._ctx.slot_ready(s):
                 break
             chain.append(s)
-            key = (self.stereo.slot_key(s), self.orb.last_slot_args)
+            key = (self.stereo.slot_key(s), req)
             if key not in self._ahead_counts:
                 if len(self._ahead_counts) > 64:
                     self._ahead_counts.clear()
                 try:
-                    self._ahead_counts[key] = self._ctx.orb_slot_count(s, *self.orb.last_slot_args)   # (finished: only collects the count)
+                    if sparse:
+                        self._ahead_counts[key] = int(self._ctx.sparse_stereo(s, *req[1:])[2])             # (finished: only collects the kept count)
+                    else:
+                        self._ahead_counts[key] = self._ctx.orb_slot_count(s, *self.orb.last_slot_args)   # (finished: only collects the count)
                 except _native.VoError:
                     self._ahead_counts[key] = -1     # that pair's own update() reports what is wrong with it; nothing is begun on it here
             counts.append(self._ahead_counts[key])
@@ -309,7 +325,10 @@ class StereoOdometer:
         pair ahead of the pair being submitted: it overlaps this thread's kernel launches and waits, this thread never touches
         image bytes, and no second Python thread competes for the interpreter lock.  The caller may refill the arrays it
         yielded as soon as it is asked for the next pair (a copy is waited for before the iterator is advanced).  Pairs whose
-        two images differ in channel count go through StereoCamera.submit() instead.
+        two images differ in channel count go through StereoCamera.submit() instead.  With depth="sparse" the pairs are submitted
+        with this odometer's sparse request (StereoCamera.submit_staged(..., sparse=) / submit_sparse()): upload, both extractions,
+        association and compaction run ahead on the look-ahead engines, update() collects, and pose steps are begun ahead on
+        the pairs that have finished -- the results are those of update() pair by pair.
 
         A pair whose disparity is undefined (update() raises SweepTimeout, see there): with on_sweep_timeout="raise" (default)
         the exception leaves the generator, which ends -- the failed pair and the pairs already taken from `pairs` but not yet
@@ -320,11 +339,7 @@ class StereoOdometer:
         from collections import deque
         if on_sweep_timeout not in ("raise", "skip"):
             raise ValueError("on_sweep_timeout must be 'raise' or 'skip'")
-        if self.depth == "sparse":
-            # no look-ahead for sparse pairs: update() pair by pair, nothing submitted and no sweep to time out
-            for L, R in pairs:
-                yield self.update(L, R)
-            return
+        sparse = self._sparse_req() if self.depth == "sparse" else None     # (sparse pairs: no sweep group, so nothing to flush)
         cam, ctx = self.stereo, self.stereo._ctx
         depth = int(cam.lookahead if depth is None else depth)
         nbuf = _native.VO_NUM_HOST_STAGE
@@ -361,17 +376,22 @@ class StereoOdometer:
                 while len(queue) <= depth and copying and (len(copying) >= 2 or state["done"]):
                     started += 1
                     item = copying.popleft()
-                    if item[0] is None:
+                    if item[0] is None and sparse is not None:
+                        queue.append(cam.submit_sparse(item[1], item[2], sparse[0], self.preprocessed_frames, *sparse[1:]))
+                    elif item[0] is None:
                         queue.append(cam.submit(item[1], item[2], preprocessed=self.preprocessed_frames))
                     else:
                         buf, w, h, ch, _keep = item
                         if state["inflight"] == buf:
                             state["inflight"] = None                     # (submit_staged waits for the copy)
-                        queue.append(cam.submit_staged(buf, w, h, ch, self.preprocessed_frames))
+                        if sparse is not None:
+                            queue.append(cam.submit_staged(buf, w, h, ch, self.preprocessed_frames, sparse=sparse))
+                        else:
+                            queue.append(cam.submit_staged(buf, w, h, ch, self.preprocessed_frames))
                     keep_one_ahead()
                 # (see StereoCamera.compute_3d: after a burst or at the end of the input nothing follows that a held-back pair
                 # could share its sweep launch with)
-                if started > 1 or (started and state["done"] and not copying):
+                if sparse is None and (started > 1 or (started and state["done"] and not copying)):
                     flush = getattr(ctx, "lookahead_flush", None)
                     if flush is not None:
                         flush()

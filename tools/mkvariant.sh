@@ -12,7 +12,7 @@ mkdir -p ../../build
 make -s
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function -Wno-unused-variable "$@" -c $src -o ../../build/${base}_$tag.o
 objs=""
-for o in vo_ctx sgbm orb match geom ransac mgpu; do
+for o in vo_ctx sgbm orb match geom ransac sparse mgpu; do
   if [ "$o" = "$base" ]; then objs="$objs ../../build/${base}_$tag.o"; else objs="$objs $o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build/libvo355_$tag.so $objs -ldl
