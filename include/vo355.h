@@ -183,7 +183,8 @@ int vo_bf_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, 
  * parity unpinned (no OpenCV to compare against where this was written; tests/test_crosscheck_host.py pins it wherever a cv2
  * is importable).  a(j) comes out of the SAME kernel launch as the kNN-2 (column minima of the distance tiles): the matcher
  * runs once, not twice.  Cross-check needs nq <= 65535 (VO_E_CAP otherwise).
- * match_flags of the _ex entries below: bit 0 = VO_MATCH_CROSSCHECK, bit 1 = VO_MATCH_WINDOW; every other bit must be 0.  The
+ * match_flags of the _ex entries below: bit 0 = VO_MATCH_CROSSCHECK, bit 1 = VO_MATCH_WINDOW, bit 2 = VO_MATCH_LOOP (the stereo pair
+ * steps only); every other bit must be 0.  The
  * entries without _ex are the same calls with match_flags = 0, unchanged.
  * Window (VO_MATCH_WINDOW), a second EXTENSION of the matcher [stereo_odometer.py:165 "# TODO config" at the match step]: train j
  * is a candidate of query i only if |xq_i - xt_j| <= rx and |yq_i - yt_j| <= ry, evaluated in float32 on the keypoint positions the
@@ -199,6 +200,19 @@ int vo_bf_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, 
  * image (the runner-up is the best of fewer candidates). */
 #define VO_MATCH_CROSSCHECK 1
 #define VO_MATCH_WINDOW 2
+/* Loop check (VO_MATCH_LOOP), a third EXTENSION, for the stereo pair steps on slots whose keypoints carry depth (vo_sparse_stereo):
+ * a match (q, t) that has passed the ratio test -- and the cross-check and the window where asked for -- is kept iff the right-image
+ * partners of q and t look alike too: popcount(kp_rdesc_a[q] ^ kp_rdesc_b[t]) <= max_hamming (the circular matching of sparse
+ * stereo odometry; tests/sparse_loop_ref.py restates it).  M counts what passes every test and every later stage works on that
+ * set; a threshold of 256 gives the step without the flag, bit for bit.  The threshold is context state like the window
+ * (vo_set_match_loop, 0 .. 256), read when a step is ENQUEUED: a step begun ahead keeps the threshold it was begun with; it is not
+ * scaled with the frames a pair spans.  VO_MATCH_LOOP without a threshold set is VO_E_ARG; on a slot whose keypoints carry no
+ * depth it is VO_E_STATE; vo_point_clouds_ex, vo_pose_pair_ex / _begin_ex and vo_pnp_pair / _begin take it, every other entry
+ * with match_flags (the monocular steps, the kNN seams) answers VO_E_ARG. */
+#define VO_MATCH_LOOP 4
+int vo_set_match_loop(vo_ctx* ctx, int max_hamming);
+/* VO_E_STATE when no threshold is set */
+int vo_clear_match_loop(vo_ctx* ctx);
 /* finite radii >= 0 (VO_E_ARG otherwise: negative, NaN, inf) */
 int vo_set_match_window(vo_ctx* ctx, float rx, float ry);
 /* back to no window; VO_E_STATE when none is set (like every call made out of order) */
@@ -443,6 +457,27 @@ int vo_sparse_stereo(vo_ctx* ctx, int slot, int nfeatures, float min_disp, float
 /* the 3-D points (n x 3) and disparities (n) of a slot's keypoints, in keypoint order; either output may be NULL.  VO_E_STATE when the
  * slot's keypoints carry no depth. */
 int vo_download_keypoint_depth(vo_ctx* ctx, int slot, float* xyz /*cap*3*/, float* disp /*cap*/, int cap, int* n_out);
+/* Association tests of step b (two EXTENSIONS of it, both off by default; tests/sparse_loop_ref.py restates them).  Candidates,
+ * distances and the key (distance << 16 | j) are those of step b.
+ *   VO_SPARSE_RATIO: (d1, j1) and (d2, j2) are the two lexicographically smallest (distance, j) among ALL candidates of left keypoint
+ *     i, the second whatever its distance.  i is accepted iff d1 <= max_hamming and (there is no second candidate or
+ *     (float)d1 < ratio * (float)d2, in float32): d1 == d2 fails for every legal ratio, a single candidate passes.  A keypoint that
+ *     fails has match -1 and is not refined.
+ *   VO_SPARSE_MUTUAL: a(j) = the lexicographically smallest (distance, i) over the left keypoints i that have j as a candidate at a
+ *     distance <= max_hamming (whether or not j is their winner).  A left keypoint i accepted with match j survives iff a(j) names
+ *     i; one that does not has match -1 and disparity NaN.  The key is (distance << 16 | i): more than 65535 left keypoints with
+ *     this bit set is VO_E_CAP.
+ * counts3[1] counts the associations that pass the threshold and every enabled test; counts3[2] what survives the refinement too.
+ * The tests are context state, read when a sparse chain is ENQUEUED (vo_sparse_stereo and the vo_prefetch_*_sparse entries) and
+ * part of the request from then on: a chain begun ahead under another state is recomputed by vo_sparse_stereo exactly as one begun
+ * with another row_tol.  ratio is read only with VO_SPARSE_RATIO and must then satisfy 0 < ratio <= 1; any other bit of flags, or
+ * such a ratio, is VO_E_ARG.  flags = 0 is the association of step b alone. */
+#define VO_SPARSE_MUTUAL 1
+#define VO_SPARSE_RATIO 2
+int vo_set_sparse_assoc(vo_ctx* ctx, int flags, float ratio);
+/* the descriptor (32 bytes) of the RIGHT keypoint each of a slot's keypoints was associated with, in keypoint order (its position is
+ * (x - disparity, about y)); valid exactly while the keypoints carry depth: VO_E_STATE otherwise.  rdesc may be NULL (the count only). */
+int vo_download_keypoint_rdesc(vo_ctx* ctx, int slot, uint8_t* rdesc /*cap*32*/, int cap, int* n_out);
 /* steps b and c on host arrays, no ORB involved (the seam the kernel tests use): two w x h images (the crop is the whole image),
  * nl / nr keypoints (x, y pairs, octaves 0 .. 7, 32-byte descriptors).  match_out[i] = the accepted right keypoint or -1;
  * disp_out[i] = d, NaN where keypoint i was not accepted or was rejected by the refinement. */
@@ -458,6 +493,15 @@ int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, 
                         float min_disp, float max_disp, float row_tol, int max_hamming, const double* Q16, int roi_x0, int roi_y0,
                         int32_t* match_out /*nl*/, float* disp_out /*nl*/, float* kp_xy /*nl*2*/, int32_t* kp_octave /*nl*/,
                         uint8_t* desc /*nl*32*/, float* kp_disp /*nl*/, float* kp_xyz /*nl*3*/, int32_t* counts3);
+/* the same with the association tests as arguments (assoc_flags / assoc_ratio as vo_set_sparse_assoc; the context's state is neither
+ * read nor changed) and one more output: kp_rdesc, the descriptor of right keypoint match[i] of every survivor (may be NULL).
+ * vo_sparse_pair_host is this entry with assoc_flags 0. */
+int vo_sparse_pair_host_ex(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l, const int32_t* oct_l,
+                           const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r, const uint8_t* desc_r, int nr,
+                           float min_disp, float max_disp, float row_tol, int max_hamming, int assoc_flags, float assoc_ratio,
+                           const double* Q16, int roi_x0, int roi_y0, int32_t* match_out /*nl*/, float* disp_out /*nl*/,
+                           float* kp_xy /*nl*2*/, int32_t* kp_octave /*nl*/, uint8_t* desc /*nl*32*/, float* kp_disp /*nl*/,
+                           float* kp_xyz /*nl*3*/, uint8_t* kp_rdesc /*nl*32*/, int32_t* counts3);
 /* Sparse stereo begun ahead (NOT part of the reference either).  The three entries are vo_prefetch_pair / vo_prefetch_host_staged /
  * vo_prefetch_staged_pair with the sparse stereo chain in place of the SGBM: on the next look-ahead engine's stream the pair is
  * ingested into the slot, both extractions run as one batch, and one launch associates, refines and compacts; the slot's `ready` is

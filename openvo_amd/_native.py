@@ -43,6 +43,7 @@ SYMBOLS = [
     "vo_set_match_window", "vo_clear_match_window", "vo_bf_knn2_hamming_window",
     "vo_sparse_stereo", "vo_download_keypoint_depth", "vo_sparse_match_host",
     "vo_sparse_pair_host", "vo_prefetch_pair_sparse", "vo_prefetch_host_staged_sparse", "vo_prefetch_staged_pair_sparse",
+    "vo_set_sparse_assoc", "vo_download_keypoint_rdesc", "vo_sparse_pair_host_ex", "vo_set_match_loop", "vo_clear_match_loop",
     "vo_get_stage_timeline",
 ]
 
@@ -224,6 +225,12 @@ def lib():
                                 ("vo_prefetch_staged_pair_sparse", [vp, ci, ci, ci] + req),
                                 ("vo_sparse_pair_host", [vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, ci, vp, ci, ci] + [vp] * 8)):
                 getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_set_sparse_assoc"):       # (likewise: an older build has no association tests)
+            cf = ctypes.c_float
+            for name, proto in (("vo_set_sparse_assoc", [vp, ci, cf]), ("vo_download_keypoint_rdesc", [vp, ci, vp, ci, vp]),
+                                ("vo_set_match_loop", [vp, ci]), ("vo_clear_match_loop", [vp]),
+                                ("vo_sparse_pair_host_ex", [vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, ci, ci, cf, vp, ci, ci] + [vp] * 9)):
+                getattr(L, name).argtypes = proto
         if hasattr(L, "vo_pnp_pair"):               # (likewise: an older build has no fused PnP step)
             L.vo_pnp_pair.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
             L.vo_pnp_pair_begin.argtypes = [vp, ci, ci, cd, ci, vp, ci, ctypes.c_float, ctypes.c_uint32, ci, ci, vp]
@@ -257,6 +264,16 @@ def lib():
 
 VO_MATCH_CROSSCHECK = 1
 VO_MATCH_WINDOW = 2
+VO_MATCH_LOOP = 4
+
+
+def loop_threshold(loop, what="loop"):
+    """None | int 0 .. 256 -> None | int; ValueError for anything else"""
+    if loop is None:
+        return None
+    if isinstance(loop, (bool, np.bool_)) or not isinstance(loop, (int, np.integer)) or not 0 <= loop <= 256:
+        raise ValueError("%s is None or an int in 0 .. 256, not %r" % (what, loop))
+    return int(loop)
 
 
 def _flags(cross_check):
@@ -282,6 +299,29 @@ def window_radii(window, what="window"):
     if not (np.isfinite(rx) and np.isfinite(ry) and rx >= 0 and ry >= 0):
         raise ValueError("%s: the radii must be finite and >= 0, not %r" % (what, window))
     return rx, ry
+
+
+VO_SPARSE_MUTUAL = 1
+VO_SPARSE_RATIO = 2
+
+
+def sparse_assoc_state(mutual=False, ratio=None):
+    """(mutual, ratio) -> (flags, float32 ratio) as vo_set_sparse_assoc takes them; ValueError for a mutual that is no bool or a
+    ratio that is neither None nor a number with 0 < ratio <= 1"""
+    if not isinstance(mutual, (bool, np.bool_)):
+        raise ValueError("mutual is True or False, not %r" % (mutual,))
+    flags = VO_SPARSE_MUTUAL if mutual else 0
+    if ratio is None:
+        return flags, 0.0
+    try:
+        if isinstance(ratio, (bool, str, bytes)) or np.ndim(ratio) != 0:
+            raise TypeError
+        r = float(np.float32(ratio))
+    except (TypeError, ValueError):
+        raise ValueError("the association ratio is None or a number with 0 < ratio <= 1, not %r" % (ratio,))
+    if not (0.0 < r <= 1.0):
+        raise ValueError("the association ratio is None or a number with 0 < ratio <= 1, not %r" % (ratio,))
+    return flags | VO_SPARSE_RATIO, r
 
 
 def _p(a):
@@ -311,6 +351,8 @@ class Context:
             self.set_engines(engines)
         self._la_orb = None
         self._window = None          # the match window this wrapper last set in the context
+        self._loop = None            # ... and the threshold of the loop check
+        self._sparse_assoc = (0, 0.0)    # ... and the association tests of the sparse chain (the context starts with none)
         self.device, self.max_w, self.max_h, self.max_disp, self.max_kp = device, max_w, max_h, max_disp, max_kp
         self.kp_cap = max_kp * 2 + 1024
 
@@ -626,6 +668,24 @@ class Context:
                                             int(max_hamming), _p(c3)))
         return c3
 
+    def set_sparse_assoc(self, mutual=False, ratio=None):
+        """The association tests of every sparse chain enqueued from now on (vo_set_sparse_assoc): mutual = a right keypoint
+        belongs to its best left claimant only; ratio (None = off, else 0 < ratio <= 1) = the winner's distance must be below
+        ratio x the runner-up's.  Remembered here: setting the state that is already in force makes no native call."""
+        state = sparse_assoc_state(mutual, ratio)
+        if state != self._sparse_assoc:
+            self._ck(self._lib.vo_set_sparse_assoc(self._h, state[0], state[1]))
+            self._sparse_assoc = state
+
+    def download_keypoint_rdesc(self, slot):
+        """-> (n, 32) uint8: the descriptor of the right keypoint each of the slot's keypoints was associated with (VoError when
+        the slot's keypoints carry no depth)."""
+        cap = self.kp_cap
+        rdesc = np.empty((cap, 32), np.uint8)
+        n = ctypes.c_int(0)
+        self._ck(self._lib.vo_download_keypoint_rdesc(self._h, int(slot), _p(rdesc), cap, ctypes.byref(n)))
+        return rdesc[:n.value].copy()
+
     def download_keypoint_depth(self, slot):
         """-> (xyz (n, 3) float32, disparity (n,) float32) of a slot whose keypoints carry depth (VoError otherwise)."""
         cap = self.kp_cap
@@ -653,9 +713,12 @@ class Context:
                                                 _p(match), _p(disp)))
         return match, disp
 
-    def sparse_pair_host(self, left, right, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, Q, roi_xy, min_disp, max_disp, row_tol=2.0, max_hamming=75):
-        """Association, refinement AND compaction of vo_sparse_stereo on host arrays in one launch (vo_sparse_pair_host) -> dict:
-        match (nl,), disp (nl,) as sparse_match_host; xy, octave, desc, kp_disp, xyz of the survivors in their order; counts3."""
+    def sparse_pair_host(self, left, right, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, Q, roi_xy, min_disp, max_disp, row_tol=2.0, max_hamming=75,
+                         mutual=False, assoc_ratio=None):
+        """Association, refinement AND compaction of vo_sparse_stereo on host arrays in one launch (vo_sparse_pair_host_ex) -> dict:
+        match (nl,), disp (nl,) as sparse_match_host; xy, octave, desc, kp_disp, xyz, rdesc of the survivors in their order; counts3.
+        mutual / assoc_ratio: the association tests as set_sparse_assoc takes them (arguments here: the context's state is not touched)."""
+        aflags, aratio = sparse_assoc_state(mutual, assoc_ratio)
         left, right = _c(left, np.uint8), _c(right, np.uint8)
         if left.ndim != 2 or left.shape != right.shape:
             raise ValueError("two 2-D uint8 images of one shape")
@@ -670,12 +733,14 @@ class Context:
         match, disp = np.full(nl, -1, np.int32), np.full(nl, np.nan, np.float32)
         xy, octave, desc = np.zeros((nl, 2), np.float32), np.zeros(nl, np.int32), np.zeros((nl, 32), np.uint8)
         kp_disp, xyz, c3 = np.zeros(nl, np.float32), np.zeros((nl, 3), np.float32), np.zeros(3, np.int32)
-        self._ck(self._lib.vo_sparse_pair_host(self._h, _p(left), _p(right), w, h, _p(xy_l), _p(oct_l), _p(desc_l), nl, _p(xy_r), _p(oct_r),
-                                               _p(desc_r), nr, float(min_disp), float(max_disp), float(row_tol), int(max_hamming), _p(Q),
-                                               int(roi_xy[0]), int(roi_xy[1]), _p(match), _p(disp), _p(xy), _p(octave), _p(desc), _p(kp_disp),
-                                               _p(xyz), _p(c3)))
+        rdesc = np.zeros((nl, 32), np.uint8)
+        self._ck(self._lib.vo_sparse_pair_host_ex(self._h, _p(left), _p(right), w, h, _p(xy_l), _p(oct_l), _p(desc_l), nl, _p(xy_r), _p(oct_r),
+                                                  _p(desc_r), nr, float(min_disp), float(max_disp), float(row_tol), int(max_hamming), aflags,
+                                                  aratio, _p(Q), int(roi_xy[0]), int(roi_xy[1]), _p(match), _p(disp), _p(xy), _p(octave),
+                                                  _p(desc), _p(kp_disp), _p(xyz), _p(rdesc), _p(c3)))
         n = int(c3[2])
-        return dict(match=match, disp=disp, xy=xy[:n], octave=octave[:n], desc=desc[:n], kp_disp=kp_disp[:n], xyz=xyz[:n], counts3=c3)
+        return dict(match=match, disp=disp, xy=xy[:n], octave=octave[:n], desc=desc[:n], kp_disp=kp_disp[:n], xyz=xyz[:n], rdesc=rdesc[:n],
+                    counts3=c3)
 
     # ---- matching / 3-D / pose
     def bf_knn2(self, q, t):
@@ -685,9 +750,26 @@ class Context:
         self._ck(self._lib.vo_bf_knn2_hamming(self._h, _p(q), len(q), _p(t), len(t), _p(idx), _p(dist)))
         return idx, dist
 
-    def _mflags(self, cross_check, window):
-        """match_flags of the _ex entries; a window goes into the context first (only when it differs from the last one set)"""
+    def set_match_loop(self, max_hamming):
+        """the threshold of the loop check (VO_MATCH_LOOP) for the steps enqueued from now on; remembered: the value in force makes no native call"""
+        n = loop_threshold(max_hamming)
+        if n is None:
+            raise ValueError("loop is an int in 0 .. 256 (clear_match_loop takes it away)")
+        if n != self._loop:
+            self._ck(self._lib.vo_set_match_loop(self._h, n))
+            self._loop = n
+
+    def clear_match_loop(self):
+        self._ck(self._lib.vo_clear_match_loop(self._h))
+        self._loop = None
+
+    def _mflags(self, cross_check, window, loop=None):
+        """match_flags of the _ex entries; a window / a loop threshold goes into the context first (only when it differs from the
+        last one set)"""
         f = _flags(cross_check)
+        if loop is not None:
+            self.set_match_loop(loop)
+            f |= VO_MATCH_LOOP
         w = window_radii(window)
         if w is not None:
             if w != self._window:
@@ -751,13 +833,14 @@ class Context:
         self._ck(self._lib.vo_bilinear_at(self._h, _p(img3d), w, h, _p(xy), len(xy), _p(out), _p(st)))
         return out, st
 
-    def point_clouds(self, slot_a, slot_b, ratio, cross_check=False, window=None):
+    def point_clouds(self, slot_a, slot_b, ratio, cross_check=False, window=None, loop=None):
+        """loop (None | 0 .. 256): the loop check on two slots whose keypoints carry depth (VO_MATCH_LOOP)"""
         cap = self.kp_cap
         q, t = np.empty(cap, np.int32), np.empty(cap, np.int32)
         pa, pb = np.empty((cap, 3), np.float32), np.empty((cap, 3), np.float32)
         sa, sb = np.empty(cap, np.uint8), np.empty(cap, np.uint8)
         m = ctypes.c_int(0)
-        self._ck(self._lib.vo_point_clouds_ex(self._h, slot_a, slot_b, float(ratio), self._mflags(cross_check, window), _p(q), _p(t), _p(pa), _p(pb),
+        self._ck(self._lib.vo_point_clouds_ex(self._h, slot_a, slot_b, float(ratio), self._mflags(cross_check, window, loop), _p(q), _p(t), _p(pa), _p(pb),
                                               _p(sa), _p(sb), cap, ctypes.byref(m)))
         m = m.value
         return q[:m], t[:m], pa[:m], pb[:m], sa[:m], sb[:m]
@@ -767,17 +850,17 @@ class Context:
         """(counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4) as the pose entries expect them on entry"""
         return np.zeros(4, np.int32), np.ones(2, np.int32), np.full((3, 4), np.nan), np.full((3, 4), np.nan)
 
-    def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False, window=None):
+    def pose_pair(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False, window=None, loop=None):
         """Fused match + ratio + 3-D lookup + clique filter + outlier pass + Umeyama for two slots.
         Returns (counts[M, n1, n2, flags], rc[first, final], T1 3x4, T2 3x4)."""
         out = self._pose_out()
-        self._ck(self._lib.vo_pose_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), int(min_matches),
+        self._ck(self._lib.vo_pose_pair_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window, loop), int(min_matches),
                                            float(rigidity_thr), float(outlier_thr), *[_p(a) for a in out]))
         return out
 
-    def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False, window=None):
+    def pose_pair_begin(self, slot_a, slot_b, ratio, min_matches, rigidity_thr, outlier_thr, cross_check=False, window=None, loop=None):
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_pose_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), int(min_matches),
+        self._ck(self._lib.vo_pose_pair_begin_ex(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window, loop), int(min_matches),
                                                  float(rigidity_thr), float(outlier_thr), ctypes.byref(t)))
         return t.value
 
@@ -973,12 +1056,13 @@ class Context:
         [, mask, q, t of length n])."""
         return self.pnp_pair_window(slot_a, slot_b, ratio, K4, None, iters, thr, seed, refine, want_matches, cross_check)
 
-    def pnp_pair_window(self, slot_a, slot_b, ratio, K4, window, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False, cross_check=False):
-        """pnp_pair with the kNN-2 inside the match window (None | (rx, ry), see bf_knn2_window).  A method of its own: the
-        signature of pnp_pair is pinned by the callers that bind against it."""
+    def pnp_pair_window(self, slot_a, slot_b, ratio, K4, window, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False, cross_check=False,
+                        loop=None):
+        """pnp_pair with the kNN-2 inside the match window (None | (rx, ry), see bf_knn2_window) and / or the loop check (loop:
+        None | 0 .. 256).  A method of its own: the signature of pnp_pair is pinned by the callers that bind against it."""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         head, arrays = self._pnp_out(want_matches)
-        self._ck(self._lib.vo_pnp_pair(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_pnp_pair(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window, loop), _p(K4), int(iters), float(thr),
                                        int(seed) & 0xFFFFFFFF, int(refine), *[_p(a) for a in head + arrays], self.kp_cap))
         return self._pnp_result(head, arrays)
 
@@ -987,11 +1071,11 @@ class Context:
         return self.pnp_pair_begin_window(slot_a, slot_b, ratio, K4, None, iters, thr, seed, refine, want_matches, cross_check)
 
     def pnp_pair_begin_window(self, slot_a, slot_b, ratio, K4, window, iters=256, thr=1.5, seed=4321, refine=0, want_matches=False,
-                              cross_check=False):
+                              cross_check=False, loop=None):
         """pnp_pair_window in two halves -> a ticket for pnp_pair_end"""
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         t = ctypes.c_int(-1)
-        self._ck(self._lib.vo_pnp_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window), _p(K4), int(iters), float(thr),
+        self._ck(self._lib.vo_pnp_pair_begin(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window, loop), _p(K4), int(iters), float(thr),
                                              int(seed) & 0xFFFFFFFF, int(refine), int(bool(want_matches)), ctypes.byref(t)))
         return t.value
 

@@ -262,7 +262,8 @@ template <bool CROSS>
 __global__ void __launch_bounds__(1024) k_ratio_compact(const int32_t* __restrict__ idx, const int32_t* __restrict__ dist, int nq, double ratio,
                                                         const float* __restrict__ xy_q, const float* __restrict__ xy_t, int32_t* __restrict__ q_out,
                                                         int32_t* __restrict__ t_out, float* __restrict__ xyq_out, float* __restrict__ xyt_out,
-                                                        int32_t* __restrict__ m_out, const uint32_t* __restrict__ colmin, int nt_c)
+                                                        int32_t* __restrict__ m_out, const uint32_t* __restrict__ colmin, int nt_c,
+                                                        const uint8_t* __restrict__ rd_q, const uint8_t* __restrict__ rd_t, int loop_max)
 {
     constexpr int K = 8;
     __shared__ int s_cnt[K * 16 + 1];
@@ -284,6 +285,7 @@ __global__ void __launch_bounds__(1024) k_ratio_compact(const int32_t* __restric
             const double a = (double)(float)ds[k].x, b = (double)(float)ds[k].y;
             bool keep = i < nq && id[k].y >= 0 && a < ratio * b;
             if constexpr (CROSS) keep = keep && knn_mutual(id[k].x, i, colmin, nt_c);
+            if (rd_q) keep = keep && loop_pass(rd_q, rd_t, i, id[k].x, loop_max);
             bal[k] = __ballot(keep);
             if (lane == 0) s_cnt[k * nw + wv] = __popcll(bal[k]);
             pq[k] = make_float2(0.f, 0.f); pt[k] = pq[k];
@@ -315,9 +317,9 @@ __global__ void __launch_bounds__(1024) k_ratio_compact(const int32_t* __restric
     if (threadIdx.x == 0) *m_out = base;
 }
 template __global__ void k_ratio_compact<false>(const int32_t*, const int32_t*, int, double, const float*, const float*, int32_t*, int32_t*, float*,
-                                                float*, int32_t*, const uint32_t*, int);
+                                                float*, int32_t*, const uint32_t*, int, const uint8_t*, const uint8_t*, int);
 template __global__ void k_ratio_compact<true>(const int32_t*, const int32_t*, int, double, const float*, const float*, int32_t*, int32_t*, float*,
-                                               float*, int32_t*, const uint32_t*, int);
+                                               float*, int32_t*, const uint32_t*, int, const uint8_t*, const uint8_t*, int);
 
 // the matched keypoints' 3-D points of two slots whose keypoints carry depth (vo_sparse_stereo)
 __global__ void k_gather_xyz(const float* __restrict__ xyz_a, const float* __restrict__ xyz_b, const int32_t* __restrict__ q, const int32_t* __restrict__ t,
@@ -336,7 +338,7 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
 {
     if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !m_out)
         return vo_fail(ctx, VO_E_ARG, "vo_point_clouds: bad argument");
-    if (int rcf = match_flags_check(ctx, match_flags, "vo_point_clouds")) return rcf;
+    if (int rcf = match_flags_check(ctx, match_flags, "vo_point_clouds", true)) return rcf;
     const int cross = match_flags & VO_MATCH_CROSSCHECK;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
@@ -344,6 +346,8 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
     const bool sparse = slot_sparse(a);
     if (sparse != slot_sparse(b)) return vo_fail(ctx, VO_E_STATE, "vo_point_clouds: one slot's keypoints carry depth, the other's do not");
     if (!sparse && (!a.has_disp || !b.has_disp)) return vo_fail(ctx, VO_E_STATE, "slots need disparity and keypoints");
+    LoopGate lg;
+    if (int rcl = match_loop_gate(ctx, a, b, match_flags, "vo_point_clouds", &lg)) return rcl;
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     *m_out = 0;
     if (a.n_kp == 0) return VO_OK;
@@ -357,7 +361,7 @@ extern "C" int vo_point_clouds_ex(vo_ctx* ctx, int slot_a, int slot_b, double ra
         auto kern = cross ? k_ratio_compact<true> : k_ratio_compact<false>;
         hipLaunchKernelGGL(kern, dim3(1), dim3(a.n_kp > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy,
                            ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
-                           cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, cross ? b.n_kp : 0);
+                           cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, cross ? b.n_kp : 0, lg.rd_a, lg.rd_b, lg.max_h);
         VO_CHECK_LAUNCH(ctx);
         // 3-D lookups for every query slot position (n_kp upper bound); only the first M are meaningful
         VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1211,9 +1215,11 @@ __global__ void __launch_bounds__(256) k_pose_prep(const int32_t* __restrict__ i
                                                    int* __restrict__ flags_dev, TapDisp ta, TapDisp tb, int cw, int ch,
                                                    float* __restrict__ pts_a, float* __restrict__ pts_b, uint8_t* __restrict__ st_a,
                                                    uint8_t* __restrict__ st_b, int* __restrict__ ncons, const uint32_t* __restrict__ colmin, int nt_c,
-                                                   const float* __restrict__ xyz_a, const float* __restrict__ xyz_b)
+                                                   const float* __restrict__ xyz_a, const float* __restrict__ xyz_b,
+                                                   const uint8_t* __restrict__ rd_a, const uint8_t* __restrict__ rd_b, int loop_max)
 {
     // xyz_a / xyz_b (both or neither): the two slots' keypoints carry depth -- the points are kp_xyz[q] / kp_xyz[t], status 0
+    // rd_a / rd_b (both or neither): the loop check on the right partners' descriptors (LoopGate)
     __shared__ int s_m;
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
@@ -1227,6 +1233,7 @@ __global__ void __launch_bounds__(256) k_pose_prep(const int32_t* __restrict__ i
                 double a = (double)(float)dist[2 * i], b = (double)(float)dist[2 * i + 1];
                 keep = idx[2 * i + 1] >= 0 && a < ratio * b;
                 if constexpr (CROSS) keep = keep && knn_mutual(t, i, colmin, nt_c);
+                if (rd_a) keep = keep && loop_pass(rd_a, rd_b, i, t, loop_max);
             }
             unsigned long long bal = __ballot(keep);
             if (keep) {
@@ -1348,7 +1355,7 @@ size_t pose_ws_bytes(int nq)
 // k_pose_solve writes the finished PoseOut record into host_out (pinned host memory the device can address) itself.  No host
 // synchronisation, no copy command.
 static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, int min_matches, double rigidity_thr,
-                        double outlier_thr, void* host_out)
+                        double outlier_thr, void* host_out, const LoopGate& lg)
 {
     const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     const bool sparse = slot_sparse(a);      // (pose_check: then b's keypoints carry depth too)
@@ -1391,7 +1398,8 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
         hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, ctx->mw->mq_idx,
                            ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, d_m, d_out, d_flags, ta, tb, x1 - x0, y1 - y0, ctx->mw->pts_a, ctx->mw->pts_b,
                            ctx->mw->st_a, ctx->mw->st_b, d_ncons, cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr,
-                           cross ? b.n_kp : 0, sparse ? (const float*)a.kp_xyz : nullptr, sparse ? (const float*)b.kp_xyz : nullptr);
+                           cross ? b.n_kp : 0, sparse ? (const float*)a.kp_xyz : nullptr, sparse ? (const float*)b.kp_xyz : nullptr,
+                           lg.rd_a, lg.rd_b, lg.max_h);
         const int use_filter = rigidity_thr > 0;
         // LDS: 4 int arrays of nq (rounded to even so the bit matrix stays 8-byte aligned) + bit matrix if <= 48 KB
         const int m_cap = (nq + 1) & ~1;
@@ -1443,16 +1451,18 @@ extern "C" int vo_pose_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio
 {
     if (!counts4 || !rc2 || !T2_12) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair: bad argument");
     int rc = pose_check(ctx, slot_a, slot_b);
-    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_pose_pair");
+    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_pose_pair", true);
     if (rc) return rc;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
+    LoopGate lg;
+    if ((rc = match_loop_gate(ctx, a, b, match_flags, "vo_pose_pair", &lg))) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
     rc2[0] = rc2[1] = 1;
     if (a.n_kp == 0) return VO_OK;
-    if ((rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, ctx->pinned))) return rc;
+    if ((rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, ctx->pinned, lg))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;
     if (!slot_sparse(a) && ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b)))) return rc;   // never a pose from an undefined disparity
     pose_unpack(ctx->pinned, counts4, rc2, T1_12, T2_12);
@@ -1470,11 +1480,13 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
 {
     if (!ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_pose_pair_begin: bad argument");
     int rc = pose_check(ctx, slot_a, slot_b);
-    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_pose_pair_begin");
+    if (!rc) rc = match_flags_check(ctx, match_flags, "vo_pose_pair_begin", true);
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
+    LoopGate lg;      // (read here, when the step is begun: the ticket keeps this threshold)
+    if ((rc = match_loop_gate(ctx, a, b, match_flags, "vo_pose_pair_begin", &lg))) return rc;
     int k;
     if ((rc = alt_open(ctx, vo_ctx::ALT_POSE, a, b, "vo_pose_pair_begin", &k))) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[k];
@@ -1483,7 +1495,7 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     rec->rc1 = rec->rc2 = 1;
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
-        rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, rec);
+        rc = pose_enqueue(ctx, a, b, ratio, match_flags, min_matches, rigidity_thr, outlier_thr, rec, lg);
     }
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;
@@ -1532,9 +1544,11 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
                                                   int32_t* __restrict__ mq, int32_t* __restrict__ mt, TapDisp ta, int cw, int ch, float x0f,
                                                   float y0f, int32_t* __restrict__ q2, int32_t* __restrict__ t2, float* __restrict__ X,
                                                   float* __restrict__ uv, int32_t* __restrict__ hdr, const uint32_t* __restrict__ colmin,
-                                                  int nt_range, const float* __restrict__ xyz_a)
+                                                  int nt_range, const float* __restrict__ xyz_a, const uint8_t* __restrict__ rd_a,
+                                                  const uint8_t* __restrict__ rd_b, int loop_max)
 {
     // xyz_a: slot a's keypoints carry depth -- the 3-D point of match (q, t) is kp_xyz[q], status 0
+    // rd_a / rd_b (both or neither): the loop check on the right partners' descriptors (LoopGate)
     __shared__ int s_m, s_flags, s_cnt[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (wv == 0) {
@@ -1548,6 +1562,7 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
                 const double a = (double)(float)dist[2 * i], b = (double)(float)dist[2 * i + 1];
                 keep = idx[2 * i + 1] >= 0 && a < ratio * b;
                 if constexpr (CROSS) keep = keep && knn_mutual(t, i, colmin, nt);
+                if (rd_a && t >= 0 && t < nt_range) keep = keep && loop_pass(rd_a, rd_b, i, t, loop_max);     // (an index out of range: flagged below, never read through)
             }
             const unsigned long long bal = __ballot(keep);
             if (__ballot(keep && (t < 0 || t >= nt_range))) fl = 2;
@@ -1594,7 +1609,7 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
     if (threadIdx.x == 0) { hdr[0] = m; hdr[1] = n; hdr[2] = s_flags; }
 }
 
-int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d)
+int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g)
 {
     int x0 = 0, y0 = 0, x1 = a.w, y1 = a.h;
     if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < a.w ? ctx->roi[2] : a.w; y1 = ctx->roi[3] < a.h ? ctx->roi[3] : a.h; }
@@ -1605,7 +1620,7 @@ int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int c
     hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, b.n_kp,
                        ctx->mw->mq_idx, ctx->mw->mt_idx, ta, x1 - x0, y1 - y0, (float)x0, (float)y0, d.q, d.t, d.X, d.uv, d.hdr,
                        cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, nt_range,
-                       slot_sparse(a) ? (const float*)a.kp_xyz : nullptr);
+                       slot_sparse(a) ? (const float*)a.kp_xyz : nullptr, g.rd_a, g.rd_b, g.max_h);
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }

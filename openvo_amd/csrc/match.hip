@@ -418,9 +418,39 @@ extern "C" int vo_clear_match_window(vo_ctx* ctx)
     return VO_OK;
 }
 
-int match_flags_check(vo_ctx* ctx, int match_flags, const char* who)
+extern "C" int vo_set_match_loop(vo_ctx* ctx, int max_hamming)
 {
-    if (match_flags & ~(VO_MATCH_CROSSCHECK | VO_MATCH_WINDOW)) return vo_fail(ctx, VO_E_ARG, "%s: bad argument (unknown match_flags bits)", who);
+    if (!ctx) return VO_E_ARG;
+    if (max_hamming < 0 || max_hamming > 256) return vo_fail(ctx, VO_E_ARG, "vo_set_match_loop: max_hamming is 0 .. 256");
+    ctx->has_loop = true; ctx->loop_max = max_hamming;
+    return VO_OK;
+}
+
+extern "C" int vo_clear_match_loop(vo_ctx* ctx)
+{
+    if (!ctx) return VO_E_ARG;
+    if (!ctx->has_loop) return vo_fail(ctx, VO_E_STATE, "vo_clear_match_loop: no threshold is set");
+    ctx->has_loop = false; ctx->loop_max = 0;
+    return VO_OK;
+}
+
+int match_loop_gate(vo_ctx* ctx, const FrameSlot& a, const FrameSlot& b, int match_flags, const char* who, LoopGate* g)
+{
+    *g = LoopGate();
+    if (!(match_flags & VO_MATCH_LOOP)) return VO_OK;      // (match_flags_check has passed: a threshold is set)
+    if (!slot_sparse(a) || !slot_sparse(b))
+        return vo_fail(ctx, VO_E_STATE, "%s: VO_MATCH_LOOP needs both slots' keypoints to carry depth (vo_sparse_stereo)", who);
+    g->rd_a = a.kp_rdesc; g->rd_b = b.kp_rdesc; g->max_h = ctx->loop_max;
+    return VO_OK;
+}
+
+int match_flags_check(vo_ctx* ctx, int match_flags, const char* who, bool loop_ok)
+{
+    if (match_flags & ~(VO_MATCH_CROSSCHECK | VO_MATCH_WINDOW | VO_MATCH_LOOP)) return vo_fail(ctx, VO_E_ARG, "%s: bad argument (unknown match_flags bits)", who);
+    if (match_flags & VO_MATCH_LOOP) {
+        if (!loop_ok) return vo_fail(ctx, VO_E_ARG, "%s: VO_MATCH_LOOP belongs to the stereo pair steps on sparse slots", who);
+        if (!ctx->has_loop) return vo_fail(ctx, VO_E_ARG, "%s: VO_MATCH_LOOP without a threshold (call vo_set_match_loop first)", who);
+    }
     if ((match_flags & VO_MATCH_WINDOW) && !ctx->has_win)
         return vo_fail(ctx, VO_E_ARG, "%s: VO_MATCH_WINDOW without a window (call vo_set_match_window first)", who);
     return VO_OK;
@@ -428,7 +458,7 @@ int match_flags_check(vo_ctx* ctx, int match_flags, const char* who)
 
 int match_knn2_slots(vo_ctx* ctx, const FrameSlot& a, const FrameSlot& b, int match_flags)
 {
-    if (int rc = match_flags_check(ctx, match_flags, "kNN of two slots")) return rc;
+    if (int rc = match_flags_check(ctx, match_flags, "kNN of two slots", true)) return rc;     // (the loop check is the prep kernel's business)
     const bool window = (match_flags & VO_MATCH_WINDOW) != 0;
     return match_knn2(ctx, a.desc, a.n_kp, b.desc, b.n_kp, ctx->mw->m_idx, ctx->mw->m_dist, match_flags & VO_MATCH_CROSSCHECK,
                       window ? a.kp_xy : nullptr, window ? b.kp_xy : nullptr, ctx->win_rx, ctx->win_ry);

@@ -415,7 +415,8 @@ static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
         auto kern = cross ? k_ratio_compact<true> : k_ratio_compact<false>;
         hipLaunchKernelGGL(kern, dim3(1), dim3(nq > 512 ? 1024 : 256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, nq, ratio, a.kp_xy, b.kp_xy,
                            ctx->mw->mq_idx, ctx->mw->mt_idx, ctx->mw->xy_a, ctx->mw->xy_b, ctx->mw->m_count,
-                           cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, cross ? b.n_kp : 0);
+                           cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, cross ? b.n_kp : 0,
+                           (const uint8_t*)nullptr, (const uint8_t*)nullptr, 0);
     }
     {
         StageTimer t(ctx, VO_T_POSE);
@@ -1603,11 +1604,13 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
     }
 }
 
-static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who)
+// lg: the loop gate of the step, as the context stands at this call (a ticket keeps it)
+static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who,
+                     LoopGate* lg)
 {
     if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v)
         return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
-    if (int rcf = match_flags_check(ctx, match_flags, who)) return rcf;
+    if (int rcf = match_flags_check(ctx, match_flags, who, true)) return rcf;
     if (iters <= 0 || iters > (1 << 22)) return vo_fail(ctx, VO_E_ARG, "%s: need 0 < iters <= 4194304", who);
     if (refine_iters < 0 || refine_iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: refine_iters is 0 .. 20", who);
     if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
@@ -1618,13 +1621,13 @@ static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const
     if (!slot_sparse(a) && (!a.has_disp || !b.has_disp)) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
     if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
     if (a.n_kp > 0 && b.n_kp < 2) return vo_fail(ctx, VO_E_ARG, "train set has fewer than 2 descriptors");
-    return VO_OK;
+    return match_loop_gate(ctx, a, b, match_flags, who, lg);
 }
 
 // the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
 // pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
 static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
-                       int refine_iters, PnpRec* rec, uint8_t* arr)
+                       int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg)
 {
     const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
@@ -1656,7 +1659,7 @@ static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, in
     }
     {
         StageTimer t(ctx, VO_T_POSE);
-        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, d))) return rc;
+        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, d, lg))) return rc;
         const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
         const float thr2 = thr * thr;
         hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d.X, d.uv, nq, K, iters, seed, d_Rt, d_P, d.hdr + 1);
@@ -1698,7 +1701,8 @@ extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, in
                            int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
 {
     if (ctx && (!counts4 || !flags || !Rt12 || !refine2)) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair: bad argument");
-    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair");
+    LoopGate lg;
+    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair", &lg);
     if (rc) return rc;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
@@ -1715,7 +1719,7 @@ extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, in
             if ((rc = xfer_flush(ctx))) return rc;
             if (!(arr = (uint8_t*)xfer_stage(ctx, bytes))) return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair: the transfer arena cannot hold %d keypoints", a.n_kp);
         }
-        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, rec, arr))) return rc;
+        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, rec, arr, lg))) return rc;
         if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
         if (!slot_sparse(a) && ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b)))) return rc;   // never a pose from an undefined disparity
     }
@@ -1728,7 +1732,8 @@ extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double rat
                                  uint32_t seed, int refine_iters, int want_matches, int* ticket_out)
 {
     if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair_begin: bad argument");
-    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair_begin");
+    LoopGate lg;
+    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair_begin", &lg);
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     FrameSlot& a = ctx->slots[slot_a];
@@ -1740,7 +1745,7 @@ extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double rat
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
         rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, (PnpRec*)p.result,
-                         want_matches ? p.result + PNP_HDR : nullptr);
+                         want_matches ? p.result + PNP_HDR : nullptr, lg);
     }
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;

@@ -7,12 +7,20 @@
 //                      ordered compaction (ballot prefix) of the surviving left keypoints from the scratch set into the slot: ONE
 //                      launch per pair (a queue entry behind other engines' kernels costs more than the two kernels it replaces)
 //   k_sparse_compact   that compaction as a launch of its own (VO_SPARSE_TWO_LAUNCHES builds only: the form k_sparse_pair is measured against)
+// The kernels are templates on the association tests (vo_set_sparse_assoc): the instantiation with none is the code without them.
+//   ratio    the wave tracks its TWO smallest keys (each lane a private best and second, two DPP minima) and accepts the winner
+//            only when it is clearly ahead of the runner-up
+//   mutual   one claim word per right keypoint: every lane lowers the word of each candidate within max_hamming to
+//            (distance << 16 | i) with a vector atomic minimum; the compaction, which runs behind every other workgroup's release,
+//            keeps keypoint i only when the word of its winner names i, and puts the words back to 0xFFFFFFFF
 // Compiled with -ffp-contract=off like the rest of the library: the float32 / float64 arithmetic below is the definition.
 #include <math.h>
 #include "vo_internal.h"
 
 #define SP_W 5     // half width of the SAD window (11 x 11)
 #define SP_L 5     // shifts -L .. L around the associated right keypoint
+#define SP_MUTUAL VO_SPARSE_MUTUAL
+#define SP_RATIO VO_SPARSE_RATIO
 
 struct SparseP {
     float min_disp, max_disp, row_tol;
@@ -54,17 +62,20 @@ __device__ __forceinline__ int sp_lower_bound(const int32_t* __restrict__ oct, i
 // octaves are non-decreasing (ORB's canonical order), so the candidates lie in one index range found by two binary searches.
 // imgL / imgR: the two crops (cw x ch, `stride` bytes per row).  xyz may be NULL (host seam: no 3-D point).
 // One wave: left keypoint i (< nl) of the keypoint sets below.  match / disp / xyz are plain pointers: k_sparse_pair reads them back
-// in the same launch behind an agent-scope acquire, and bytes handed over that way must stay off the scalar path.
+// in the same launch behind an agent-scope acquire, and bytes handed over that way must stay off the scalar path.  claim: the words
+// of the mutual test (read only with SP_MUTUAL); ratio: of the ratio test (read only with SP_RATIO).
+template <int FLAGS>
 __device__ __forceinline__ void sparse_match_one(int i, int lane, int nr,
                                                  const float* __restrict__ xy_l, const int32_t* __restrict__ oct_l, const uint8_t* __restrict__ desc_l,
                                                  const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
                                                  int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
-                                                 int cw, int ch, const SparseP& P, int32_t* match, float* disp, float* xyz)
+                                                 int cw, int ch, const SparseP& P, int32_t* match, float* disp, float* xyz,
+                                                 float ratio, uint32_t* claim)
 {
     const float nanf_ = __builtin_nanf("");
     const float xi = xy_l[2 * i], yi = xy_l[2 * i + 1];
     const int oi = oct_l[i];
-    unsigned key = 0xFFFFFFFFu;
+    unsigned key = 0xFFFFFFFFu, key2 = 0xFFFFFFFFu;      // (a real key is below 257 << 16)
     if (nr <= 65535 && (unsigned)oi < VO_ORB_LEVELS) {
         int lo = 0, hi = nr;
         if (sorted_r) { lo = sp_lower_bound(oct_r, nr, oi - 1); hi = sp_lower_bound(oct_r, nr, oi + 2); }
@@ -79,11 +90,25 @@ __device__ __forceinline__ void sparse_match_one(int i, int lane, int nr,
             const uint4 b0 = ((const uint4*)desc_r)[2 * (size_t)j], b1 = ((const uint4*)desc_r)[2 * (size_t)j + 1];
             const int dist = (__popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y)) + (__popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w)) +
                              (__popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y)) + (__popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w));
-            key = min(key, ((unsigned)dist << 16) | (unsigned)j);
+            const unsigned k = ((unsigned)dist << 16) | (unsigned)j;
+            if (FLAGS & SP_RATIO) key2 = min(key2, max(key, k));
+            key = min(key, k);
+            if ((FLAGS & SP_MUTUAL) && dist <= P.max_hamming && i <= 65535)
+                (void)__hip_atomic_fetch_min(claim + j, ((unsigned)dist << 16) | (unsigned)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        key = sp_wave_min_u32(key);
+        if (FLAGS & SP_RATIO) {
+            // the keys are distinct (j is): exactly one lane holds the wave's smallest, and the runner-up is the smallest of its
+            // second and every other lane's best
+            const unsigned k1 = sp_wave_min_u32(key);
+            key2 = sp_wave_min_u32(key == k1 ? key2 : key);
+            key = k1;
+        } else {
+            key = sp_wave_min_u32(key);
+        }
     }
-    if (key == 0xFFFFFFFFu || (int)(key >> 16) > P.max_hamming) {         // (wave-uniform from here on)
+    bool ok = key != 0xFFFFFFFFu && (int)(key >> 16) <= P.max_hamming;
+    if ((FLAGS & SP_RATIO) && ok && key2 != 0xFFFFFFFFu) ok = (float)(key >> 16) < ratio * (float)(key2 >> 16);
+    if (!ok) {                                                            // (wave-uniform from here on)
         if (lane == 0) { match[i] = -1; disp[i] = nanf_; }
         return;
     }
@@ -152,28 +177,34 @@ __device__ __forceinline__ void sparse_match_one(int i, int lane, int nr,
     }
 }
 
+template <int FLAGS>
 __global__ void __launch_bounds__(256) k_sparse_match(const int32_t* nl_p, const int32_t* nr_p, int cap,
                                                       const float* __restrict__ xy_l, const int32_t* __restrict__ oct_l, const uint8_t* __restrict__ desc_l,
                                                       const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
                                                       int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
                                                       int cw, int ch, const SparseP P, int32_t* __restrict__ match, float* __restrict__ disp,
-                                                      float* __restrict__ xyz)
+                                                      float* __restrict__ xyz, float ratio, uint32_t* claim)
 {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int nl = min(*nl_p, cap), nr = min(*nr_p, cap);
     if (i >= nl) return;
-    sparse_match_one(i, lane, nr, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, sorted_r, imgL, imgR, stride, cw, ch, P, match, disp, xyz);
+    sparse_match_one<FLAGS>(i, lane, nr, xy_l, oct_l, desc_l, xy_r, oct_r, desc_r, sorted_r, imgL, imgR, stride, cw, ch, P, match, disp, xyz,
+                            ratio, claim);
 }
 
 struct KpSet { float *xy, *size, *angle, *resp; int32_t* oct; uint8_t* desc; };
 
 // One workgroup of 256: the left keypoints whose disparity is a number move, in their order, from the scratch set into the slot (six
-// keypoint arrays, descriptors, kp_xyz, kp_disp).  rec (pinned, the slot's) = {left keypoints, accepted associations, kept, right
+// keypoint arrays, descriptors, kp_xyz, kp_disp) and the descriptor of the right keypoint each was associated with goes to dst_rdesc.
+// With SP_MUTUAL a keypoint whose winner's claim word names another left keypoint is dropped first (match -1, disparity NaN), and the
+// words are put back behind the last read.  rec (pinned, the slot's) = {left keypoints, accepted associations, kept, right
 // keypoints} -- the two counts as the extractions left them, so that the host can hold them against the capacity --; n_kp_host = kept.
-__device__ __forceinline__ void sparse_compact_block(int nl_raw, int nr_raw, int cap, const KpSet& src, const int32_t* match, const float* disp,
-                                                     const float* xyz, const KpSet& dst, float* dst_xyz, float* dst_disp, int32_t* rec,
-                                                     int32_t* n_kp_host, int* s_keep, int* s_acc)
+template <int FLAGS>
+__device__ __forceinline__ void sparse_compact_block(int nl_raw, int nr_raw, int cap, const KpSet& src, int32_t* match, float* disp,
+                                                     const float* xyz, const uint8_t* __restrict__ desc_r, const KpSet& dst, float* dst_xyz,
+                                                     float* dst_disp, uint8_t* dst_rdesc, int32_t* rec, int32_t* n_kp_host, uint32_t* claim,
+                                                     int* s_keep, int* s_acc)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nl = min(nl_raw, cap);
@@ -182,7 +213,15 @@ __device__ __forceinline__ void sparse_compact_block(int nl_raw, int nr_raw, int
         const int i = i0 + threadIdx.x;
         float d = 0.f;
         bool keep = false, got = false;
-        if (i < nl) { d = disp[i]; keep = d == d; got = match[i] >= 0; }
+        int m = -1;
+        if (i < nl) {
+            d = disp[i]; m = match[i];
+            if ((FLAGS & SP_MUTUAL) && m >= 0 && (claim[m] & 0xFFFFu) != (unsigned)i) {
+                m = -1; d = __builtin_nanf("");
+                match[i] = m; disp[i] = d;
+            }
+            keep = d == d; got = m >= 0;
+        }
         const unsigned long long bal = __ballot(keep), bag = __ballot(got);
         if (lane == 0) { s_keep[wv] = __popcll(bal); s_acc[wv] = __popcll(bag); }
         __syncthreads();
@@ -197,10 +236,16 @@ __device__ __forceinline__ void sparse_compact_block(int nl_raw, int nr_raw, int
             dst_xyz[3 * (size_t)pos] = xyz[3 * (size_t)i]; dst_xyz[3 * (size_t)pos + 1] = xyz[3 * (size_t)i + 1];
             dst_xyz[3 * (size_t)pos + 2] = xyz[3 * (size_t)i + 2];
             dst_disp[pos] = d;
+            ((uint4*)dst_rdesc)[2 * (size_t)pos] = ((const uint4*)desc_r)[2 * (size_t)m];
+            ((uint4*)dst_rdesc)[2 * (size_t)pos + 1] = ((const uint4*)desc_r)[2 * (size_t)m + 1];
         }
         base += (s_keep[0] + s_keep[1]) + (s_keep[2] + s_keep[3]);
         acc += (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
         __syncthreads();
+    }
+    if (FLAGS & SP_MUTUAL) {
+        const int nr = min(nr_raw, cap);
+        for (int j = threadIdx.x; j < nr; j += 256) __hip_atomic_store(claim + j, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x == 0) {
         __hip_atomic_store(rec + 0, nl_raw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -212,12 +257,15 @@ __device__ __forceinline__ void sparse_compact_block(int nl_raw, int nr_raw, int
 }
 
 #ifdef VO_SPARSE_TWO_LAUNCHES
-__global__ void __launch_bounds__(256) k_sparse_compact(const int32_t* nl_p, const int32_t* nr_p, int cap, const KpSet src, const int32_t* match,
-                                                        const float* disp, const float* xyz, const KpSet dst, float* dst_xyz, float* dst_disp,
-                                                        int32_t* rec, int32_t* n_kp_host)
+template <int FLAGS>
+__global__ void __launch_bounds__(256) k_sparse_compact(const int32_t* nl_p, const int32_t* nr_p, int cap, const KpSet src, int32_t* match,
+                                                        float* disp, const float* xyz, const uint8_t* __restrict__ desc_r, const KpSet dst,
+                                                        float* dst_xyz, float* dst_disp, uint8_t* dst_rdesc, int32_t* rec, int32_t* n_kp_host,
+                                                        uint32_t* claim)
 {
     __shared__ int s_lds[8];
-    sparse_compact_block(*nl_p, *nr_p, cap, src, match, disp, xyz, dst, dst_xyz, dst_disp, rec, n_kp_host, s_lds, s_lds + 4);
+    sparse_compact_block<FLAGS>(*nl_p, *nr_p, cap, src, match, disp, xyz, desc_r, dst, dst_xyz, dst_disp, dst_rdesc, rec, n_kp_host, claim,
+                                s_lds, s_lds + 4);
 }
 #endif
 
@@ -226,12 +274,16 @@ __global__ void __launch_bounds__(256) k_sparse_compact(const int32_t* nl_p, con
 // arrive and compacts.  Nothing waits and nothing polls.  The hand-off is agent-scope release / acquire in its counter form: every
 // wave drains its stores, the workgroup meets, lane 0 releases (fence, then the wait the fence may not carry itself) and adds to the
 // ticket; the last arriver acquires, waits, the workgroup meets again and reads match / disp / xyz with plain vector loads.  The
-// ticket reads zero before the first launch (sparse_ws_prepare) and the last arriver puts it back.
+// ticket reads zero before the first launch (sparse_ws_prepare) and the last arriver puts it back.  The claim words of the mutual test
+// travel the same way: atomics at agent scope, drained by every wave's wait before the release, read with plain vector loads behind
+// the acquire.
+template <int FLAGS>
 __global__ void __launch_bounds__(256) k_sparse_pair(const int32_t* nl_p, const int32_t* nr_p, int cap, const KpSet src,
                                                      const float* __restrict__ xy_r, const int32_t* __restrict__ oct_r, const uint8_t* __restrict__ desc_r,
                                                      int sorted_r, const uint8_t* __restrict__ imgL, const uint8_t* __restrict__ imgR, int stride,
                                                      int cw, int ch, const SparseP P, int32_t* match, float* disp, float* xyz, const KpSet dst,
-                                                     float* dst_xyz, float* dst_disp, int32_t* rec, int32_t* n_kp_host, int32_t* ticket)
+                                                     float* dst_xyz, float* dst_disp, uint8_t* dst_rdesc, int32_t* rec, int32_t* n_kp_host,
+                                                     int32_t* ticket, float ratio, uint32_t* claim)
 {
     __shared__ int s_lds[12];           // ONE LDS object: the compaction's per-wave counts [0 .. 7] and "I am last" [8]
     const int lane = threadIdx.x & 63;
@@ -239,7 +291,8 @@ __global__ void __launch_bounds__(256) k_sparse_pair(const int32_t* nl_p, const 
     const int nl_raw = *nl_p, nr_raw = *nr_p;
     const int nl = min(nl_raw, cap), nr = min(nr_raw, cap);
     if (i < nl)
-        sparse_match_one(i, lane, nr, src.xy, src.oct, src.desc, xy_r, oct_r, desc_r, sorted_r, imgL, imgR, stride, cw, ch, P, match, disp, xyz);
+        sparse_match_one<FLAGS>(i, lane, nr, src.xy, src.oct, src.desc, xy_r, oct_r, desc_r, sorted_r, imgL, imgR, stride, cw, ch, P, match, disp,
+                                xyz, ratio, claim);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -255,7 +308,8 @@ __global__ void __launch_bounds__(256) k_sparse_pair(const int32_t* nl_p, const 
     }
     __syncthreads();
     if (!s_lds[8]) return;
-    sparse_compact_block(nl_raw, nr_raw, cap, src, match, disp, xyz, dst, dst_xyz, dst_disp, rec, n_kp_host, s_lds, s_lds + 4);
+    sparse_compact_block<FLAGS>(nl_raw, nr_raw, cap, src, match, disp, xyz, desc_r, dst, dst_xyz, dst_disp, dst_rdesc, rec, n_kp_host, claim,
+                                s_lds, s_lds + 4);
     if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -275,25 +329,62 @@ static int sparse_params(vo_ctx* ctx, float min_disp, float max_disp, float row_
     return VO_OK;
 }
 
+// 0 < ratio <= 1 (finite) with VO_SPARSE_RATIO; the ratio of a request without that bit is stored as 0 (it is never read)
+static int sparse_assoc_check(vo_ctx* ctx, int flags, float* ratio, const char* who)
+{
+    if (flags & ~(VO_SPARSE_MUTUAL | VO_SPARSE_RATIO)) return vo_fail(ctx, VO_E_ARG, "%s: association flags %d (bits 0 and 1 only)", who, flags);
+    if (!(flags & VO_SPARSE_RATIO)) { *ratio = 0.f; return VO_OK; }
+    if (!(*ratio > 0.f) || !(*ratio <= 1.f)) return vo_fail(ctx, VO_E_ARG, "%s: the association ratio must satisfy 0 < ratio <= 1", who);
+    return VO_OK;
+}
+
+extern "C" int vo_set_sparse_assoc(vo_ctx* ctx, int flags, float ratio)
+{
+    if (!ctx) return VO_E_ARG;
+    if (int rc = sparse_assoc_check(ctx, flags, &ratio, "vo_set_sparse_assoc")) return rc;
+    ctx->sp_assoc_flags = flags; ctx->sp_assoc_ratio = ratio;
+    return VO_OK;
+}
+
+// the one launch of a pair, in the instantiation the request's association tests name
+#define SP_PAIR_ARGS(FL) hipLaunchKernelGGL(k_sparse_pair<FL>, dim3(grid), dim3(256), 0, stream, nl_p, nr_p, cap, src, r.kp_xy, r.kp_oct, r.desc, sorted_r, \
+                                            imgL, imgR, stride, cw, ch, P, ws.match, ws.disp, ws.xyz, dst, dst_xyz, dst_disp, dst_rdesc, rec, n_kp_host,      \
+                                            ws.ticket, ratio, ws.claim)
+static void sparse_pair_launch(int flags, float ratio, int grid, hipStream_t stream, const int32_t* nl_p, const int32_t* nr_p, int cap, const KpSet& src,
+                               const FrameSlot& r, int sorted_r, const uint8_t* imgL, const uint8_t* imgR, int stride, int cw, int ch, const SparseP& P,
+                               SparseWs& ws, const KpSet& dst, float* dst_xyz, float* dst_disp, uint8_t* dst_rdesc, int32_t* rec, int32_t* n_kp_host)
+{
+    switch (flags & 3) {
+    case 0: SP_PAIR_ARGS(0); break;
+    case 1: SP_PAIR_ARGS(1); break;
+    case 2: SP_PAIR_ARGS(2); break;
+    default: SP_PAIR_ARGS(3); break;
+    }
+}
+#undef SP_PAIR_ARGS
+
 static KpSet kp_set(const FrameSlot& f) { return KpSet{ f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc }; }
 
 int sparse_req_check(vo_ctx* ctx, const SparseReq& q, const char* who)
 {
     if (q.nfeatures < 0 || q.nfeatures > ctx->max_kp) return vo_fail(ctx, VO_E_CAP, "nfeatures %d exceeds max_kp %d", q.nfeatures, ctx->max_kp);
     SparseP P;
-    return sparse_params(ctx, q.min_disp, q.max_disp, q.row_tol, q.max_hamming, who, &P);
+    if (int rc = sparse_params(ctx, q.min_disp, q.max_disp, q.row_tol, q.max_hamming, who, &P)) return rc;
+    float ratio = q.assoc_ratio;
+    return sparse_assoc_check(ctx, q.assoc_flags, &ratio, who);
 }
 
 static bool sparse_req_same(const SparseReq& a, const SparseReq& b)
 {
     // (bit patterns: -0.f and 0.f are two requests, which only costs a recomputation)
     return a.nfeatures == b.nfeatures && a.max_hamming == b.max_hamming && !memcmp(&a.min_disp, &b.min_disp, sizeof(float)) &&
-           !memcmp(&a.max_disp, &b.max_disp, sizeof(float)) && !memcmp(&a.row_tol, &b.row_tol, sizeof(float));
+           !memcmp(&a.max_disp, &b.max_disp, sizeof(float)) && !memcmp(&a.row_tol, &b.row_tol, sizeof(float)) &&
+           a.assoc_flags == b.assoc_flags && !memcmp(&a.assoc_ratio, &b.assoc_ratio, sizeof(float));
 }
 
 void sparse_ws_free(SparseWs& ws)
 {
-    void* ps[] = { ws.match, ws.disp, ws.xyz, ws.ticket };
+    void* ps[] = { ws.match, ws.disp, ws.xyz, ws.ticket, ws.claim };
     for (void* p : ps) if (p) (void)hipFree(p);
     orb_ws_free(ws.orb_r);
     if (ws.own) {
@@ -327,10 +418,12 @@ int sparse_ws_prepare(vo_ctx* ctx, SparseWs& ws, hipStream_t stream, bool own_se
     }
     if (e == hipSuccess && with_orb && !ws.orb_ready && orb_ws_alloc(ctx, ws.orb_r)) e = hipErrorOutOfMemory;
     take((void**)&ws.match, cap * 4); take((void**)&ws.disp, cap * 4); take((void**)&ws.xyz, cap * 12);
-    take((void**)&ws.ticket, 64);
-    // the ticket must read zero before the first launch on WHATEVER stream that is: cleared on that stream, and waited for
+    take((void**)&ws.ticket, 64); take((void**)&ws.claim, cap * 4);
+    // the ticket must read zero, and every claim word 0xFFFFFFFF, before the first launch on WHATEVER stream that is: set on that
+    // stream, and waited for
     if (e == hipSuccess && !ws.ready) {
         e = hipMemsetAsync(ws.ticket, 0, 64, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(ws.claim, 0xFF, cap * 4, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
     }
     if (e != hipSuccess) {
@@ -370,29 +463,40 @@ int sparse_enqueue(vo_ctx* ctx, FrameSlot& f, SparseWs& ws, const SparseReq& q)
     P.x0f = (float)x0; P.y0f = (float)y0;
     StageTimer t(ctx, VO_T_MATCH);
 #ifdef VO_SPARSE_TWO_LAUNCHES
-    hipLaunchKernelGGL(k_sparse_match, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap,
-                       sl.kp_xy, sl.kp_oct, sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, 1, f.left + off, f.right + off, f.w, cw, ch, P,
-                       ws.match, ws.disp, ws.xyz);
-    VO_CHECK_LAUNCH(ctx);
-    hipLaunchKernelGGL(k_sparse_compact, dim3(1), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl), ws.match, ws.disp,
-                       ws.xyz, kp_set(f), f.kp_xyz, f.kp_disp, f.sp_rec, f.n_kp_host);
+#define SP_TWO(FL)                                                                                                                                   \
+    do {                                                                                                                                              \
+        hipLaunchKernelGGL(k_sparse_match<FL>, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap,      \
+                           sl.kp_xy, sl.kp_oct, sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, 1, f.left + off, f.right + off, f.w, cw, ch, P,                 \
+                           ws.match, ws.disp, ws.xyz, q.assoc_ratio, ws.claim);                                                                       \
+        VO_CHECK_LAUNCH(ctx);                                                                                                                         \
+        hipLaunchKernelGGL(k_sparse_compact<FL>, dim3(1), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl), ws.match,   \
+                           ws.disp, ws.xyz, sr.desc, kp_set(f), f.kp_xyz, f.kp_disp, f.kp_rdesc, f.sp_rec, f.n_kp_host, ws.claim);                    \
+    } while (0)
+    switch (q.assoc_flags & 3) {
+    case 0: SP_TWO(0); break;
+    case 1: SP_TWO(1); break;
+    case 2: SP_TWO(2); break;
+    default: SP_TWO(3); break;
+    }
+#undef SP_TWO
 #else
-    hipLaunchKernelGGL(k_sparse_pair, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl),
-                       sr.kp_xy, sr.kp_oct, sr.desc, 1, f.left + off, f.right + off, f.w, cw, ch, P, ws.match, ws.disp, ws.xyz, kp_set(f),
-                       f.kp_xyz, f.kp_disp, f.sp_rec, f.n_kp_host, ws.ticket);
+    sparse_pair_launch(q.assoc_flags, q.assoc_ratio, div_up(ctx->kp_cap, 4), ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl), sr, 1,
+                       f.left + off, f.right + off, f.w, cw, ch, P, ws, kp_set(f), f.kp_xyz, f.kp_disp, f.kp_rdesc, f.sp_rec, f.n_kp_host);
 #endif
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }
 
 // the chain into the slot has finished and the host has waited for it: today's checks from the slot's record, then the slot's state
-static int sparse_collect(vo_ctx* ctx, FrameSlot& f, int32_t* counts3)
+static int sparse_collect(vo_ctx* ctx, FrameSlot& f, int32_t* counts3, int assoc_flags)
 {
     const volatile int32_t* rec = f.sp_rec;
     const int nl = rec[0], nr = rec[3];
     if (nl > ctx->kp_cap || nr > ctx->kp_cap)
         return vo_fail(ctx, VO_E_CAP, "%d / %d keypoints (response ties included) exceed capacity %d; raise max_kp", nl, nr, ctx->kp_cap);
     if (nr > 65535) return vo_fail(ctx, VO_E_CAP, "vo_sparse_stereo: %d right keypoints (at most 65535)", nr);
+    if ((assoc_flags & VO_SPARSE_MUTUAL) && nl > 65535)
+        return vo_fail(ctx, VO_E_CAP, "vo_sparse_stereo: %d left keypoints with the mutual test (at most 65535)", nl);
     counts3[0] = rec[0]; counts3[1] = rec[1]; counts3[2] = rec[2];
     f.n_kp = rec[2];
     f.has_kp = true; f.kp_depth = true;
@@ -403,7 +507,7 @@ extern "C" int vo_sparse_stereo(vo_ctx* ctx, int slot, int nfeatures, float min_
                                 int32_t* counts3)
 {
     if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS || !counts3) return vo_fail(ctx, VO_E_ARG, "vo_sparse_stereo: bad argument");
-    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming, ctx->sp_assoc_flags, ctx->sp_assoc_ratio };
     if (int rcq = sparse_req_check(ctx, q, "vo_sparse_stereo")) return rcq;
     FrameSlot& f = ctx->slots[slot];
     if (!f.has_pair) return vo_fail(ctx, VO_E_STATE, "slot %d holds no image pair", slot);
@@ -417,7 +521,7 @@ extern "C" int vo_sparse_stereo(vo_ctx* ctx, int slot, int nfeatures, float min_
         VO_HIP(ctx, hipEventSynchronize(f.ready));
         if (f.pending && f.counted && ctx->inflight > 0) ctx->inflight--;
         f.pending = false; f.counted = false;
-        if ((rc = sparse_collect(ctx, f, counts3))) return rc;
+        if ((rc = sparse_collect(ctx, f, counts3, q.assoc_flags))) return rc;
         f.sp_ahead = true;
         return VO_OK;
     }
@@ -437,7 +541,7 @@ extern "C" int vo_sparse_stereo(vo_ctx* ctx, int slot, int nfeatures, float min_
     if ((rc = sparse_enqueue(ctx, f, ctx->sp_main, q))) return rc;
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the one synchronisation
     f.sp_req = q;
-    return sparse_collect(ctx, f, counts3);
+    return sparse_collect(ctx, f, counts3, q.assoc_flags);
 }
 
 extern "C" int vo_download_keypoint_depth(vo_ctx* ctx, int slot, float* xyz, float* disp, int cap, int* n_out)
@@ -455,6 +559,21 @@ extern "C" int vo_download_keypoint_depth(vo_ctx* ctx, int slot, float* xyz, flo
     if (xyz) rc = xfer_d2h(ctx, xyz, f.kp_xyz, (size_t)n * 12);
     if (disp && !rc) rc = xfer_d2h(ctx, disp, f.kp_disp, (size_t)n * 4);
     if (rc) return rc;
+    return xfer_flush(ctx);
+}
+
+extern "C" int vo_download_keypoint_rdesc(vo_ctx* ctx, int slot, uint8_t* rdesc, int cap, int* n_out)
+{
+    if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS) return vo_fail(ctx, VO_E_ARG, "vo_download_keypoint_rdesc: bad slot");
+    FrameSlot& f = ctx->slots[slot];
+    if (!slot_sparse(f)) return vo_fail(ctx, VO_E_STATE, "slot %d: the keypoints carry no depth (vo_sparse_stereo)", slot);
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    { int rcw = slot_wait(ctx, f); if (rcw) return rcw; }
+    const int n = f.n_kp;
+    if (n_out) *n_out = n;
+    if (n == 0 || !rdesc) return VO_OK;
+    if (n > cap) return vo_fail(ctx, VO_E_CAP, "%d keypoints exceed the output capacity %d", n, cap);
+    if (int rc = xfer_d2h(ctx, rdesc, f.kp_rdesc, (size_t)n * 32)) return rc;
     return xfer_flush(ctx);
 }
 
@@ -494,8 +613,9 @@ extern "C" int vo_sparse_match_host(vo_ctx* ctx, const uint8_t* left, const uint
     if (rc) return rc;
     sl.has_kp = false; sl.kp_depth = false;
     *sl.n_kp_host = nl; *sr.n_kp_host = nr;
-    hipLaunchKernelGGL(k_sparse_match, dim3(div_up(nl, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, sl.kp_xy, sl.kp_oct,
-                       sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, sorted_r, sl.left, sl.right, w, w, h, P, ctx->sp_main.match, ctx->sp_main.disp, (float*)nullptr);
+    hipLaunchKernelGGL(k_sparse_match<0>, dim3(div_up(nl, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, sl.kp_xy, sl.kp_oct,
+                       sl.desc, sr.kp_xy, sr.kp_oct, sr.desc, sorted_r, sl.left, sl.right, w, w, h, P, ctx->sp_main.match, ctx->sp_main.disp, (float*)nullptr,
+                       0.f, (uint32_t*)nullptr);
     VO_CHECK_LAUNCH(ctx);
     rc = xfer_d2h(ctx, match_out, ctx->sp_main.match, (size_t)nl * 4);
     if (!rc) rc = xfer_d2h(ctx, disp_out, ctx->sp_main.disp, (size_t)nl * 4);
@@ -506,16 +626,20 @@ extern "C" int vo_sparse_match_host(vo_ctx* ctx, const uint8_t* left, const uint
 // k_sparse_pair alone on host arrays (the seam its tests use): vo_sparse_match_host's inputs plus Q and the ROI origin; the survivors
 // are compacted from the scratch set into a destination of their own (never the source) and come back with their disparity and 3-D
 // point.  The scratch set's size / angle / response are whatever an earlier call left there: they travel, nobody reads them.
-extern "C" int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l,
+// The association tests are arguments here: the context's state is neither read nor changed.
+extern "C" int vo_sparse_pair_host_ex(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l,
                                    const int32_t* oct_l, const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r,
                                    const uint8_t* desc_r, int nr, float min_disp, float max_disp, float row_tol, int max_hamming,
-                                   const double* Q16, int roi_x0, int roi_y0, int32_t* match_out, float* disp_out, float* kp_xy,
-                                   int32_t* kp_octave, uint8_t* desc, float* kp_disp, float* kp_xyz, int32_t* counts3)
+                                   int assoc_flags, float assoc_ratio, const double* Q16, int roi_x0, int roi_y0, int32_t* match_out,
+                                   float* disp_out, float* kp_xy, int32_t* kp_octave, uint8_t* desc, float* kp_disp, float* kp_xyz,
+                                   uint8_t* kp_rdesc, int32_t* counts3)
 {
     if (!ctx || !left || !right || w <= 0 || h <= 0 || nl < 0 || nr < 0 || !Q16 || !counts3) return vo_fail(ctx, VO_E_ARG, "vo_sparse_pair_host: bad argument");
     if (w > ctx->max_w || h > ctx->max_h) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context", w, h);
     if (nr > 65535) return vo_fail(ctx, VO_E_CAP, "vo_sparse_pair_host: %d right keypoints (at most 65535)", nr);
     if (nl > ctx->kp_cap || nr > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "%d / %d keypoints exceed capacity %d", nl, nr, ctx->kp_cap);
+    if (int rca = sparse_assoc_check(ctx, assoc_flags, &assoc_ratio, "vo_sparse_pair_host")) return rca;
+    if ((assoc_flags & VO_SPARSE_MUTUAL) && nl > 65535) return vo_fail(ctx, VO_E_CAP, "vo_sparse_pair_host: %d left keypoints with the mutual test (at most 65535)", nl);
     if ((nl > 0 && (!xy_l || !oct_l || !desc_l || !match_out || !disp_out || !kp_xy || !kp_octave || !desc || !kp_disp || !kp_xyz)) ||
         (nr > 0 && (!xy_r || !oct_r || !desc_r)))
         return vo_fail(ctx, VO_E_ARG, "vo_sparse_pair_host: null pointer");
@@ -537,12 +661,13 @@ extern "C" int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8
     // the destination: one allocation cut into the keypoint arrays (a test seam: allocated and freed per call)
     const size_t cap = ((size_t)ctx->kp_cap + 63) & ~(size_t)63;
     uint8_t* d = nullptr;
-    VO_HIP(ctx, hipMalloc((void**)&d, cap * (8 + 4 + 4 + 4 + 4 + 32 + 12 + 4) + 256));
+    VO_HIP(ctx, hipMalloc((void**)&d, cap * (8 + 4 + 4 + 4 + 4 + 32 + 12 + 4 + 32) + 256));
     KpSet dst;
     dst.xy = (float*)d; dst.size = (float*)(d + cap * 8); dst.angle = (float*)(d + cap * 12); dst.resp = (float*)(d + cap * 16);
     dst.oct = (int32_t*)(d + cap * 20); dst.desc = d + cap * 24;
     float* const dst_xyz = (float*)(d + cap * 56);
     float* const dst_disp = (float*)(d + cap * 68);
+    uint8_t* const dst_rdesc = d + cap * 72;
     const size_t npx = (size_t)w * h;
     int rc = VO_OK;
     do {
@@ -557,9 +682,8 @@ extern "C" int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8
         sl.has_kp = false; sl.kp_depth = false;
         *sl.n_kp_host = nl; *sr.n_kp_host = nr;
         // (the product's grid: every workgroup draws a ticket, most of them with no keypoint of their own)
-        hipLaunchKernelGGL(k_sparse_pair, dim3(div_up(ctx->kp_cap, 4)), dim3(256), 0, ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl),
-                           sr.kp_xy, sr.kp_oct, sr.desc, sorted_r, sl.left, sl.right, w, w, h, P, ws.match, ws.disp, ws.xyz, dst, dst_xyz, dst_disp,
-                           sl.sp_rec, sl.n_kp_host, ws.ticket);
+        sparse_pair_launch(assoc_flags, assoc_ratio, div_up(ctx->kp_cap, 4), ctx->stream, sl.n_kp_host, sr.n_kp_host, ctx->kp_cap, kp_set(sl), sr,
+                           sorted_r, sl.left, sl.right, w, w, h, P, ws, dst, dst_xyz, dst_disp, dst_rdesc, sl.sp_rec, sl.n_kp_host);
         if (hipGetLastError() != hipSuccess) { rc = vo_fail(ctx, VO_E_HIP, "vo_sparse_pair_host: launch failed"); break; }
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = vo_fail(ctx, VO_E_HIP, "vo_sparse_pair_host: the launch failed"); break; }
         const volatile int32_t* rec = sl.sp_rec;
@@ -573,9 +697,20 @@ extern "C" int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8
         if ((rc = xfer_d2h(ctx, desc, dst.desc, (size_t)n * 32))) break;
         if ((rc = xfer_d2h(ctx, kp_disp, dst_disp, (size_t)n * 4))) break;
         if ((rc = xfer_d2h(ctx, kp_xyz, dst_xyz, (size_t)n * 12))) break;
+        if (kp_rdesc && (rc = xfer_d2h(ctx, kp_rdesc, dst_rdesc, (size_t)n * 32))) break;
         rc = xfer_flush(ctx);
     } while (0);
     if (rc) (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
     return rc;
+}
+
+extern "C" int vo_sparse_pair_host(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, const float* xy_l,
+                                   const int32_t* oct_l, const uint8_t* desc_l, int nl, const float* xy_r, const int32_t* oct_r,
+                                   const uint8_t* desc_r, int nr, float min_disp, float max_disp, float row_tol, int max_hamming,
+                                   const double* Q16, int roi_x0, int roi_y0, int32_t* match_out, float* disp_out, float* kp_xy,
+                                   int32_t* kp_octave, uint8_t* desc, float* kp_disp, float* kp_xyz, int32_t* counts3)
+{
+    return vo_sparse_pair_host_ex(ctx, left, right, w, h, xy_l, oct_l, desc_l, nl, xy_r, oct_r, desc_r, nr, min_disp, max_disp, row_tol, max_hamming,
+                                  0, 0.f, Q16, roi_x0, roi_y0, match_out, disp_out, kp_xy, kp_octave, desc, kp_disp, kp_xyz, nullptr, counts3);
 }

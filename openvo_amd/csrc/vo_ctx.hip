@@ -194,7 +194,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         DALLOC(f.kp_xy, (size_t)ctx->kp_cap * 2); DALLOC(f.kp_size, ctx->kp_cap); DALLOC(f.kp_angle, ctx->kp_cap);
         DALLOC(f.kp_resp, ctx->kp_cap); DALLOC(f.kp_oct, ctx->kp_cap); DALLOC(f.desc, (size_t)ctx->kp_cap * 32);
         DALLOC(f.mono_depth, ctx->kp_cap); DALLOC(f.mono_serial_dev, 16);
-        DALLOC(f.kp_xyz, (size_t)ctx->kp_cap * 3); DALLOC(f.kp_disp, ctx->kp_cap);
+        DALLOC(f.kp_xyz, (size_t)ctx->kp_cap * 3); DALLOC(f.kp_disp, ctx->kp_cap); DALLOC(f.kp_rdesc, (size_t)ctx->kp_cap * 32);
         if (dev_zero(f.mono_serial_dev, 64) != hipSuccess) { g_create_err = "clearing a slot's depth serial failed"; vo_destroy(ctx); return VO_E_HIP; }
     }
     {
@@ -287,7 +287,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     for (int s = 0; s <= VO_NUM_SLOTS; s++) {
         FrameSlot& f = ctx->slots[s];
         void* ps[] = { f.left, f.right, f.disp16, f.kp_xy, f.kp_size, f.kp_angle, f.kp_resp, f.kp_oct, f.desc, f.mono_depth, f.mono_serial_dev,
-                       f.kp_xyz, f.kp_disp };
+                       f.kp_xyz, f.kp_disp, f.kp_rdesc };
         for (void* p : ps) if (p) (void)hipFree(p);
         if (f.ready) (void)hipEventDestroy(f.ready);
     }
@@ -855,7 +855,7 @@ extern "C" int vo_prefetch_staged_pair_sparse(vo_ctx* ctx, int slot, int index, 
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     if (index < 0 || index >= ctx->staged_n) return vo_fail(ctx, VO_E_ARG, "vo_prefetch_staged_pair_sparse: bad index");
-    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming, ctx->sp_assoc_flags, ctx->sp_assoc_ratio };
     if ((rc = sparse_entry_check(ctx, q, "vo_prefetch_staged_pair_sparse"))) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t per = (size_t)ctx->staged_w * ctx->staged_h * ctx->staged_ch;
@@ -870,7 +870,7 @@ extern "C" int vo_prefetch_pair_sparse(vo_ctx* ctx, int slot, const uint8_t* lef
     if (rc) return rc;
     if (!left || !right || (channels != 1 && channels != 3)) return vo_fail(ctx, VO_E_ARG, "vo_prefetch_pair_sparse: bad argument");
     if (w > ctx->max_w || h > ctx->max_h || w < 16 || h < 16) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context %dx%d", w, h, ctx->max_w, ctx->max_h);
-    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming, ctx->sp_assoc_flags, ctx->sp_assoc_ratio };
     if ((rc = sparse_entry_check(ctx, q, "vo_prefetch_pair_sparse"))) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     return prefetch_pair(ctx, slot, left, right, true, w, h, channels, preprocessed, nullptr, &q);
@@ -883,7 +883,7 @@ extern "C" int vo_prefetch_host_staged_sparse(vo_ctx* ctx, int slot, int buf, in
     if (rc) return rc;
     if (buf < 0 || buf >= vo_ctx::N_HOST_STAGE || (channels != 1 && channels != 3)) return vo_fail(ctx, VO_E_ARG, "vo_prefetch_host_staged_sparse: bad argument");
     if (w > ctx->max_w || h > ctx->max_h || w < 16 || h < 16) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context %dx%d", w, h, ctx->max_w, ctx->max_h);
-    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming };
+    const SparseReq q = { nfeatures, min_disp, max_disp, row_tol, max_hamming, ctx->sp_assoc_flags, ctx->sp_assoc_ratio };
     if ((rc = sparse_entry_check(ctx, q, "vo_prefetch_host_staged_sparse"))) return rc;
     vo_ctx::HostStage& hs = ctx->host_stage[buf];
     if (!hs.pinned) return vo_fail(ctx, VO_E_STATE, "staging buffer %d has not been filled (vo_host_stage_pair / vo_host_stage_begin)", buf);

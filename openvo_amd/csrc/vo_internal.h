@@ -76,6 +76,9 @@ struct FrameSlot {
     float* kp_xyz = nullptr;
     float* kp_disp = nullptr;
     bool kp_depth = false;
+    // ... and the descriptor (32 bytes) of the RIGHT keypoint each of them was associated with: valid exactly while kp_depth is
+    // (its x is the keypoint's x - kp_disp); the loop check of the pair steps reads it
+    uint8_t* kp_rdesc = nullptr;
     // sparse stereo begun ahead (vo_prefetch_*_sparse): the whole chain was enqueued on a look-ahead engine's stream with the request
     // sp_req, and the slot's pinned record sp_rec = {left keypoints, accepted, kept, right keypoints} (the two extractions' counts as
     // they left them, unclamped) is written by its last kernel; vo_sparse_stereo with the same request only waits for `ready` and
@@ -85,7 +88,8 @@ struct FrameSlot {
     bool sp_pending = false;
     bool sp_ahead = false;       // the sparse result the slot holds was begun ahead and has been collected: the same request again returns its counts
                                  // (never set by a synchronous computation, which always recomputes; voided by vo_set_Q / vo_set_roi)
-    struct SparseReq { int nfeatures; float min_disp, max_disp, row_tol; int max_hamming; } sp_req = {-1, 0.f, 0.f, 0.f, 0};
+    // assoc_flags / assoc_ratio: the association tests in force when the chain was enqueued (vo_set_sparse_assoc): part of the request
+    struct SparseReq { int nfeatures; float min_disp, max_disp, row_tol; int max_hamming; int assoc_flags; float assoc_ratio; } sp_req = {-1, 0.f, 0.f, 0.f, 0, 0, 0.f};
     // the slot's look-ahead run is a member of the context's open sweep group: its diagonal sweep, post filters and ORB chain are
     // not enqueued and `ready` is NOT recorded for this run yet -- whoever is about to wait on, read, refill or drop the slot
     // closes the group first (sweep_group_close_for)
@@ -104,7 +108,8 @@ struct OrbWs {
 // Scratch of one sparse stereo chain (sparse.hip): the two extractions' keypoint sets, each with its pinned count word (keypoint
 // arrays and n_kp_host of a FrameSlot, nothing else), the ORB scratch of the second extraction (the first runs in the scratch the
 // context works in: *ctx->orbws), per left keypoint the associated right keypoint (-1: none), the refined disparity (NaN: rejected)
-// and its 3-D position, and the ticket word of k_sparse_pair (zero between launches).  The context owns one for its main stream
+// and its 3-D position, the ticket word of k_sparse_pair (zero between launches) and one claim word per right keypoint for the mutual
+// test (0xFFFFFFFF between launches: set once by sparse_ws_prepare, put back by the launch that used them).  The context owns one for its main stream
 // (l / r: the scratch slot of the *_host seams and sparse_r) and one per look-ahead engine, each completed at its first sparse use
 // (sparse_ws_prepare) and freed by vo_destroy.
 struct SparseWs {
@@ -113,6 +118,7 @@ struct SparseWs {
     int32_t* match = nullptr;
     float *disp = nullptr, *xyz = nullptr;
     int32_t* ticket = nullptr;
+    uint32_t* claim = nullptr;       // kp_cap words
     FrameSlot* own = nullptr;        // an engine's two sets (the main one borrows the context's)
     int32_t* own_words = nullptr;    // ... and their pinned count words
     bool ready = false, orb_ready = false;
@@ -265,6 +271,12 @@ struct vo_ctx {
     // the match window of VO_MATCH_WINDOW (vo_set_match_window): read when a step is ENQUEUED and handed to the kernel by value
     bool has_win = false;
     float win_rx = 0.f, win_ry = 0.f;
+    // the loop check of VO_MATCH_LOOP (vo_set_match_loop): read when a step is ENQUEUED and handed to the kernel by value
+    bool has_loop = false;
+    int loop_max = 0;
+    // the association tests of the sparse stereo chain (vo_set_sparse_assoc): read when a chain is ENQUEUED, kept in the slot's request
+    int sp_assoc_flags = 0;
+    float sp_assoc_ratio = 0.f;
     uint8_t* mq = nullptr;
     uint8_t* mt = nullptr;
     double* red = nullptr;         // reduction scratch
@@ -456,10 +468,11 @@ __device__ __forceinline__ double wave_sum_f64_dpp(double v)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 // CROSS: a match must also pass the cross-check (knn_mutual on the column words of the same kNN launch)
+// rd_q / rd_t (both or neither) + loop_max: the loop check -- the right partners' descriptors of the two slots (kp_rdesc)
 template <bool CROSS>
 __global__ void k_ratio_compact(const int32_t* idx, const int32_t* dist, int nq, double ratio, const float* xy_q, const float* xy_t,
                                 int32_t* q_out, int32_t* t_out, float* xyq_out, float* xyt_out, int32_t* m_out,
-                                const uint32_t* colmin, int nt);   // pose / clique scratch for nq query keypoints
+                                const uint32_t* colmin, int nt, const uint8_t* rd_q, const uint8_t* rd_t, int loop_max);   // pose / clique scratch for nq query keypoints
 
 // implemented in the per-stage files
 // f.left, f.right (w x h) -> f.disp16; gives the run its generation.  srcL / srcR (both or neither): the rectified gray pair lies
@@ -527,7 +540,23 @@ void match_ws_free(vo_ctx::MatchWs& m);
 int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx,
                int32_t* d_dist, int cross = 0, const float* xy_q = nullptr, const float* xy_t = nullptr, float rx = 0.f, float ry = 0.f);
 // match_flags of an _ex / fused entry: VO_E_ARG for an unknown bit, and for VO_MATCH_WINDOW while the context has no window
-int match_flags_check(vo_ctx* ctx, int match_flags, const char* who);
+// loop_ok: the entry takes VO_MATCH_LOOP (the stereo pair steps; everywhere else the bit is VO_E_ARG)
+int match_flags_check(vo_ctx* ctx, int match_flags, const char* who, bool loop_ok = false);
+// The loop check of a stereo pair step (VO_MATCH_LOOP): a match (q, t) is kept only when the right partners of q and t -- the
+// slots' kp_rdesc -- are within max_h bits of each other.  Without the flag the pointers are NULL and the kernels run the
+// instructions they ran before it existed, behind one uniform branch.
+struct LoopGate { const uint8_t *rd_a = nullptr, *rd_b = nullptr; int max_h = 0; };
+// -> the gate of a step on slots a and b as the context stands now (the threshold travels by value: a step begun ahead keeps
+// it); VO_E_STATE when the flag is set and a slot's keypoints carry no depth
+int match_loop_gate(vo_ctx* ctx, const FrameSlot& a, const FrameSlot& b, int match_flags, const char* who, LoopGate* g);
+__device__ __forceinline__ bool loop_pass(const uint8_t* __restrict__ rd_q, const uint8_t* __restrict__ rd_t, int q, int t, int loop_max)
+{
+    const uint4 a0 = ((const uint4*)rd_q)[2 * (size_t)q], a1 = ((const uint4*)rd_q)[2 * (size_t)q + 1];
+    const uint4 b0 = ((const uint4*)rd_t)[2 * (size_t)t], b1 = ((const uint4*)rd_t)[2 * (size_t)t + 1];
+    const int d = (__popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y)) + (__popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w)) +
+                  (__popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y)) + (__popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w));
+    return d <= loop_max;
+}
 // the kNN-2 of a pair step into the current match scratch: slot a's descriptors against slot b's; with VO_MATCH_WINDOW inside
 // the context's window around the two slots' keypoint positions
 int match_knn2_slots(vo_ctx* ctx, const FrameSlot& a, const FrameSlot& b, int match_flags);
@@ -549,7 +578,7 @@ static inline size_t pnp_cap(int kp_cap) { return ((size_t)kp_cap + 15) & ~(size
 // device scratch of one step behind the RANSAC arrays: hdr {M, n, flags}, the n usable correspondences in match order
 struct PnpDev { int32_t *hdr, *q, *t; float *X, *uv; };
 // kNN-2 is done (m_idx / m_dist of the current match scratch): ratio test (+ cross-check), 3-D lookup in slot a, compaction
-int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d);
+int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g);
 
 // ---- asynchronous steps (match.hip): see vo_ctx::AsyncAlt -------------------------------------------------------------------
 static const size_t MONO_HDR = 4096;             // monocular record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on

@@ -124,6 +124,7 @@ class FrameHandle:
         self._cache = {}
         self._lazy_kps = []                 # weak refs of KeyPointLists still living only in the slot
         self.sparse = False                 # a frame of StereoCamera.compute_sparse: keypoints with depth, no disparity image
+        self.keep_rdesc = False             # a sparse frame downloads KeypointDepth.right_desc before it leaves the device (off: one copy less per frame)
 
     @property
     def live(self):
@@ -145,6 +146,8 @@ class FrameHandle:
                 self._cache[kind] = self.ctx.download_left(self.slot, (self.h, self.w))
             elif kind in ("kp_xyz", "kp_disp"):
                 self._cache["kp_xyz"], self._cache["kp_disp"] = self.ctx.download_keypoint_depth(self.slot)
+            elif kind == "kp_rdesc":
+                self._cache[kind] = self.ctx.download_keypoint_rdesc(self.slot)
         return self._cache[kind]
 
     def materialize_keypoints(self):
@@ -156,6 +159,8 @@ class FrameHandle:
         self._lazy_kps = []
         if self.sparse and self.live:
             self.full("kp_xyz")             # the depths belong to the keypoints: they go when the keypoints go
+            if self.keep_rdesc:
+                self.full("kp_rdesc")       # ... and so do the right partners' descriptors, for whoever has asked to keep them
 
     def evict(self):
         """Detach from the device slot, keeping host copies of everything."""
@@ -290,7 +295,9 @@ _forward_operators()
 
 class KeypointDepth(DeviceImage):
     """Per-keypoint array of a frame whose keypoints carry depth (StereoCamera.compute_sparse): kind "kp_xyz" (n, 3) or "kp_disp"
-    (n,), float32, in keypoint order; downloaded on first numpy use like every DeviceImage."""
+    (n,), float32, in keypoint order; downloaded on first numpy use like every DeviceImage.  right_desc: (n, 32) uint8, the
+    descriptor of the right keypoint each keypoint was associated with, downloaded on first use while the frame is on the device
+    (set frame.keep_rdesc to have it survive the frame's eviction)."""
 
     _dt = {"kp_xyz": np.float32, "kp_disp": np.float32}
 
@@ -304,6 +311,10 @@ class KeypointDepth(DeviceImage):
 
     def numpy(self):
         return self.frame.full(self.kind)
+
+    @property
+    def right_desc(self):
+        return self.frame.full("kp_rdesc")
 
     def __repr__(self):
         return "KeypointDepth(%s, shape=%s)" % (self.kind, self.shape)

@@ -27,16 +27,19 @@ class SubmittedPair:
     odometer has announced its ORB settings, keypoints) already run on a look-ahead engine.  Pass it
     as `img_left` (with img_right=None) to compute_3d / StereoOdometer.update.
     A pair from StereoCamera.submit_sparse() is of the sparse kind: `sparse` = (nfeatures, min_disp, max_disp, row_tol,
-    max_hamming), the request its sparse stereo chain was begun with; it goes to compute_sparse / a depth="sparse" odometer."""
+    max_hamming), the request its sparse stereo chain was begun with -- followed by (mutual, assoc_ratio) when an association
+    test is on (sparse_request) --; it goes to compute_sparse / a depth="sparse" odometer."""
 
     def __init__(self, slot, shape, preprocessed, images=None, sparse=None):
         self.slot, self.shape, self.preprocessed, self.images = slot, shape, bool(preprocessed), images
         self.sparse = None if sparse is None else tuple(sparse)
 
 
-def sparse_request(nfeatures, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75):
+def sparse_request(nfeatures, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75, mutual=False, assoc_ratio=None):
     """The request of a sparse stereo chain as the tuple a SubmittedPair remembers, held to the rules the library applies
-    (ValueError here, before a slot is taken or anything is submitted)."""
+    (ValueError here, before a slot is taken or anything is submitted).  mutual / assoc_ratio: the association tests
+    (Context.set_sparse_assoc); with both off the tuple has the five leading entries only, else (mutual, float32 ratio or None)
+    follow."""
     def number(v):
         return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)) and np.isfinite(v)
     if isinstance(nfeatures, (bool, np.bool_)) or not isinstance(nfeatures, (int, np.integer)) or nfeatures < 0:
@@ -48,7 +51,9 @@ def sparse_request(nfeatures, min_disp=4, max_disp=100, row_tol=2.0, max_hamming
     if isinstance(max_hamming, (bool, np.bool_)) or not isinstance(max_hamming, (int, np.integer)) or not 0 <= max_hamming <= 256:
         raise ValueError("max_hamming must be an int in 0 .. 256")
     # (the float32 values the library compares with: two requests that differ only beyond them are one request)
-    return (int(nfeatures), float(np.float32(min_disp)), float(np.float32(max_disp)), float(np.float32(row_tol)), int(max_hamming))
+    flags, ratio = _native.sparse_assoc_state(mutual, assoc_ratio)
+    req = (int(nfeatures), float(np.float32(min_disp)), float(np.float32(max_disp)), float(np.float32(row_tol)), int(max_hamming))
+    return req if not flags else req + (bool(mutual), ratio if assoc_ratio is not None else None)
 
 
 def _RESERVED():
@@ -256,8 +261,13 @@ class StereoCamera:
         pair start on a look-ahead engine (no disparity image); the SubmittedPair remembers that it is sparse and with which
         request, and goes to compute_sparse -- with the same request it only collects -- or to a depth="sparse" odometer's
         update(), in submission order.  Not in the reference.  With no free slot the pair is kept on the host and processed
-        synchronously when consumed, like submit()."""
-        req = sparse_request(nfeatures, min_disp, max_disp, row_tol, max_hamming)
+        synchronously when consumed, like submit().  (A request with association tests goes through submit_request().)"""
+        return self.submit_request(img_left, img_right, sparse_request(nfeatures, min_disp, max_disp, row_tol, max_hamming), preprocessed)
+
+    def submit_request(self, img_left, img_right, request, preprocessed=False):
+        """submit_sparse() with the request as sparse_request() returns it: the form that carries the association tests
+        (sparse_request(..., mutual=, assoc_ratio=))."""
+        req = sparse_request(*request)
         img_left, img_right = np.asarray(img_left), np.asarray(img_right)
         if img_left.ndim != img_right.ndim:
             if img_left.ndim == 3:
@@ -268,17 +278,26 @@ class StereoCamera:
         slot = self._free_slot() if held < _native.VO_NUM_SLOTS - 3 else None
         if slot is None:
             return SubmittedPair(None, None, preprocessed, (img_left.copy(), img_right.copy()), sparse=req)
-        shape = self._ctx.prefetch_pair_sparse(slot, img_left, img_right, preprocessed, *req)
+        self._sparse_assoc(req)
+        shape = self._ctx.prefetch_pair_sparse(slot, img_left, img_right, preprocessed, *req[:5])
         self._slot_gen[slot] += 1
         self._slot_owner[slot] = _RESERVED
         return SubmittedPair(slot, shape, preprocessed, sparse=req)
+
+    def _sparse_assoc(self, req):
+        """the association tests of a sparse request into the context, ahead of the call that enqueues its chain (a native call
+        only when they differ from the ones the context wrapper remembers to be in force: the steady path makes none)"""
+        state = tuple(req[5:7]) if len(req) > 5 else (False, None)
+        if _native.sparse_assoc_state(*state) != getattr(self._ctx, "_sparse_assoc", (0, 0.0)):
+            self._ctx.set_sparse_assoc(*state)
 
     def submit_staged(self, buf, w, h, ch, preprocessed, sparse=None):
         """Second half of submit() for a pair that a helper thread has already copied into pinned staging buffer `buf`
         (Context.host_stage_pair): upload + disparity (+ keypoints) start on a look-ahead engine, nothing is copied on
         this thread.  With no free slot the pair is taken back out of the staging buffer and processed synchronously when
         consumed, like submit() (the caller's own arrays may have been reused by then).
-        sparse = (nfeatures, min_disp, max_disp, row_tol, max_hamming): the second half of submit_sparse() instead."""
+        sparse = (nfeatures, min_disp, max_disp, row_tol, max_hamming[, mutual, assoc_ratio]) as sparse_request() returns it: the
+        second half of submit_sparse() instead."""
         if sparse is not None:
             sparse = sparse_request(*sparse)
         held = sum(1 for o in self._slot_owner if o is _RESERVED)
@@ -286,7 +305,8 @@ class StereoCamera:
         if slot is None:
             return SubmittedPair(None, None, preprocessed, self._ctx.host_stage_fetch(buf, w, h, ch), sparse=sparse)
         if sparse is not None:
-            shape = self._ctx.prefetch_host_staged_sparse(slot, buf, w, h, ch, preprocessed, *sparse)
+            self._sparse_assoc(sparse)
+            shape = self._ctx.prefetch_host_staged_sparse(slot, buf, w, h, ch, preprocessed, *sparse[:5])
         else:
             shape = self._ctx.prefetch_host_staged(slot, buf, w, h, ch, preprocessed)
         self._slot_gen[slot] += 1
@@ -343,13 +363,17 @@ class StereoCamera:
         vr = self.valid_region_right
         return img[vr[1]: vr[3], vr[0]: vr[2]]
 
-    def compute_sparse(self, img_left, img_right, nfeatures, preprocessed=False, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75):
+    def compute_sparse(self, img_left, img_right, nfeatures, preprocessed=False, min_disp=4, max_disp=100, row_tol=2.0, max_hamming=75,
+                       mutual=False, assoc_ratio=None):
         """Sparse stereo depth (not in the reference): ORB on both rectified images, association along the row, sub-pixel
         refinement -- no disparity image (include/vo355.h, vo_sparse_stereo).  -> (keypoints, descriptors, xyz (n, 3),
         disparity (n,), img_left): the left keypoints that have a depth, device-resident and lazy like compute_3d's results.
         Takes host arrays, a StagedPair, or a SubmittedPair from submit_sparse() (with the request it was submitted under the call
         only collects what the look-ahead engine computed; with another it recomputes from the slot's pair; `preprocessed` is
-        then the pair's own); a dense SubmittedPair has SGBM work in flight and is refused.  Starts no look-ahead itself."""
+        then the pair's own); a dense SubmittedPair has SGBM work in flight and is refused.  Starts no look-ahead itself.
+        mutual / assoc_ratio: the association tests (off by default; part of the request); the returned xyz / disparity carry
+        .right_desc, the right partners' descriptors."""
+        assoc = sparse_request(nfeatures, min_disp, max_disp, row_tol, max_hamming, mutual, assoc_ratio)
         submitted = None
         if isinstance(img_left, SubmittedPair):
             if img_left.sparse is None:
@@ -384,6 +408,7 @@ class StereoCamera:
             else:
                 w, h = self._ctx.upload_pair(slot, img_left, img_right, preprocessed)
         try:
+            self._sparse_assoc(assoc)
             n = int(self._ctx.sparse_stereo(slot, nfeatures, min_disp, max_disp, row_tol, max_hamming)[2])
         except Exception:
             if submitted is not None:

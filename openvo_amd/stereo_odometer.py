@@ -6,12 +6,18 @@ test, 3-D lookup, rigid-body clique filter, Umeyama fit) runs in libvo355 on the
 stays in Python is the sequential bookkeeping of `update` -- it decides which frames pair up,
 so it follows the reference decision for decision (pinned by tests/golden/g5_state_machine.json).
 """
+import collections
 import os
 
 import numpy as np
 
 from . import _native
 from .features import BFMatcher, DeviceImage, DisparityMask, KeyPointList, ORB
+
+
+# the loop check's entry in the key of a pose step begun ahead (_pose_params): a type of its own, so that nothing has to guess
+# which trailing entry of the key is the match window (a plain (rx, ry) tuple) and which the threshold
+LoopCheck = collections.namedtuple("LoopCheck", "max_hamming")
 
 
 class StereoOdometer:
@@ -25,7 +31,8 @@ class StereoOdometer:
     def __init__(self, stereo_camera, nfeatures=500, match_threshold=0.8, rigidity_threshold=0,
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
-                 match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75):
+                 match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
+                 loop_check=None):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -50,7 +57,16 @@ class StereoOdometer:
         include/vo355.h); a frame's keypoints are then the left keypoints that have a depth, current_3d / prev_3d are their (n, 3)
         points and current_disparity their (n,) disparities.  The state machine, both pose methods, cross_check and match_window
         are unchanged; feature_mask is not used.  run() submits sparse pairs ahead like dense ones (StereoCamera.submit_sparse): their
-        upload, both extractions, association and compaction run on the look-ahead engines, update() collects."""
+        upload, both extractions, association and compaction run on the look-ahead engines, update() collects.
+        sparse_mutual / sparse_ratio (depth="sparse" only; off by default): two tests on the left/right association
+        (include/vo355.h, vo_set_sparse_assoc) -- a right keypoint belongs to its best left claimant only; the winner's Hamming
+        distance must be below sparse_ratio (0 < ratio <= 1) times the runner-up's.  They are part of the sparse request: update(),
+        run() and the pairs begun ahead all carry them.
+        loop_check (None, or a Hamming threshold 0 .. 256; depth="sparse" only): the circular check of sparse stereo odometry -- a
+        temporal match (q, t) is kept only when the RIGHT-image partners of q and t are within loop_check bits of each other
+        (include/vo355.h, VO_MATCH_LOOP).  Applied after the ratio test, cross_check and match_window, in update() and run(),
+        with both pose methods and on the one-frame-back fallback; the threshold is not scaled with the frames a pair spans.  The
+        generic path (a replaced matcher or seam) applies the same test on KeypointDepth.right_desc."""
         if not isinstance(depth, str) or depth not in ("dense", "sparse"):
             raise ValueError("depth must be 'dense' or 'sparse'")
         if (isinstance(sparse_row_tol, (bool, np.bool_)) or not isinstance(sparse_row_tol, (int, float, np.integer, np.floating))
@@ -60,6 +76,16 @@ class StereoOdometer:
                 or not 0 <= sparse_max_hamming <= 256):
             raise ValueError("sparse_max_hamming must be an int in 0 .. 256")
         self.depth, self.sparse_row_tol, self.sparse_max_hamming = depth, float(sparse_row_tol), int(sparse_max_hamming)
+        try:
+            _native.sparse_assoc_state(sparse_mutual, sparse_ratio)
+        except ValueError as e:
+            raise ValueError("sparse_mutual / sparse_ratio: %s" % e)
+        if depth == "dense" and (sparse_mutual or sparse_ratio is not None):
+            raise ValueError("sparse_mutual / sparse_ratio need depth='sparse'")
+        self.sparse_mutual, self.sparse_ratio = bool(sparse_mutual), None if sparse_ratio is None else float(sparse_ratio)
+        self.loop_check = _native.loop_threshold(loop_check, "loop_check")
+        if depth == "dense" and self.loop_check is not None:
+            raise ValueError("loop_check needs depth='sparse'")
         if pose_method not in ("umeyama", "pnp"):
             raise ValueError("pose_method must be 'umeyama' or 'pnp'")
         if not isinstance(cross_check, (bool, np.bool_)):
@@ -142,9 +168,13 @@ class StereoOdometer:
         pair.  The odometer's state is that of before the call (the frame is neither saved nor counted as skipped); the same
         pair may be passed again, or the next one."""
         if self.depth == "sparse":
+            # (the association keywords only where a test is on: a camera stand-in with the earlier signature keeps working)
+            assoc = dict(mutual=self.sparse_mutual, assoc_ratio=self.sparse_ratio) if self.sparse_mutual or self.sparse_ratio is not None else {}
             next_kps, next_desc, next_3d, next_disp, next_img = self.stereo.compute_sparse(
                 img_left, img_right, self.orb.nfeatures, preprocessed=self.preprocessed_frames, min_disp=self.MIN_VALID_DISPARITY,
-                max_disp=self.MAX_VALID_DISPARITY, row_tol=self.sparse_row_tol, max_hamming=self.sparse_max_hamming)
+                max_disp=self.MAX_VALID_DISPARITY, row_tol=self.sparse_row_tol, max_hamming=self.sparse_max_hamming, **assoc)
+            if self.loop_check is not None and isinstance(next_3d, DeviceImage):
+                next_3d.frame.keep_rdesc = True         # (the right partners' descriptors stay with a frame that leaves the device)
         else:
             next_3d, next_disp, next_img = self.stereo.compute_3d(img_left, img_right,
                                                                   preprocessed=self.preprocessed_frames)
@@ -201,6 +231,8 @@ class StereoOdometer:
         """What a pose step begun ahead must have been begun with to be this odometer's step (part of its ticket's key).  With a
         match window its effective radii are the last entry: a step begun with another window (another span) is never reused."""
         tail = () if self.match_window is None else (self._window(),)
+        if self.loop_check is not None:
+            tail += (LoopCheck(self.loop_check),)
         if self.pose_method == "pnp":
             Q = self.stereo.Q
             return ("pnp", float(self.match_threshold), (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3])),
@@ -219,15 +251,27 @@ class StereoOdometer:
         pnp_pair_window / pnp_pair_begin_window)"""
         _, ratio, K4, iters, thr, seed, refine, cross_check = params[:8]
         kw = dict(ratio=ratio, K4=K4, iters=iters, thr=thr, seed=seed, refine=refine, want_matches=False, cross_check=cross_check)
+        params, loop = StereoOdometer._split_loop(params)
         if len(params) > 8:
             kw["window"] = params[8]
+        if loop:
+            kw.setdefault("window", None)       # (the loop check travels through the _window forms, with or without a window)
+            kw.update(loop)
         return kw
+
+    @staticmethod
+    def _split_loop(params):
+        """_pose_params() -> (the parameters without the loop entry, {} or {"loop": threshold})"""
+        if params and isinstance(params[-1], LoopCheck):
+            return params[:-1], {"loop": params[-1].max_hamming}
+        return params, {}
 
     def _step_begin(self, slot_a, slot_b, params):
         if params[0] == "pnp":
             kw = self._pnp_kwargs(params)
             return (self._ctx.pnp_pair_begin_window if "window" in kw else self._ctx.pnp_pair_begin)(slot_a, slot_b, **kw)
-        return self._ctx.pose_pair_begin(slot_a, slot_b, *params)
+        params, loop = self._split_loop(params)
+        return self._ctx.pose_pair_begin(slot_a, slot_b, *params, **loop)
 
     def _step_end(self, params, ticket):
         """Collect a step begun ahead with the _end of its kind."""
@@ -258,7 +302,8 @@ class StereoOdometer:
     def _sparse_req(self):
         """the request of this odometer's sparse stereo chain, as StereoCamera.submit_sparse / SubmittedPair.sparse hold it"""
         from .stereo_camera import sparse_request
-        return sparse_request(self.orb.nfeatures, self.MIN_VALID_DISPARITY, self.MAX_VALID_DISPARITY, self.sparse_row_tol, self.sparse_max_hamming)
+        return sparse_request(self.orb.nfeatures, self.MIN_VALID_DISPARITY, self.MAX_VALID_DISPARITY, self.sparse_row_tol, self.sparse_max_hamming,
+                              self.sparse_mutual, self.sparse_ratio)
 
     def _start_next_pose(self):
         """The frame just accepted is the new `current`.  The pairs that will come next may already be on the device
@@ -293,7 +338,8 @@ class StereoOdometer:
                     self._ahead_counts.clear()
                 try:
                     if sparse:
-                        self._ahead_counts[key] = int(self._ctx.sparse_stereo(s, *req[1:])[2])             # (finished: only collects the kept count)
+                        self.stereo._sparse_assoc(req[1:])
+                        self._ahead_counts[key] = int(self._ctx.sparse_stereo(s, *req[1:6])[2])            # (finished: only collects the kept count)
                     else:
                         self._ahead_counts[key] = self._ctx.orb_slot_count(s, *self.orb.last_slot_args)   # (finished: only collects the count)
                 except _native.VoError:
@@ -377,7 +423,7 @@ class StereoOdometer:
                     started += 1
                     item = copying.popleft()
                     if item[0] is None and sparse is not None:
-                        queue.append(cam.submit_sparse(item[1], item[2], sparse[0], self.preprocessed_frames, *sparse[1:]))
+                        queue.append(cam.submit_request(item[1], item[2], sparse, self.preprocessed_frames))
                     elif item[0] is None:
                         queue.append(cam.submit(item[1], item[2], preprocessed=self.preprocessed_frames))
                     else:
@@ -457,7 +503,7 @@ class StereoOdometer:
         if not (self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b) and len(kps_b) >= 2):
             raise ValueError("pose_method='pnp' needs the device-resident frames compute_3d returns")
         q, t, pts_a, _, st_a, _ = self._ctx.point_clouds(kps_a.frame.slot, kps_b.frame.slot, self.match_threshold, self.cross_check,
-                                                         **self._window_kw())
+                                                         **self._window_kw(), **self._loop_kw())
         if len(q) < self.min_matches:
             self.skip_cause = "matches"
             return None
@@ -510,7 +556,8 @@ class StereoOdometer:
         if ticket is not None:
             counts, rc, _, T34 = self._ctx.pose_pair_end(ticket)         # started by an earlier update()
         else:
-            counts, rc, _, T34 = self._ctx.pose_pair(slot_a, slot_b, *params)
+            plain, loop = self._split_loop(params)
+            counts, rc, _, T34 = self._ctx.pose_pair(slot_a, slot_b, *plain, **loop)
         M, n1, n2, flags = (int(v) for v in counts)
         if M < self.min_matches:
             self.skip_cause = "matches"
@@ -537,7 +584,7 @@ class StereoOdometer:
                  and self._on_device(kps2, desc2, im3d2) and len(kps2) >= 2)
         if fused:
             q, t, pts1, pts2, st1, st2 = self._ctx.point_clouds(kps1.frame.slot, kps2.frame.slot,
-                                                                self.match_threshold, self.cross_check, **self._window_kw())
+                                                                self.match_threshold, self.cross_check, **self._window_kw(), **self._loop_kw())
             if len(q) < self.min_matches:
                 return None, None
             if (st1 == 2).any() or (st2 == 2).any():
@@ -562,6 +609,14 @@ class StereoOdometer:
             # a(j), the nearest query of every train descriptor: the matcher with the roles swapped (k = 1, ties -> lower index)
             back = knn(desc2, desc1, k=1)
             matches = [m for m in matches if len(back[m.trainIdx]) and back[m.trainIdx][0].trainIdx == m.queryIdx]
+        if self.loop_check is not None:
+            # the loop check: the right partners of the two matched keypoints must look alike too
+            rd1, rd2 = getattr(im3d1, "right_desc", None), getattr(im3d2, "right_desc", None)
+            if rd1 is None or rd2 is None:
+                raise ValueError("loop_check needs the per-keypoint clouds compute_sparse returns (their right_desc)")
+            rd1, rd2 = np.asarray(rd1, np.uint8).reshape(-1, 32), np.asarray(rd2, np.uint8).reshape(-1, 32)
+            matches = [m for m in matches
+                       if int(np.unpackbits(np.bitwise_xor(rd1[m.queryIdx], rd2[m.trainIdx])).sum()) <= self.loop_check]
         if len(matches) < self.min_matches:
             return None, None
         if self.depth == "sparse":
@@ -576,6 +631,10 @@ class StereoOdometer:
         point_clouds keeps the signature it has)"""
         w = self._window()
         return {} if w is None else {"window": w}
+
+    def _loop_kw(self):
+        """the loop check as the keyword of the context's calls (none without it, like _window_kw)"""
+        return {} if self.loop_check is None else {"loop": self.loop_check}
 
     @staticmethod
     def _on_device(kps, desc, im3d):

@@ -30,6 +30,8 @@ ap.add_argument("--engines", type=int, default=None, help="--run: look-ahead eng
 ap.add_argument("--host", action="store_true", help="--run: time the driving thread's native calls in one more sparse run() pass")
 ap.add_argument("--rounds", type=int, default=3, help="timed passes per mode, after one warm-up pass")
 ap.add_argument("--steps", type=int, default=200, help="timed vo_sparse_stereo calls")
+ap.add_argument("--assoc", action="store_true", help="--run: the sparse legs with sparse_mutual=True, sparse_ratio=0.8, loop_check=48")
+ap.add_argument("--tag", default=None, help="--run: a label for the result line")
 args = ap.parse_args()
 if args.pairs is None:
     args.pairs = 480 if args.run else 48
@@ -135,17 +137,21 @@ def host_pass(kw):
 
 if args.run:
     LEGS = {"run_dense": ("dense", "run"), "run_sparse": ("sparse", "run"), "update_sparse": ("sparse", "update")}
+    ON = dict(sparse_mutual=True, sparse_ratio=0.8, loop_check=48) if args.assoc else {}
+
+    def leg_kw(d, pkw):
+        return dict(depth=d, **pkw, **(ON if d == "sparse" else {}))
     result = {"tool": "bench_sparse --run", "workload": "C2 1280x720 D=128, 500 features, %d host pairs per pass (synthetic corridor, one GPU)" % len(stream),
               "device": ctx.device_name(), "engines": ctx.set_engines(0), "rounds": args.rounds, "library": os.path.basename(os.environ.get("VO355_LIB", "libvo355.so")),
-              "pairs_per_s": {}}
+              "sparse_options": {k: v for k, v in ON.items()}, "tag": args.tag, "pairs_per_s": {}}
     for p, pkw in POSE.items():
         for leg, (d, how) in LEGS.items():
-            stream_pass(dict(depth=d, **pkw), how)     # warm-up: allocations (an engine's scratch comes with its first pair), clocks
+            stream_pass(leg_kw(d, pkw), how)           # warm-up: allocations (an engine's scratch comes with its first pair), clocks
     rates = {"%s_%s" % (leg, p): [] for p in POSE for leg in LEGS}
     for r in range(args.rounds):                       # the modes alternate inside every round
         for p, pkw in POSE.items():
             for leg, (d, how) in LEGS.items():
-                rates["%s_%s" % (leg, p)].append(stream_pass(dict(depth=d, **pkw), how))
+                rates["%s_%s" % (leg, p)].append(stream_pass(leg_kw(d, pkw), how))
     for k, v in rates.items():
         result["pairs_per_s"][k] = {"per_round": [round(x, 1) for x, _ in v], "median": round(float(np.median([x for x, _ in v])), 1),
                                     "accepted": [a for _, a in v]}
@@ -154,7 +160,7 @@ if args.run:
     # the feature: run() in sparse mode must beat the update() loop in every round of every invocation (exit status 1 otherwise)
     result["run_sparse_above_update_sparse"] = all(result["pairs_per_s"]["run_over_update_sparse_%s" % p] > 1.0 for p in POSE)
     if args.host:
-        result["host"] = {p: host_pass(dict(depth="sparse", **pkw)) for p, pkw in POSE.items()}
+        result["host"] = {p: host_pass(leg_kw("sparse", pkw)) for p, pkw in POSE.items()}
     print(json.dumps(result))
     sys.exit(0 if result["run_sparse_above_update_sparse"] else 1)
 
