@@ -248,6 +248,9 @@ def lib():
             L.vo_set_sweep_group.argtypes = [vp, ci]
             L.vo_lookahead_flush.argtypes = [vp]
             L.vo_sweep_group_stats.argtypes = [vp, vp, vp]
+        plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
+        if plant is not None:
+            plant.argtypes = [vp, ci, ci, vp, vp, vp, vp]
         L.vo_device_count.argtypes = [vp]
         L.vo_mgpu_unique_id.argtypes = [vp]
         L.vo_mgpu_create.argtypes = [ci, ci, ci, vp, vp]
@@ -685,6 +688,21 @@ class Context:
         n = ctypes.c_int(0)
         self._ck(self._lib.vo_download_keypoint_rdesc(self._h, int(slot), _p(rdesc), cap, ctypes.byref(n)))
         return rdesc[:n.value].copy()
+
+    def plant_keypoints(self, slot, xy, desc, xyz, rdesc=None):
+        """Test-only build of the library: n keypoints (xy (n, 2), desc (n, 32), xyz (n, 3)[, rdesc (n, 32)]) straight into a slot,
+        which then stands as sparse_stereo leaves it (vo_test_plant_keypoints).  The product library has no such entry."""
+        if not hasattr(self._lib, "vo_test_plant_keypoints"):
+            raise RuntimeError("plant_keypoints needs the test-only build of the library (libvo355_hooks.so)")
+        xy, desc, xyz = _c(xy, np.float32).reshape(-1, 2), _c(desc, np.uint8).reshape(-1, 32), _c(xyz, np.float32).reshape(-1, 3)
+        n = len(xy)
+        if len(desc) != n or len(xyz) != n:
+            raise ValueError("one descriptor and one 3-D point per keypoint")
+        if rdesc is not None:
+            rdesc = _c(rdesc, np.uint8).reshape(-1, 32)
+            if len(rdesc) != n:
+                raise ValueError("one right descriptor per keypoint")
+        self._ck(self._lib.vo_test_plant_keypoints(self._h, int(slot), n, _p(xy), _p(desc), _p(xyz), _p(rdesc)))
 
     def download_keypoint_depth(self, slot):
         """-> (xyz (n, 3) float32, disparity (n,) float32) of a slot whose keypoints carry depth (VoError otherwise)."""

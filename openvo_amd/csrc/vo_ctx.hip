@@ -1466,3 +1466,42 @@ extern "C" int vo_sgbm_last_geometry(vo_ctx* ctx, int64_t* cells, int* n_paths)
     if (n_paths) *n_paths = ctx->last_paths;
     return VO_OK;
 }
+
+#ifdef VO_TEST_HOOKS
+// Test-only build (libvo355_hooks.so): n keypoints with their descriptors and 3-D points written straight into a slot, which then
+// stands exactly as vo_sparse_stereo leaves it (keypoints that carry depth; nothing pending, begun ahead or monocular).  The seam
+// through which the tests drive the fused pose and PnP steps at chosen (nq, M) instead of what ORB finds in an image.  xy (n, 2)
+// float32, desc (n, 32), xyz (n, 3) float32, rdesc (n, 32) or null (then zeros); size / angle / response / octave / disparity read 0.
+extern "C" int vo_test_plant_keypoints(vo_ctx* ctx, int slot, int n, const float* xy, const uint8_t* desc, const float* xyz, const uint8_t* rdesc)
+{
+    if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS || n < 0) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_keypoints: bad argument");
+    if (n > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "vo_test_plant_keypoints: %d keypoints exceed capacity %d", n, ctx->kp_cap);
+    if (n > 0 && (!xy || !desc || !xyz)) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_keypoints: null pointer");
+    FrameSlot& f = ctx->slots[slot];
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = slot_wait(ctx, f)) || (rc = slot_before_overwrite(ctx, f))) return rc;     // (as vo_sparse_stereo: steps begun ahead may still read the slot)
+    f.has_kp = false; f.kp_depth = false; f.kp_pending = false; f.sp_pending = false; f.sp_ahead = false;
+    f.mono_serial = 0;
+    f.kp_params[0] = f.kp_params[1] = f.kp_params[2] = f.kp_params[3] = -1;
+    f.sp_req.nfeatures = -1;                 // no request ever equals it: vo_sparse_stereo on this slot recomputes
+    if ((rc = xfer_h2d(ctx, f.kp_xy, xy, (size_t)n * 8))) return rc;
+    if ((rc = xfer_h2d(ctx, f.desc, desc, (size_t)n * 32))) return rc;
+    if ((rc = xfer_h2d(ctx, f.kp_xyz, xyz, (size_t)n * 12))) return rc;
+    if (rdesc) { if ((rc = xfer_h2d(ctx, f.kp_rdesc, rdesc, (size_t)n * 32))) return rc; }
+    else if (n > 0) VO_HIP(ctx, hipMemsetAsync(f.kp_rdesc, 0, (size_t)n * 32, ctx->stream));
+    if (n > 0) {
+        VO_HIP(ctx, hipMemsetAsync(f.kp_size, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_angle, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_resp, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_oct, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_disp, 0, (size_t)n * 4, ctx->stream));
+    }
+    if ((rc = xfer_flush(ctx))) return rc;
+    f.sp_rec[0] = f.sp_rec[1] = f.sp_rec[2] = f.sp_rec[3] = n;
+    *f.n_kp_host = n;
+    f.n_kp = n;
+    f.has_kp = true; f.kp_depth = true;
+    return VO_OK;
+}
+#endif

@@ -91,7 +91,7 @@ def svd3(A):
         a = [0.0, 1.0, 0.0] if abs(Uc[0][0]) > 0.9 else [1.0, 0.0, 0.0]
         Uc[1] = _cross(Uc[0], a)
         nn = math.sqrt(Uc[1][0] * Uc[1][0] + Uc[1][1] * Uc[1][1] + Uc[1][2] * Uc[1][2])
-        Uc[1] = [x / nn for x in Uc[1]]
+        Uc[1] = [(x / nn if nn != 0 else math.nan) for x in Uc[1]]     # (a zero covariance: 0 / 0 on the device, then rc = -2)
     if w[2] <= tiny or w[2] <= 1e-14 * w[0]:
         Uc[2] = _cross(Uc[0], Uc[1])
         nn = math.sqrt(Uc[2][0] * Uc[2][0] + Uc[2][1] * Uc[2][1] + Uc[2][2] * Uc[2][2])
