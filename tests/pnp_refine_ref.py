@@ -20,18 +20,23 @@ def exp_so3(w):
     return np.eye(3) + A * W + B * (np.outer(w, w) - th2 * np.eye(3))
 
 
-def normal_sums(Rt, X, uv, K4, order):
-    """(H 6x6, g 6): the sums of one step over the points `order` lists, taken in that order."""
-    fx, fy, cx, cy = (float(v) for v in K4)
-    H, g = np.zeros((6, 6)), np.zeros(6)
+def normal_sums(Rt, X, uv, K4, order, dtype=np.float64):
+    """(H 6x6, g 6): the sums of one step over the points `order` lists, taken in that order.  dtype: the type every term is
+    computed and accumulated in (np.longdouble: the high-precision run of the same sums); H and g come back in it."""
+    dt = dtype
+    fx, fy, cx, cy = (dt(float(v)) for v in K4)
+    R = np.asarray(Rt, np.float64).astype(dt)
+    H, g = np.zeros((6, 6), dt), np.zeros(6, dt)
+    one = dt(1)
     for i in order:
-        x, y, z = Rt[:, :3] @ X[i].astype(np.float64) + Rt[:, 3]
-        iz = 1.0 / z
-        r = ((fx * x * iz + cx) - float(uv[i, 0]), (fy * y * iz + cy) - float(uv[i, 1]))
-        a = ((fx * iz, 0.0, -fx * x * iz * iz), (0.0, fy * iz, -fy * y * iz * iz))
+        x, y, z = R[:, :3] @ X[i].astype(dt) + R[:, 3]
+        iz = one / z
+        r = ((fx * x * iz + cx) - dt(uv[i, 0]), (fy * y * iz + cy) - dt(uv[i, 1]))
+        zero = dt(0)
+        a = ((fx * iz, zero, -fx * x * iz * iz), (zero, fy * iz, -fy * y * iz * iz))
         for e in range(2):
             a0, a1, a2 = a[e]
-            j = np.array([a2 * y - a1 * z, a0 * z - a2 * x, a1 * x - a0 * y, a0, a1, a2])
+            j = np.array([a2 * y - a1 * z, a0 * z - a2 * x, a1 * x - a0 * y, a0, a1, a2], dt)
             H += np.outer(j, j)
             g += j * r[e]
     return H, g
@@ -56,8 +61,9 @@ def cholesky_solve(H, g):
     return d
 
 
-def refine(Rt, X, uv, K4, mask, steps, order=None):
-    """-> (Rt 3x4 float64, status, steps run).  order: the inliers' indices in the order to sum them (default ascending)."""
+def refine(Rt, X, uv, K4, mask, steps, order=None, dtype=np.float64):
+    """-> (Rt 3x4 float64, status, steps run).  order: the inliers' indices in the order to sum them (default ascending).
+    dtype: the type of the sums (normal_sums); they are rounded to float64 for the solve and the update."""
     Rt = np.array(Rt, np.float64).reshape(3, 4)
     X, uv = np.asarray(X, np.float32).reshape(-1, 3), np.asarray(uv, np.float32).reshape(-1, 2)
     inl = np.flatnonzero(np.asarray(mask)) if order is None else np.asarray(order)
@@ -65,7 +71,8 @@ def refine(Rt, X, uv, K4, mask, steps, order=None):
         return Rt, 1, 0
     for k in range(steps):
         with np.errstate(all="ignore"):
-            H, g = normal_sums(Rt, X, uv, K4, inl)
+            H, g = normal_sums(Rt, X, uv, K4, inl, dtype)
+            H, g = np.asarray(H, np.float64), np.asarray(g, np.float64)
             d = cholesky_solve(H, g) if np.isfinite(H).all() and np.isfinite(g).all() else None
             if d is None:
                 return Rt, -1, k
