@@ -528,6 +528,64 @@ int vo_prefetch_staged_pair_sparse(vo_ctx* ctx, int slot, int index, int preproc
  * per-keypoint array instead of the bilinear lookup in the reprojected disparity (status 0; the slots need no disparity and its
  * health is not consulted); when neither does, nothing changes; when exactly one does, VO_E_STATE. */
 
+/* Landmark map (NOT part of the reference, whose every pose is the pose of one pair of frames, stereo_odometer.py:115-160): up to
+ * `capacity` landmarks resident on the device, so that a frame can be tracked against a local map instead of against the previous
+ * frame (StereoOdometer(track="map")).  Defined by this build; tests/map_ref.py restates both kernels in numpy.  A landmark is
+ * xyz (3 x float32, WORLD coordinates = the camera frame of the first tracked frame), desc (32 B), rdesc (32 B: the right-image
+ * partner's descriptor of its last observation, so that VO_MATCH_LOOP works on a view), octave, obs (observations so far) and last
+ * (serial of the frame that last observed it).  A map is an int handle inside the context, at most VO_NUM_MAPS per context; every
+ * byte of it is allocated by vo_map_create (two sets of the arrays: an update compacts from one into the other, never in place),
+ * nothing on the per-frame path.  16 <= capacity <= kp_cap (= 2 max_kp + 1024), so that a view always fits a frame slot.
+ * With T(Rt, p)[i] = (float)(((R[i][0] * (double)p.x + R[i][1] * (double)p.y) + R[i][2] * (double)p.z) + t[i]), R | t the row-major
+ * 3x4 Rt:
+ *
+ * vo_map_view (one launch of one workgroup, ONE host synchronisation): the map as seen under the world-to-camera pose Rt12_cw
+ *   becomes the keypoints of view_slot.  For landmark l in map order: Xc = T(Rt12_cw, xyz[l]);
+ *   u = (float)(fx * ((double)Xc[0] / (double)Xc[2]) + cx) - (float)roi_x0, v likewise with fy, cy, roi_y0 (float32 subtractions);
+ *   K4 = fx, fy, cx, cy in full-image pixels as vo_pnp_pair takes it; the ROI origin and the crop (crop_w x crop_h) are those
+ *   vo_orb_detect_and_compute uses for ref_slot's image -- ref_slot is the frame that will be matched against the view and must
+ *   hold an image (VO_E_STATE otherwise).  l is VISIBLE iff Xc is finite in all three, Xc[2] >= z_min, 0 <= u <= (float)(crop_w - 1)
+ *   and 0 <= v <= (float)(crop_h - 1).  The visible landmarks, in map order, are view_slot's keypoints: position (u, v), 3-D point
+ *   Xc (CAMERA coordinates: what the PnP step sees stays small however far the camera has travelled, and its result is the motion
+ *   from Rt12_cw to the new frame), desc, right descriptor, octave; size = angle = response = 0, disparity NaN.  The slot then
+ *   stands as vo_sparse_stereo leaves one (keypoints that carry depth; nothing pending or begun ahead; no request equals its
+ *   own), ordered behind whatever still reads or writes it.  Which landmark each keypoint came from is kept with the map (the LAST
+ *   VIEW) for vo_map_update.  counts2 = {map size, visible}.  z_min finite >= 0, every entry of Rt12_cw / K4 finite, fx, fy > 0,
+ *   view_slot != ref_slot: VO_E_ARG otherwise.
+ *
+ * vo_map_update (one launch of one workgroup, ONE host synchronisation): folds the tracked frame in slot_new (whose keypoints must
+ *   carry depth: VO_E_STATE otherwise) into the map.  q_idx / t_idx / mask (n entries each, host arrays; NULL only with n = 0) are
+ *   what vo_pnp_pair(view_slot, slot_new, ...) delivered: q indexes the last view, t slot_new's keypoints.  Rt12_wc = the
+ *   camera-to-world pose of slot_new.  Checked on the host before anything is enqueued (VO_E_ARG): 0 <= n <= kp_cap, every
+ *   0 <= q < the last view's count (0 after an update, a reset or no view yet), every 0 <= t < slot_new's keypoints, no q twice among
+ *   the entries with mask != 0, max_age >= 0, 1 <= max_obs <= 65535, serial >= 0 and >= every serial used since the last reset,
+ *   every entry of Rt12_wc finite.
+ *   1. observations: for every c with mask[c] != 0, l = the landmark of view keypoint q[c], t = t_idx[c], Xo = T(Rt12_wc, the 3-D
+ *      point of keypoint t).  Xo not finite: the landmark is left alone (counted as skipped).  Otherwise m = min(obs[l], max_obs),
+ *      xyz[l][i] = (float)((double)xyz[l][i] + ((double)Xo[i] - (double)xyz[l][i]) / (double)(m + 1)) -- a running mean whose
+ *      weight stops shrinking at 1 / (max_obs + 1) --, obs[l] += 1, last[l] = serial, desc / rdesc / octave from keypoint t, and t
+ *      is CLAIMED (several landmarks may claim one t: each takes its own observation).
+ *   2. survivors: the landmarks with serial - last[l] <= max_age, in their order; the others are counted as culled.
+ *   3. insertions: the unclaimed keypoints t of slot_new with a finite Xo, in keypoint order, enter behind the survivors with
+ *      xyz = Xo, obs = 1, last = serial until `capacity` is reached; the rest are counted as dropped (an unclaimed keypoint
+ *      without a finite point is neither).
+ *   4. the other set of arrays becomes the map; the last view is void.
+ *   counts6 = {observed, skipped, culled, inserted, dropped, size}.  n = 0 is insert-and-age only: how a first frame fills the map.
+ *
+ * With vo_enable_timing on, the view's launch is bracketed under VO_T_MATCH and the update's under VO_T_POSE.
+ * A refused call leaves the map as it was.  vo_map_reset: size 0, no view, serials start over.  vo_map_download: the landmarks in
+ * map order (any output may be NULL; VO_E_CAP when cap is below the size).  A fifth map: VO_E_CAP. */
+#define VO_NUM_MAPS 4
+int vo_map_create(vo_ctx* ctx, int capacity, int* map_out);
+int vo_map_destroy(vo_ctx* ctx, int map);
+int vo_map_reset(vo_ctx* ctx, int map);
+int vo_map_view(vo_ctx* ctx, int map, const double* Rt12_cw, const double* K4, float z_min, int ref_slot, int view_slot,
+                int32_t* counts2);
+int vo_map_update(vo_ctx* ctx, int map, int slot_new, const double* Rt12_wc, int serial, int max_age, int max_obs,
+                  const int32_t* q_idx, const int32_t* t_idx, const uint8_t* mask, int n, int32_t* counts6);
+int vo_map_download(vo_ctx* ctx, int map, float* xyz /*cap*3*/, uint8_t* desc /*cap*32*/, int32_t* octave, int32_t* obs, int32_t* last,
+                    int cap, int* n_out);
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */

@@ -17,6 +17,7 @@ VO_NUM_SLOTS = 28
 VO_NUM_HOST_STAGE = 20
 VO_NUM_MONO_ASYNC = 5
 VO_NUM_POSE_ASYNC = 8
+VO_NUM_MAPS = 4
 SCHED_DIAG, SCHED_DIAG_RAGGED, SCHED_UNFUSED = 1, 2, 3
 T_STAGES = ("upload", "sgbm_cost", "sgbm_agg", "sgbm_wta", "sgbm_post", "orb", "match", "pose", "knn")
 
@@ -45,6 +46,7 @@ SYMBOLS = [
     "vo_sparse_pair_host", "vo_prefetch_pair_sparse", "vo_prefetch_host_staged_sparse", "vo_prefetch_staged_pair_sparse",
     "vo_set_sparse_assoc", "vo_download_keypoint_rdesc", "vo_sparse_pair_host_ex", "vo_set_match_loop", "vo_clear_match_loop",
     "vo_get_stage_timeline",
+    "vo_map_create", "vo_map_destroy", "vo_map_reset", "vo_map_view", "vo_map_update", "vo_map_download",
 ]
 
 
@@ -248,9 +250,18 @@ def lib():
             L.vo_set_sweep_group.argtypes = [vp, ci]
             L.vo_lookahead_flush.argtypes = [vp]
             L.vo_sweep_group_stats.argtypes = [vp, vp, vp]
+        if hasattr(L, "vo_map_create"):             # (likewise: an older build has no landmark map)
+            for name, proto in (("vo_map_create", [vp, ci, vp]), ("vo_map_destroy", [vp, ci]), ("vo_map_reset", [vp, ci]),
+                                ("vo_map_view", [vp, ci, vp, vp, ctypes.c_float, ci, ci, vp]),
+                                ("vo_map_update", [vp, ci, ci, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
+                                ("vo_map_download", [vp, ci, vp, vp, vp, vp, vp, ci, vp])):
+                getattr(L, name).argtypes = proto
         plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+        plant = getattr(L, "vo_test_plant_map", None)            # (likewise)
+        if plant is not None:
+            plant.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
         L.vo_device_count.argtypes = [vp]
         L.vo_mgpu_unique_id.argtypes = [vp]
         L.vo_mgpu_create.argtypes = [ci, ci, ci, vp, vp]
@@ -1101,6 +1112,78 @@ class Context:
         head, arrays = self._pnp_out(want_matches)
         self._ck(self._lib.vo_pnp_pair_end(self._h, int(ticket), *[_p(a) for a in head + arrays], self.kp_cap))
         return self._pnp_result(head, arrays)
+
+    # ---- landmark map (vo_map_*: NOT part of the reference)
+    def map_create(self, capacity):
+        """-> the handle of a new landmark map of `capacity` landmarks (16 .. kp_cap; at most VO_NUM_MAPS per context)."""
+        h = ctypes.c_int(-1)
+        self._ck(self._lib.vo_map_create(self._h, int(capacity), ctypes.byref(h)))
+        return h.value
+
+    def map_destroy(self, handle):
+        self._ck(self._lib.vo_map_destroy(self._h, int(handle)))
+
+    def map_reset(self, handle):
+        """size 0, no view, serials start over"""
+        self._ck(self._lib.vo_map_reset(self._h, int(handle)))
+
+    @staticmethod
+    def _pose12(Rt):
+        Rt = np.asarray(Rt, np.float64)
+        if Rt.shape == (4, 4):
+            Rt = Rt[:3]
+        if Rt.size != 12:
+            raise ValueError("a pose is 3x4 (or 4x4), not %s" % (Rt.shape,))
+        return _c(Rt.reshape(12), np.float64)
+
+    def map_view(self, handle, Rt_cw, K4, z_min, ref_slot, view_slot):
+        """The map as seen under the world-to-camera pose Rt_cw (3x4 or 4x4) becomes the keypoints of view_slot, placed in the crop
+        of ref_slot's image (vo_map_view).  -> counts2 = [map size, visible]."""
+        Rt, K4 = self._pose12(Rt_cw), _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        c2 = np.zeros(2, np.int32)
+        self._ck(self._lib.vo_map_view(self._h, int(handle), _p(Rt), _p(K4), float(z_min), int(ref_slot), int(view_slot), _p(c2)))
+        return c2
+
+    def map_update(self, handle, slot_new, Rt_wc, serial, max_age, max_obs, q=None, t=None, mask=None):
+        """Fold the tracked frame in slot_new (camera-to-world pose Rt_wc) into the map: q / t / mask as pnp_pair(view_slot,
+        slot_new, want_matches=True) delivered them, or none of them for insert-and-age only (vo_map_update).
+        -> counts6 = [observed, skipped, culled, inserted, dropped, size]."""
+        Rt = self._pose12(Rt_wc)
+        if q is None and t is None and mask is None:
+            q, t, mask = np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint8)
+        elif q is None or t is None or mask is None:
+            raise ValueError("q, t and mask come together")
+        q, t, mask = _c(q, np.int32).reshape(-1), _c(t, np.int32).reshape(-1), _c(mask, np.uint8).reshape(-1)
+        if not len(q) == len(t) == len(mask):
+            raise ValueError("q, t and mask differ in length")
+        c6 = np.zeros(6, np.int32)
+        n = len(q)
+        self._ck(self._lib.vo_map_update(self._h, int(handle), int(slot_new), _p(Rt), int(serial), int(max_age), int(max_obs),
+                                         _p(q) if n else None, _p(t) if n else None, _p(mask) if n else None, n, _p(c6)))
+        return c6
+
+    def map_download(self, handle):
+        """-> dict(xyz (n, 3) float32 world coordinates, desc (n, 32), octave, obs, last (n,) int32) in map order"""
+        n = ctypes.c_int(0)
+        self._ck(self._lib.vo_map_download(self._h, int(handle), None, None, None, None, None, 0, ctypes.byref(n)))
+        n = n.value
+        out = dict(xyz=np.empty((n, 3), np.float32), desc=np.empty((n, 32), np.uint8), octave=np.empty(n, np.int32),
+                   obs=np.empty(n, np.int32), last=np.empty(n, np.int32))
+        if n:
+            self._ck(self._lib.vo_map_download(self._h, int(handle), _p(out["xyz"]), _p(out["desc"]), _p(out["octave"]), _p(out["obs"]),
+                                               _p(out["last"]), n, ctypes.byref(ctypes.c_int(0))))
+        return out
+
+    def plant_map(self, handle, xyz, desc, rdesc, octave, obs, last):
+        """Test-only build of the library: n landmarks straight into a map (vo_test_plant_map).  The product library has no such entry."""
+        if not hasattr(self._lib, "vo_test_plant_map"):
+            raise RuntimeError("plant_map needs the test-only build of the library (libvo355_hooks.so)")
+        xyz, desc, rdesc = _c(xyz, np.float32).reshape(-1, 3), _c(desc, np.uint8).reshape(-1, 32), _c(rdesc, np.uint8).reshape(-1, 32)
+        octave, obs, last = (_c(a, np.int32).reshape(-1) for a in (octave, obs, last))
+        n = len(xyz)
+        if not all(len(a) == n for a in (desc, rdesc, octave, obs, last)):
+            raise ValueError("one entry of every array per landmark")
+        self._ck(self._lib.vo_test_plant_map(self._h, int(handle), n, _p(xyz), _p(desc), _p(rdesc), _p(octave), _p(obs), _p(last)))
 
     def umeyama(self, src, dst, force_rotation=True):
         src, dst = _c(src, np.float32).reshape(-1, 3), _c(dst, np.float32).reshape(-1, 3)

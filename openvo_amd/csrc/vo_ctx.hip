@@ -296,6 +296,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
                    ctx->sparse_r.kp_angle, ctx->sparse_r.kp_resp, ctx->sparse_r.kp_oct, ctx->sparse_r.desc };
     for (void* p : ps) if (p) (void)hipFree(p);
     alt_free(ctx);
+    for (LandmarkMap& m : ctx->maps) map_free(m);
     sparse_ws_free(ctx->sp_main);
     for (SparseWs& w : ctx->sp_alt) sparse_ws_free(w);
     match_ws_free(ctx->main_mw);
@@ -1502,6 +1503,32 @@ extern "C" int vo_test_plant_keypoints(vo_ctx* ctx, int slot, int n, const float
     *f.n_kp_host = n;
     f.n_kp = n;
     f.has_kp = true; f.kp_depth = true;
+    return VO_OK;
+}
+
+// ... and n landmarks written straight into a map (vo_map_create), which then stands as n insertions would have left it -- with
+// any float32 bits as positions (NaN, inf: what no update ever inserts) and chosen obs / last.  The last view is void; the largest
+// `last` counts as a serial used.  xyz (n, 3) float32, desc / rdesc (n, 32), octave / obs / last (n) int32, last >= 0, obs >= 1.
+extern "C" int vo_test_plant_map(vo_ctx* ctx, int map, int n, const float* xyz, const uint8_t* desc, const uint8_t* rdesc, const int32_t* octave,
+                                 const int32_t* obs, const int32_t* last)
+{
+    if (!ctx || map < 0 || map >= VO_NUM_MAPS || !ctx->maps[map].used || n < 0) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_map: bad argument");
+    LandmarkMap& m = ctx->maps[map];
+    if (n > m.capacity) return vo_fail(ctx, VO_E_CAP, "vo_test_plant_map: %d landmarks exceed capacity %d", n, m.capacity);
+    if (n > 0 && (!xyz || !desc || !rdesc || !octave || !obs || !last)) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_map: null pointer");
+    int top = -1;
+    for (int i = 0; i < n; i++) {
+        if (last[i] < 0 || obs[i] < 1) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_map: need last >= 0 and obs >= 1");
+        if (last[i] > top) top = last[i];
+    }
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    const MapSet& s = m.set[m.cur];
+    int rc;
+    if ((rc = xfer_h2d(ctx, s.xyz, xyz, (size_t)n * 12)) || (rc = xfer_h2d(ctx, s.desc, desc, (size_t)n * 32)) ||
+        (rc = xfer_h2d(ctx, s.rdesc, rdesc, (size_t)n * 32)) || (rc = xfer_h2d(ctx, s.oct, octave, (size_t)n * 4)) ||
+        (rc = xfer_h2d(ctx, s.obs, obs, (size_t)n * 4)) || (rc = xfer_h2d(ctx, s.last, last, (size_t)n * 4)) || (rc = xfer_flush(ctx)))
+        return rc;
+    m.n = n; m.view_n = 0; m.max_serial = top;
     return VO_OK;
 }
 #endif

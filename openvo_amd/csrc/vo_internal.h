@@ -125,6 +125,27 @@ struct SparseWs {
 };
 typedef FrameSlot::SparseReq SparseReq;
 
+// Landmark map (map.hip; include/vo355.h, vo_map_*): one set of the per-landmark arrays, `capacity` entries each
+struct MapSet {
+    float* xyz = nullptr;                      // 3 floats, world coordinates
+    uint8_t *desc = nullptr, *rdesc = nullptr; // 32 bytes each
+    int32_t *oct = nullptr, *obs = nullptr, *last = nullptr;
+};
+// A map of a context.  set[cur] holds the n landmarks; an update compacts into set[cur ^ 1] and flips.  view_src[k] = the landmark
+// keypoint k of the last view came from (view_n of them; 0 = no view: void after every update, reset and plant).  claimed: one byte
+// per keypoint of the frame being folded in; d_q / d_t / d_mask: the device copies of the caller's match arrays (kp_cap entries
+// each).  seen: the host's scratch of the duplicate check (kp_cap bytes).  Everything is allocated by vo_map_create.
+struct LandmarkMap {
+    bool used = false;
+    int capacity = 0, n = 0, cur = 0, view_n = 0;
+    int max_serial = -1;                       // the largest serial an update has used since the last reset (-1: none)
+    MapSet set[2];
+    int32_t *view_src = nullptr, *d_q = nullptr, *d_t = nullptr;
+    uint8_t *claimed = nullptr, *d_mask = nullptr;
+    std::vector<uint8_t> seen;
+};
+void map_free(LandmarkMap& m);
+
 struct vo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -216,6 +237,7 @@ struct vo_ctx {
     // (keypoint arrays and pinned count word only); sp_main: the SparseWs of the main stream built on the two, sp_alt[k]: look-ahead
     // engine k's own
     FrameSlot sparse_r;
+    LandmarkMap maps[VO_NUM_MAPS];      // vo_map_create .. vo_map_destroy (freed by vo_destroy too)
     SparseWs sp_main;
     SparseWs sp_alt[MAX_ENGINES];
 

@@ -61,6 +61,12 @@ def _RESERVED():
     return _RESERVED
 
 
+def _VIEW():
+    """Stand-in "owner" of a slot an odometer has set aside for the view of its landmark map (reserve_view_slot): never dead, never
+    handed out or evicted, and -- unlike _RESERVED -- not a look-ahead pair, so the look-ahead's count of held slots leaves it out."""
+    return _VIEW
+
+
 def _load_plain(path):
     path = os.fspath(path)
     if path.lower().endswith(".json"):
@@ -212,7 +218,7 @@ class StereoCamera:
         # (slots reserved by submit() hold work that cannot be redone and are never taken)
         s = self._next_slot
         for k in range(n):
-            if self._slot_owner[(self._next_slot + k) % n] is not _RESERVED:
+            if self._slot_owner[(self._next_slot + k) % n] not in (_RESERVED, _VIEW):
                 s = (self._next_slot + k) % n
                 break
         else:
@@ -223,6 +229,21 @@ class StereoCamera:
         self._slot_owner[s] = None
         self._next_slot = (s + 1) % n
         return s, weakref
+
+    def reserve_view_slot(self):
+        """Set one frame slot aside for the view of a landmark map (StereoOdometer(track="map")): it is not handed out to frames,
+        not counted by the look-ahead and never evicted until release_view_slot.  Not in the reference."""
+        s = self._free_slot()
+        if s is None:
+            s, _ = self._acquire_slot()
+        self._slot_gen[s] += 1
+        self._slot_owner[s] = _VIEW
+        return s
+
+    def release_view_slot(self, slot):
+        """Give a slot from reserve_view_slot back (idempotent)."""
+        if slot is not None and self._slot_owner[slot] is _VIEW:
+            self._slot_owner[slot] = None
 
     def stage_pairs(self, pairs):
         """Upload (left, right) pairs once and keep them in HBM; returns StagedPair handles.

@@ -32,7 +32,7 @@ class StereoOdometer:
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
                  match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
-                 loop_check=None):
+                 loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -66,7 +66,45 @@ class StereoOdometer:
         temporal match (q, t) is kept only when the RIGHT-image partners of q and t are within loop_check bits of each other
         (include/vo355.h, VO_MATCH_LOOP).  Applied after the ratio test, cross_check and match_window, in update() and run(),
         with both pose methods and on the one-frame-back fallback; the threshold is not scaled with the frames a pair spans.  The
-        generic path (a replaced matcher or seam) applies the same test on KeypointDepth.right_desc."""
+        generic path (a replaced matcher or seam) applies the same test on KeypointDepth.right_desc.
+        track="map" (an extension, NOT in the reference; default "pair" = every pose is the pose of one pair of frames, as ever;
+        needs depth="sparse" and pose_method="pnp"): the new frame is tracked against a landmark map resident on the device
+        (include/vo355.h, vo_map_*).  The map as seen under the last pose becomes one more depth-carrying frame slot (the VIEW: the
+        camera sets a slot aside for it), the fused PnP step runs on (view, new frame) and its result goes through exactly the
+        decisions and gates of the pairwise step; an accepted frame is folded into the map: matched inliers update their landmark's
+        position by a running mean (weight never below 1 / (map_max_obs + 1)) and take the new descriptors, unmatched keypoints
+        enter as landmarks, landmarks not observed for more than map_max_age accepted frames leave.  When the map step gives no
+        pose, today's two pairwise attempts run unchanged and the frame enters the map without observations; track_source says
+        which of the two ("map" | "pair") placed the last accepted frame, map_counts holds the last counts of view / update,
+        landmarks() downloads the map.  map_capacity: None = min(kp_cap, 4 * nfeatures); map_z_min: landmarks nearer than this
+        (metres along the optical axis) are not in a view.  cross_check, match_window (a guided search around the landmark's
+        predicted pixel, scaled by the span as ever), pnp_refine and loop_check compose unchanged.  No pose step is begun ahead in
+        this mode; run() still submits sparse pairs ahead.  Where the fused PnP step cannot run (a replaced matcher or seam),
+        update() raises ValueError."""
+        if not isinstance(track, str) or track not in ("pair", "map"):
+            raise ValueError("track must be 'pair' or 'map'")
+        if track == "map" and (depth != "sparse" or pose_method != "pnp"):
+            raise ValueError("track='map' needs depth='sparse' and pose_method='pnp'")
+
+        def _int(v, lo, hi):
+            return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and lo <= v <= hi
+        if not _int(map_max_age, 0, 2 ** 31 - 1):
+            raise ValueError("map_max_age must be an int >= 0")
+        if not _int(map_max_obs, 1, 65535):
+            raise ValueError("map_max_obs must be an int in 1 .. 65535")
+        kp_cap = getattr(getattr(stereo_camera, "_ctx", None), "kp_cap", 2 ** 31 - 1)
+        if map_capacity is not None and not _int(map_capacity, 16, kp_cap):
+            raise ValueError("map_capacity must be None or an int in 16 .. kp_cap (%d)" % kp_cap)
+        with np.errstate(over="ignore"):               # (too large for float32: inf, refused)
+            if (isinstance(map_z_min, (bool, np.bool_)) or not isinstance(map_z_min, (int, float, np.integer, np.floating))
+                    or not np.isfinite(np.float32(map_z_min)) or map_z_min < 0):
+                raise ValueError("map_z_min must be a finite number >= 0")
+        self.track, self.map_max_age, self.map_max_obs, self.map_z_min = track, int(map_max_age), int(map_max_obs), float(map_z_min)
+        self.map_capacity = None if map_capacity is None else int(map_capacity)
+        self.track_source = None     # "map" | "pair": what placed the last accepted frame (track="map")
+        self.map_counts = {}         # {"view": counts2, "update": counts6} of the last map calls
+        self._map = self._view_slot = None
+        self._map_serial = 0
         if not isinstance(depth, str) or depth not in ("dense", "sparse"):
             raise ValueError("depth must be 'dense' or 'sparse'")
         if (isinstance(sparse_row_tol, (bool, np.bool_)) or not isinstance(sparse_row_tol, (int, float, np.integer, np.floating))
@@ -184,6 +222,13 @@ class StereoOdometer:
             self.skip_cause = "keypoints"
             return False
         if self.current_img is None:           # very first usable frame
+            if self.track == "map":
+                self._map_first(next_kps, next_desc, next_3d)
+            self.save_frame_update(next_img, next_disp, next_3d, next_kps, next_desc)
+            return True
+
+        if self.track == "map" and self._map_track(next_kps, next_desc, next_3d):
+            self.skipped_frames = 0
             self.save_frame_update(next_img, next_disp, next_3d, next_kps, next_desc)
             return True
 
@@ -206,9 +251,92 @@ class StereoOdometer:
             self.skipped_frames += 1          # frame is dropped, `current` stays
             return False
         self.skipped_frames = 0
+        if self.track == "map":                # placed by a pairwise attempt: the frame enters the map without observations
+            self._map_fold(next_kps.frame.slot)
+            self.track_source = "pair"
         self.save_frame_update(next_img, next_disp, next_3d, next_kps, next_desc)
         self._start_next_pose()
         return True
+
+    # ---- frame-to-map tracking (track="map") ------------------------------------------------------------------------------------
+    def _map_ready(self, kps, desc, im3d):
+        """The map step is the fused PnP step on device-resident slots: where that cannot run there is no map mode.  Creates the
+        map and takes the view slot at first use."""
+        if not (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and self._pnp_fused_ok()
+                and not any(n in self.__dict__ for n in self._SEAMS) and self._on_device(kps, desc, im3d)):
+            raise ValueError("track='map' needs the fused PnP step on device-resident frames: a replaced matcher or seam "
+                             "(or a frame that has left the device) leaves it nothing to run on")
+        if self._map is None:
+            cap = self.map_capacity if self.map_capacity is not None else min(self._ctx.kp_cap, 4 * self.orb.nfeatures)
+            self._map = self._ctx.map_create(max(16, cap))
+        if self._view_slot is None:
+            self._view_slot = self.stereo.reserve_view_slot()
+
+    def _map_first(self, kps, desc, im3d):
+        """the first usable frame: an empty map, the frame enters it with the identity pose and serial 0"""
+        self._map_ready(kps, desc, im3d)
+        self._ctx.map_reset(self._map)
+        self._map_serial = 0
+        self.track_source = None
+        self._map_fold(kps.frame.slot)
+
+    def _map_fold(self, slot, r=None):
+        """the frame in `slot`, placed at c_T_w, into the map (r: the PnP record of the map step, or None = no observations)"""
+        m = (r["q"], r["t"], r["mask"]) if r is not None else (None, None, None)
+        self.map_counts["update"] = self._ctx.map_update(self._map, slot, np.linalg.inv(self.c_T_w), self._map_serial, self.map_max_age,
+                                                         self.map_max_obs, *m)
+        self._map_serial += 1
+
+    def _map_track(self, kps, desc, im3d):
+        """The map step: view under c_T_w (the prediction is the last pose) -> fused PnP step on (view, new frame) -> the decisions
+        of _pair_pnp_fused -> c_T_w and the map updated.  -> True when the frame was placed."""
+        self._map_ready(kps, desc, im3d)
+        slot = kps.frame.slot
+        Q = self.stereo.Q
+        K4 = (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3]))
+        c2 = self.map_counts["view"] = self._ctx.map_view(self._map, self.c_T_w, K4, self.map_z_min, slot, self._view_slot)
+        if not (max(self.min_matches, 2) <= int(c2[1]) <= 3800 and len(kps) >= 2):
+            return False
+        got = {}
+        self._pair_span = None
+        T = self._pair_pnp_fused(self._view_slot, slot, want_matches=True, record=got)
+        if T is None:
+            return False
+        self.c_T_w_prev = self.c_T_w
+        self.c_T_w = T @ self.c_T_w
+        self._map_fold(slot, got["r"])
+        self.track_source = "map"
+        return True
+
+    def landmarks(self):
+        """-> the map as a dict of arrays in map order: xyz (n, 3) float32 world coordinates (the camera frame of the first tracked
+        frame), desc (n, 32), octave, obs, last (n,); empty before the first frame (track="map" only)"""
+        if self.track != "map":
+            raise ValueError("landmarks() needs track='map'")
+        if self._map is None:
+            return dict(xyz=np.zeros((0, 3), np.float32), desc=np.zeros((0, 32), np.uint8), octave=np.zeros(0, np.int32),
+                        obs=np.zeros(0, np.int32), last=np.zeros(0, np.int32))
+        return self._ctx.map_download(self._map)
+
+    def release_map(self):
+        """Give the map and the view slot back (idempotent; also done when the odometer is collected)."""
+        ctx, cam = self._ctx, self.stereo
+        if self._map is not None and ctx is not None and getattr(ctx, "_h", None):
+            try:
+                ctx.map_destroy(self._map)
+            except _native.VoError:
+                pass
+        self._map = None
+        if self._view_slot is not None and hasattr(cam, "release_view_slot"):
+            cam.release_view_slot(self._view_slot)
+        self._view_slot = None
+
+    def __del__(self):
+        try:
+            if self.__dict__.get("_map") is not None or self.__dict__.get("_view_slot") is not None:
+                self.release_map()
+        except Exception:
+            pass
 
     _pnp_fused = True        # False: pose_method="pnp" takes the composed path (_pair_pnp) whatever the conditions
     _PNP_CTX_SEAMS = ("point_clouds", "ransac_pnp")
@@ -313,6 +441,8 @@ class StereoOdometer:
         results arrive in a burst (a cold start: every pair in flight finishes at about the same time) the short kernel
         chains of many pairs run side by side instead of one after the other behind the host.  Purely an ordering change:
         _pair_fused looks a step up by its slots and parameters and computes on the spot when the guess was wrong."""
+        if self.track == "map":        # (the map step needs the pose of the frame before it: nothing to begin ahead)
+            return
         sparse = self.depth == "sparse"
         if not self._fused_ok() or (not sparse and self.orb.last_slot_args is None):
             return self._drop_specs()
@@ -523,16 +653,21 @@ class StereoOdometer:
             return None
         return self._gate(np.vstack([r["Rt"], [0, 0, 0, 1]]))
 
-    def _pair_pnp_fused(self, slot_a, slot_b):
+    def _pair_pnp_fused(self, slot_a, slot_b, want_matches=False, record=None):
         """_pair_pnp in one native call (vo_pnp_pair: one device synchronisation, nothing but the record comes back): the same
-        decisions in the same order; with pnp_refine > 0 the gates see the refined pose when the refinement succeeded."""
+        decisions in the same order; with pnp_refine > 0 the gates see the refined pose when the refinement succeeded.
+        want_matches / record (the map step): the step delivers q / t / mask too and the whole record is left in record["r"]."""
         params = self._pose_params()
-        ticket = self._specs.pop((self.stereo.slot_key(slot_a), self.stereo.slot_key(slot_b), params), None)
+        ticket = None if want_matches else self._specs.pop((self.stereo.slot_key(slot_a), self.stereo.slot_key(slot_b), params), None)
         if ticket is not None:
             r = self._ctx.pnp_pair_end(ticket)                           # started by an earlier update()
         else:
             kw = self._pnp_kwargs(params)
+            if want_matches:
+                kw["want_matches"] = True
             r = (self._ctx.pnp_pair_window if "window" in kw else self._ctx.pnp_pair)(slot_a, slot_b, **kw)
+        if record is not None:
+            record["r"] = r
         if r["matches"] < self.min_matches:
             self.skip_cause = "matches"
             return None
