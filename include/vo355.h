@@ -50,7 +50,10 @@ int vo_synchronize(vo_ctx* ctx);
  * first use: ~0.95 GB at 1280x720 / D = 128).  n <= 0 only asks.  Returns the count in effect (clamped to 1 .. 24 and to what
  * fits 40 % of the device's free memory), or a negative status.  May be called at any time; engines already created above a
  * lowered count keep their memory until vo_destroy but receive no further pairs.  The reference has no counterpart (cv2 keeps
- * one StereoSGBM object per StereoCamera, stereo_camera.py:23): this bounds the footprint of the replacement. */
+ * one StereoSGBM object per StereoCamera, stereo_camera.py:23): this bounds the footprint of the replacement.
+ * While sweep groups are in force (below) the dense look-ahead pairs of all engines travel on the context's two lane streams:
+ * an engine then contributes its workspaces and staging, not its stream, and the automatic group size follows the count
+ * (half the engines, so that consecutive groups use disjoint engines).  The open group is closed by a change of the count. */
 int vo_set_engines(vo_ctx* ctx, int n);
 
 /* one-off configuration (stereo_camera.py:16-27) ------------------------------------ */
@@ -92,6 +95,11 @@ int vo_lookahead_drop(vo_ctx* ctx, int slot);
  * enqueued and runs their aggregation sweeps as ONE launch; a pair's remaining work follows when its group closes: when it
  * has B members, when anything is about to wait on, read, refill or drop a member's slot (so no call ever sees a half-done
  * slot), or when the caller says that no further pair follows now (vo_lookahead_flush).  Results do not depend on B.
+ * While B > 1 the dense look-ahead pairs go on two lane streams the context owns instead of the engines' own: a group's
+ * members and its launches share one lane and consecutive groups alternate, so a group's early stages run beside the launches
+ * of the group before it.  Without a request B follows the queue budget: 1 with a queue per stream, min(12, engines / 2) with
+ * fewer.  VO_GROUP_LANES=0 in the environment at vo_create keeps every engine on its own stream (B without a request is then
+ * min(12, engines)).  Sparse and monocular look-ahead submissions always use the engines' own streams.
  * vo_set_sweep_group: n <= 0 only asks, otherwise B = min(n, VO_MAX_SWEEP_GROUP) from now on (the open group is closed);
  * returns the size in force (never above the number of engines) or a negative status.  VO_SWEEP_GROUP in the environment
  * does the same at vo_create.  vo_lookahead_flush closes the open group and returns the size in force as well -- 1 tells a

@@ -661,6 +661,9 @@ int alt_open(vo_ctx* ctx, int kind, FrameSlot& a, FrameSlot& b, const char* who,
     // and behind the main stream's work on them
     if (int rc = sweep_group_close_for(ctx, a)) return rc;
     if (int rc = sweep_group_close_for(ctx, b)) return rc;
+    // a pose alternate runs on one of the shared pose streams: which of them is decided per step (the alternate is free: its
+    // previous step has been waited for, so nothing of it is left on the stream it used then)
+    if (kind == vo_ctx::ALT_POSE) ctx->alt(kind, k).stream = ctx->pose_streams[k % pose_stream_count(ctx)];
     const hipStream_t st = ctx->alt(kind, k).stream;
     VO_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     hipError_t e = hipStreamWaitEvent(st, ctx->ev0, 0);

@@ -174,8 +174,7 @@ int orb_prepare_tables(vo_ctx* ctx, int w, int h)
     // The resize tables are one device array shared by the main and all look-ahead streams: extractions still
     // in flight anywhere read them, so everything queued so far must finish before they are rewritten for a
     // new image size (rare: once per size).  What those extractions produced stays valid.
-    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
-        if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
+    VO_HIP(ctx, engine_streams_sync(ctx));
     for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
         for (int k = 0; k < vo_ctx::alt_count(kind); k++)
             if (ctx->alt(kind, k).stream) VO_HIP(ctx, hipStreamSynchronize(ctx->alt(kind, k).stream));

@@ -1614,6 +1614,7 @@ struct SweepGroup {
     typedef int (*WeLaunch)(vo_ctx*, const WeJobs&, int, const SgbmGeom&);
     struct Member {
         int engine;
+        hipStream_t stream;      // the stream that carries the member's front
         FrameSlot* f;
         int w, h;
         SgbmGeom g;
@@ -1625,6 +1626,8 @@ struct SweepGroup {
     WeLaunch we_launch = nullptr;
     int nstrips = 0;
     int n = 0;
+    hipStream_t lane = nullptr;  // the lane stream of the open group: its members' fronts lie on it and its chain follows there
+                                 // (nullptr: per-engine streams, the chain goes on the closing member's)
     Member m[DG_MAXJOBS];
     // hand-over between sgbm_run and the forward sweep's launch site: want_defer = this run's sweep joins the group instead of
     // being launched; did_defer = it has (cand* are filled)
@@ -1848,6 +1851,7 @@ static int sgbm_run_done(vo_ctx* ctx)
         VO_HIP(ctx, hipEventRecord(ctx->ws->done, ctx->stream));
         ctx->ws->done_valid = true;
         ctx->ws->done_on_engine0 = false;
+        ctx->ws->done_lane = nullptr;
     }
     return VO_OK;
 }
@@ -1865,7 +1869,8 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
     if (ctx->cur_engine < 0 && sweep_group_has_engine(ctx, 0) && (rc = sweep_group_close(ctx, VO_GRP_CONSUMER))) return rc;
     const bool shared = ctx->ws == &ctx->main_ws;
     // (a sweep group's record on its closing stream: engine 0's stream stands behind it through `swept` -- no second wait)
-    if (shared && ctx->ws->done_valid && !(ctx->cur_engine == 0 && ctx->ws->done_on_engine0)) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ws->done, 0));
+    // (... or, on a lane, through the lane's order)
+    if (shared && ctx->ws->done_valid && !(ctx->cur_engine == 0 && ctx->ws->done_on_engine0) && !(ctx->ws->done_lane && ctx->ws->done_lane == ctx->stream)) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ws->done, 0));
     if (++ctx->sweep_gen_next <= 0) ctx->sweep_gen_next = 1;     // this run's generation: never 0 (FrameSlot::sweep_word)
     f.disp_gen = ctx->sweep_gen_next;
     const bool defer = deferred && ctx->cur_engine >= 0 && sweep_group_size(ctx) > 1 && ctx->sg.set && ctx->sg.ur < 100 && ctx->sg.mode == 0 &&
@@ -1888,7 +1893,8 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
                 return rc;
             SweepGroup::Member& m = G->m[G->n++];
             m = G->cand;
-            m.engine = ctx->cur_engine; m.f = &f; m.w = w; m.h = h;
+            m.engine = ctx->cur_engine; m.stream = ctx->stream; m.f = &f; m.w = w; m.h = h;
+            if (G->n == 1) G->lane = stream_is_lane(ctx, ctx->stream) ? ctx->stream : nullptr;
             m.post = post_job(ctx, f);
             G->launch = G->cand_launch; G->we_launch = G->cand_we_launch; G->nstrips = G->cand_nstrips;
             f.in_group = true;
@@ -1898,6 +1904,15 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
     }
     if (int rcd = sgbm_run_done(ctx)) return rcd;
     return rc;
+}
+
+hipStream_t dense_stream(const vo_ctx* ctx, int engine)
+{
+    // (a run that cannot defer whatever its geometry -- MODE_HH, the unfused schedule -- keeps to its engine's stream: a stream
+    //  of such pairs would otherwise travel on ONE lane, one pair after the other)
+    if (!lane_mode(ctx) || !ctx->sg.set || ctx->sg.ur >= 100 || ctx->sg.mode != 0) return ctx->la_stream[engine];
+    const SweepGroup* const G = ctx->grp;
+    return G && G->n > 0 && G->lane ? G->lane : ctx->lane[ctx->lane_next];
 }
 
 bool sweep_group_has_engine(const vo_ctx* ctx, int engine)
@@ -1957,6 +1972,26 @@ int engine_behind_chain(vo_ctx* ctx, int engine)
     return VO_OK;
 }
 
+// With lanes an engine's work lies on one stream at a time: its own (sparse and monocular submissions, dense ones with group size
+// 1) or a lane (dense ones while groups are in force: fronts, and the chain of the group it was a member of).  Given work on
+// another stream than the one that carries its latest work -- the other lane, when consecutive groups share engines; a lane
+// after its own stream or the reverse -- the stream it leaves gets one record and the stream it enters one wait: that orders
+// the new work behind everything that uses the engine's workspaces, staging and ORB scratch, the chain included.  On the same
+// stream the stream's order does it and nothing is enqueued.
+int engine_enter(vo_ctx* ctx, int engine, hipStream_t target)
+{
+    vo_ctx::SgbmWs& a = ctx->ws_alt[engine];
+    hipStream_t const from = a.on ? a.on : ctx->la_stream[engine];
+    if (from != target) {
+        VO_HIP(ctx, hipEventRecord(a.moved, from));
+        VO_HIP(ctx, hipStreamWaitEvent(target, a.moved, 0));
+    }
+    a.on = target == ctx->la_stream[engine] ? nullptr : target;
+    ctx->lane_used = a.on != nullptr;
+    ctx->stream = target;
+    return engine_behind_chain(ctx, engine);         // (per-engine groups, VO_GROUP_LANES=0: the chain ran on another engine's stream)
+}
+
 int sweep_group_close(vo_ctx* ctx, int why)
 {
     SweepGroup* const G = ctx->grp;
@@ -1973,8 +2008,18 @@ int sweep_group_close(vo_ctx* ctx, int why)
         // (where the fronts left it to the group), the sweep, the post filters: one launch each for all members -- and its
         // control block holds the sweep's ticket counter (its next front, which clears the block, is ordered behind the
         // launch there) ...
+        // With lanes the whole chain goes on the group's lane instead, behind the members' fronts: no wait for a member whose
+        // front lies there (all of them), no `swept` record and no `chain` to remember -- the lane's order is the ordering,
+        // and an engine that is next given work elsewhere brings one event of its own (engine_enter).  The next new group
+        // takes the other lane.
         SweepGroup::Member& last = G->m[n - 1];
         scope.enter(last.engine);
+        hipStream_t const lane = G->lane;
+        G->lane = nullptr;
+        if (lane) {
+            ctx->stream = lane;
+            ctx->lane_next = lane == ctx->lane[0] ? 1 : 0;
+        }
         DiagJobs jobs;
         WeJobs we;
         PostJobs post;
@@ -1988,6 +2033,7 @@ int sweep_group_close(vo_ctx* ctx, int why)
             jobs.j[i + 1] = G->m[i].job; we.j[i + 1] = G->m[i].we; post.j[i + 1] = G->m[i].post;
             main_member |= G->m[i].engine == 0;
             const vo_ctx::SgbmWs& a = ctx->ws_alt[G->m[i].engine];
+            if (lane && G->m[i].stream == lane) continue;
             if (!a.mid_valid || hipStreamWaitEvent(ctx->stream, a.mid, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "sweep group: waiting for a member's early stages failed");
         }
         if (!rc && G->we_launch) {
@@ -2007,7 +2053,7 @@ int sweep_group_close(vo_ctx* ctx, int why)
             }
             // the main workspace's run ends here, on this stream: a synchronous run on the main stream waits for this record
             if (!rc && main_member && ctx->main_ws.done) {
-                if (hipEventRecord(ctx->main_ws.done, ctx->stream) == hipSuccess) { ctx->main_ws.done_valid = true; ctx->main_ws.done_on_engine0 = false; }
+                if (hipEventRecord(ctx->main_ws.done, ctx->stream) == hipSuccess) { ctx->main_ws.done_valid = true; ctx->main_ws.done_on_engine0 = false; ctx->main_ws.done_lane = lane; }
                 else rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
             }
         }
@@ -2028,19 +2074,21 @@ int sweep_group_close(vo_ctx* ctx, int why)
             }
             for (int i = 0; i < n && !rc; i++)
                 if (hipEventRecord(G->m[i].f->ready, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
-            if (!rc && n > 1) {
+            if (!rc && n > 1 && !lane) {
                 if (hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
                 for (int i = 0; i + 1 < n && !rc; i++) ctx->ws_alt[G->m[i].engine].chain = swept;
             }
             // (engine 0's stream stands behind the main workspace's record only where it carried it)
-            if (!rc && main_member) ctx->main_ws.done_on_engine0 = last.engine == 0;
+            if (!rc && main_member) ctx->main_ws.done_on_engine0 = !lane && last.engine == 0;
         } else if (!rc) {
             // (the members' post passes are per member by construction: each finishes on its own engine's stream behind the sweep)
-            if (n > 1 && hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
+            // (on a lane: one after the other behind the sweep, in the members' own workspaces)
+            if (n > 1 && !lane && hipEventRecord(swept, ctx->stream) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipEventRecord failed");
             if (!rc) rc = sweep_member_back(ctx, last);
             for (int i = 0; i + 1 < n && !rc; i++) {
                 scope.enter(G->m[i].engine);
-                if (hipStreamWaitEvent(ctx->stream, swept, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed");
+                if (lane) ctx->stream = lane;
+                else if (hipStreamWaitEvent(ctx->stream, swept, 0) != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "hipStreamWaitEvent failed");
                 if (!rc) rc = sweep_member_back(ctx, G->m[i]);
             }
         }

@@ -16,6 +16,7 @@ int vo_fail(vo_ctx* ctx, int code, const char* fmt, ...)
 }
 
 static thread_local std::string g_create_err;
+static int lanes_ensure(vo_ctx* ctx);
 
 // ---- pinned transfer arena ---------------------------------------------------------------
 static const size_t ARENA_BASE = 4096;
@@ -181,6 +182,18 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         snprintf(ctx->devname, sizeof(ctx->devname), "%s (%s)", prop.name[0] ? prop.name : generic, prop.gcnArchName);
     }
     if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete ctx; return VO_E_HIP; }
+    // The hardware queues this process may open decide whether the look-ahead pairs' sweeps are grouped (sweep_group_size), and
+    // where they are -- by the budget or by VO_SWEEP_GROUP -- the two lane streams come right here: the runtime maps streams onto
+    // hardware queues in the order they are created and first used, so with four queues the main stream and the two lanes lie
+    // on three different ones and the null stream (dev_zero below) with the pose streams on the fourth (measured: created at
+    // the end of this function, a lane shared its queue with the pose stream and the flagship lost 9 % instead of gaining 7 %).
+    // A context with a queue per stream creates none, now or later, unless a setter puts groups in force.
+    // VO_GROUP_LANES=0: no lanes, sweep groups keep to the engines' own streams.
+    if (const char* e8 = getenv("VO_ENGINES")) { int v = atoi(e8); if (v >= 1 && v <= vo_ctx::MAX_ENGINES) ctx->n_engines = v; }
+    if (const char* eq = getenv("GPU_MAX_HW_QUEUES")) { int v = atoi(eq); if (v >= 1) ctx->hw_queues = v; }
+    if (const char* eg = getenv("VO_SWEEP_GROUP")) { int v = atoi(eg); if (v >= 1 && v <= VO_MAX_SWEEP_GROUP) ctx->sweep_group_req = v; }
+    if (const char* el = getenv("VO_GROUP_LANES")) ctx->lanes_on = atoi(el) != 0;
+    if (lanes_ensure(ctx)) { g_create_err = "hipStreamCreate failed (lane streams)"; vo_destroy(ctx); return VO_E_HIP; }
     (void)hipEventCreate(&ctx->ev0);
     (void)hipEventCreate(&ctx->ev1);
 
@@ -238,7 +251,6 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     ctx->sparse_r.n_kp_host = ctx->slot_words + 32;      // (words 29 .. 63 belong to no slot)
     DALLOC(ctx->d_sweep_errs, 64);
     if (dev_zero(ctx->d_sweep_errs, 64 * sizeof(int)) != hipSuccess) { g_create_err = "clearing the sweep error counter failed"; vo_destroy(ctx); return VO_E_HIP; }
-    if (const char* e8 = getenv("VO_ENGINES")) { int v = atoi(e8); if (v >= 1 && v <= vo_ctx::MAX_ENGINES) ctx->n_engines = v; }
     {
         // every engine owns a full SGBM workspace: cost volume + 3 aggregated volumes + boundary granules (< 1 volume) + planes.
         // Keep all of them within 40 % of what the device has free right now (frame slots, ORB scratch and the caller's staged
@@ -251,10 +263,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
         ctx->engines_fit = fit < 2 ? 2 : fit;
         if (ctx->n_engines > ctx->engines_fit) ctx->n_engines = ctx->engines_fit;
     }
-    // the hardware queues this process may open decide whether the look-ahead pairs' sweeps are grouped (sweep_group_size)
-    if (const char* eq = getenv("GPU_MAX_HW_QUEUES")) { int v = atoi(eq); if (v >= 1) ctx->hw_queues = v; }
-    if (const char* eg = getenv("VO_SWEEP_GROUP")) { int v = atoi(eg); if (v >= 1 && v <= VO_MAX_SWEEP_GROUP) ctx->sweep_group_req = v; }
-    if (const char* e9 = getenv("VO_POSE_STREAMS")) { int v = atoi(e9); if (v >= 1 && v <= vo_ctx::N_POSE_STREAMS) ctx->n_pose_streams = v; }
+    if (const char* e9 = getenv("VO_POSE_STREAMS")) { int v = atoi(e9); if (v >= 1 && v <= vo_ctx::N_POSE_STREAMS) { ctx->n_pose_streams = v; ctx->pose_streams_env = true; } }
     if (const char* e27 = getenv("VO_STAGGER")) ctx->tune_stagger = atoi(e27);
     if (const char* e25 = getenv("VO_DIAG_WAVES")) { const int v = atoi(e25); ctx->tune_diag_nwc = (v == 7 || v == 11 || v == 15) ? v : 0; }   // the three strip widths that are built
 #ifdef VO_TEST_HOOKS
@@ -267,7 +276,21 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     if (const char* e12 = getenv("VO_FAULT_PNP_RANGE")) ctx->fault_pnp_range = atoi(e12);
 #endif
     if (const char* e6 = getenv("VO_SWEEP_TY")) { int v = atoi(e6); if (v >= 4 && v <= 4096) ctx->tune_sweep_ty = v; }
+    // (the memory bound above may have put groups in force that the request alone did not)
+    if (lanes_ensure(ctx)) { g_create_err = "hipStreamCreate failed (lane streams)"; vo_destroy(ctx); return VO_E_HIP; }
     *out = ctx;
+    return VO_OK;
+}
+
+// the two lane streams exist once the group size in force is above 1 (lane_mode)
+static int lanes_ensure(vo_ctx* ctx)
+{
+    if (!ctx->lanes_on || sweep_group_size(ctx) <= 1) return VO_OK;
+    for (hipStream_t& l : ctx->lane)
+        if (!l) VO_HIP(ctx, hipStreamCreateWithFlags(&l, hipStreamNonBlocking));
+    // ... and the first pose stream behind them -- the one the pose steps keep to beside the lanes (pose_stream_count) -- so
+    // that it takes the queue after the lanes' whatever the number of engine streams created before the first pose step
+    if (!ctx->pose_streams[0]) VO_HIP(ctx, hipStreamCreateWithFlags(&ctx->pose_streams[0], hipStreamNonBlocking));
     return VO_OK;
 }
 
@@ -282,7 +305,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
         ctx->stage_cv.notify_all();
         ctx->stage_thread.join();
     }
-    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++) if (ctx->la_stream[k]) (void)hipStreamSynchronize(ctx->la_stream[k]);
+    (void)engine_streams_sync(ctx);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (int s = 0; s <= VO_NUM_SLOTS; s++) {
         FrameSlot& f = ctx->slots[s];
@@ -315,6 +338,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
         if (a.h2d_done) (void)hipEventDestroy(a.h2d_done);
         if (a.mid) (void)hipEventDestroy(a.mid);
         if (a.swept) (void)hipEventDestroy(a.swept);
+        if (a.moved) (void)hipEventDestroy(a.moved);
         if (ctx->la_stream[k]) (void)hipStreamDestroy(ctx->la_stream[k]);
     }
     for (vo_ctx::HostStage& hs : ctx->host_stage) {
@@ -323,6 +347,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     }
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    for (hipStream_t l : ctx->lane) if (l) (void)hipStreamDestroy(l);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -336,6 +361,7 @@ extern "C" int vo_set_engines(vo_ctx* ctx, int n)
         if (n > ctx->engines_fit) n = ctx->engines_fit;
         ctx->n_engines = n;
         ctx->next_engine %= n;          // (the stagger wait and the monocular span index modulo n_engines: nothing else remembers one)
+        if (int rc = lanes_ensure(ctx)) return rc;
     }
     return ctx->n_engines;
 }
@@ -348,6 +374,7 @@ extern "C" int vo_set_sweep_group(vo_ctx* ctx, int n)
     if (n > 0) {
         if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;
         ctx->sweep_group_req = n > VO_MAX_SWEEP_GROUP ? VO_MAX_SWEEP_GROUP : n;
+        if (int rc = lanes_ensure(ctx)) return rc;
     }
     return sweep_group_size(ctx);
 }
@@ -382,8 +409,7 @@ extern "C" int vo_synchronize(vo_ctx* ctx)
 {
     if (!ctx) return VO_E_ARG;
     if (int rc = sweep_group_close(ctx, VO_GRP_CONSUMER)) return rc;
-    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
-        if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
+    VO_HIP(ctx, engine_streams_sync(ctx));
     for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
         for (int k = 0; k < vo_ctx::alt_count(kind); k++)
             if (ctx->alt(kind, k).stream) VO_HIP(ctx, hipStreamSynchronize(ctx->alt(kind, k).stream));
@@ -670,6 +696,7 @@ static int engine_prepare(vo_ctx* ctx, int engine, bool want_sgbm)
     if (!ctx->ws_alt[engine].mid) {
         VO_HIP(ctx, hipEventCreateWithFlags(&ctx->ws_alt[engine].mid, hipEventDisableTiming));
         VO_HIP(ctx, hipEventCreateWithFlags(&ctx->ws_alt[engine].swept, hipEventDisableTiming));
+        VO_HIP(ctx, hipEventCreateWithFlags(&ctx->ws_alt[engine].moved, hipEventDisableTiming));
     }
     if (!ctx->la_stage[engine]) {
         VO_HIP(ctx, hipMalloc((void**)&ctx->la_stage[engine], ctx->stage_bytes * 2 + 256));
@@ -772,9 +799,13 @@ static int prefetch_pair(vo_ctx* ctx, int slot, const uint8_t* srcL, const uint8
     if (sp) { f.mono_serial = 0; f.kp_params[0] = f.kp_params[1] = f.kp_params[2] = f.kp_params[3] = -1; }   // (as vo_sparse_stereo)
     {
         EngineScope on_engine(ctx, engine);          // ctx->stream / staging / SGBM + ORB workspaces are the engine's in here
-        rc = engine_behind_chain(ctx, engine);
+        // a dense pair that may defer goes on the open group's lane while groups are in force (ingest, front, and the whole chain
+        // where the geometry then keeps it from deferring), everything else on the engine's own stream
+        hipStream_t const target = sp ? ctx->la_stream[engine] : dense_stream(ctx, engine);
+        const bool on_lane = stream_is_lane(ctx, target);
+        rc = engine_enter(ctx, engine, target);
         const int stagger = ctx->tune_stagger >= 0 ? ctx->tune_stagger : (7 * ctx->n_engines + 8) / 16;
-        if (!sp && stagger > 0 && stagger < ctx->n_engines) {          // (the stagger spreads SGBM stages: a sparse pair has none)
+        if (!sp && !on_lane && stagger > 0 && stagger < ctx->n_engines) {          // (the stagger spreads SGBM stages: a sparse pair has none; a lane is in order already)
             vo_ctx::SgbmWs& p = ctx->ws_alt[(engine - stagger + ctx->n_engines) % ctx->n_engines];
             if (p.mid_valid) (void)hipStreamWaitEvent(ctx->stream, p.mid, 0);
         }
@@ -916,7 +947,7 @@ extern "C" int vo_prefetch_staged_mono(vo_ctx* ctx, int slot, int index, int nfe
     f.w = w; f.h = h; f.has_kp = false; f.kp_depth = false; f.sp_pending = false; f.n_kp = 0; f.kp_pending = false; f.has_disp = false;
     {
         EngineScope on_engine(ctx, engine);
-        rc = engine_behind_chain(ctx, engine);       // (the engine's ORB scratch may still serve the group it was last a member of)
+        rc = engine_enter(ctx, engine, ctx->la_stream[engine]);   // (the engine's ORB scratch may still serve the group it was last a member of)
         if (!rc) rc = slot_before_overwrite(ctx, f);
         if (!rc) {
             StageTimer t(ctx, VO_T_UPLOAD);
@@ -1298,8 +1329,7 @@ extern "C" int vo_get_stage_timeline(vo_ctx* ctx, int cap, int32_t* stage_out, i
     VO_HIP(ctx, hipSetDevice(ctx->device));
     // brackets lie on the engines' and the pose steps' streams as well (the open sweep group, if any, stays open: its
     // members' fronts are complete brackets, the rest has not been recorded yet)
-    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
-        if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
+    VO_HIP(ctx, engine_streams_sync(ctx));
     for (int kind : { vo_ctx::ALT_POSE, vo_ctx::ALT_MONO })
         for (int k = 0; k < vo_ctx::alt_count(kind); k++)
             if (ctx->alt(kind, k).stream) VO_HIP(ctx, hipStreamSynchronize(ctx->alt(kind, k).stream));
@@ -1364,8 +1394,7 @@ extern "C" int vo_measure_copy(vo_ctx* ctx, int64_t bytes, int reps, int nontemp
     if (bytes <= 0 || !ctx->ws->C || !ctx->ws->S) return vo_fail(ctx, VO_E_STATE, "vo_measure_copy: no volumes to copy between");
     VO_HIP(ctx, hipSetDevice(ctx->device));
     // the volumes belong to the main workspace (engine 0 uses it too): nothing of the pipeline may still be running
-    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
-        if (ctx->la_stream[k]) VO_HIP(ctx, hipStreamSynchronize(ctx->la_stream[k]));
+    VO_HIP(ctx, engine_streams_sync(ctx));
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     hipEvent_t e0, e1;
     VO_HIP(ctx, hipEventCreate(&e0));

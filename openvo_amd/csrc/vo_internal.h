@@ -154,6 +154,18 @@ struct vo_ctx {
     // pair's latency-bound kernels overlap another's bandwidth-bound ones)
     static const int MAX_ENGINES = 24;
     hipStream_t la_stream[MAX_ENGINES] = {};
+    // Lane streams (DESIGN 4f'''): while the group size in force is above 1, every dense look-ahead submission that may defer goes on the open
+    // group's lane instead of its engine's stream, the group's chain follows on the same lane, and consecutive groups alternate
+    // between the two lanes -- group g + 1's fronts run beside group g's chain, and nothing of one group can queue up behind the
+    // other's chain in a hardware queue the two share.  Created at vo_create where groups are in force from the start -- the
+    // first streams behind the main one -- otherwise when a setter puts them in force; used by nothing else.  An engine
+    // whose latest work lies on another stream than the one it is given work on now is ordered by ONE event (engine_enter).
+    // lanes_on: VO_GROUP_LANES (0 = every engine keeps to its own stream, as before the lanes).  lane_next: the lane the next
+    // new group takes (the one the group closed last did not use).
+    hipStream_t lane[2] = {nullptr, nullptr};
+    bool lanes_on = true;
+    bool lane_used = false;          // the latest look-ahead submission went on a lane (a dense stream is running on the lanes)
+    int lane_next = 0;
     int cur_engine = -1;
     // VO_STAGGER = K: a pair's early stages (cost volume, W + E) start only after those of the pair K places before it have finished
     // (an event wait on the engine's stream; default: 7/16 of the engines, 0 = off).  Keeps the pairs in flight spread over the stages
@@ -178,6 +190,7 @@ struct vo_ctx {
         hipEvent_t done = nullptr;       // end of the latest SGBM run in this workspace (any stream)
         bool done_valid = false;
         bool done_on_engine0 = false;    // ... and look-ahead engine 0's stream is already ordered behind that record
+        hipStream_t done_lane = nullptr; // ... which a sweep group left on this lane stream: work on that lane is behind it already
         bool ready = false;
         OrbWs orb;
         uint8_t* pinned = nullptr;       // host staging of vo_prefetch_pair (two raw images)
@@ -190,6 +203,9 @@ struct vo_ctx {
         hipEvent_t chain = nullptr;      // borrowed: `swept` of the engine that closed the group this engine was last a non-closing member of,
                                          // until this engine's stream has been ordered behind it (engine_behind_chain); a later close on that
                                          // engine's stream re-records it later on the same stream, which only orders more
+                                         // (per-engine streams only: with lanes the stream order and `moved` do all of this)
+        hipStream_t on = nullptr;        // the lane stream that carries this engine's latest work (nullptr: the engine's own stream)
+        hipEvent_t moved = nullptr;      // recorded on the stream the engine leaves when it is given work on another one (engine_enter)
     } ws_alt[MAX_ENGINES];           // [0]: only its ORB scratch / staging / events are used (engine 0 works in main_ws)
     SgbmWs main_ws;
     SgbmWs* ws = &main_ws;
@@ -323,6 +339,11 @@ struct vo_ctx {
     static const int N_POSE_ALT = VO_NUM_POSE_ASYNC;
     static const int N_POSE_STREAMS = 3;
     int n_pose_streams = N_POSE_STREAMS;     // VO_POSE_STREAMS (1..3): fewer when the GPU's hardware queues are shared with other processes
+    // While dense pairs travel on the lanes, a pose step parked on a slot's `ready` event holds back everything behind it in
+    // its hardware queue: on a queue it shares with a lane that is the lane's next fronts, until the OTHER lane's chain is over.
+    // Without VO_POSE_STREAMS in the environment the steps then keep to what the queue budget leaves beside the main stream and
+    // the two lanes (hw_queues - 3, at least one: ONE stream with four queues) -- pose_stream_count, asked when a step is begun.
+    bool pose_streams_env = false;
     hipStream_t pose_streams[N_POSE_STREAMS] = {};
     struct PoseAlt : AsyncAlt {
         int slot_a = -1, slot_b = -1;
@@ -507,11 +528,33 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL = null
 enum { VO_GRP_FULL = 0, VO_GRP_CONSUMER = 1, VO_GRP_FLUSH = 2, VO_GRP_OTHER = 3 };
 // the group size in force: the request if there is one, else 1 with a hardware queue per stream (GPU_MAX_HW_QUEUES >= engines
 // + 4) and VO_SWEEP_GROUP_FEW_QUEUES without; never above the number of engines (an engine holds one member at a time)
+// With lanes the automatic size is at most half the engines: two consecutive groups then use disjoint engines (two banks), and
+// no front ever waits for the other lane's chain.
 #define VO_SWEEP_GROUP_FEW_QUEUES 12
 static inline int sweep_group_size(const vo_ctx* ctx)
 {
-    int b = ctx->sweep_group_req > 0 ? ctx->sweep_group_req : (ctx->hw_queues >= ctx->n_engines + 4 ? 1 : VO_SWEEP_GROUP_FEW_QUEUES);
+    int few = VO_SWEEP_GROUP_FEW_QUEUES;
+    if (ctx->lanes_on && few > ctx->n_engines / 2) few = ctx->n_engines >= 2 ? ctx->n_engines / 2 : 1;
+    int b = ctx->sweep_group_req > 0 ? ctx->sweep_group_req : (ctx->hw_queues >= ctx->n_engines + 4 ? 1 : few);
     return b < ctx->n_engines ? b : ctx->n_engines;
+}
+// lane mode is in force exactly while groups are: with group size 1 every launch and stream is the per-engine one
+static inline bool lane_mode(const vo_ctx* ctx) { return ctx->lanes_on && ctx->lane[0] && ctx->lane[1] && sweep_group_size(ctx) > 1; }
+static inline int pose_stream_count(const vo_ctx* ctx)
+{
+    int n = ctx->n_pose_streams;
+    if (!ctx->pose_streams_env && ctx->lane_used && lane_mode(ctx) && n > ctx->hw_queues - 3) n = ctx->hw_queues - 3 > 1 ? ctx->hw_queues - 3 : 1;
+    return n;
+}
+static inline bool stream_is_lane(const vo_ctx* ctx, hipStream_t s) { return s && (s == ctx->lane[0] || s == ctx->lane[1]); }
+// every stream look-ahead engines' work can lie on has drained: the engines' own and the two lanes
+static inline hipError_t engine_streams_sync(const vo_ctx* ctx)
+{
+    for (int k = 0; k < 2; k++)
+        if (ctx->lane[k]) { const hipError_t e = hipStreamSynchronize(ctx->lane[k]); if (e != hipSuccess) return e; }
+    for (int k = 0; k < vo_ctx::MAX_ENGINES; k++)
+        if (ctx->la_stream[k]) { const hipError_t e = hipStreamSynchronize(ctx->la_stream[k]); if (e != hipSuccess) return e; }
+    return hipSuccess;
 }
 // The open group's members finish on the closing member's stream: W + E, the sweep, the post filters and the ORB chain as one
 // launch per kernel for all of them, then every member's `ready` record.  No other member's stream receives anything: an engine
@@ -519,6 +562,13 @@ static inline int sweep_group_size(const vo_ctx* ctx)
 // failure every member's slot is left holding nothing.
 int sweep_group_close(vo_ctx* ctx, int why);
 int engine_behind_chain(vo_ctx* ctx, int engine);
+// The engine is about to be given work on `target` (its own stream or a lane), inside its EngineScope: ctx->stream becomes
+// `target`, and where the engine's latest work lies on another stream, that stream gets an event record and `target` one wait
+// for it (host-side decision, no host wait).  Includes engine_behind_chain.
+int engine_enter(vo_ctx* ctx, int engine, hipStream_t target);
+// the stream a dense look-ahead submission on `engine` goes on now: the open group's lane (without one: the lane the next
+// group will take) in lane mode for a run that may defer (MODE_SGBM, the fused schedule), the engine's own otherwise
+hipStream_t dense_stream(const vo_ctx* ctx, int engine);
 bool sweep_group_has_engine(const vo_ctx* ctx, int engine);
 int sweep_group_members(const vo_ctx* ctx);
 void sweep_group_free(vo_ctx* ctx);
