@@ -259,6 +259,9 @@ def lib():
         plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+        plant = getattr(L, "vo_test_plant_dense", None)          # (likewise)
+        if plant is not None:
+            plant.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp]
         plant = getattr(L, "vo_test_plant_map", None)            # (likewise)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
@@ -714,6 +717,22 @@ class Context:
             if len(rdesc) != n:
                 raise ValueError("one right descriptor per keypoint")
         self._ck(self._lib.vo_test_plant_keypoints(self._h, int(slot), n, _p(xy), _p(desc), _p(xyz), _p(rdesc)))
+
+    def plant_dense(self, slot, disp16, xy, desc):
+        """Test-only build of the library: a disparity image (h, w) int16 in 1/16 px and n keypoints (xy (n, 2), desc (n, 32)) straight
+        into a slot, which then stands as sgbm_compute followed by an ORB extraction leaves it (vo_test_plant_dense): the keypoints
+        carry no depth.  Positions outside the crop under the ROI in force are refused.  The product library has no such entry."""
+        if not hasattr(self._lib, "vo_test_plant_dense"):
+            raise RuntimeError("plant_dense needs the test-only build of the library (libvo355_hooks.so)")
+        disp16 = _c(disp16, np.int16)
+        if disp16.ndim != 2:
+            raise ValueError("disp16 is a (h, w) image")
+        xy, desc = _c(xy, np.float32).reshape(-1, 2), _c(desc, np.uint8).reshape(-1, 32)
+        n = len(xy)
+        if len(desc) != n:
+            raise ValueError("one descriptor per keypoint")
+        h, w = disp16.shape
+        self._ck(self._lib.vo_test_plant_dense(self._h, int(slot), w, h, _p(disp16), n, _p(xy), _p(desc)))
 
     def download_keypoint_depth(self, slot):
         """-> (xyz (n, 3) float32, disparity (n,) float32) of a slot whose keypoints carry depth (VoError otherwise)."""

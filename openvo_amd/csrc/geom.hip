@@ -151,11 +151,12 @@ extern "C" int vo_points3d_at(vo_ctx* ctx, int slot, const float* xy, int n, flo
     if (!xy || !xyz_out || !status_out) return vo_fail(ctx, VO_E_ARG, "vo_points3d_at: null pointer");
     VO_HIP(ctx, hipSetDevice(ctx->device));
     { int rcw = slot_wait(ctx, f); if (rcw) return rcw; }
-    // keypoints must lie inside the cropped image, as img[floor_y, floor_x] requires
+    // keypoints must lie inside the cropped image, as img[floor_y, floor_x] requires (compared as floats: for 0 <= x that is
+    // (int)x < cw, and unlike the cast it also refuses +inf and values beyond the range of int)
     int cw = (ctx->has_roi ? (ctx->roi[2] < f.w ? ctx->roi[2] : f.w) - ctx->roi[0] : f.w);
     int chh = (ctx->has_roi ? (ctx->roi[3] < f.h ? ctx->roi[3] : f.h) - ctx->roi[1] : f.h);
     for (int i = 0; i < n; i++)
-        if (!(xy[2 * i] >= 0 && xy[2 * i + 1] >= 0 && (int)xy[2 * i] < cw && (int)xy[2 * i + 1] < chh))
+        if (!(xy[2 * i] >= 0 && xy[2 * i + 1] >= 0 && xy[2 * i] < (float)cw && xy[2 * i + 1] < (float)chh))
             return vo_fail(ctx, VO_E_ARG, "keypoint %d (%g,%g) outside the %dx%d cropped image", i, xy[2 * i], xy[2 * i + 1], cw, chh);
     int rc = xfer_h2d(ctx, ctx->mw->xy_a, xy, (size_t)n * 8);
     if (rc) return rc;
@@ -185,7 +186,7 @@ extern "C" int vo_bilinear_at(vo_ctx* ctx, const float* img3d, int w, int h, con
     if (n < 0 || n > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "n=%d exceeds keypoint capacity", n);
     if (n == 0) return VO_OK;
     for (int i = 0; i < n; i++)
-        if (!(xy[2 * i] >= 0 && xy[2 * i + 1] >= 0 && (int)xy[2 * i] < w && (int)xy[2 * i + 1] < h))
+        if (!(xy[2 * i] >= 0 && xy[2 * i + 1] >= 0 && xy[2 * i] < (float)w && xy[2 * i + 1] < (float)h))      // (as floats: see vo_points3d_at)
             return vo_fail(ctx, VO_E_ARG, "point %d outside the image", i);
     VO_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_ws(ctx, &ctx->img3_ws, &ctx->img3_ws_bytes, (size_t)w * h * 12);

@@ -1535,6 +1535,52 @@ extern "C" int vo_test_plant_keypoints(vo_ctx* ctx, int slot, int n, const float
     return VO_OK;
 }
 
+// ... and a DENSE slot: a w x h disparity image (int16, 1/16 px) and n keypoints with their descriptors, after which the slot stands
+// as a synchronous vo_sgbm_compute followed by an ORB extraction leaves it (a disparity of a fresh, healthy generation; keypoints
+// that carry NO depth) -- the seam through which the tests drive the bilinear lookup of vo_points3d_at / vo_point_clouds and the
+// dense arm of the fused pose and PnP steps.  disp16 (h, w) int16, xy (n, 2) float32, desc (n, 32).  Everything is validated BEFORE
+// the slot is touched: the kernels trust a keypoint to lie inside the crop under the ROI in force (as ORB's do), so a position
+// outside it is refused here with the condition vo_points3d_at checks on the host -- set Q and the ROI first, and keep the ROI.
+extern "C" int vo_test_plant_dense(vo_ctx* ctx, int slot, int w, int h, const int16_t* disp16, int n, const float* xy, const uint8_t* desc)
+{
+    if (!ctx || slot < 0 || slot >= VO_NUM_SLOTS || n < 0) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_dense: bad argument");
+    if (w > ctx->max_w || h > ctx->max_h || w < 16 || h < 16) return vo_fail(ctx, VO_E_CAP, "vo_test_plant_dense: image %dx%d exceeds context %dx%d", w, h, ctx->max_w, ctx->max_h);
+    if (n > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "vo_test_plant_dense: %d keypoints exceed capacity %d", n, ctx->kp_cap);
+    if (!disp16 || (n > 0 && (!xy || !desc))) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_dense: null pointer");
+    const int cw = ctx->has_roi ? (ctx->roi[2] < w ? ctx->roi[2] : w) - ctx->roi[0] : w;
+    const int ch = ctx->has_roi ? (ctx->roi[3] < h ? ctx->roi[3] : h) - ctx->roi[1] : h;
+    if (cw <= 0 || ch <= 0) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_dense: the ROI leaves nothing of a %dx%d image", w, h);
+    for (int i = 0; i < n; i++)      // (compared as floats: for 0 <= x that is (int)x < cw, and it also holds for inf and for values no int holds)
+        if (!(xy[2 * i] >= 0 && xy[2 * i + 1] >= 0 && xy[2 * i] < (float)cw && xy[2 * i + 1] < (float)ch))
+            return vo_fail(ctx, VO_E_ARG, "vo_test_plant_dense: keypoint %d (%g,%g) outside the %dx%d cropped image", i, xy[2 * i], xy[2 * i + 1], cw, ch);
+    FrameSlot& f = ctx->slots[slot];
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = slot_wait(ctx, f)) || (rc = slot_before_overwrite(ctx, f))) return rc;     // (steps begun ahead may still read the slot)
+    f.has_pair = false; f.has_disp = false;      // (the images the slot may hold belong to another disparity: nothing recomputes from them)
+    f.has_kp = false; f.kp_depth = false; f.kp_pending = false; f.sp_pending = false; f.sp_ahead = false;
+    f.mono_serial = 0;
+    f.kp_params[0] = f.kp_params[1] = f.kp_params[2] = f.kp_params[3] = -1;
+    f.sp_req.nfeatures = -1;
+    if ((rc = xfer_h2d(ctx, f.disp16, disp16, (size_t)w * h * 2))) return rc;
+    if ((rc = xfer_h2d(ctx, f.kp_xy, xy, (size_t)n * 8))) return rc;
+    if ((rc = xfer_h2d(ctx, f.desc, desc, (size_t)n * 32))) return rc;
+    if (n > 0) {
+        VO_HIP(ctx, hipMemsetAsync(f.kp_size, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_angle, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_resp, 0, (size_t)n * 4, ctx->stream));
+        VO_HIP(ctx, hipMemsetAsync(f.kp_oct, 0, (size_t)n * 4, ctx->stream));
+    }
+    if ((rc = xfer_flush(ctx))) return rc;
+    if (++ctx->sweep_gen_next <= 0) ctx->sweep_gen_next = 1;     // a generation of its own, as every SGBM run gets: no sweep ever wrote it into the slot's word
+    f.disp_gen = ctx->sweep_gen_next;
+    f.w = w; f.h = h;
+    *f.n_kp_host = n;
+    f.n_kp = n;
+    f.has_disp = true; f.has_kp = true;
+    return VO_OK;
+}
+
 // ... and n landmarks written straight into a map (vo_map_create), which then stands as n insertions would have left it -- with
 // any float32 bits as positions (NaN, inf: what no update ever inserts) and chosen obs / last.  The last view is void; the largest
 // `last` counts as a serial used.  xyz (n, 3) float32, desc / rdesc (n, 32), octave / obs / last (n) int32, last >= 0, obs >= 1.

@@ -54,7 +54,9 @@ class PnpCase:
     """nq query keypoints, M planted matches; bad: the matches (positions in match order) whose 3-D point is non-finite, or "all";
     n_in inliers among the usable ones (None: 70 %), at the compacted positions `inliers` lists (None: drawn); scene: the seed of
     the construction; dup: that many further queries copy the descriptor of a train that is already matched (what the cross-check
-    must remove); loop / window / cross / roi: the match flags and the ROI origin; collinear: the matched 3-D points lie on one line."""
+    must remove); loop / window / cross / roi: the match flags and the ROI origin; collinear: the matched 3-D points lie on one line.
+    K4: the intrinsics the model scores under (a subclass with another camera sets its own)."""
+    K4 = K4
 
     def __init__(self, name, nq, M, bad=(), n_in=None, noise=0.0, iters=ITERS, seed=SEED, refine=0, scene=0, inliers=None, cross=False, loop=None,
                  window=None, roi=None, dup=0, collinear=False):
@@ -159,7 +161,7 @@ class PnpCase:
         X, q, t = np.ascontiguousarray(Xa[ok]), mq[ok], mt[ok]
         org = np.float32([0, 0] if self.roi is None else self.roi[:2])
         uv = np.ascontiguousarray((self.xy_b[t] + org).astype(np.float32)).reshape(-1, 2)
-        n = len(q)
+        n, K4 = len(q), self.K4
         m = dict(mq=mq, mt=mt, M=len(mq), n=n, ok=ok, q=q, t=t, X=X, uv=uv)
         if n >= 4:
             r = O.ransac_pnp(X, uv, K4, self.iters, THR, self.seed)

@@ -744,3 +744,45 @@ def test_ransac_fuzz_against_the_cpu_restatement(oracle, seed):
                 assert np.allclose(g["Rt"], r["Rt"], rtol=0, atol=1e-10, equal_nan=True), ("pnp", n, it)
     finally:
         ctx.close()
+
+
+def test_remap_with_maps_that_leave_the_source(oracle):
+    """k_remap where the rectification maps of the rigs never go: integer parts -32768, -2, -1, 0, sw - 2, sw - 1, sw, 32767 (and the
+    same in y) in every combination, all 1024 fraction codes with random bits 10 .. 15 set in map2, a map (64 x 48) that is not the
+    size of the source (40 x 30).  Every source read of the kernel stands behind an unsigned compare of its own coordinate against
+    sw / sh, so these maps read nothing outside the source: constant border 0.  The weights sum to 2^15: an all-255 source gives
+    exactly 255 wherever the four taps lie inside and falls off at the border."""
+    from openvo_amd import _native
+    sw, sh, mw, mh = 40, 30, 64, 48
+    xs, ys = [-32768, -2, -1, 0, sw - 2, sw - 1, sw, 32767], [-32768, -2, -1, 0, sh - 2, sh - 1, sh, 32767]
+    rng = np.random.default_rng(77)
+    ctx = _native.Context(0, 64, 64, 16, 16)
+    try:
+        seen_xy, seen_f = set(), set()
+        for rnd in range(4):
+            n = mw * mh
+            combo = (np.arange(n) + rng.integers(0, 64)) % 64
+            sx, sy = np.asarray(xs)[combo % 8], np.asarray(ys)[combo // 8]
+            inner = rng.random(n) < 0.25                                   # a quarter of the pixels: integer parts around and inside the source
+            sx = np.where(inner, rng.integers(-3, sw + 3, n), sx)
+            sy = np.where(inner, rng.integers(-3, sh + 3, n), sy)
+            frac = rng.permutation(np.arange(n) % 1024)
+            map1 = np.stack([sx, sy], 1).astype(np.int16).reshape(mh, mw, 2)
+            map2 = (frac | (rng.integers(0, 64, n) << 10)).astype(np.uint16).reshape(mh, mw)
+            seen_xy |= set(zip(sx[~inner].tolist(), sy[~inner].tolist()))
+            seen_f |= set(frac.tolist())
+            assert (map2 >> 10).any()
+            ctx.set_rectify_maps(rnd % 2, map1, map2)
+            inside = ((sx >= 0) & (sx + 1 < sw) & (sy >= 0) & (sy + 1 < sh)).reshape(mh, mw)
+            for src in (rng.integers(0, 256, (sh, sw), dtype=np.uint8), np.full((sh, sw), 255, np.uint8)):
+                got, ref = ctx.remap(rnd % 2, src, (mh, mw)), oracle.remap_bilinear(src, map1, map2)
+                assert np.array_equal(got, ref), "round %d: %d pixels differ from the oracle" % (rnd, int((got != ref).sum()))
+            assert (got[inside] == 255).all() and inside.sum() > 100            # (got: the all-255 source)
+            fx, fy = (frac & 31).reshape(mh, mw), (frac >> 5).reshape(mh, mw)
+            cut = ((sx.reshape(mh, mw) == sw - 1) & (fx > 0)) | ((sy.reshape(mh, mw) == -1) & (fy < 32))
+            assert (got[cut] < 255).all() and cut.sum() > 100                   # a tap of non-zero weight lies outside: darker
+            far = (np.abs(sx) > 1000).reshape(mh, mw)
+            assert not got[far].any() and far.sum() > 100
+        assert seen_xy == {(x, y) for x in xs for y in ys} and seen_f == set(range(1024))
+    finally:
+        ctx.close()

@@ -33,8 +33,8 @@ CPU figures of the restatement (tests/test_planted_pnp_ref.py prints them; they 
                                     2.0e-4; 2400: 2.2e-3 -> 2.6e-4; noise-free 6 / 7 of 12: 1.6e-7 -> 5.3e-8, 3.5e-7 -> 2.4e-7
     flags at (nq, M) = (600, 520)   cross-check 520 -> 480 matches, loop <= 48: 461, window (80, 60): 397, all three + ROI (3, 5): 358
 
-Not covered here.  The dense arm of k_pnp_prep (bilinear lookup, status 1 / 2, flag bit 0): planted slots are sparse slots, the corridor
-tests stay its coverage.  Refit status -1: a winner with six inliers or more contains its own three non-collinear sample points, so
+Not covered here.  The dense arm of k_pnp_prep (bilinear lookup, status 1 / 2, flag bit 0): the slots planted here are sparse slots;
+tests/test_gpu_planted_dense.py plants dense ones (a disparity image under the keypoints) and drives that arm.  Refit status -1: a winner with six inliers or more contains its own three non-collinear sample points, so
 J^T J has full rank, and float32-finite inliers give finite float64 sums -- no honest input reaches it; it stays covered by
 tests/test_pnp_refine_ref.py on the CPU and tests/test_pnp_pair_host.py on the odometer's side, and no hook forces it.
 

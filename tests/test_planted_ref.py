@@ -149,5 +149,6 @@ def test_only_the_test_build_exports_the_planting_entry():
     prod = os.path.join(ROOT, "openvo_amd", "libvo355.so")
     hooks = os.path.join(ROOT, "openvo_amd", "libvo355_hooks.so")
     assert os.path.exists(prod) and os.path.exists(hooks), "build the libraries first (__graft_entry__.build())"
-    assert not hasattr(ctypes.CDLL(prod), "vo_test_plant_keypoints")
-    assert hasattr(ctypes.CDLL(hooks), "vo_test_plant_keypoints")
+    for entry in ("vo_test_plant_keypoints", "vo_test_plant_dense"):
+        assert not hasattr(ctypes.CDLL(prod), entry), entry
+        assert hasattr(ctypes.CDLL(hooks), entry), entry
