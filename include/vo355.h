@@ -100,6 +100,11 @@ int vo_lookahead_drop(vo_ctx* ctx, int slot);
  * of the group before it.  Without a request B follows the queue budget: 1 with a queue per stream, min(12, engines / 2) with
  * fewer.  VO_GROUP_LANES=0 in the environment at vo_create keeps every engine on its own stream (B without a request is then
  * min(12, engines)).  Sparse and monocular look-ahead submissions always use the engines' own streams.
+ * On a lane the members also leave their planes and cost volumes to the group: F members' worth, or however many are pending when
+ * the group closes, go in one launch each (F = 8 without a request).  Whatever would change what a pending launch still reads
+ * -- vo_stage_pairs_alloc, vo_stage_pair, a setter, a consumer of a member's slot, vo_synchronize -- has them launched first,
+ * with the parameters in force when each pair was submitted.  VO_GROUP_FRONTS=n in the environment at vo_create sets F; 0
+ * gives every pair its own two launches, as without lanes.
  * vo_set_sweep_group: n <= 0 only asks, otherwise B = min(n, VO_MAX_SWEEP_GROUP) from now on (the open group is closed);
  * returns the size in force (never above the number of engines) or a negative status.  VO_SWEEP_GROUP in the environment
  * does the same at vo_create.  vo_lookahead_flush closes the open group and returns the size in force as well -- 1 tells a

@@ -106,11 +106,34 @@ __device__ __forceinline__ void chan_bounds(const uint8_t* img, int W, int H, in
     hi = max(max(vl, vr), v);
 }
 
-__global__ void k_sgbm_planes(const uint8_t* __restrict__ L, const uint8_t* __restrict__ R, int W, int H,
-                              int ft, uint32_t* __restrict__ PL, uint32_t* __restrict__ PR, int* __restrict__ d2key,
-                              int* __restrict__ sw_ctl, int sw_ctl_words, uint32_t* __restrict__ c_dummy, int dummy_words, uint32_t P2_2,
-                              uint8_t* __restrict__ keepL, uint8_t* __restrict__ keepR)
+// The two front kernels (planes, cost volume) serve up to VO_MAX_SWEEP_GROUP pairs of one geometry per launch, like the W + E and
+// post kernels behind them (FrontJobs: what differs between the members of a sweep group; a pair on its own is a table of one).
+// The member is a grid dimension of its own (planes: blockIdx.z; cost sweep: blockIdx.y, so that the linear workgroup id modulo 8
+// -- the XCD a tile lands on -- is what it is for one pair), and the table's pointers arrive as scalar loads from the kernel
+// arguments.
+struct FrontJob {
+    const uint8_t *L, *R;            // the rectified pair (the slot's copy, or where it lies in HBM: keepL / keepR then take the copy)
+    uint32_t *planesL, *planesR;
+    int* d2key;                      // null with the fused schedule's LDS post rows
+    int* sw_ctl;
+    uint32_t* dummy;                 // the row of P2 cells behind the used part of C
+    uint8_t *keepL, *keepR;
+    int16_t* C;
+};
+struct FrontJobs { FrontJob j[VO_MAX_SWEEP_GROUP]; };
+
+__global__ void k_sgbm_planes(FrontJobs jobs, int W, int H, int ft, int sw_ctl_words, int dummy_words, uint32_t P2_2)
 {
+    const FrontJob& J = jobs.j[blockIdx.z];
+    const uint8_t* __restrict__ const L = J.L;
+    const uint8_t* __restrict__ const R = J.R;
+    uint32_t* __restrict__ const PL = J.planesL;
+    uint32_t* __restrict__ const PR = J.planesR;
+    int* __restrict__ const d2key = J.d2key;
+    int* __restrict__ const sw_ctl = J.sw_ctl;
+    uint32_t* __restrict__ const c_dummy = J.dummy;
+    uint8_t* __restrict__ const keepL = J.keepL;
+    uint8_t* __restrict__ const keepR = J.keepR;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     // (a few hundred workgroups walking the rows instead of one per 256 pixels: a short kernel's workgroups each have to win a
     // slot from the dispatcher against the other pairs' sweeps)
@@ -194,9 +217,12 @@ __device__ __forceinline__ uint32_t bt_regs(uint32_t lw0, uint32_t lw1, const ui
 }
 
 template <int XT, int SW2>
-__global__ void __launch_bounds__(128) k_sgbm_cost_sweep(const uint32_t* __restrict__ PL, const uint32_t* __restrict__ PR,
-                                                        SgbmGeom g, int TY, int16_t* __restrict__ C)
+__global__ void __launch_bounds__(128) k_sgbm_cost_sweep(FrontJobs jobs, SgbmGeom g, int TY)
 {
+    const FrontJob& J = jobs.j[blockIdx.y];
+    const uint32_t* __restrict__ const PL = J.planesL;
+    const uint32_t* __restrict__ const PR = J.planesR;
+    int16_t* __restrict__ const C = J.C;
     constexpr int WIN = 2 * SW2 + 1, NC = XT + 2 * SW2;
     // The vertical window's ring -- the horizontal sums of the last WIN rows per column and lane.  Blocks up to 5 x 5: 40 registers
     // (the row loop is unrolled by WIN, so every ring index is a constant); the LDS the sweep then asks for is 3.3 KB per wave and
@@ -416,9 +442,13 @@ __global__ void __launch_bounds__(128) k_sgbm_cost_sweep(const uint32_t* __restr
 }
 
 // any block size: direct box sum, one thread per (x1, d pair); slow but exact
-__global__ void k_sgbm_cost_generic(const uint32_t* __restrict__ PL, const uint32_t* __restrict__ PR,
-                                    SgbmGeom g, int16_t* __restrict__ C)
+// (x1 and y take blockIdx.x and blockIdx.y: the member is blockIdx.z here)
+__global__ void k_sgbm_cost_generic(FrontJobs jobs, SgbmGeom g)
 {
+    const FrontJob& J = jobs.j[blockIdx.z];
+    const uint32_t* __restrict__ const PL = J.planesL;
+    const uint32_t* __restrict__ const PR = J.planesR;
+    int16_t* __restrict__ const C = J.C;
     const int dpl = threadIdx.x;
     if (2 * dpl >= g.Dp) return;
     const bool pad = 2 * dpl >= g.D;
@@ -1621,6 +1651,8 @@ struct SweepGroup {
         DiagJob job;
         WeJob we;
         PostJob post;
+        FrontJob front;          // planes + cost volume, where the member left them to the group (front_pending)
+        bool front_pending;
     };
     Launch launch = nullptr;
     WeLaunch we_launch = nullptr;
@@ -1738,6 +1770,26 @@ static int launch_diag(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1, int16
     return pad ? launch_diag_k<NP, true, 7, REV, WTA>(ctx, g, in1, sout, ctl) : launch_diag_k<NP, false, 7, REV, WTA>(ctx, g, in1, sout, ctl);
 }
 
+// rows cut at their middle (k_sgbm_we2): the W + E geometry that a sweep group carries for all its members in one launch
+static bool we2_geometry(const vo_ctx* ctx, const SgbmGeom& g) { return g.W1 % 16 == 0 && g.W1 >= 32 && !(ctx->tune_diag_dbg & 8); }
+
+// Whether the run being enqueued leaves its W + E to the open sweep group: it is about to become a member (want_defer), runs the
+// fused schedule on the k_sgbm_we2 geometry, and is no MODE_HH run.  Asked where the front is launched and where the W + E is.
+static bool run_defers_we(const vo_ctx* ctx, const SgbmGeom& g, bool hh)
+{
+    const SweepGroup* const G = ctx->grp;
+    return G && G->want_defer && g.ur < 100 && g.W1 > 0 && we2_geometry(ctx, g) && !hh && !(ctx->tune_diag_dbg & 16);
+}
+
+// ... and its front with it: front batching is on, and the run lies on the lane that carries the open group (the lane's order
+// then places its ingest before the later launch, and the launch before the group's W + E)
+static bool run_defers_front(const vo_ctx* ctx, const SgbmGeom& g, bool hh)
+{
+    if (ctx->front_batch < 2 || ctx->cur_engine < 0 || (ctx->tune_diag_dbg & 4) || !run_defers_we(ctx, g, hh)) return false;
+    if (!lane_mode(ctx) || !stream_is_lane(ctx, ctx->stream)) return false;
+    return ctx->grp->n == 0 || ctx->grp->lane == ctx->stream;
+}
+
 // Aggregation + winner-take-all of one pair.  The schedule follows from the parameters alone (nothing per pair, no
 // context member is written):
 //   uniquenessRatio < 100 (the reference's own setting is 10):
@@ -1766,9 +1818,9 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
         // a row cut at its middle (k_sgbm_we2: two waves per four rows, half the chain each) is the W + E that a sweep group
         // carries for all its members in one launch: a deferring run leaves it to sweep_group_close (and `mid` below then
         // stands behind the cost volume)
-        const bool cut = g.W1 % 16 == 0 && g.W1 >= 32 && !(ctx->tune_diag_dbg & 8);
+        const bool cut = we2_geometry(ctx, g);
         SweepGroup* const G = ctx->grp;
-        const bool defer_we = cut && G && G->want_defer && !hh && !(ctx->tune_diag_dbg & 16);
+        const bool defer_we = run_defers_we(ctx, g, hh);
         if (G) G->cand_we_launch = nullptr;
         {
             StageTimer t(ctx, VO_T_SGBM_AGG, defer_we ? 0 : 1);
@@ -1841,6 +1893,85 @@ static int sgbm_post_launch(vo_ctx* ctx, const PostJobs& jobs, int n, const Sgbm
 static uint32_t pk_rep_host(int v) { return (uint32_t)(v & 0xFFFF) * 0x00010001u; }
 static int post_rows_per_block(int w) { return std::min(6, (int)(150 * 1024 / ((size_t)w * 6)) - 2); }
 
+// planes and cost volume of n pairs of one geometry on the current stream: one launch each
+static int front_launch(vo_ctx* ctx, const FrontJobs& jobs, int n, const SgbmGeom& g)
+{
+    const int w = g.W, h = g.H;
+    hipLaunchKernelGGL(k_sgbm_planes, dim3(div_up(w, 256), std::min(h, 128), n), dim3(256), 0, ctx->stream, jobs, w, h, g.ftzero,
+                       ctx->sw_ctl_words, g.Dp / 2, pk_rep_host(g.P2));
+    const int bx = ((g.Dp / 2 + 63) / 64) * 64;
+    const int TY = ctx->tune_sweep_ty;
+    const int nw = bx / 64;
+#define LAUNCH_SWEEP(XT, SW)                                                                                                   \
+    hipLaunchKernelGGL((k_sgbm_cost_sweep<XT, SW>), dim3(8 * div_up(div_up(g.W1, XT) * div_up(h, TY), 8), n), dim3(bx),         \
+                       (size_t)nw * (((2 * SW + 1) <= 5 ? 0 : (2 * SW + 1) * XT * 64) + 12 * (64 + (XT + 2 * SW - 1) / 2)) * 4, ctx->stream, jobs, g, TY)
+    if (ctx->tune_diag_dbg & 4) {                // development only (VO_DIAG_DEBUG): 4 / 8 / 16 / 32 skip the cost / W+E / diagonal / post stage
+    } else
+    switch (g.SW2) {
+        case 0: LAUNCH_SWEEP(8, 0); break;
+        case 1: LAUNCH_SWEEP(8, 1); break;
+        case 2: LAUNCH_SWEEP(8, 2); break;
+        case 3: LAUNCH_SWEEP(8, 3); break;
+        case 4: LAUNCH_SWEEP(8, 4); break;
+        case 5: LAUNCH_SWEEP(8, 5); break;
+        default:
+            hipLaunchKernelGGL(k_sgbm_cost_generic, dim3(g.W1, h, n), dim3(bx), 0, ctx->stream, jobs, g);
+    }
+#undef LAUNCH_SWEEP
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
+// the fronts that members [0, n) of the group left to it: one planes launch and one cost launch for all of them, on the lane
+static int sweep_group_launch_fronts(vo_ctx* ctx, SweepGroup* G, int n, hipStream_t lane)
+{
+    FrontJobs fj;
+    memset(&fj, 0, sizeof(fj));
+    int k = 0;
+    for (int i = 0; i < n; i++)
+        if (G->m[i].front_pending) { fj.j[k++] = G->m[i].front; G->m[i].front_pending = false; }
+    if (k == 0) return VO_OK;
+    hipStream_t const s0 = ctx->stream;
+    ctx->stream = lane;
+    int rc;
+    {
+        StageTimer t(ctx, VO_T_SGBM_COST, k);
+        rc = front_launch(ctx, fj, k, G->m[0].g);
+    }
+    ctx->stream = s0;
+    return rc;
+}
+
+// the open group is given up: no member's slot may hand anything out (a batched front launch failed)
+static void sweep_group_abandon(vo_ctx* ctx)
+{
+    SweepGroup* const G = ctx->grp;
+    for (int i = 0; i < G->n; i++) {
+        FrameSlot& f = *G->m[i].f;
+        f.in_group = false; f.kp_pending = false; f.has_pair = false; f.has_disp = false;
+        if (f.counted && ctx->inflight > 0) ctx->inflight--;
+        f.counted = false;
+    }
+    G->n = 0;
+    G->lane = nullptr;
+}
+
+// Something is about to change or free what a pending front still has to read (the staged images of an in-place pair): the
+// open group's pending fronts are launched now; wait = ... and the host returns only when they have run.
+int sweep_group_flush_fronts(vo_ctx* ctx, bool wait)
+{
+    SweepGroup* const G = ctx->grp;
+    if (!G || G->n == 0 || !G->lane) return VO_OK;
+    bool any = false;
+    for (int i = 0; i < G->n; i++) any |= G->m[i].front_pending;
+    if (!any) return VO_OK;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t const lane = G->lane;
+    if (int rc = sweep_group_launch_fronts(ctx, G, G->n, lane)) { sweep_group_abandon(ctx); return rc; }
+    if (wait) VO_HIP(ctx, hipStreamSynchronize(lane));
+    return VO_OK;
+}
+
 // The MAIN SGBM workspace (planes, C, S volumes, CCL arrays) is shared by the main stream and look-ahead engine 0's: a run on
 // one of them must not start before the previous run -- possibly on the other -- has finished.  An event chain orders them on
 // the device without blocking the host.  An engine's own workspace is only ever used on that engine's stream, which is ordered
@@ -1879,6 +2010,7 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
         if (!ctx->grp) ctx->grp = new SweepGroup();
         ctx->grp->want_defer = true;
         ctx->grp->did_defer = false;
+        ctx->grp->cand.front_pending = false;
     }
     rc = sgbm_run_impl(ctx, f, w, h, srcL, srcR);
     if (defer) {
@@ -1899,6 +2031,13 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
             G->launch = G->cand_launch; G->we_launch = G->cand_we_launch; G->nstrips = G->cand_nstrips;
             f.in_group = true;
             *deferred = true;
+            // F members' fronts are pending: one planes launch and one cost launch for all of them
+            int pending = 0;
+            for (int i = 0; i < G->n; i++) pending += G->m[i].front_pending ? 1 : 0;
+            if (pending >= ctx->front_batch && G->lane && (rc = sweep_group_launch_fronts(ctx, G, G->n, G->lane))) {
+                sweep_group_abandon(ctx);
+                return rc;
+            }
             return VO_OK;
         }
     }
@@ -2029,6 +2168,8 @@ int sweep_group_close(vo_ctx* ctx, int why)
         jobs.n = n; jobs.nstrips = G->nstrips;
         jobs.j[0] = last.job; we.j[0] = last.we; post.j[0] = last.post;
         bool main_member = last.engine == 0;         // engine 0's member works in the main workspace
+        // the fronts the members left to the group go first, whatever closes it
+        if (lane) rc = sweep_group_launch_fronts(ctx, G, n, lane);
         for (int i = 0; i + 1 < n && !rc; i++) {
             jobs.j[i + 1] = G->m[i].job; we.j[i + 1] = G->m[i].we; post.j[i + 1] = G->m[i].post;
             main_member |= G->m[i].engine == 0;
@@ -2147,31 +2288,23 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
     const PathPlan plan = make_plan(g, e.mode);
     ctx->last_cells = (int64_t)g.W1 * h * g.D;
     {
-        StageTimer t(ctx, VO_T_SGBM_COST);
-        const int dbg = ctx->tune_diag_dbg;          // development only (VO_DIAG_DEBUG): 4 / 8 / 16 / 32 skip the cost / W+E / diagonal / post stage
-        hipLaunchKernelGGL(k_sgbm_planes, dim3(div_up(w, 256), std::min(h, 128)), dim3(256), 0, ctx->stream, dL, dR, w, h, g.ftzero,
-                           ctx->ws->planesL, ctx->ws->planesR, (g.ur >= 100 || post_rows_per_block(w) < 1) ? ctx->ws->ccl_size : nullptr, ctx->ws->sw_ctl, ctx->sw_ctl_words,
-                           (uint32_t*)(ctx->ws->C + vol), g.Dp / 2, pk_rep_host(g.P2), srcL ? f.left : nullptr, srcL ? f.right : nullptr);
-        const int bx = ((g.Dp / 2 + 63) / 64) * 64;
-        const int TY = ctx->tune_sweep_ty;
-        const int nw = bx / 64;
-#define LAUNCH_SWEEP(XT, SW)                                                                                                   \
-    hipLaunchKernelGGL((k_sgbm_cost_sweep<XT, SW>), dim3(8 * div_up(div_up(g.W1, XT) * div_up(h, TY), 8)), dim3(bx),            \
-                       (size_t)nw * (((2 * SW + 1) <= 5 ? 0 : (2 * SW + 1) * XT * 64) + 12 * (64 + (XT + 2 * SW - 1) / 2)) * 4, ctx->stream, ctx->ws->planesL, ctx->ws->planesR, g, TY, ctx->ws->C)
-        if (dbg & 4) {
-        } else
-        switch (g.SW2) {
-            case 0: LAUNCH_SWEEP(8, 0); break;
-            case 1: LAUNCH_SWEEP(8, 1); break;
-            case 2: LAUNCH_SWEEP(8, 2); break;
-            case 3: LAUNCH_SWEEP(8, 3); break;
-            case 4: LAUNCH_SWEEP(8, 4); break;
-            case 5: LAUNCH_SWEEP(8, 5); break;
-            default:
-                hipLaunchKernelGGL(k_sgbm_cost_generic, dim3(g.W1, h), dim3(bx), 0, ctx->stream, ctx->ws->planesL, ctx->ws->planesR, g, ctx->ws->C);
+        FrontJobs fj;
+        memset(&fj, 0, sizeof(fj));
+        FrontJob& j = fj.j[0];
+        j.L = dL; j.R = dR; j.planesL = ctx->ws->planesL; j.planesR = ctx->ws->planesR;
+        j.d2key = (g.ur >= 100 || post_rows_per_block(w) < 1) ? ctx->ws->ccl_size : nullptr;
+        j.sw_ctl = ctx->ws->sw_ctl; j.dummy = (uint32_t*)(ctx->ws->C + vol);
+        j.keepL = srcL ? f.left : nullptr; j.keepR = srcL ? f.right : nullptr;
+        j.C = ctx->ws->C;
+        // a run that is about to leave its W + E to the open group on a lane leaves its front to it as well (the same predicate
+        // launch_agg reads): sweep_group_launch_fronts carries it with the other members'
+        if (run_defers_front(ctx, g, plan.n_dirs == 8)) {
+            ctx->grp->cand.front = j;
+            ctx->grp->cand.front_pending = true;
+        } else {
+            StageTimer t(ctx, VO_T_SGBM_COST);
+            if (int rcf = front_launch(ctx, fj, 1, g)) return rcf;
         }
-#undef LAUNCH_SWEEP
-        VO_CHECK_LAUNCH(ctx);
     }
     int rc;
     switch (g.Dp / 32) {

@@ -193,6 +193,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     if (const char* eq = getenv("GPU_MAX_HW_QUEUES")) { int v = atoi(eq); if (v >= 1) ctx->hw_queues = v; }
     if (const char* eg = getenv("VO_SWEEP_GROUP")) { int v = atoi(eg); if (v >= 1 && v <= VO_MAX_SWEEP_GROUP) ctx->sweep_group_req = v; }
     if (const char* el = getenv("VO_GROUP_LANES")) ctx->lanes_on = atoi(el) != 0;
+    if (const char* ef = getenv("VO_GROUP_FRONTS")) { int v = atoi(ef); if (v >= 0) ctx->front_batch = v > VO_MAX_SWEEP_GROUP ? VO_MAX_SWEEP_GROUP : v; }
     if (lanes_ensure(ctx)) { g_create_err = "hipStreamCreate failed (lane streams)"; vo_destroy(ctx); return VO_E_HIP; }
     (void)hipEventCreate(&ctx->ev0);
     (void)hipEventCreate(&ctx->ev1);
@@ -621,6 +622,8 @@ extern "C" int vo_stage_pairs_alloc(vo_ctx* ctx, int n, int w, int h, int channe
     if (!ctx || n <= 0 || (channels != 1 && channels != 3)) return vo_fail(ctx, VO_E_ARG, "vo_stage_pairs_alloc: bad argument");
     if (w > ctx->max_w || h > ctx->max_h || w < 16 || h < 16) return vo_fail(ctx, VO_E_CAP, "image %dx%d exceeds context", w, h);
     VO_HIP(ctx, hipSetDevice(ctx->device));
+    // (an in-place pair's front reads the staged images: the fronts the open group still holds are launched before they go)
+    if (int rc = sweep_group_flush_fronts(ctx, true)) return rc;
     if (ctx->staged) { (void)hipFree(ctx->staged); ctx->staged = nullptr; }
     ctx->staged_n = 0;
     const size_t per = (size_t)w * h * channels;
@@ -634,6 +637,7 @@ extern "C" int vo_stage_pair(vo_ctx* ctx, int index, const uint8_t* left, const 
     if (!ctx || !left || !right || index < 0 || index >= ctx->staged_n) return vo_fail(ctx, VO_E_ARG, "vo_stage_pair: bad index");
     VO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t per = (size_t)ctx->staged_w * ctx->staged_h * ctx->staged_ch;
+    if (int rc = sweep_group_flush_fronts(ctx, true)) return rc;     // (a pending front may still have to read this pair)
     VO_HIP(ctx, hipMemcpyAsync(ctx->staged + per * 2 * index, left, per, hipMemcpyHostToDevice, ctx->stream));
     VO_HIP(ctx, hipMemcpyAsync(ctx->staged + per * (2 * index + 1), right, per, hipMemcpyHostToDevice, ctx->stream));
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -164,6 +164,10 @@ struct vo_ctx {
     // new group takes (the one the group closed last did not use).
     hipStream_t lane[2] = {nullptr, nullptr};
     bool lanes_on = true;
+    // front_batch: VO_GROUP_FRONTS.  F >= 2: a dense look-ahead run that becomes a member of the open group on a lane leaves its
+    // planes and cost volume to the group as well, and F pending members' fronts (or however many are pending when the group
+    // closes) go in one launch each (DESIGN 4f'''').  0 / 1: every run launches its own front, as before.
+    int front_batch = 8;
     bool lane_used = false;          // the latest look-ahead submission went on a lane (a dense stream is running on the lanes)
     int lane_next = 0;
     int cur_engine = -1;
@@ -561,6 +565,8 @@ static inline hipError_t engine_streams_sync(const vo_ctx* ctx)
 // orders itself behind the chain when it is next given work (engine_behind_chain).  Nothing to do without an open group.  On
 // failure every member's slot is left holding nothing.
 int sweep_group_close(vo_ctx* ctx, int why);
+// the open group's pending fronts are launched now (what they read is about to change); wait: and have run on return
+int sweep_group_flush_fronts(vo_ctx* ctx, bool wait);
 int engine_behind_chain(vo_ctx* ctx, int engine);
 // The engine is about to be given work on `target` (its own stream or a lane), inside its EngineScope: ctx->stream becomes
 // `target`, and where the engine's latest work lies on another stream, that stream gets an event record and `target` one wait

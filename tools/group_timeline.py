@@ -4,8 +4,8 @@ C2 through StereoOdometer.update() in the environment as it is (GPU_MAX_HW_QUEUE
 look-ahead pairs travel in sweep groups), 12 warm-up pairs, then 60 pairs with every stage timed.  The stage timers record a
 HIP event pair per stage on the stage's own stream (vo_get_stage_timeline), so -- unlike a kernel trace, which serialises the
 dispatches -- they show what overlaps.  Per group: the chain interval (begin of the group's W + E bracket to the end of its
-post-filter bracket) and how many cost-volume / ORB brackets of OTHER pairs begin inside it, with the microseconds of them that
-lie inside.  Last line: the share of chain time during which at least one such bracket was running.
+post-filter bracket) and how many cost-volume / ORB brackets of OTHER pairs begin inside it (a batched front bracket counts as
+its members), with the microseconds of them that lie inside.  Last line: the share of chain time during which at least one such bracket was running.
 The events cost throughput: never part of a rate.   Usage: python tools/group_timeline.py [steady pairs, default 60]"""
 import gc
 import os
@@ -47,15 +47,17 @@ for i, (st, n, b, e) in enumerate(tl):
             own.add(i + 3)
             orb = tl[i + 3]
         chains.append((n, b, tl[i + 2][3], orb))
-fronts = [(st, b, e) for i, (st, n, b, e) in enumerate(tl) if i not in own and st in ("sgbm_cost", "orb")]
+# (a bracket of another group's batched fronts -- one planes launch and one cost launch for n members, VO_GROUP_FRONTS -- counts
+# as n fronts)
+fronts = [(st, n, b, e) for i, (st, n, b, e) in enumerate(tl) if i not in own and st in ("sgbm_cost", "orb")]
 tot_chain = tot_cover = 0.0
 for g, (n, b, e, orb) in enumerate(chains):
     inside = {"sgbm_cost": [0, 0.0], "orb": [0, 0.0]}
     cover = []
-    for (st, fb, fe) in fronts:
+    for (st, fn, fb, fe) in fronts:
         lo, hi = max(fb, b), min(fe, e)
         if b <= fb < e:
-            inside[st][0] += 1
+            inside[st][0] += max(fn, 1)
         if hi > lo:
             inside[st][1] += (hi - lo) * 1e3
             cover.append((lo, hi))
