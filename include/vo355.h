@@ -587,8 +587,58 @@ int vo_prefetch_staged_pair_sparse(vo_ctx* ctx, int slot, int index, int preproc
  *
  * With vo_enable_timing on, the view's launch is bracketed under VO_T_MATCH and the update's under VO_T_POSE.
  * A refused call leaves the map as it was.  vo_map_reset: size 0, no view, serials start over.  vo_map_download: the landmarks in
- * map order (any output may be NULL; VO_E_CAP when cap is below the size).  A fifth map: VO_E_CAP. */
+ * map order (any output may be NULL; VO_E_CAP when cap is below the size).  A fifth map: VO_E_CAP.
+ *
+ * vo_track_map (ONE host synchronisation; tests/map_fused_ref.py restates it): vo_map_view + vo_pnp_pair(view_slot, slot_new) +
+ *   the odometer's decisions and motion gates + vo_map_update as one chain of launches on the context's stream; nothing but the
+ *   record (and q / t / mask when asked for) comes back.  With n = the map's size as the host knows it and vis = the visible count, which only the device knows:
+ *   a. padded view: rows [0, vis) of view_slot are exactly vo_map_view's keypoints under Rt12_cw_pred (ref_slot = slot_new), and
+ *      view_src is written as there.  Rows [vis, n) are PADDING so that the later launches can be shaped for n: clones of row 0
+ *      in position, octave, descriptor and right descriptor, with a NaN 3-D point (size = angle = response = 0, disparity NaN as
+ *      every view row).  With vis = 0 the padding's position, octave and descriptors are zero.
+ *   b. kNN-2 with n query rows (match_flags as vo_pnp_pair).  A clone ties with row 0 in every column minimum of the cross-check
+ *      and loses to it (the lower query index wins), and under VO_MATCH_WINDOW carries row 0's pixel: rows [0, vis) get the
+ *      results of the compacted view.  The ratio test and everything behind it see the first vis rows only, so M, n_usable, the
+ *      RANSAC and the refinement are those of vo_pnp_pair on vo_map_view's slot, bit for bit.
+ *   c. decision, the first that applies (Rt = Rt12_refined when the refinement's status is 0, else the winner; mm = min_matches):
+ *        1  vis < max(mm, 2) or vis > 3800         the view is refused (no skip cause: the caller falls back)
+ *        2  M < mm                                   "matches"
+ *        8  flag bit 1 of the PnP step             a match index outside the train set: the call returns VO_E_STATE
+ *        3  n_usable < max(mm, 4)                    "matches"
+ *        4  best_count < mm                          "outlier"
+ *        5  an entry of Rt is NaN                    "nan"
+ *        6  |t| > max_dist (and not 7)               "bigdist"
+ *        7  angle > max_rot                          "bigrot"
+ *        0  otherwise: accepted
+ *      |t| = sqrt((t0 t0 + t1 t1) + t2 t2); angle = atan2(s, c), s = sqrt((a a + b b) + c' c') / 2 over (a, b, c') = (R32 - R23,
+ *      R13 - R31, R21 - R12), c = (((R11 + R22) + R33) - 1) / 2, all float64.  max_dist / max_rot are the caller's gates already
+ *      multiplied by the frames the step spans.
+ *   d. on 0: c_T_w = Rt . Rt12_cw_pred as 4x4 products, entry (i, j) = ((Rt[i][0] P[0][j] + Rt[i][1] P[1][j]) + Rt[i][2] P[2][j]) +
+ *      Rt[i][3] P[3][j] with P's last row (0, 0, 0, 1), no fused multiply-add; w_T_c = [R^T | -(R^T t)] of it, row i of the last
+ *      column = -((R[0][i] t0 + R[1][i] t1) + R[2][i] t2).  Then vo_map_update's steps 1 - 4 with Rt12_wc = w_T_c and the n_usable
+ *      correspondences of b (q, t, mask), all read from device memory; the kernel makes the range checks itself (q < vis, t <
+ *      slot_new's keypoints, as unsigned compares): one violation and nothing is applied, bit 0 of update_flags is set and the call
+ *      returns VO_E_STATE.  On any other decision the six counts are -1 and the map is not touched.
+ *   Afterwards view_slot stands exactly as vo_map_view leaves it (vis keypoints); on 0 the other set of arrays is the map and the
+ *   last view is void, otherwise the last view is this one.  mask_out / q_idx / t_idx as vo_pnp_pair (cap >= n, any may be NULL).
+ *   Checked before anything is enqueued: vo_map_view's arguments (ref_slot = slot_new), vo_pnp_pair's, vo_map_update's serial /
+ *   max_age / max_obs / depth-carrying slot_new, min_matches >= 0, max_dist and max_rot not NaN; a map of more than 3800 landmarks
+ *   is VO_E_CAP (the fused PnP step's bound applies to n).  A refused call leaves the map as it was.
+ *   With vo_enable_timing on: the padded view is one bracket under VO_T_MATCH, the decision and the update one each under VO_T_POSE. */
 #define VO_NUM_MAPS 4
+#define VO_MAP_TRACK_MAX 3800
+typedef struct vo_track_map_rec {
+    int32_t decision, map_n, vis, update_flags;
+    int32_t M, n, best_iter, best_count;       /* counts4 of vo_pnp_pair */
+    int32_t flags, rstatus, rsteps, pad;       /* its flags and refine2 */
+    int32_t counts6[6], pad2[2];               /* vo_map_update's counts; -1 each unless decision == 0 */
+    double Rt[12], Rtr[12];                    /* its Rt12 and Rt12_refined */
+    double c_T_w[12], w_T_c[12];               /* the new world-to-camera pose and its inverse (decision == 0; zeros otherwise) */
+} vo_track_map_rec;
+int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, const double* Rt12_cw_pred, const double* K4, float z_min,
+                 double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters,
+                 int min_matches, double max_dist, double max_rot, int serial, int max_age, int max_obs,
+                 vo_track_map_rec* rec, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
 int vo_map_create(vo_ctx* ctx, int capacity, int* map_out);
 int vo_map_destroy(vo_ctx* ctx, int map);
 int vo_map_reset(vo_ctx* ctx, int map);

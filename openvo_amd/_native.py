@@ -47,6 +47,7 @@ SYMBOLS = [
     "vo_set_sparse_assoc", "vo_download_keypoint_rdesc", "vo_sparse_pair_host_ex", "vo_set_match_loop", "vo_clear_match_loop",
     "vo_get_stage_timeline",
     "vo_map_create", "vo_map_destroy", "vo_map_reset", "vo_map_view", "vo_map_update", "vo_map_download",
+    "vo_track_map",
 ]
 
 
@@ -78,6 +79,26 @@ class MonoPose(ctypes.Structure):
                     n_depth=int(self.n_depth), n_shared=int(self.n_shared), flags=int(self.flags), serial=int(self.serial),
                     votes4=np.array(self.votes4[:], np.int32), E=np.array(self.E[:], np.float64).reshape(3, 3),
                     R=np.array(self.R[:], np.float64).reshape(3, 3), t=np.array(self.t[:], np.float64), scale_rel=float(self.scale_rel))
+
+
+class MapTrackRec(ctypes.Structure):
+    """vo_track_map_rec of include/vo355.h: the record of the fused map step."""
+    _fields_ = [("decision", ctypes.c_int32), ("map_n", ctypes.c_int32), ("vis", ctypes.c_int32), ("update_flags", ctypes.c_int32),
+                ("M", ctypes.c_int32), ("n", ctypes.c_int32), ("best_iter", ctypes.c_int32), ("best_count", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("rstatus", ctypes.c_int32), ("rsteps", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("counts6", ctypes.c_int32 * 6), ("pad2", ctypes.c_int32 * 2),
+                ("Rt", ctypes.c_double * 12), ("Rtr", ctypes.c_double * 12), ("c_T_w", ctypes.c_double * 12), ("w_T_c", ctypes.c_double * 12)]
+
+    def as_dict(self):
+        m34 = lambda a: np.array(a[:], np.float64).reshape(3, 4)                     # noqa: E731
+        return dict(decision=int(self.decision), view=np.array([self.map_n, self.vis], np.int32), update_flags=int(self.update_flags),
+                    matches=int(self.M), n=int(self.n), best_iter=int(self.best_iter), best_count=int(self.best_count), flags=int(self.flags),
+                    refine_status=int(self.rstatus), refine_steps=int(self.rsteps), update=np.array(self.counts6[:], np.int32),
+                    Rt=m34(self.Rt), Rt_refined=m34(self.Rtr), c_T_w=m34(self.c_T_w), w_T_c=m34(self.w_T_c))
+
+
+MAP_TRACK_MAX = 3800     # VO_MAP_TRACK_MAX: the largest map the fused map step takes
+MAP_DECISIONS = {0: "", 1: None, 2: "matches", 3: "matches", 4: "outlier", 5: "nan", 6: "bigdist", 7: "bigrot"}     # decision -> skip_cause (None: none set)
 
 
 def _image(img):
@@ -256,6 +277,10 @@ def lib():
                                 ("vo_map_update", [vp, ci, ci, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
                                 ("vo_map_download", [vp, ci, vp, vp, vp, vp, vp, ci, vp])):
                 getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_track_map"):              # (likewise: an older build has no fused map step)
+            cf, cu = ctypes.c_float, ctypes.c_uint32
+            for name, proto in (("vo_track_map", [vp, ci, ci, ci, vp, vp, cf, cd, ci, ci, cf, cu, ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp, ci]),):
+                getattr(L, name).argtypes = proto
         plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, vp, vp, vp, vp]
@@ -265,6 +290,9 @@ def lib():
         plant = getattr(L, "vo_test_plant_map", None)            # (likewise)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
+        plant = getattr(L, "vo_test_peek_view", None)            # (likewise)
+        if plant is not None:
+            plant.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.vo_device_count.argtypes = [vp]
         L.vo_mgpu_unique_id.argtypes = [vp]
         L.vo_mgpu_create.argtypes = [ci, ci, ci, vp, vp]
@@ -1181,6 +1209,27 @@ class Context:
                                          _p(q) if n else None, _p(t) if n else None, _p(mask) if n else None, n, _p(c6)))
         return c6
 
+    def map_track(self, handle, slot_new, view_slot, Rt_cw_pred, K4, z_min, ratio, iters, thr, seed, refine, min_matches, max_dist, max_rot,
+                  serial, max_age, max_obs, cross_check=False, window=None, loop=None, want_matches=True):
+        """The map step in one native call with one synchronisation (vo_track_map): the view of the map under Rt_cw_pred into
+        view_slot, the PnP step on (view, slot_new), the odometer's decisions and gates (max_dist / max_rot already scaled by the
+        span), and on acceptance the update of the map under the composed pose.  -> the record as a dict (MapTrackRec.as_dict:
+        decision, view = counts2, update = counts6, the PnP record, c_T_w / w_T_c 3x4) [+ mask, q, t of length n]."""
+        Rt, K4 = self._pose12(Rt_cw_pred), _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        rec = MapTrackRec()
+        arrays = [None, None, None]
+        if want_matches:
+            arrays = self._pnp_out(True)[1]
+        self._ck(self._lib.vo_track_map(self._h, int(handle), int(slot_new), int(view_slot), _p(Rt), _p(K4), float(z_min), float(ratio),
+                                        self._mflags(cross_check, window, loop), int(iters), float(thr), int(seed) & 0xFFFFFFFF, int(refine),
+                                        int(min_matches), float(max_dist), float(max_rot), int(serial), int(max_age), int(max_obs),
+                                        ctypes.byref(rec), *[_p(a) for a in arrays], self.kp_cap))
+        out = rec.as_dict()
+        if want_matches:
+            n = out["n"]
+            out.update(mask=arrays[0][:n].copy(), q=arrays[1][:n].copy(), t=arrays[2][:n].copy())
+        return out
+
     def map_download(self, handle):
         """-> dict(xyz (n, 3) float32 world coordinates, desc (n, 32), octave, obs, last (n,) int32) in map order"""
         n = ctypes.c_int(0)
@@ -1203,6 +1252,16 @@ class Context:
         if not all(len(a) == n for a in (desc, rdesc, octave, obs, last)):
             raise ValueError("one entry of every array per landmark")
         self._ck(self._lib.vo_test_plant_map(self._h, int(handle), n, _p(xyz), _p(desc), _p(rdesc), _p(octave), _p(obs), _p(last)))
+
+    def peek_view(self, handle, slot, n):
+        """Test-only build of the library: the first n rows of a view slot's keypoint arrays and of the map's view_src, whatever
+        the slot's count says (vo_test_peek_view) -- the padding of map_track's padded view.  The product library has no such entry."""
+        if not hasattr(self._lib, "vo_test_peek_view"):
+            raise RuntimeError("peek_view needs the test-only build of the library (libvo355_hooks.so)")
+        out = dict(xy=np.empty((n, 2), np.float32), xyz=np.empty((n, 3), np.float32), octave=np.empty(n, np.int32),
+                   desc=np.empty((n, 32), np.uint8), rdesc=np.empty((n, 32), np.uint8), src=np.empty(n, np.int32))
+        self._ck(self._lib.vo_test_peek_view(self._h, int(handle), int(slot), int(n), *[_p(out[k]) for k in ("xy", "xyz", "octave", "desc", "rdesc", "src")]))
+        return out
 
     def umeyama(self, src, dst, force_rotation=True):
         src, dst = _c(src, np.float32).reshape(-1, 3), _c(dst, np.float32).reshape(-1, 3)

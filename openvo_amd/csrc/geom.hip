@@ -1546,11 +1546,14 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
                                                   float y0f, int32_t* __restrict__ q2, int32_t* __restrict__ t2, float* __restrict__ X,
                                                   float* __restrict__ uv, int32_t* __restrict__ hdr, const uint32_t* __restrict__ colmin,
                                                   int nt_range, const float* __restrict__ xyz_a, const uint8_t* __restrict__ rd_a,
-                                                  const uint8_t* __restrict__ rd_b, int loop_max)
+                                                  const uint8_t* __restrict__ rd_b, int loop_max, const int32_t* __restrict__ nq_dev)
 {
     // xyz_a: slot a's keypoints carry depth -- the 3-D point of match (q, t) is kp_xyz[q], status 0
     // rd_a / rd_b (both or neither): the loop check on the right partners' descriptors (LoopGate)
+    // nq_dev (may be NULL): only the first min(nq, *nq_dev) query rows exist -- the rows behind them are padding (vo_track_map) that
+    // never counts in M, never reaches mq, and through which nothing is read
     __shared__ int s_m, s_flags, s_cnt[4];
+    if (nq_dev) { const int lim = *nq_dev; nq = lim < nq ? (lim > 0 ? lim : 0) : nq; }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (wv == 0) {
         int base = 0, fl = 0;
@@ -1610,7 +1613,7 @@ __global__ void __launch_bounds__(256) k_pnp_prep(const int32_t* __restrict__ id
     if (threadIdx.x == 0) { hdr[0] = m; hdr[1] = n; hdr[2] = s_flags; }
 }
 
-int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g)
+int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g, const int32_t* nq_dev)
 {
     int x0 = 0, y0 = 0, x1 = a.w, y1 = a.h;
     if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < a.w ? ctx->roi[2] : a.w; y1 = ctx->roi[3] < a.h ? ctx->roi[3] : a.h; }
@@ -1621,7 +1624,7 @@ int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int c
     hipLaunchKernelGGL(prep, dim3(1), dim3(256), 0, ctx->stream, ctx->mw->m_idx, ctx->mw->m_dist, a.n_kp, ratio, a.kp_xy, b.kp_xy, b.n_kp,
                        ctx->mw->mq_idx, ctx->mw->mt_idx, ta, x1 - x0, y1 - y0, (float)x0, (float)y0, d.q, d.t, d.X, d.uv, d.hdr,
                        cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, nt_range,
-                       slot_sparse(a) ? (const float*)a.kp_xyz : nullptr, g.rd_a, g.rd_b, g.max_h);
+                       slot_sparse(a) ? (const float*)a.kp_xyz : nullptr, g.rd_a, g.rd_b, g.max_h, nq_dev);
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }

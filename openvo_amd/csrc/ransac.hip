@@ -1494,8 +1494,10 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
                                                     const float* __restrict__ P_all, const float* __restrict__ X, const float* __restrict__ uv,
                                                     int nq, const int32_t* __restrict__ hdr, const int32_t* __restrict__ q2,
                                                     const int32_t* __restrict__ t2, float thr2, K4 K, int refine_iters,
-                                                    uint8_t* __restrict__ mask, PnpRec* __restrict__ rec, uint8_t* __restrict__ arr, size_t cap)
+                                                    uint8_t* __restrict__ mask, PnpRec* __restrict__ rec, uint8_t* __restrict__ arr, size_t cap,
+                                                    PnpRec* __restrict__ rec_dev)
 {
+    // rec_dev (may be NULL): device memory that receives the record too, for a kernel that follows on the stream (vo_track_map)
     __shared__ long long s_key[4];
     __shared__ int s_best[2], s_status;
     __shared__ double s_pose[12], s_red[4][27];
@@ -1536,6 +1538,10 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
     if (threadIdx.x == 0) {
         rec->M = hdr[0]; rec->n = n; rec->best_iter = best; rec->best_count = best_count; rec->flags = hdr[2]; rec->pad = 0;
         for (int k = 0; k < 12; k++) rec->Rt[k] = s_pose[k];
+        if (rec_dev) {
+            rec_dev->M = hdr[0]; rec_dev->n = n; rec_dev->best_iter = best; rec_dev->best_count = best_count; rec_dev->flags = hdr[2]; rec_dev->pad = 0;
+            for (int k = 0; k < 12; k++) rec_dev->Rt[k] = s_pose[k];
+        }
     }
     const bool refine = refine_iters > 0 && best_count >= 6;
     int steps = 0;
@@ -1601,12 +1607,16 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
     if (threadIdx.x == 0) {
         rec->rstatus = s_status; rec->rsteps = steps;
         for (int k = 0; k < 12; k++) rec->Rtr[k] = s_pose[k];
+        if (rec_dev) {
+            rec_dev->rstatus = s_status; rec_dev->rsteps = steps;
+            for (int k = 0; k < 12; k++) rec_dev->Rtr[k] = s_pose[k];
+        }
     }
 }
 
 // lg: the loop gate of the step, as the context stands at this call (a ticket keeps it)
-static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who,
-                     LoopGate* lg)
+int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who,
+              LoopGate* lg, int view_n)
 {
     if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v)
         return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
@@ -1616,6 +1626,14 @@ static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const
     if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
+    if (view_n >= 0) {                       // slot a will be a view: depth-carrying keypoints, view_n of them
+        if (!slot_sparse(b)) return vo_fail(ctx, VO_E_STATE, "%s: slot %d: the keypoints carry no depth (vo_sparse_stereo)", who, slot_b);
+        if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
+        if (view_n > 0 && b.n_kp < 2) return vo_fail(ctx, VO_E_ARG, "train set has fewer than 2 descriptors");
+        *lg = LoopGate();
+        if (match_flags & VO_MATCH_LOOP) { lg->rd_a = a.kp_rdesc; lg->rd_b = b.kp_rdesc; lg->max_h = ctx->loop_max; }
+        return VO_OK;
+    }
     if (!a.has_kp || !b.has_kp) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
     if (slot_sparse(a) != slot_sparse(b)) return vo_fail(ctx, VO_E_STATE, "%s: one slot's keypoints carry depth, the other's do not", who);
     if (!slot_sparse(a) && (!a.has_disp || !b.has_disp)) return vo_fail(ctx, VO_E_STATE, "%s: both slots need disparity and keypoints", who);
@@ -1626,8 +1644,8 @@ static int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const
 
 // the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
 // pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
-static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
-                       int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg)
+int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
+                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain)
 {
     const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
@@ -1659,15 +1677,16 @@ static int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, in
     }
     {
         StageTimer t(ctx, VO_T_POSE);
-        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, d, lg))) return rc;
+        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, d, lg, chain ? chain->nq_dev : nullptr))) return rc;
         const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
         const float thr2 = thr * thr;
         hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d.X, d.uv, nq, K, iters, seed, d_Rt, d_P, d.hdr + 1);
         hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d.X, d.uv, nq, d_P, iters, thr2, d_counts, d.hdr + 1);
         hipLaunchKernelGGL(k_pnp_finish, dim3(1), dim3(256), 0, ctx->stream, d_counts, iters, d_Rt, d_P, d.X, d.uv, nq, d.hdr, d.q, d.t, thr2, K,
-                           refine_iters, d_mask, rec, arr, pnp_cap(ctx->kp_cap));
+                           refine_iters, d_mask, rec, arr, pnp_cap(ctx->kp_cap), chain ? chain->rec_dev : nullptr);
         VO_CHECK_LAUNCH(ctx);
     }
+    if (chain) { chain->d = d; chain->mask = d_mask; }
     return VO_OK;
 }
 

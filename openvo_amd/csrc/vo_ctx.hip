@@ -275,6 +275,7 @@ extern "C" int vo_create(int device_id, int max_w, int max_h, int max_disp, int 
     if (const char* e10 = getenv("VO_FAULT_PREFETCH")) ctx->fault_prefetch = atoi(e10);   // test-only build (libvo355_hooks.so)
     if (const char* e11 = getenv("VO_FAULT_SWEEP")) ctx->fault_sweep = atoi(e11);
     if (const char* e12 = getenv("VO_FAULT_PNP_RANGE")) ctx->fault_pnp_range = atoi(e12);
+    if (const char* e13 = getenv("VO_FAULT_MAP_NAN")) ctx->fault_map_nan = atoi(e13);
 #endif
     if (const char* e6 = getenv("VO_SWEEP_TY")) { int v = atoi(e6); if (v >= 4 && v <= 4096) ctx->tune_sweep_ty = v; }
     // (the memory bound above may have put groups in force that the request alone did not)
@@ -1609,5 +1610,27 @@ extern "C" int vo_test_plant_map(vo_ctx* ctx, int map, int n, const float* xyz, 
         return rc;
     m.n = n; m.view_n = 0; m.max_serial = top;
     return VO_OK;
+}
+
+// ... and a look at what vo_track_map left BEHIND the keypoints the view slot admits to: the first n rows of the slot's keypoint
+// arrays (the padding of the padded view lies in [visible, map size)) and of the map's view_src, whatever the slot's count says.
+// Any output may be NULL.
+extern "C" int vo_test_peek_view(vo_ctx* ctx, int map, int slot, int n, float* xy, float* xyz, int32_t* octave, uint8_t* desc, uint8_t* rdesc,
+                                 int32_t* view_src)
+{
+    if (!ctx || map < 0 || map >= VO_NUM_MAPS || !ctx->maps[map].used || slot < 0 || slot >= VO_NUM_SLOTS || n < 0 || n > ctx->kp_cap)
+        return vo_fail(ctx, VO_E_ARG, "vo_test_peek_view: bad argument");
+    if (n == 0) return VO_OK;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    const FrameSlot& f = ctx->slots[slot];
+    int rc = VO_OK;
+    if (xy) rc = xfer_d2h(ctx, xy, f.kp_xy, (size_t)n * 8);
+    if (xyz && !rc) rc = xfer_d2h(ctx, xyz, f.kp_xyz, (size_t)n * 12);
+    if (octave && !rc) rc = xfer_d2h(ctx, octave, f.kp_oct, (size_t)n * 4);
+    if (desc && !rc) rc = xfer_d2h(ctx, desc, f.desc, (size_t)n * 32);
+    if (rdesc && !rc) rc = xfer_d2h(ctx, rdesc, f.kp_rdesc, (size_t)n * 32);
+    if (view_src && !rc) rc = xfer_d2h(ctx, view_src, ctx->maps[map].view_src, (size_t)n * 4);
+    if (rc) return rc;
+    return xfer_flush(ctx);
 }
 #endif

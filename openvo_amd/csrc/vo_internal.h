@@ -142,6 +142,7 @@ struct LandmarkMap {
     MapSet set[2];
     int32_t *view_src = nullptr, *d_q = nullptr, *d_t = nullptr;
     uint8_t *claimed = nullptr, *d_mask = nullptr;
+    uint8_t* d_track = nullptr;                // the device block of vo_track_map (MapTrackDev: what its kernels hand each other)
     std::vector<uint8_t> seen;
 };
 void map_free(LandmarkMap& m);
@@ -400,6 +401,7 @@ struct vo_ctx {
     int mono_engine = 0;            // round robin of vo_prefetch_staged_mono
     int inflight = 0;               // look-ahead pairs submitted and not yet waited for (vo_lookahead_depth)
     int fault_pnp_range = 0;        // VO_FAULT_PNP_RANGE=n (VO_TEST_HOOKS builds only): the n-th PnP pair step holds its match indices to a train set of ONE descriptor (flag bit 1, VO_E_STATE)
+    int fault_map_nan = 0;          // VO_FAULT_MAP_NAN=n (VO_TEST_HOOKS builds only): the n-th vo_track_map hands its decision kernel a pose with one NaN entry (decision 5: no planted input reaches it, the PnP step returns zeros where it has no pose)
     int fault_prefetch = 0;         // VO_FAULT_PREFETCH=n (VO_TEST_HOOKS builds only): the n-th look-ahead submission fails inside its engine scope
 
     // timing
@@ -656,7 +658,19 @@ static inline size_t pnp_cap(int kp_cap) { return ((size_t)kp_cap + 15) & ~(size
 // device scratch of one step behind the RANSAC arrays: hdr {M, n, flags}, the n usable correspondences in match order
 struct PnpDev { int32_t *hdr, *q, *t; float *X, *uv; };
 // kNN-2 is done (m_idx / m_dist of the current match scratch): ratio test (+ cross-check), 3-D lookup in slot a, compaction
-int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g);
+// nq_dev (may be NULL): a device word that bounds the query rows the kernel looks at (vo_track_map: the rows behind it are padding)
+int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g,
+                    const int32_t* nq_dev = nullptr);
+// The chain as a link of a longer one (vo_track_map).  in: nq_dev as above, rec_dev = device memory that receives a copy of the
+// record (the next kernel need not read pinned host memory); out: where the step left its correspondences and their mask
+struct PnpChain { const int32_t* nq_dev = nullptr; PnpRec* rec_dev = nullptr; PnpDev d = {}; uint8_t* mask = nullptr; };
+// the checks of the PnP pair entries.  view_n >= 0: slot_a is a view slot about to be written with view_n depth-carrying keypoints
+// (its present contents are not looked at)
+int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who,
+              LoopGate* lg, int view_n = -1);
+// the whole chain on ctx->stream (ransac.hip); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
+int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
+                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain = nullptr);
 
 // ---- asynchronous steps (match.hip): see vo_ctx::AsyncAlt -------------------------------------------------------------------
 static const size_t MONO_HDR = 4096;             // monocular record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on

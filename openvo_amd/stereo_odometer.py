@@ -32,7 +32,7 @@ class StereoOdometer:
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
                  match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
-                 loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1):
+                 loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -80,11 +80,22 @@ class StereoOdometer:
         (metres along the optical axis) are not in a view.  cross_check, match_window (a guided search around the landmark's
         predicted pixel, scaled by the span as ever), pnp_refine and loop_check compose unchanged.  No pose step is begun ahead in
         this mode; run() still submits sparse pairs ahead.  Where the fused PnP step cannot run (a replaced matcher or seam),
-        update() raises ValueError."""
+        update() raises ValueError.
+        map_fused=True (track="map" only; default False): the map step -- view, PnP step, decisions, motion gates, pose composition
+        and the update of the map -- is ONE native call with one device synchronisation (vo_track_map) instead of three calls with
+        the host's arithmetic between them.  The decisions and counts are those of the unfused chain; c_T_w comes from the device
+        (composed and inverted there in a fixed order: equal to the host's to the last bits, not bit for bit).  A frame that finds
+        more than 3800 landmarks in the map takes the unfused chain."""
         if not isinstance(track, str) or track not in ("pair", "map"):
             raise ValueError("track must be 'pair' or 'map'")
         if track == "map" and (depth != "sparse" or pose_method != "pnp"):
             raise ValueError("track='map' needs depth='sparse' and pose_method='pnp'")
+        if not isinstance(map_fused, (bool, np.bool_)):
+            raise ValueError("map_fused must be True or False")
+        if map_fused and track != "map":
+            raise ValueError("map_fused=True needs track='map'")
+        if map_fused:                # (an instance attribute only where the option is on: without it the object is what it was)
+            self.map_fused = True
 
         def _int(v, lo, hi):
             return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and lo <= v <= hi
@@ -285,6 +296,7 @@ class StereoOdometer:
         m = (r["q"], r["t"], r["mask"]) if r is not None else (None, None, None)
         self.map_counts["update"] = self._ctx.map_update(self._map, slot, np.linalg.inv(self.c_T_w), self._map_serial, self.map_max_age,
                                                          self.map_max_obs, *m)
+        self._map_size = int(self.map_counts["update"][5])
         self._map_serial += 1
 
     def _map_track(self, kps, desc, im3d):
@@ -294,6 +306,8 @@ class StereoOdometer:
         slot = kps.frame.slot
         Q = self.stereo.Q
         K4 = (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3]))
+        if self.map_fused and len(kps) >= 2 and self._map_size <= _native.MAP_TRACK_MAX:
+            return self._map_track_fused(slot, K4)
         c2 = self.map_counts["view"] = self._ctx.map_view(self._map, self.c_T_w, K4, self.map_z_min, slot, self._view_slot)
         if not (max(self.min_matches, 2) <= int(c2[1]) <= 3800 and len(kps) >= 2):
             return False
@@ -305,6 +319,31 @@ class StereoOdometer:
         self.c_T_w_prev = self.c_T_w
         self.c_T_w = T @ self.c_T_w
         self._map_fold(slot, got["r"])
+        self.track_source = "map"
+        return True
+
+    def _map_track_fused(self, slot, K4):
+        """_map_track in one native call (vo_track_map): the same decisions in the same order, taken on the device."""
+        self._pair_span = None
+        span = self.skipped_frames + 1
+        kw = self._pnp_kwargs(self._pose_params())
+        r = self._ctx.map_track(self._map, slot, self._view_slot, self.c_T_w, K4, self.map_z_min, kw["ratio"], kw["iters"], kw["thr"],
+                                kw["seed"], kw["refine"], self.min_matches, self.MAX_DISTANCE_CHANGE * span, self.MAX_ROTATION_CHANGE * span,
+                                self._map_serial, self.map_max_age, self.map_max_obs, cross_check=kw["cross_check"],
+                                window=kw.get("window"), loop=kw.get("loop"), want_matches=False)
+        self.map_counts["view"] = r["view"]
+        if r["flags"] & 1 and r["decision"] not in (1, 2):     # (behind the view and the match count, as in _pair_pnp_fused)
+            raise ZeroDivisionError("division by zero")
+        cause = _native.MAP_DECISIONS[r["decision"]]
+        if r["decision"] != 0:
+            if cause is not None:
+                self.skip_cause = cause
+            return False
+        self.c_T_w_prev = self.c_T_w
+        self.c_T_w = np.vstack([r["c_T_w"], [0, 0, 0, 1]])
+        self.map_counts["update"] = r["update"]
+        self._map_size = int(r["update"][5])
+        self._map_serial += 1
         self.track_source = "map"
         return True
 
@@ -338,6 +377,8 @@ class StereoOdometer:
         except Exception:
             pass
 
+    map_fused = False        # True (constructor): the map step is one native call (_map_track_fused)
+    _map_size = 0            # landmarks in the map as its last update reported (set with the first fold)
     _pnp_fused = True        # False: pose_method="pnp" takes the composed path (_pair_pnp) whatever the conditions
     _PNP_CTX_SEAMS = ("point_clouds", "ransac_pnp")
 
