@@ -61,7 +61,8 @@ def svd3(A):
             a = [0.0, 1.0, 0.0]
         Uc[1] = _cross(Uc[0], a)
         nn = math.sqrt(Uc[1][0] * Uc[1][0] + Uc[1][1] * Uc[1][1] + Uc[1][2] * Uc[1][2])
-        Uc[1] = [v / nn for v in Uc[1]]
+        with np.errstate(all="ignore"):               # (a zero E: 0 / 0 = NaN as on the device, where Python's floats would raise)
+            Uc[1] = [float(np.float64(v) / np.float64(nn)) for v in Uc[1]]
     if w[2] <= tiny or w[2] <= 1e-14 * w[0]:
         Uc[2] = _cross(Uc[0], Uc[1])
         nn = math.sqrt(Uc[2][0] * Uc[2][0] + Uc[2][1] * Uc[2][1] + Uc[2][2] * Uc[2][2])
