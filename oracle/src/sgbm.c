@@ -182,6 +182,10 @@ static void wta_row(const cost_t* Srow, const sgbm_eff* e, int w, int16_t* disp1
     for (int x = W1 - 1; x >= 0; x--) {
         const cost_t* Sp = Srow + (size_t)x * D;
         int minS = minS_in[x], bestDisp = best_in[x], d;
+        /* every sum saturated: no winner.  stereosgbm.cpp goes on with bestDisp = -1, changes nothing (its disp2 test cannot
+         * pass at minS = 32767 and -16 + minD * 16 is the invalid value already) but reads disp2cost one column further right:
+         * past the buffer for the last column at minDisparity <= 0.  Left out here. */
+        if (bestDisp < 0) continue;
         for (d = 0; d < D; d++)
             if (Sp[d] * (100 - e->ur) < minS * 100 && abs(bestDisp - d) > 1) break;
         if (d < D) continue;

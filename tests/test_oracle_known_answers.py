@@ -106,6 +106,31 @@ def test_median_and_speckle(oracle):
     assert (out[d == 320] == 320).all()
 
 
+def test_sgbm_every_sum_saturated_in_the_last_column(oracle):
+    """The saturating scene of tests/sgbm_def_cases.py in MODE_HH, at minDisparity 0 and -16: pixels whose eight path costs sum
+    to 32767 and more at every disparity have no winner and come out invalid, the others (ratio 0, no left-right limit) valid.
+    In the band's last column stereosgbm.cpp's bestDisp = -1 reads disp2cost[w], one element past the buffer; the oracle leaves
+    that step out, and under the sanitizer build this test is the one that walks over the place.  At minDisparity -16 every row
+    has such a pixel; at 0 the last column is ftzero against ftzero at d = 0 and one row has."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import sgbm_def
+    import sgbm_def_cases as C
+    for name, last in (("saturating-m1", 1), ("saturating-minD-16-m1", 24)):
+        c = C.BY_NAME[name]
+        assert c.p["minDisparity"] <= 0 and c.mode == 1
+        e = sgbm_def.effective(c.p, c.w)
+        L, R = C.images(c)
+        d, info = C.definition(c)
+        none = (d["S"] == sgbm_def.MAX_S).all(axis=2)
+        assert none[:, -1].sum() >= last and 100 <= none.sum() == info["no_winner"] <= none.size - 100
+        raw, _, fin = oracle.sgbm_compute(L, R, c.p, 1, stages=True)
+        band = raw[:, e.x0:e.x1]
+        assert (band[none] == e.invalid).all() and (band[~none] >= e.minD * 16).all()
+        assert np.array_equal(raw, d["raw"]) and np.array_equal(fin, d["final"])
+
+
 def test_fast_corner_and_nms(oracle):
     img = np.full((40, 40), 50, np.uint8)
     img[20, 20] = 200                      # isolated bright pixel: all 16 ring pixels darker
