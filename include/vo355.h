@@ -444,6 +444,31 @@ int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int mat
                       uint32_t seed, int refine_iters, int want_matches, int* ticket_out);
 int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
                     uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
+/* The PnP step with local-optimisation rounds (LO-RANSAC): the refit re-selects its inliers.  tests/pnp_lo_ref.py restates it.
+ * With the winner Rt_0 (float64), its mask S_0, the n usable correspondences X / uv (float32), K4, thr (float32), steps =
+ * refine_iters (1 .. 20) and R = lo_rounds (1 .. 8), for r = 1 .. R:
+ *   1. (Rt_r, status) = the refinement above from Rt_{r-1} on the set S_{r-1}, `steps` steps: the same arithmetic.  Status 1: fewer
+ *      than 6 points in S_{r-1}; -1: a pivot was not positive or a value was not finite.
+ *   2. status != 0: the round is discarded entirely and the loop ends.
+ *   3. S_r[i], for every i < n, = the scoring kernels' own test under Rt_r: P = K [R | t] rounded to float32 the way a
+ *      hypothesis's P is formed -- (float)(fx Rt[c] + cx Rt[8 + c]), (float)(fy Rt[4 + c] + cy Rt[8 + c]), (float)Rt[8 + c] for
+ *      c = 0 .. 3 -- then the division-free float32 test of vo_ransac_pnp against thr * thr.
+ * The result is (Rt_c, S_c) of the last completed round c = 0 .. R; status 0 when c >= 1, otherwise round 1's status, which is
+ * the plain refinement's for the same inputs.  No early exit, no acceptance test: a function of the inputs alone.  With R = 1 the
+ * pose is vo_pnp_pair's Rt12_refined, bit for bit.
+ *   lo_rounds 0 .. 8; a value >= 1 needs refine_iters >= 1 (VO_E_ARG otherwise).  lo_rounds == 0: every output equals the plain
+ *           entry's, bit for bit, and lo2 = {0, best_count}.
+ *   lo2     = {rounds completed c, |S_c|}
+ *   counts4, Rt12, q_idx, t_idx: unchanged -- the RANSAC's own result stays inspectable.  mask_out: S_c.  Rt12_refined: the LO pose
+ *           Rt_c, valid for status 0.  refine2 = {status, Gauss-Newton steps applied in the completed rounds (c * refine_iters)}.
+ * The rounds are part of a ticket's parameters; either _end ends a PnP ticket of either kind, the plain one returns no lo2. */
+int vo_pnp_pair_lo(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                   uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                   int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int lo_rounds, int32_t* lo2);
+int vo_pnp_pair_begin_lo(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4, int iters, float thr,
+                         uint32_t seed, int refine_iters, int want_matches, int lo_rounds, int* ticket_out);
+int vo_pnp_pair_end_lo(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                       uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int32_t* lo2);
 
 /* Sparse stereo depth (NOT part of the reference, which reads a dense disparity at its keypoints, stereo_odometer.py:50-79,117):
  * per-keypoint 3-D from ORB on BOTH rectified images of a slot, without any SGBM run.  Defined by this build; tests/sparse_stereo_ref.py
@@ -639,6 +664,14 @@ int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, const double
                  double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters,
                  int min_matches, double max_dist, double max_rot, int serial, int max_age, int max_obs,
                  vo_track_map_rec* rec, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap);
+/* vo_track_map with the PnP step of vo_pnp_pair_lo (lo_rounds as there; 0: this IS vo_track_map).  The decisions, the gates and the
+ * composition of c / d see the LO pose when its status is 0 (decision 4 still reads the winner's best_count); step 1 of the update
+ * reads S_c; mask_out is S_c.  The record keeps its size and offsets: rec->pad = rounds completed, rec->pad2[0] = |S_c| (both 0
+ * with lo_rounds == 0). */
+int vo_track_map_lo(vo_ctx* ctx, int map, int slot_new, int view_slot, const double* Rt12_cw_pred, const double* K4, float z_min,
+                    double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters,
+                    int min_matches, double max_dist, double max_rot, int serial, int max_age, int max_obs,
+                    vo_track_map_rec* rec, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int lo_rounds);
 int vo_map_create(vo_ctx* ctx, int capacity, int* map_out);
 int vo_map_destroy(vo_ctx* ctx, int map);
 int vo_map_reset(vo_ctx* ctx, int map);

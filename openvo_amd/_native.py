@@ -48,6 +48,7 @@ SYMBOLS = [
     "vo_get_stage_timeline",
     "vo_map_create", "vo_map_destroy", "vo_map_reset", "vo_map_view", "vo_map_update", "vo_map_download",
     "vo_track_map",
+    "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
 ]
 
 
@@ -280,6 +281,13 @@ def lib():
         if hasattr(L, "vo_track_map"):              # (likewise: an older build has no fused map step)
             cf, cu = ctypes.c_float, ctypes.c_uint32
             for name, proto in (("vo_track_map", [vp, ci, ci, ci, vp, vp, cf, cd, ci, ci, cf, cu, ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp, ci]),):
+                getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_pnp_pair_lo"):            # (likewise: an older build has no local-optimisation rounds)
+            cf, cu = ctypes.c_float, ctypes.c_uint32
+            for name, proto in (("vo_pnp_pair_lo", [vp, ci, ci, cd, ci, vp, ci, cf, cu, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
+                                ("vo_pnp_pair_begin_lo", [vp, ci, ci, cd, ci, vp, ci, cf, cu, ci, ci, ci, vp]),
+                                ("vo_pnp_pair_end_lo", [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]),
+                                ("vo_track_map_lo", [vp, ci, ci, ci, vp, vp, cf, cd, ci, ci, cf, cu, ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp, ci, ci])):
                 getattr(L, name).argtypes = proto
         plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
@@ -1160,6 +1168,45 @@ class Context:
         self._ck(self._lib.vo_pnp_pair_end(self._h, int(ticket), *[_p(a) for a in head + arrays], self.kp_cap))
         return self._pnp_result(head, arrays)
 
+    # ---- the PnP step with local-optimisation rounds (vo_pnp_pair_lo; new methods: the signatures above are pinned)
+    @staticmethod
+    def lo_rounds_arg(lo_rounds, refine):
+        """int 0 .. 8, and a value above 0 needs refine >= 1; ValueError for anything else"""
+        if isinstance(lo_rounds, bool) or not isinstance(lo_rounds, (int, np.integer)) or not 0 <= int(lo_rounds) <= 8:
+            raise ValueError("lo_rounds is an int 0 .. 8, not %r" % (lo_rounds,))
+        if lo_rounds > 0 and int(refine) < 1:
+            raise ValueError("lo_rounds >= 1 needs refine >= 1 (a round is `refine` Gauss-Newton steps and a re-selection)")
+        return int(lo_rounds)
+
+    def pnp_pair_lo(self, slot_a, slot_b, ratio, K4, lo_rounds, iters=256, thr=1.5, seed=4321, refine=3, want_matches=False, cross_check=False,
+                    window=None, loop=None):
+        """pnp_pair_window whose refit runs `lo_rounds` (0 .. 8) rounds of {refine steps, re-selection of the inliers under the
+        refitted pose} (vo_pnp_pair_lo).  The dict gains lo_rounds (completed) and lo_support (|S_c|); Rt_refined is the LO pose,
+        mask the final set S_c, refine_steps the steps of the completed rounds; Rt, best_iter, best_count, q, t stay the RANSAC's."""
+        lo_rounds = self.lo_rounds_arg(lo_rounds, refine)
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        head, arrays = self._pnp_out(want_matches)
+        lo2 = np.zeros(2, np.int32)
+        self._ck(self._lib.vo_pnp_pair_lo(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window, loop), _p(K4), int(iters),
+                                          float(thr), int(seed) & 0xFFFFFFFF, int(refine), *[_p(a) for a in head + arrays], self.kp_cap, lo_rounds, _p(lo2)))
+        return dict(self._pnp_result(head, arrays), lo_rounds=int(lo2[0]), lo_support=int(lo2[1]))
+
+    def pnp_pair_begin_lo(self, slot_a, slot_b, ratio, K4, lo_rounds, iters=256, thr=1.5, seed=4321, refine=3, want_matches=False, cross_check=False,
+                          window=None, loop=None):
+        """pnp_pair_lo in two halves -> a ticket for pnp_pair_end_lo (or pnp_pair_end, which returns no lo_rounds / lo_support)"""
+        lo_rounds = self.lo_rounds_arg(lo_rounds, refine)
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        t = ctypes.c_int(-1)
+        self._ck(self._lib.vo_pnp_pair_begin_lo(self._h, int(slot_a), int(slot_b), float(ratio), self._mflags(cross_check, window, loop), _p(K4), int(iters),
+                                                float(thr), int(seed) & 0xFFFFFFFF, int(refine), int(bool(want_matches)), lo_rounds, ctypes.byref(t)))
+        return t.value
+
+    def pnp_pair_end_lo(self, ticket, want_matches=False):
+        head, arrays = self._pnp_out(want_matches)
+        lo2 = np.zeros(2, np.int32)
+        self._ck(self._lib.vo_pnp_pair_end_lo(self._h, int(ticket), *[_p(a) for a in head + arrays], self.kp_cap, _p(lo2)))
+        return dict(self._pnp_result(head, arrays), lo_rounds=int(lo2[0]), lo_support=int(lo2[1]))
+
     # ---- landmark map (vo_map_*: NOT part of the reference)
     def map_create(self, capacity):
         """-> the handle of a new landmark map of `capacity` landmarks (16 .. kp_cap; at most VO_NUM_MAPS per context)."""
@@ -1225,6 +1272,26 @@ class Context:
                                         int(min_matches), float(max_dist), float(max_rot), int(serial), int(max_age), int(max_obs),
                                         ctypes.byref(rec), *[_p(a) for a in arrays], self.kp_cap))
         out = rec.as_dict()
+        if want_matches:
+            n = out["n"]
+            out.update(mask=arrays[0][:n].copy(), q=arrays[1][:n].copy(), t=arrays[2][:n].copy())
+        return out
+
+    def track_map_lo(self, handle, slot_new, view_slot, Rt_cw_pred, K4, z_min, ratio, iters, thr, seed, refine, min_matches, max_dist, max_rot,
+                     serial, max_age, max_obs, lo_rounds, cross_check=False, window=None, loop=None, want_matches=True):
+        """map_track whose PnP step is pnp_pair_lo's (vo_track_map_lo): the decisions, gates and composition see the LO pose, the
+        update reads S_c.  The dict gains lo_rounds (completed) and lo_support (|S_c|)."""
+        lo_rounds = self.lo_rounds_arg(lo_rounds, refine)
+        Rt, K4 = self._pose12(Rt_cw_pred), _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        rec = MapTrackRec()
+        arrays = [None, None, None]
+        if want_matches:
+            arrays = self._pnp_out(True)[1]
+        self._ck(self._lib.vo_track_map_lo(self._h, int(handle), int(slot_new), int(view_slot), _p(Rt), _p(K4), float(z_min), float(ratio),
+                                           self._mflags(cross_check, window, loop), int(iters), float(thr), int(seed) & 0xFFFFFFFF, int(refine),
+                                           int(min_matches), float(max_dist), float(max_rot), int(serial), int(max_age), int(max_obs),
+                                           ctypes.byref(rec), *[_p(a) for a in arrays], self.kp_cap, lo_rounds))
+        out = dict(rec.as_dict(), lo_rounds=int(rec.pad), lo_support=int(rec.pad2[0]))
         if want_matches:
             n = out["n"]
             out.update(mask=arrays[0][:n].copy(), q=arrays[1][:n].copy(), t=arrays[2][:n].copy())

@@ -520,11 +520,12 @@ extern "C" int vo_map_update(vo_ctx* ctx, int map, int slot_new, const double* R
 }
 
 // view + PnP step + decisions + update as one chain on ctx->stream: see the header.  Everything is checked first; the map's host
-// state changes only behind the one synchronisation, and only on decision 0.
-extern "C" int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, const double* Rt12_cw_pred, const double* K4v, float z_min,
-                            double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters, int min_matches,
-                            double max_dist, double max_rot, int serial, int max_age, int max_obs, vo_track_map_rec* rec, uint8_t* mask_out,
-                            int32_t* q_idx, int32_t* t_idx, int cap)
+// state changes only behind the one synchronisation, and only on decision 0.  lo_rounds > 0 (vo_track_map_lo): the PnP step runs
+// its LO form -- k_map_decide reads the LO pose from the record, k_map_update_dev the set S_c from the step's mask.
+static int track_map_impl(vo_ctx* ctx, int map, int slot_new, int view_slot, const double* Rt12_cw_pred, const double* K4v, float z_min,
+                          double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters, int min_matches,
+                          double max_dist, double max_rot, int serial, int max_age, int max_obs, vo_track_map_rec* rec, uint8_t* mask_out,
+                          int32_t* q_idx, int32_t* t_idx, int cap, int lo_rounds)
 {
     LandmarkMap* m;
     if (int rc = map_get(ctx, map, "vo_track_map", &m)) return rc;
@@ -589,7 +590,7 @@ extern "C" int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, c
         f.n_kp = n; f.has_kp = true; f.kp_depth = true;
         PnpChain chain;
         chain.nq_dev = &td->vis; chain.rec_dev = &td->pnp;
-        rc = pnp_enqueue(ctx, f, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, prec, arr, lg, &chain);
+        rc = pnp_enqueue(ctx, f, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, prec, arr, lg, &chain, lo_rounds);
         if (!rc) {
             {
                 StageTimer t(ctx, VO_T_POSE);
@@ -616,9 +617,11 @@ extern "C" int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, c
     m->view_n = vis;
     rec->decision = dec; rec->map_n = n; rec->vis = vis; rec->update_flags = tail->update_flags;
     rec->M = prec->M; rec->n = prec->n; rec->best_iter = prec->best_iter; rec->best_count = prec->best_count;
-    rec->flags = prec->flags; rec->rstatus = prec->rstatus; rec->rsteps = prec->rsteps; rec->pad = 0;
+    rec->flags = prec->flags; rec->rstatus = prec->rstatus; rec->rsteps = prec->rsteps;
+    rec->pad = lo_rounds > 0 ? prec->lo_rounds : 0;                  // (vo_track_map_lo: rounds completed ...
     for (int i = 0; i < 6; i++) rec->counts6[i] = tail->counts6[i];
-    rec->pad2[0] = rec->pad2[1] = 0;
+    rec->pad2[0] = lo_rounds > 0 ? prec->lo_support : 0;             //  ... and |S_c|)
+    rec->pad2[1] = 0;
     memcpy(rec->Rt, prec->Rt, sizeof(rec->Rt)); memcpy(rec->Rtr, prec->Rtr, sizeof(rec->Rtr));
     memcpy(rec->c_T_w, tail->cw, sizeof(rec->c_T_w)); memcpy(rec->w_T_c, tail->wc, sizeof(rec->w_T_c));
     if (arr) {
@@ -637,6 +640,25 @@ extern "C" int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, c
         m->max_serial = serial;
     }
     return VO_OK;
+}
+
+extern "C" int vo_track_map(vo_ctx* ctx, int map, int slot_new, int view_slot, const double* Rt12_cw_pred, const double* K4v, float z_min,
+                            double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters, int min_matches,
+                            double max_dist, double max_rot, int serial, int max_age, int max_obs, vo_track_map_rec* rec, uint8_t* mask_out,
+                            int32_t* q_idx, int32_t* t_idx, int cap)
+{
+    return track_map_impl(ctx, map, slot_new, view_slot, Rt12_cw_pred, K4v, z_min, ratio, match_flags, iters, thr, seed, refine_iters, min_matches,
+                          max_dist, max_rot, serial, max_age, max_obs, rec, mask_out, q_idx, t_idx, cap, 0);
+}
+
+extern "C" int vo_track_map_lo(vo_ctx* ctx, int map, int slot_new, int view_slot, const double* Rt12_cw_pred, const double* K4v, float z_min,
+                               double ratio, int match_flags, int iters, float thr, uint32_t seed, int refine_iters, int min_matches,
+                               double max_dist, double max_rot, int serial, int max_age, int max_obs, vo_track_map_rec* rec, uint8_t* mask_out,
+                               int32_t* q_idx, int32_t* t_idx, int cap, int lo_rounds)
+{
+    if (int rc = pnp_lo_check(ctx, lo_rounds, refine_iters, "vo_track_map_lo")) return rc;
+    return track_map_impl(ctx, map, slot_new, view_slot, Rt12_cw_pred, K4v, z_min, ratio, match_flags, iters, thr, seed, refine_iters, min_matches,
+                          max_dist, max_rot, serial, max_age, max_obs, rec, mask_out, q_idx, t_idx, cap, lo_rounds);
 }
 
 extern "C" int vo_map_download(vo_ctx* ctx, int map, float* xyz, uint8_t* desc, int32_t* octave, int32_t* obs, int32_t* last, int cap, int* n_out)

@@ -1484,16 +1484,83 @@ __device__ __forceinline__ void pn_apply_twist(double* Rt, const double* d)
     for (int k = 0; k < 12; k++) Rt[k] = out[k];
 }
 
+// One Gauss-Newton step of the refit by the whole block (256 threads): every thread sums its points of `mask` (i = thread + 256 k,
+// ascending) into the 21 + 6 sums of J^T J and J^T r, a DPP tree sums the wave, thread 0 adds the four waves' values from LDS in
+// wave order, solves and updates s_pose, or sets *s_status = -1 and leaves s_pose alone.  Ends behind a barrier: every thread may
+// read s_pose and *s_status.  Shared by both forms of k_pnp_finish.
+__device__ __forceinline__ void pn_gn_step(double* s_pose, double (*s_red)[27], int* s_status, const float* __restrict__ X,
+                                           const float* __restrict__ uv, const uint8_t* mask, int live, const K4& K)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double R[12], acc[27];
+#pragma unroll
+    for (int k = 0; k < 12; k++) R[k] = s_pose[k];
+#pragma unroll
+    for (int k = 0; k < 27; k++) acc[k] = 0.0;
+    for (int i = threadIdx.x; i < live; i += blockDim.x) {
+        if (!mask[i]) continue;
+        const double x = (double)X[3 * i], y = (double)X[3 * i + 1], z = (double)X[3 * i + 2];
+        const double xc = ((R[0] * x + R[1] * y) + R[2] * z) + R[3];
+        const double yc = ((R[4] * x + R[5] * y) + R[6] * z) + R[7];
+        const double zc = ((R[8] * x + R[9] * y) + R[10] * z) + R[11];
+        const double iz = 1.0 / zc;
+        const double r[2] = { (K.fx * xc * iz + K.cx) - (double)uv[2 * i], (K.fy * yc * iz + K.cy) - (double)uv[2 * i + 1] };
+        const double a[2][3] = { { K.fx * iz, 0.0, -K.fx * xc * iz * iz }, { 0.0, K.fy * iz, -K.fy * yc * iz * iz } };
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const double j[6] = { a[e][2] * yc - a[e][1] * zc, a[e][0] * zc - a[e][2] * xc, a[e][1] * xc - a[e][0] * yc,
+                                  a[e][0], a[e][1], a[e][2] };
+#pragma unroll
+            for (int u = 0, k = 0; u < 6; u++)
+#pragma unroll
+                for (int v = u; v < 6; v++, k++) acc[k] += j[u] * j[v];
+#pragma unroll
+            for (int u = 0; u < 6; u++) acc[21 + u] += j[u] * r[e];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 27; k++) {
+        const double sum = wave_sum_f64_dpp(acc[k]);
+        if (lane == 0) s_red[wv][k] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double H[21], g[6], d[6] = { 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+        for (int k = 0; k < 27; k++) {
+            const double sum = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
+            if (k < 21) H[k] = sum; else g[k - 21] = sum;
+        }
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 21; k++) ok = ok && isfinite(H[k]);
+#pragma unroll
+        for (int k = 0; k < 6; k++) ok = ok && isfinite(g[k]);
+        ok = ok && pn_solve6(H, g, d);
+        double Rn[12];
+        for (int k = 0; k < 12; k++) Rn[k] = s_pose[k];
+        if (ok) pn_apply_twist(Rn, d);
+        for (int k = 0; k < 12; k++) ok = ok && isfinite(Rn[k]);
+        if (ok) for (int k = 0; k < 12; k++) s_pose[k] = Rn[k];
+        else *s_status = -1;
+    }
+    __syncthreads();
+}
+
 // The end of the step in ONE block of four waves: argmax of the inlier counts (most inliers, then the lowest index: k_ransac_best)
 // -> the winner's mask (k_pnp_mask's arithmetic) -> refine_iters Gauss-Newton steps in float64 on the winner's inliers: residual
-// (fx X'/Z' + cx - u, fy Y'/Z' + cy - v), X' = R X + t, d X' / d (w, v) = [-[X']x | I]; every thread sums its points (i = thread
-// + 256 k, ascending) into the 21 + 6 sums of J^T J and J^T r, a DPP tree sums the wave, lane 0 adds the four waves' values from
-// LDS in wave order and solves -- a fixed order, so the result is a function of the inputs alone; no early exit -> the whole
+// (fx X'/Z' + cx - u, fy Y'/Z' + cy - v), X' = R X + t, d X' / d (w, v) = [-[X']x | I]; the sums of a step are taken in a fixed
+// order (pn_gn_step), so the result is a function of the inputs alone; no early exit -> the whole
 // record (and the mask / q / t arrays when `arr` is given) written straight into pinned host memory.
+// LO (vo_pnp_pair_lo, lo_rounds >= 1): the refit becomes lo_rounds rounds of {refine_iters steps on the present set, re-selection
+// of the set under the refitted pose by the scoring kernels' own float32 test}; a round that cannot run -- fewer than 6 points in
+// its set, a pivot that is not positive, a value that is not finite -- is discarded whole and ends the loop.  The record carries
+// the pose and the mask arrays the set of the last completed round; see include/vo355.h.
+template <bool LO>
 __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ counts, int iters, const double* __restrict__ Rt_all,
                                                     const float* __restrict__ P_all, const float* __restrict__ X, const float* __restrict__ uv,
                                                     int nq, const int32_t* __restrict__ hdr, const int32_t* __restrict__ q2,
-                                                    const int32_t* __restrict__ t2, float thr2, K4 K, int refine_iters,
+                                                    const int32_t* __restrict__ t2, float thr2, K4 K, int refine_iters, int lo_rounds,
                                                     uint8_t* __restrict__ mask, PnpRec* __restrict__ rec, uint8_t* __restrict__ arr, size_t cap,
                                                     PnpRec* __restrict__ rec_dev)
 {
@@ -1544,72 +1611,73 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
         }
     }
     const bool refine = refine_iters > 0 && best_count >= 6;
-    int steps = 0;
-    if (refine) {
-        if (threadIdx.x == 0) s_status = 0;
-        for (; steps < refine_iters; steps++) {
-            double R[12], acc[27];
-#pragma unroll
-            for (int k = 0; k < 12; k++) R[k] = s_pose[k];
-#pragma unroll
-            for (int k = 0; k < 27; k++) acc[k] = 0.0;
-            for (int i = threadIdx.x; i < live; i += blockDim.x) {
-                if (!mask[i]) continue;
-                const double x = (double)X[3 * i], y = (double)X[3 * i + 1], z = (double)X[3 * i + 2];
-                const double xc = ((R[0] * x + R[1] * y) + R[2] * z) + R[3];
-                const double yc = ((R[4] * x + R[5] * y) + R[6] * z) + R[7];
-                const double zc = ((R[8] * x + R[9] * y) + R[10] * z) + R[11];
-                const double iz = 1.0 / zc;
-                const double r[2] = { (K.fx * xc * iz + K.cx) - (double)uv[2 * i], (K.fy * yc * iz + K.cy) - (double)uv[2 * i + 1] };
-                const double a[2][3] = { { K.fx * iz, 0.0, -K.fx * xc * iz * iz }, { 0.0, K.fy * iz, -K.fy * yc * iz * iz } };
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const double j[6] = { a[e][2] * yc - a[e][1] * zc, a[e][0] * zc - a[e][2] * xc, a[e][1] * xc - a[e][0] * yc,
-                                          a[e][0], a[e][1], a[e][2] };
-#pragma unroll
-                    for (int u = 0, k = 0; u < 6; u++)
-#pragma unroll
-                        for (int v = u; v < 6; v++, k++) acc[k] += j[u] * j[v];
-#pragma unroll
-                    for (int u = 0; u < 6; u++) acc[21 + u] += j[u] * r[e];
-                }
+    int steps = 0, done = 0, support = best_count;
+    if (!LO) {
+        if (refine) {
+            if (threadIdx.x == 0) s_status = 0;
+            for (; steps < refine_iters; steps++) {
+                pn_gn_step(s_pose, s_red, &s_status, X, uv, mask, live, K);
+                if (s_status < 0) break;
             }
-#pragma unroll
-            for (int k = 0; k < 27; k++) {
-                const double sum = wave_sum_f64_dpp(acc[k]);
-                if (lane == 0) s_red[wv][k] = sum;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                double H[21], g[6], d[6] = { 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-                for (int k = 0; k < 27; k++) {
-                    const double sum = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
-                    if (k < 21) H[k] = sum; else g[k - 21] = sum;
-                }
-                bool ok = true;
-#pragma unroll
-                for (int k = 0; k < 21; k++) ok = ok && isfinite(H[k]);
-#pragma unroll
-                for (int k = 0; k < 6; k++) ok = ok && isfinite(g[k]);
-                ok = ok && pn_solve6(H, g, d);
-                double Rn[12];
-                for (int k = 0; k < 12; k++) Rn[k] = s_pose[k];
-                if (ok) pn_apply_twist(Rn, d);
-                for (int k = 0; k < 12; k++) ok = ok && isfinite(Rn[k]);
-                if (ok) for (int k = 0; k < 12; k++) s_pose[k] = Rn[k];
-                else s_status = -1;
-            }
-            __syncthreads();
-            if (s_status < 0) break;
         }
+    } else if (refine) {
+        __shared__ double s_prev[12];
+        __shared__ float s_P[12];
+        __shared__ int s_cnt[4];
+        int round_status = 0;                   // (uniform: what s_status would read, kept in a register between the barriers)
+        for (; done < lo_rounds && support >= 6; done++) {
+            if (threadIdx.x < 12) s_prev[threadIdx.x] = s_pose[threadIdx.x];
+            if (threadIdx.x == 0) s_status = 0;
+            __syncthreads();
+            for (int k = 0; k < refine_iters; k++) {
+                pn_gn_step(s_pose, s_red, &s_status, X, uv, mask, live, K);
+                if (s_status < 0) break;
+            }
+            round_status = s_status;
+            if (round_status < 0) {             // the round is discarded: the pose of the round before, the set untouched
+                __syncthreads();
+                if (threadIdx.x < 12) s_pose[threadIdx.x] = s_prev[threadIdx.x];
+                break;
+            }
+            if (threadIdx.x < 4) {              // P = K [R | t] rounded to float32, as k_pnp_hyp forms a hypothesis's
+                const int c = threadIdx.x;
+                s_P[c] = (float)(K.fx * s_pose[c] + K.cx * s_pose[8 + c]);
+                s_P[4 + c] = (float)(K.fy * s_pose[4 + c] + K.cy * s_pose[8 + c]);
+                s_P[8 + c] = (float)s_pose[8 + c];
+            }
+            __syncthreads();
+            for (int k = 0; k < 12; k++) P[k] = s_P[k];
+            int cnt = 0;
+            for (int i0 = 0; i0 < nq; i0 += blockDim.x) {       // (uniform trip count: every lane takes part in the ballot)
+                const int i = i0 + threadIdx.x;
+                bool in = false;
+                if (i < live) {
+                    const float2 b = ((const float2*)uv)[i];
+                    in = reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2);
+                }
+                if (i < nq) mask[i] = in ? 1 : 0;              // (its own points: read back by the thread that wrote them)
+                cnt += __popcll(__ballot(in));
+            }
+            if (lane == 0) s_cnt[wv] = cnt;
+            __syncthreads();
+            support = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+            steps += refine_iters;
+        }
+        __syncthreads();
+        // status: 0 once a round is complete; otherwise round 1's, which is the plain refit's for the same inputs
+        if (threadIdx.x == 0) s_status = done >= 1 ? 0 : (round_status < 0 ? -1 : 1);
+        if (arr && done >= 1)
+            for (int i = threadIdx.x; i < nq; i += blockDim.x) arr[i] = mask[i];
+        __syncthreads();
     }
     if (threadIdx.x == 0) {
         rec->rstatus = s_status; rec->rsteps = steps;
         for (int k = 0; k < 12; k++) rec->Rtr[k] = s_pose[k];
+        if (LO) { rec->lo_rounds = done; rec->lo_support = support; }
         if (rec_dev) {
             rec_dev->rstatus = s_status; rec_dev->rsteps = steps;
             for (int k = 0; k < 12; k++) rec_dev->Rtr[k] = s_pose[k];
+            if (LO) { rec_dev->lo_rounds = done; rec_dev->lo_support = support; }
         }
     }
 }
@@ -1645,7 +1713,7 @@ int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double
 // the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
 // pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
 int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
-                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain)
+                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain, int lo_rounds)
 {
     const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
@@ -1682,8 +1750,10 @@ int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match
         const float thr2 = thr * thr;
         hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d.X, d.uv, nq, K, iters, seed, d_Rt, d_P, d.hdr + 1);
         hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d.X, d.uv, nq, d_P, iters, thr2, d_counts, d.hdr + 1);
-        hipLaunchKernelGGL(k_pnp_finish, dim3(1), dim3(256), 0, ctx->stream, d_counts, iters, d_Rt, d_P, d.X, d.uv, nq, d.hdr, d.q, d.t, thr2, K,
-                           refine_iters, d_mask, rec, arr, pnp_cap(ctx->kp_cap), chain ? chain->rec_dev : nullptr);
+        // (the plain form is launched whenever no round is asked for: the LO entries with lo_rounds == 0 ARE the plain entries)
+        auto finish = lo_rounds > 0 ? k_pnp_finish<true> : k_pnp_finish<false>;
+        hipLaunchKernelGGL(finish, dim3(1), dim3(256), 0, ctx->stream, d_counts, iters, d_Rt, d_P, d.X, d.uv, nq, d.hdr, d.q, d.t, thr2, K,
+                           refine_iters, lo_rounds, d_mask, rec, arr, pnp_cap(ctx->kp_cap), chain ? chain->rec_dev : nullptr);
         VO_CHECK_LAUNCH(ctx);
     }
     if (chain) { chain->d = d; chain->mask = d_mask; }
@@ -1696,14 +1766,15 @@ static void pnp_rec_clear(PnpRec* r)
     r->rstatus = 1;
 }
 
-// record (+ arrays) -> the caller's outputs; VO_E_STATE for a pair the step refused
+// record (+ arrays) -> the caller's outputs; VO_E_STATE for a pair the step refused.  lo2 (may be NULL) = {rounds completed, |S_c|}
 static int pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
-                      int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, const char* who)
+                      int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, const char* who, int lo_rounds = 0, int32_t* lo2 = nullptr)
 {
     counts4[0] = r->M; counts4[1] = r->n; counts4[2] = r->best_iter; counts4[3] = r->best_count;
     *flags = r->flags;
     memcpy(Rt12, r->Rt, sizeof(r->Rt));
     refine2[0] = r->rstatus; refine2[1] = r->rsteps;
+    if (lo2) { lo2[0] = lo_rounds > 0 ? r->lo_rounds : 0; lo2[1] = lo_rounds > 0 ? r->lo_support : r->best_count; }
     if (Rt12_refined) memcpy(Rt12_refined, r->Rtr, sizeof(r->Rtr));
     if (arr) {
         const size_t cap = pnp_cap(ctx->kp_cap);
@@ -1715,18 +1786,26 @@ static int pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, 
     return VO_OK;
 }
 
-extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
-                           uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
-                           int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+int pnp_lo_check(vo_ctx* ctx, int lo_rounds, int refine_iters, const char* who)
 {
-    if (ctx && (!counts4 || !flags || !Rt12 || !refine2)) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair: bad argument");
+    if (!ctx) return VO_E_ARG;
+    if (lo_rounds < 0 || lo_rounds > 8) return vo_fail(ctx, VO_E_ARG, "%s: lo_rounds is 0 .. 8", who);
+    if (lo_rounds > 0 && refine_iters < 1) return vo_fail(ctx, VO_E_ARG, "%s: lo_rounds >= 1 needs refine_iters >= 1", who);
+    return VO_OK;
+}
+
+static int pnp_pair_impl(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                         uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                         int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int lo_rounds, int32_t* lo2, const char* who)
+{
+    if (ctx && (!counts4 || !flags || !Rt12 || !refine2)) return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
     LoopGate lg;
-    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair", &lg);
+    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, who, &lg);
     if (rc) return rc;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
     const bool want = mask_out || q_idx || t_idx;
-    if (want && cap < a.n_kp) return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair: outputs hold %d entries, %d keypoints", cap, a.n_kp);
+    if (want && cap < a.n_kp) return vo_fail(ctx, VO_E_CAP, "%s: outputs hold %d entries, %d keypoints", who, cap, a.n_kp);
     VO_HIP(ctx, hipSetDevice(ctx->device));
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     PnpRec* rec = (PnpRec*)ctx->pinned;
@@ -1736,53 +1815,86 @@ extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, in
         const size_t bytes = pnp_cap(ctx->kp_cap) * 9;
         if (want && !(arr = (uint8_t*)xfer_stage(ctx, bytes))) {
             if ((rc = xfer_flush(ctx))) return rc;
-            if (!(arr = (uint8_t*)xfer_stage(ctx, bytes))) return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair: the transfer arena cannot hold %d keypoints", a.n_kp);
+            if (!(arr = (uint8_t*)xfer_stage(ctx, bytes))) return vo_fail(ctx, VO_E_CAP, "%s: the transfer arena cannot hold %d keypoints", who, a.n_kp);
         }
-        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, rec, arr, lg))) return rc;
+        if ((rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, rec, arr, lg, nullptr, lo_rounds))) return rc;
         if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
         if (!slot_sparse(a) && ((rc = slot_health(ctx, a, slot_a)) || (rc = slot_health(ctx, b, slot_b)))) return rc;   // never a pose from an undefined disparity
     }
-    return pnp_unpack(ctx, rec, arr, a.n_kp, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, t_idx, "vo_pnp_pair");
+    return pnp_unpack(ctx, rec, arr, a.n_kp, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, t_idx, who, lo_rounds, lo2);
+}
+
+extern "C" int vo_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                           uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                           int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+{
+    return pnp_pair_impl(ctx, slot_a, slot_b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, counts4, flags, Rt12, Rt12_refined, refine2,
+                         mask_out, q_idx, t_idx, cap, 0, nullptr, "vo_pnp_pair");
+}
+
+extern "C" int vo_pnp_pair_lo(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                              uint32_t seed, int refine_iters, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+                              int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int lo_rounds, int32_t* lo2)
+{
+    if (ctx && !lo2) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair_lo: bad argument");
+    if (int rc = pnp_lo_check(ctx, lo_rounds, refine_iters, "vo_pnp_pair_lo")) return rc;
+    return pnp_pair_impl(ctx, slot_a, slot_b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, counts4, flags, Rt12, Rt12_refined, refine2,
+                         mask_out, q_idx, t_idx, cap, lo_rounds, lo2, "vo_pnp_pair_lo");
 }
 
 // The same step in two halves on a POSE alternate (vo_ctx::ALT_POSE: the tickets, streams and scratch of vo_pose_pair_begin --
 // VO_NUM_POSE_ASYNC bounds both kinds together, no stream is added)
-extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
-                                 uint32_t seed, int refine_iters, int want_matches, int* ticket_out)
+static int pnp_begin_impl(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                          uint32_t seed, int refine_iters, int want_matches, int lo_rounds, int* ticket_out, const char* who)
 {
-    if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "vo_pnp_pair_begin: bad argument");
+    if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
     LoopGate lg;
-    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, "vo_pnp_pair_begin", &lg);
+    int rc = pnp_check(ctx, slot_a, slot_b, match_flags, K4v, iters, thr, refine_iters, who, &lg);
     if (rc) return rc;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
     int k;
-    if ((rc = alt_open(ctx, vo_ctx::ALT_POSE, a, b, "vo_pnp_pair_begin", &k))) return rc;
+    if ((rc = alt_open(ctx, vo_ctx::ALT_POSE, a, b, who, &k))) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[k];
     pnp_rec_clear((PnpRec*)p.result);
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
         rc = pnp_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, (PnpRec*)p.result,
-                         want_matches ? p.result + PNP_HDR : nullptr, lg);
+                         want_matches ? p.result + PNP_HDR : nullptr, lg, nullptr, lo_rounds);
     }
     if (rc) return rc;
     p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
     if (slot_sparse(a)) p.gen_a = p.gen_b = 0;       // the step read no disparity: nothing to check at _end
-    p.pnp = true; p.want = want_matches != 0 && a.n_kp > 0; p.nq = a.n_kp;
+    p.pnp = true; p.want = want_matches != 0 && a.n_kp > 0; p.nq = a.n_kp; p.lo = lo_rounds;
     return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }
 
-extern "C" int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
-                               uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+extern "C" int vo_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                                 uint32_t seed, int refine_iters, int want_matches, int* ticket_out)
 {
-    int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && flags && Rt12 && refine2, "vo_pnp_pair_end");
+    return pnp_begin_impl(ctx, slot_a, slot_b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, want_matches, 0, ticket_out, "vo_pnp_pair_begin");
+}
+
+extern "C" int vo_pnp_pair_begin_lo(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int match_flags, const double* K4v, int iters, float thr,
+                                    uint32_t seed, int refine_iters, int want_matches, int lo_rounds, int* ticket_out)
+{
+    if (int rc = pnp_lo_check(ctx, lo_rounds, refine_iters, "vo_pnp_pair_begin_lo")) return rc;
+    return pnp_begin_impl(ctx, slot_a, slot_b, ratio, match_flags, K4v, iters, thr, seed, refine_iters, want_matches, lo_rounds, ticket_out,
+                          "vo_pnp_pair_begin_lo");
+}
+
+// either _end ends a PnP ticket of either kind (the rounds are the ticket's); the plain one returns no lo2
+static int pnp_end_impl(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                        uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int32_t* lo2, const char* who)
+{
+    int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && flags && Rt12 && refine2, who);
     if (rc) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
-    if (!p.pnp) return vo_fail(ctx, VO_E_STATE, "vo_pnp_pair_end: ticket %d belongs to vo_pose_pair_begin (end it with vo_pose_pair_end)", ticket);
+    if (!p.pnp) return vo_fail(ctx, VO_E_STATE, "%s: ticket %d belongs to vo_pose_pair_begin (end it with vo_pose_pair_end)", who, ticket);
     if ((mask_out || q_idx || t_idx) && p.nq > 0 && (!p.want || cap < p.nq))
-        return vo_fail(ctx, VO_E_CAP, "vo_pnp_pair_end: outputs hold %d entries, %d keypoints (or the step was begun without want_matches)", cap, p.nq);
+        return vo_fail(ctx, VO_E_CAP, "%s: outputs hold %d entries, %d keypoints (or the step was begun without want_matches)", who, cap, p.nq);
     if ((rc = alt_wait(ctx, p))) return rc;
     const int32_t gens[2] = { p.gen_a, p.gen_b };
     const int slots[2] = { p.slot_a, p.slot_b };
@@ -1793,5 +1905,17 @@ extern "C" int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_
                                             "disparity is undefined and no pose is derived from it", ticket, slots[i]);
     }
     return pnp_unpack(ctx, (const PnpRec*)p.result, p.want ? p.result + PNP_HDR : nullptr, p.nq, counts4, flags, Rt12, Rt12_refined, refine2,
-                      mask_out, q_idx, t_idx, "vo_pnp_pair_end");
+                      mask_out, q_idx, t_idx, who, p.lo, lo2);
+}
+
+extern "C" int vo_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                               uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap)
+{
+    return pnp_end_impl(ctx, ticket, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, t_idx, cap, nullptr, "vo_pnp_pair_end");
+}
+
+extern "C" int vo_pnp_pair_end_lo(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                                  uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, int cap, int32_t* lo2)
+{
+    return pnp_end_impl(ctx, ticket, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, t_idx, cap, lo2, "vo_pnp_pair_end_lo");
 }

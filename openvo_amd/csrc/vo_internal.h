@@ -355,6 +355,7 @@ struct vo_ctx {
         int32_t gen_a = 0, gen_b = 0;      // disparity generations of the two slots when the step was begun (slot health at _end)
         bool pnp = false, want = false;    // a vo_pnp_pair_begin step (its record is a PnpRec) / whose record carries mask, q, t
         int nq = 0;                        // query keypoints of that step
+        int lo = 0;                        // its lo_rounds (vo_pnp_pair_begin_lo; 0: the plain step)
     } pose_alt[N_POSE_ALT];
     static const int N_MONO_ALT = VO_NUM_MONO_ASYNC;
     struct MonoAlt : AsyncAlt {
@@ -652,6 +653,7 @@ struct PnpRec {
     int32_t flags;                         // bit 0: a 3-D lookup in slot a had no usable tap; bit 1: a match index outside [0, nt)
     int32_t rstatus, rsteps, pad;          // refinement: 0 ok, 1 not requested / not attempted, -1 failed; steps run
     double Rt[12], Rtr[12];                // the winner as vo_ransac_pnp returns it; the refined pose (valid for rstatus 0)
+    int32_t lo_rounds, lo_support;         // the LO form only (the plain one leaves them 0): rounds completed, |S_c|
 };
 static const size_t PNP_HDR = 1024;
 static inline size_t pnp_cap(int kp_cap) { return ((size_t)kp_cap + 15) & ~(size_t)15; }
@@ -670,7 +672,9 @@ int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double
               LoopGate* lg, int view_n = -1);
 // the whole chain on ctx->stream (ransac.hip); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
 int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
-                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain = nullptr);
+                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain = nullptr, int lo_rounds = 0);
+// lo_rounds of the _lo entries: 0 .. 8, and a value above 0 needs refine_iters >= 1 (VO_E_ARG otherwise)
+int pnp_lo_check(vo_ctx* ctx, int lo_rounds, int refine_iters, const char* who);
 
 // ---- asynchronous steps (match.hip): see vo_ctx::AsyncAlt -------------------------------------------------------------------
 static const size_t MONO_HDR = 4096;             // monocular record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on

@@ -18,6 +18,7 @@ from .features import BFMatcher, DeviceImage, DisparityMask, KeyPointList, ORB
 # the loop check's entry in the key of a pose step begun ahead (_pose_params): a type of its own, so that nothing has to guess
 # which trailing entry of the key is the match window (a plain (rx, ry) tuple) and which the threshold
 LoopCheck = collections.namedtuple("LoopCheck", "max_hamming")
+LoRounds = collections.namedtuple("LoRounds", "rounds")          # the marker of pnp_lo_rounds > 0 in _pose_params(): always the last entry
 
 
 class StereoOdometer:
@@ -32,7 +33,8 @@ class StereoOdometer:
                  outlier_threshold=0, preprocessed_frames=False, min_matches=10,
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
                  match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
-                 loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False):
+                 loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False,
+                 pnp_lo_rounds=0):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -85,7 +87,15 @@ class StereoOdometer:
         and the update of the map -- is ONE native call with one device synchronisation (vo_track_map) instead of three calls with
         the host's arithmetic between them.  The decisions and counts are those of the unfused chain; c_T_w comes from the device
         (composed and inverted there in a fixed order: equal to the host's to the last bits, not bit for bit).  A frame that finds
-        more than 3800 landmarks in the map takes the unfused chain."""
+        more than 3800 landmarks in the map takes the unfused chain.
+        pnp_lo_rounds (0 .. 8; default 0 = the refit as above; a value above 0 needs pose_method="pnp" and pnp_refine >= 1):
+        local-optimisation rounds of the fused PnP step (LO-RANSAC; include/vo355.h, vo_pnp_pair_lo).  A round is pnp_refine
+        Gauss-Newton steps on the present inlier set, then the re-selection of that set under the refitted pose by the scoring
+        kernels' own test; a round that cannot run (fewer than 6 points, a failed solve) is discarded and ends the loop.  One
+        round is today's refit; 3 is the value the tables of DESIGN were made with.  The decisions are unchanged: "outlier" still
+        reads the RANSAC winner's count, the gates see the LO pose.  With track="map" the final set is what updates the map.  It
+        is part of the key of a step begun ahead.  Where the fused step cannot run, the winner is returned as it is, as with
+        pnp_refine.  pnp_lo_counts = (rounds completed, support) of the last fused step."""
         if not isinstance(track, str) or track not in ("pair", "map"):
             raise ValueError("track must be 'pair' or 'map'")
         if track == "map" and (depth != "sparse" or pose_method != "pnp"):
@@ -145,6 +155,13 @@ class StereoOdometer:
         if isinstance(pnp_refine, (bool, np.bool_)) or not isinstance(pnp_refine, (int, np.integer)) or not 0 <= pnp_refine <= 20:
             raise ValueError("pnp_refine must be an int in 0 .. 20")
         self.pnp_refine = int(pnp_refine)
+        if isinstance(pnp_lo_rounds, (bool, np.bool_)) or not isinstance(pnp_lo_rounds, (int, np.integer)) or not 0 <= pnp_lo_rounds <= 8:
+            raise ValueError("pnp_lo_rounds must be an int in 0 .. 8")
+        if pnp_lo_rounds > 0 and (pose_method != "pnp" or self.pnp_refine < 1):
+            raise ValueError("pnp_lo_rounds > 0 needs pose_method='pnp' and pnp_refine >= 1")
+        if pnp_lo_rounds > 0:        # (instance attributes only where the option is on: without it the object is what it was)
+            self.pnp_lo_rounds = int(pnp_lo_rounds)
+            self.pnp_lo_counts = None
         self.pose_method, self.pnp_iters, self.pnp_threshold, self.pnp_seed = pose_method, pnp_iters, pnp_threshold, pnp_seed
         self.stereo = stereo_camera
         self.current_img = self.current_disparity = self.current_3d = None
@@ -327,10 +344,15 @@ class StereoOdometer:
         self._pair_span = None
         span = self.skipped_frames + 1
         kw = self._pnp_kwargs(self._pose_params())
-        r = self._ctx.map_track(self._map, slot, self._view_slot, self.c_T_w, K4, self.map_z_min, kw["ratio"], kw["iters"], kw["thr"],
-                                kw["seed"], kw["refine"], self.min_matches, self.MAX_DISTANCE_CHANGE * span, self.MAX_ROTATION_CHANGE * span,
-                                self._map_serial, self.map_max_age, self.map_max_obs, cross_check=kw["cross_check"],
-                                window=kw.get("window"), loop=kw.get("loop"), want_matches=False)
+        args = (self._map, slot, self._view_slot, self.c_T_w, K4, self.map_z_min, kw["ratio"], kw["iters"], kw["thr"], kw["seed"], kw["refine"],
+                self.min_matches, self.MAX_DISTANCE_CHANGE * span, self.MAX_ROTATION_CHANGE * span, self._map_serial, self.map_max_age,
+                self.map_max_obs)
+        more = dict(cross_check=kw["cross_check"], window=kw.get("window"), loop=kw.get("loop"), want_matches=False)
+        if "lo_rounds" in kw:
+            r = self._ctx.track_map_lo(*args, kw["lo_rounds"], **more)
+            self.pnp_lo_counts = (r["lo_rounds"], r["lo_support"])
+        else:
+            r = self._ctx.map_track(*args, **more)
         self.map_counts["view"] = r["view"]
         if r["flags"] & 1 and r["decision"] not in (1, 2):     # (behind the view and the match count, as in _pair_pnp_fused)
             raise ZeroDivisionError("division by zero")
@@ -377,6 +399,8 @@ class StereoOdometer:
         except Exception:
             pass
 
+    pnp_lo_rounds = 0        # 1 .. 8 (constructor): local-optimisation rounds of the fused PnP step (the _lo entries are called)
+    pnp_lo_counts = None     # (rounds completed, support) of the last fused step with pnp_lo_rounds > 0
     map_fused = False        # True (constructor): the map step is one native call (_map_track_fused)
     _map_size = 0            # landmarks in the map as its last update reported (set with the first fold)
     _pnp_fused = True        # False: pose_method="pnp" takes the composed path (_pair_pnp) whatever the conditions
@@ -404,6 +428,8 @@ class StereoOdometer:
             tail += (LoopCheck(self.loop_check),)
         if self.pose_method == "pnp":
             Q = self.stereo.Q
+            if self.pnp_lo_rounds > 0:
+                tail += (LoRounds(self.pnp_lo_rounds),)
             return ("pnp", float(self.match_threshold), (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3])),
                     int(self.pnp_iters), float(self.pnp_threshold), int(self.pnp_seed), int(self.pnp_refine), bool(self.cross_check)) + tail
         return (float(self.match_threshold), int(self.min_matches), float(max(self.rigidity_threshold, 0)),
@@ -417,9 +443,12 @@ class StereoOdometer:
     @staticmethod
     def _pnp_kwargs(params):
         """_pose_params() of the PnP mode as the keyword arguments of Context.pnp_pair / pnp_pair_begin (with a match window: of
-        pnp_pair_window / pnp_pair_begin_window)"""
+        pnp_pair_window / pnp_pair_begin_window; with the LoRounds marker: of pnp_pair_lo / pnp_pair_begin_lo, which take the
+        window and the loop check as keywords -- "lo_rounds" in the result says so)"""
         _, ratio, K4, iters, thr, seed, refine, cross_check = params[:8]
         kw = dict(ratio=ratio, K4=K4, iters=iters, thr=thr, seed=seed, refine=refine, want_matches=False, cross_check=cross_check)
+        if isinstance(params[-1], LoRounds):
+            kw["lo_rounds"], params = params[-1].rounds, params[:-1]
         params, loop = StereoOdometer._split_loop(params)
         if len(params) > 8:
             kw["window"] = params[8]
@@ -438,6 +467,8 @@ class StereoOdometer:
     def _step_begin(self, slot_a, slot_b, params):
         if params[0] == "pnp":
             kw = self._pnp_kwargs(params)
+            if "lo_rounds" in kw:
+                return self._ctx.pnp_pair_begin_lo(slot_a, slot_b, **kw)
             return (self._ctx.pnp_pair_begin_window if "window" in kw else self._ctx.pnp_pair_begin)(slot_a, slot_b, **kw)
         params, loop = self._split_loop(params)
         return self._ctx.pose_pair_begin(slot_a, slot_b, *params, **loop)
@@ -445,6 +476,8 @@ class StereoOdometer:
     def _step_end(self, params, ticket):
         """Collect a step begun ahead with the _end of its kind."""
         if params[0] == "pnp":
+            if isinstance(params[-1], LoRounds):
+                return self._ctx.pnp_pair_end_lo(ticket)
             return self._ctx.pnp_pair_end(ticket)
         return self._ctx.pose_pair_end(ticket)
 
@@ -701,12 +734,17 @@ class StereoOdometer:
         params = self._pose_params()
         ticket = None if want_matches else self._specs.pop((self.stereo.slot_key(slot_a), self.stereo.slot_key(slot_b), params), None)
         if ticket is not None:
-            r = self._ctx.pnp_pair_end(ticket)                           # started by an earlier update()
+            r = self._step_end(params, ticket)                           # started by an earlier update()
         else:
             kw = self._pnp_kwargs(params)
             if want_matches:
                 kw["want_matches"] = True
-            r = (self._ctx.pnp_pair_window if "window" in kw else self._ctx.pnp_pair)(slot_a, slot_b, **kw)
+            if "lo_rounds" in kw:
+                r = self._ctx.pnp_pair_lo(slot_a, slot_b, **kw)
+            else:
+                r = (self._ctx.pnp_pair_window if "window" in kw else self._ctx.pnp_pair)(slot_a, slot_b, **kw)
+        if "lo_rounds" in r:
+            self.pnp_lo_counts = (r["lo_rounds"], r["lo_support"])
         if record is not None:
             record["r"] = r
         if r["matches"] < self.min_matches:
