@@ -682,6 +682,62 @@ int vo_map_update(vo_ctx* ctx, int map, int slot_new, const double* Rt12_wc, int
 int vo_map_download(vo_ctx* ctx, int map, float* xyz /*cap*3*/, uint8_t* desc /*cap*32*/, int32_t* octave, int32_t* obs, int32_t* last,
                     int cap, int* n_out);
 
+/* Lucas-Kanade tracking (NOT part of the reference, whose every temporal association is a descriptor match,
+ * stereo_odometer.py:162-175): pyramidal KLT with a forward-backward check, the front end of StereoOdometer(match="klt").  Defined by
+ * this build, operation by operation, so that the kernels are held bit for bit to tests/klt_ref.py; parity with OpenCV's
+ * calcOpticalFlowPyrLK (whose fixed-point variant differs in its tap weights and border rule) is not claimed.  Integer stages are
+ * exact; the scalar step is float64 in the order written below, every product and sum rounded on its own (no fused multiply-add).
+ *   Parameters: win odd, 5 .. 31; levels 1 .. 6; iters 1 .. 100; eps, min_eig, fb finite and >= 0 (fb = 0: no forward-backward
+ *   check).  The defaults of the Python layer are 21, 4, 30, 0.01, 1e-4, 1.0.
+ *   Pyramid: level 0 is the u8 image; level l + 1 has size ((w + 1) / 2, (h + 1) / 2) and pixel (x, y) =
+ *   (sum_{i, j = -2 .. 2} k[i] k[j] I[r(2 y + j)][r(2 x + i)] + 128) >> 8 with k = 1 4 6 4 1 and r the reflection that does not repeat
+ *   the edge: |i| below 0, 2 (n - 1) - i past the end (clamped to the image afterwards, which only acts on an image narrower than 3).
+ *   Reads: a read of a level at (x, y) is the pixel at (clamp(x, 0, w - 1), clamp(y, 0, h - 1)): none is out of bounds, none is
+ *   refused.  Gradient at the integer pixel (x, y), on such reads, as integers: Dx = 3 (I[y-1][x+1] - I[y-1][x-1]) +
+ *   10 (I[y][x+1] - I[y][x-1]) + 3 (I[y+1][x+1] - I[y+1][x-1]), Dy the transpose of it.
+ *   Window at the real position c (win x win): t = c - (win - 1) / 2, i = floor(t) (as an integer, saturated at +-2^30), f = t -
+ *   floor(t), per axis, in float64; w00 = rint(((1 - fx) (1 - fy)) 16384), w01 = rint((fx (1 - fy)) 16384), w10 = rint(((1 - fx) fy) 16384)
+ *   (half to even), w11 = 16384 - w00 - w01 - w10.  Window pixel (u, v), with x = ix + u, y = iy + v: image sample =
+ *   (w00 I[y][x] + w01 I[y][x+1] + w10 I[y+1][x] + w11 I[y+1][x+1] + 256) >> 9 (5 fractional bits); gradient sample = the same four
+ *   taps of Dx (Dy), (... + 8192) >> 14, arithmetic shifts.
+ *   Per point: a non-finite input has status 4, is returned as it came and reads nothing.  Otherwise p0 = (double)xy + origin (the
+ *   origin is 0 for vo_klt_track_host and the ROI origin for vo_klt_track), q = p0 / 2^(levels - 1), and for L = levels - 1 .. 0, on
+ *   level L of both pyramids:
+ *     template I, Dx, Dy = the samples of image A at p0 / 2^L; A11 = sum Dx Dx, A12 = sum Dx Dy, A22 = sum Dy Dy in integers, then
+ *     as doubles (exact); D = A11 A22 - A12 A12; with s = 2^-20:
+ *     minEig = ((A22 + A11) s - sqrt(((A11 - A22) s) ((A11 - A22) s) + (4 (A12 s)) (A12 s))) / (2 win win).
+ *     minEig < min_eig or D <= 0: the level is skipped (at L = 0: status bit 1).  Otherwise at most iters iterations k = 1, 2, ...:
+ *       unless -win <= qx <= (wL - 1) + win and -win <= qy <= (hL - 1) + win the point is LOST: status bit 2, q = q 2^L, nothing
+ *       further is computed for it;
+ *       the iteration counts; J = the image samples of B at q; b1 = sum (J - I) Dx, b2 = sum (J - I) Dy in integers, then doubles;
+ *       dx = (A12 b2 - A22 b1) / D, dy = (A12 b1 - A11 b2) / D; q = q + (dx, dy);
+ *       dx dx + dy dy <= eps eps: the level ends;
+ *       otherwise, for k >= 2, |dx + dx_prev| < 0.01 and |dy + dy_prev| < 0.01 (an oscillation): q = q - 0.5 (dx, dy), the level ends.
+ *     Behind every level but the last, q = 2 q.
+ *   A point that was not lost on the way gets status bit 2 unless 0 <= qx <= w - 1 and 0 <= qy <= h - 1.
+ *   Outputs, per point: xy_out = (float)(q - origin); status_out = 0 tracked | 1 eigenvalue at level 0 | 2 left the image |
+ *   4 non-finite input | 8 forward-backward; iters_out = the iterations that counted, over all levels and both directions.
+ *   Forward-backward (fb > 0): every point with status 0 is tracked from B to A in the same way, starting at xy_out as float32;
+ *   with (x', y') its float32 result and (x, y) the float32 input, d2 = (x' - x)(x' - x) + (y' - y)(y' - y) in float64; the point keeps
+ *   status 0 iff the backward track has status 0 and d2 <= fb fb, and gets bit 8 otherwise; xy_out stays the forward result.
+ * Both entries are synchronous on the context's stream; with vo_enable_timing on, the pyramid launches are bracketed under VO_T_ORB
+ * and the tracking launches under VO_T_MATCH.  The two pyramids live in a workspace the context owns (allocated at the first call
+ * from max_w, max_h and the keypoint capacity, freed by vo_destroy; nothing is allocated per call) and are rebuilt by every call.
+ * vo_klt_track_host: two w x h host images and n points in full-image coordinates (0 <= n <= keypoint capacity = 2 max_kp + 1024;
+ *   n = 0 is valid and launches nothing).  A bad parameter, a NULL pointer or n < 0: VO_E_ARG; w / h above max_w / max_h or n above
+ *   the capacity: VO_E_CAP; nothing is launched and no output is written by a refused call.
+ * vo_klt_track: slot_a's keypoints (ROI-cropped coordinates, as every keypoint of a slot) from slot_a's rectified left image into
+ *   slot_b's; the ROI origin is added in float64 on the way in and subtracted before the float32 rounding on the way out, the images
+ *   are the whole rectified images (a track may leave the crop and stay inside the image).  The call orders itself behind whatever
+ *   still writes either slot, as vo_point_clouds_ex does, and registers nothing that outlives it.  *n_out = slot_a's keypoint count
+ *   (VO_E_CAP when cap is below it; iters_out may be NULL).  VO_E_STATE: no pair in a slot, no keypoints in slot_a, or two slots of
+ *   different shapes. */
+int vo_klt_track_host(vo_ctx* ctx, const uint8_t* img_a, const uint8_t* img_b, int w, int h, const float* xy /*n*2*/, int n, int win,
+                      int levels, int iters, double eps, double min_eig, double fb, float* xy_out /*n*2*/, uint8_t* status_out /*n*/,
+                      int32_t* iters_out /*n*/);
+int vo_klt_track(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int iters, double eps, double min_eig, double fb,
+                 float* xy_out /*cap*2*/, uint8_t* status_out /*cap*/, int32_t* iters_out /*cap*/, int cap, int* n_out);
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */

@@ -49,6 +49,7 @@ SYMBOLS = [
     "vo_map_create", "vo_map_destroy", "vo_map_reset", "vo_map_view", "vo_map_update", "vo_map_download",
     "vo_track_map",
     "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
+    "vo_klt_track_host", "vo_klt_track",
 ]
 
 
@@ -288,6 +289,10 @@ def lib():
                                 ("vo_pnp_pair_begin_lo", [vp, ci, ci, cd, ci, vp, ci, cf, cu, ci, ci, ci, vp]),
                                 ("vo_pnp_pair_end_lo", [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]),
                                 ("vo_track_map_lo", [vp, ci, ci, ci, vp, vp, cf, cd, ci, ci, cf, cu, ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp, ci, ci])):
+                getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_klt_track"):              # (likewise: an older build has no Lucas-Kanade tracker)
+            for name, proto in (("vo_klt_track_host", [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, cd, cd, cd, vp, vp, vp]),
+                                ("vo_klt_track", [vp, ci, ci, ci, ci, ci, cd, cd, cd, vp, vp, vp, ci, vp])):
                 getattr(L, name).argtypes = proto
         plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
@@ -916,6 +921,48 @@ class Context:
         st = np.empty(len(xy), np.uint8)
         self._ck(self._lib.vo_bilinear_at(self._h, _p(img3d), w, h, _p(xy), len(xy), _p(out), _p(st)))
         return out, st
+
+    @staticmethod
+    def klt_params(win=21, levels=4, iters=30, eps=0.01, min_eig=1e-4, fb=1.0):
+        """the parameters of the Lucas-Kanade entries (include/vo355.h) as their C arguments; ValueError for a value the
+        library would refuse"""
+        def _int(v, lo, hi):
+            return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and lo <= v <= hi
+        if not _int(win, 5, 31) or win % 2 == 0:
+            raise ValueError("win must be an odd int in 5 .. 31, not %r" % (win,))
+        if not _int(levels, 1, 6):
+            raise ValueError("levels must be an int in 1 .. 6, not %r" % (levels,))
+        if not _int(iters, 1, 100):
+            raise ValueError("iters must be an int in 1 .. 100, not %r" % (iters,))
+        for name, v in (("eps", eps), ("min_eig", min_eig), ("fb", fb)):
+            if (isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0):
+                raise ValueError("%s must be a finite number >= 0, not %r" % (name, v))
+        return int(win), int(levels), int(iters), float(eps), float(min_eig), float(fb)
+
+    def klt_track_host(self, a, b, xy, **kw):
+        """Pyramidal Lucas-Kanade with a forward-backward check (vo_klt_track_host): the points xy (n, 2; full-image pixels) of image a
+        tracked into image b -> (xy_out (n, 2) float32, status (n,) uint8: 0 tracked | 1 eigenvalue | 2 left the image | 4 non-finite
+        | 8 forward-backward, iters (n,) int32).  Keywords: win, levels, iters, eps, min_eig, fb."""
+        prm = self.klt_params(**kw)
+        (a, ch_a), (b, ch_b) = _image(a), _image(b)
+        if ch_a != 1 or ch_b != 1 or a.shape != b.shape:
+            raise ValueError("klt_track_host takes two grey images of one shape")
+        xy = _c(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        out, st, it = np.empty((n, 2), np.float32), np.empty(n, np.uint8), np.empty(n, np.int32)
+        self._ck(self._lib.vo_klt_track_host(self._h, _p(a), _p(b), a.shape[1], a.shape[0], _p(xy), n, *prm, _p(out), _p(st), _p(it)))
+        return out, st, it
+
+    def klt_track(self, slot_a, slot_b, **kw):
+        """vo_klt_track: slot_a's keypoints (ROI-cropped pixels) tracked from slot_a's rectified left image into slot_b's
+        -> (xy_out, status, iters) as klt_track_host, in keypoint order and ROI-cropped pixels"""
+        prm = self.klt_params(**kw)
+        cap = self.kp_cap
+        out, st, it = np.empty((cap, 2), np.float32), np.empty(cap, np.uint8), np.empty(cap, np.int32)
+        n = ctypes.c_int(0)
+        self._ck(self._lib.vo_klt_track(self._h, slot_a, slot_b, *prm, _p(out), _p(st), _p(it), cap, ctypes.byref(n)))
+        n = n.value
+        return out[:n].copy(), st[:n].copy(), it[:n].copy()
 
     def point_clouds(self, slot_a, slot_b, ratio, cross_check=False, window=None, loop=None):
         """loop (None | 0 .. 256): the loop check on two slots whose keypoints carry depth (VO_MATCH_LOOP)"""

@@ -322,6 +322,7 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     for (void* p : ps) if (p) (void)hipFree(p);
     alt_free(ctx);
     for (LandmarkMap& m : ctx->maps) map_free(m);
+    klt_ws_free(ctx->klt);
     sparse_ws_free(ctx->sp_main);
     for (SparseWs& w : ctx->sp_alt) sparse_ws_free(w);
     match_ws_free(ctx->main_mw);

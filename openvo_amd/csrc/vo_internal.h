@@ -147,6 +147,20 @@ struct LandmarkMap {
 };
 void map_free(LandmarkMap& m);
 
+// Lucas-Kanade tracking (klt.hip; include/vo355.h, vo_klt_*): the two pyramids of a call -- image 0 / 1, level l at byte off[l] of
+// pyr[k], laid out for max_w x max_h (level 0 is only used by the host entry: the slot entry reads the slots' own images) -- and the
+// per-point arrays, kp_cap entries each.  Allocated at the first call, freed by vo_destroy.
+#define VO_KLT_MAX_LEVELS 6
+struct KltWs {
+    uint8_t* pyr[2] = {nullptr, nullptr};
+    size_t off[VO_KLT_MAX_LEVELS] = {};
+    float *xy_in = nullptr, *xy_out = nullptr;
+    uint8_t* status = nullptr;
+    int32_t* iters = nullptr;
+    bool ready = false;
+};
+void klt_ws_free(KltWs& k);
+
 struct vo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -259,6 +273,7 @@ struct vo_ctx {
     // engine k's own
     FrameSlot sparse_r;
     LandmarkMap maps[VO_NUM_MAPS];      // vo_map_create .. vo_map_destroy (freed by vo_destroy too)
+    KltWs klt;                          // vo_klt_track / vo_klt_track_host
     SparseWs sp_main;
     SparseWs sp_alt[MAX_ENGINES];
 

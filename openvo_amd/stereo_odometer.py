@@ -34,7 +34,7 @@ class StereoOdometer:
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
                  match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
                  loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False,
-                 pnp_lo_rounds=0):
+                 pnp_lo_rounds=0, match="orb", klt_window=21, klt_levels=4, klt_fb=1.0):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -95,7 +95,21 @@ class StereoOdometer:
         round is today's refit; 3 is the value the tables of DESIGN were made with.  The decisions are unchanged: "outlier" still
         reads the RANSAC winner's count, the gates see the LO pose.  With track="map" the final set is what updates the map.  It
         is part of the key of a step begun ahead.  Where the fused step cannot run, the winner is returned as it is, as with
-        pnp_refine.  pnp_lo_counts = (rounds completed, support) of the last fused step."""
+        pnp_refine.  pnp_lo_counts = (rounds completed, support) of the last fused step.
+        match="klt" (an extension, NOT in the reference; default "orb" = every temporal association is a descriptor match, as ever):
+        the keypoints of the older frame are TRACKED into the newer frame's rectified left image by pyramidal Lucas-Kanade with a
+        forward-backward check (include/vo355.h, vo_klt_track) instead of being matched against its descriptors: klt_window (odd,
+        5 .. 31) is the window, klt_levels (1 .. 6) the pyramid levels, klt_fb the forward-backward radius in pixels (0: no check).
+        A track with a non-zero status is dropped; fewer than min_matches tracks: skip_cause "matches".  pose_method="pnp": the
+        3-D points of the older frame at its own keypoints and the tracked sub-pixel positions go through vo_ransac_pnp and the
+        decisions of the composed PnP path; pose_method="umeyama" (depth="dense" only: a tracked position is no keypoint of the
+        newer frame, so only a dense disparity has a depth for it): the newer frame's 3-D points are looked up at the tracked
+        positions and point_cloud_transform runs unchanged.  A track whose 3-D lookup in either frame has no usable tap or no finite
+        point, or which has left the crop, is DROPPED (the keypoint paths raise ZeroDivisionError there).  The new frame's ORB
+        extraction still runs: its keypoints are what the next pair tracks.  Both frames must be on the device (ValueError
+        otherwise, as with pose_method="pnp"); no pose step is begun ahead, run() still submits pairs ahead; the one-frame-back
+        fallback takes the same path.  cross_check, match_window, loop_check and track="map" belong to the descriptor matcher and
+        are refused with match="klt".  klt_counts = (keypoints tracked from, tracks kept) of the last pair."""
         if not isinstance(track, str) or track not in ("pair", "map"):
             raise ValueError("track must be 'pair' or 'map'")
         if track == "map" and (depth != "sparse" or pose_method != "pnp"):
@@ -152,6 +166,22 @@ class StereoOdometer:
         self.cross_check = bool(cross_check)
         self.match_window = _native.window_radii(match_window, "match_window")
         self._pair_span = None       # frames the pair being tried spans (_try_pair); None: skipped_frames + 1
+        if not isinstance(match, str) or match not in ("orb", "klt"):
+            raise ValueError("match must be 'orb' or 'klt'")
+        try:
+            klt = _native.Context.klt_params(win=klt_window, levels=klt_levels, fb=klt_fb)
+        except ValueError as e:
+            raise ValueError("klt_window / klt_levels / klt_fb: %s" % e)
+        if match == "klt":
+            if depth == "sparse" and pose_method == "umeyama":
+                raise ValueError("match='klt' with depth='sparse' needs pose_method='pnp' (a tracked position has no sparse depth)")
+            if track == "map":
+                raise ValueError("match='klt' needs track='pair'")
+            if self.cross_check or self.match_window is not None or self.loop_check is not None:
+                raise ValueError("cross_check, match_window and loop_check belong to the descriptor matcher: not with match='klt'")
+            # (instance attributes only where the option is on: without it the object is what it was)
+            self.match, self.klt_window, self.klt_levels, self.klt_fb = "klt", klt[0], klt[1], klt[5]
+            self.klt_counts = None
         if isinstance(pnp_refine, (bool, np.bool_)) or not isinstance(pnp_refine, (int, np.integer)) or not 0 <= pnp_refine <= 20:
             raise ValueError("pnp_refine must be an int in 0 .. 20")
         self.pnp_refine = int(pnp_refine)
@@ -399,6 +429,7 @@ class StereoOdometer:
         except Exception:
             pass
 
+    match = "orb"            # "klt" (constructor): pairs are associated by Lucas-Kanade tracking (_pair_klt)
     pnp_lo_rounds = 0        # 1 .. 8 (constructor): local-optimisation rounds of the fused PnP step (the _lo entries are called)
     pnp_lo_counts = None     # (rounds completed, support) of the last fused step with pnp_lo_rounds > 0
     map_fused = False        # True (constructor): the map step is one native call (_map_track_fused)
@@ -516,6 +547,8 @@ class StereoOdometer:
         chains of many pairs run side by side instead of one after the other behind the host.  Purely an ordering change:
         _pair_fused looks a step up by its slots and parameters and computes on the spot when the guess was wrong."""
         if self.track == "map":        # (the map step needs the pose of the frame before it: nothing to begin ahead)
+            return
+        if self.match == "klt":        # (the tracking step is synchronous: nothing is begun ahead)
             return
         sparse = self.depth == "sparse"
         if not self._fused_ok() or (not sparse and self.orb.last_slot_args is None):
@@ -686,6 +719,8 @@ class StereoOdometer:
             self._pair_span = None
 
     def _try_pair_span(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b):
+        if self.match == "klt":
+            return self._pair_klt(kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b)
         # fused device path when nothing along the way was replaced by the user
         fused = (type(self) is StereoOdometer and type(self.matcher) is BFMatcher and 2 <= len(kps_b) and len(kps_a) <= 3800
                  and self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)
@@ -726,6 +761,50 @@ class StereoOdometer:
             self.skip_cause = "outlier"
             return None
         return self._gate(np.vstack([r["Rt"], [0, 0, 0, 1]]))
+
+    def _pair_klt(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b):
+        """Extension (match="klt"): frame a's keypoints tracked into frame b (vo_klt_track), then the pose from (3-D of a, pixels
+        of b) by RANSAC PnP with the decisions of _pair_pnp, or from (3-D of a, 3-D of b at the tracked positions) through
+        point_cloud_transform.  A track is dropped, never an error, where a lookup has no usable tap or no finite point."""
+        if not (self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)):
+            raise ValueError("match='klt' needs the device-resident frames compute_3d returns")
+        fa, fb = kps_a.frame, kps_b.frame
+        xy_b, st, _ = self._ctx.klt_track(fa.slot, fb.slot, win=self.klt_window, levels=self.klt_levels, fb=self.klt_fb)
+        idx = np.nonzero(st == 0)[0]
+        self.klt_counts = (len(st), len(idx))
+        if len(idx) < self.min_matches:
+            self.skip_cause = "matches"
+            return None
+        if self.depth == "sparse":
+            pts_a = np.asarray(im3d_a, np.float32).reshape(-1, 3)[idx]           # the per-keypoint cloud
+            ok = np.isfinite(pts_a).all(axis=1)
+        else:
+            pts_a, st_a = self._ctx.points3d_at(fa.slot, kps_a.xy[idx])
+            ok = (st_a == 0) & np.isfinite(pts_a).all(axis=1)
+        idx, pts_a = idx[ok], pts_a[ok]
+        uv = xy_b[idx]
+        if self.pose_method == "pnp":
+            if len(idx) < max(self.min_matches, 4):
+                self.skip_cause = "matches"
+                return None
+            Q = self.stereo.Q
+            K4 = [Q[2, 3], Q[2, 3], -Q[0, 3], -Q[1, 3]]
+            r = self._ctx.ransac_pnp(pts_a, uv + np.array([fb.roi[0], fb.roi[1]], np.float32), K4, self.pnp_iters, self.pnp_threshold, self.pnp_seed)
+            if r["best_count"] < self.min_matches:
+                self.skip_cause = "outlier"
+                return None
+            return self._gate(np.vstack([r["Rt"], [0, 0, 0, 1]]))
+        # 3-D of frame b where the tracks ended: inside the crop only (a track may leave it and stay inside the image)
+        cw, ch = fb.roi[2] - fb.roi[0], fb.roi[3] - fb.roi[1]
+        inside = (uv[:, 0] >= 0) & (uv[:, 1] >= 0) & (uv[:, 0] < np.float32(cw)) & (uv[:, 1] < np.float32(ch))
+        pts_a, uv = pts_a[inside], uv[inside]
+        pts_b, st_b = self._ctx.points3d_at(fb.slot, uv)
+        ok = (st_b == 0) & np.isfinite(pts_b).all(axis=1)
+        pts_a, pts_b = pts_a[ok], pts_b[ok]
+        if len(pts_a) < self.min_matches:
+            self.skip_cause = "matches"
+            return None
+        return self.point_cloud_transform(pts_a, pts_b)
 
     def _pair_pnp_fused(self, slot_a, slot_b, want_matches=False, record=None):
         """_pair_pnp in one native call (vo_pnp_pair: one device synchronisation, nothing but the record comes back): the same
