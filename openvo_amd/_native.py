@@ -306,6 +306,9 @@ def lib():
         plant = getattr(L, "vo_test_peek_view", None)            # (likewise)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        plant = getattr(L, "vo_test_klt_level", None)            # (likewise)
+        if plant is not None:
+            plant.argtypes = [vp, ci, ci, ci, ci, vp]
         L.vo_device_count.argtypes = [vp]
         L.vo_mgpu_unique_id.argtypes = [vp]
         L.vo_mgpu_create.argtypes = [ci, ci, ci, vp, vp]
@@ -963,6 +966,15 @@ class Context:
         self._ck(self._lib.vo_klt_track(self._h, slot_a, slot_b, *prm, _p(out), _p(st), _p(it), cap, ctypes.byref(n)))
         n = n.value
         return out[:n].copy(), st[:n].copy(), it[:n].copy()
+
+    def klt_level(self, which, level, w_l, h_l):
+        """Test-only build of the library: level `level` (w_l x h_l) of the pyramid of image `which` (0 = a, 1 = b) as the last
+        klt_track_host left it (vo_test_klt_level) -> (h_l, w_l) uint8.  The product library has no such entry."""
+        if not hasattr(self._lib, "vo_test_klt_level"):
+            raise RuntimeError("klt_level needs the test-only build of the library (libvo355_hooks.so)")
+        out = np.empty((max(int(h_l), 0), max(int(w_l), 0)), np.uint8)
+        self._ck(self._lib.vo_test_klt_level(self._h, int(which), int(level), int(w_l), int(h_l), _p(out)))
+        return out
 
     def point_clouds(self, slot_a, slot_b, ratio, cross_check=False, window=None, loop=None):
         """loop (None | 0 .. 256): the loop check on two slots whose keypoints carry depth (VO_MATCH_LOOP)"""

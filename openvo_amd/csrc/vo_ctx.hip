@@ -1634,4 +1634,22 @@ extern "C" int vo_test_peek_view(vo_ctx* ctx, int map, int slot, int n, float* x
     if (rc) return rc;
     return xfer_flush(ctx);
 }
+
+// ... and a look at one level of the Lucas-Kanade pyramids as the last vo_klt_track_host left them: the w_l x h_l bytes at level
+// `level` of image `which` (0 = A, 1 = B) of the workspace, copied on the context's stream.  The caller states the level's size (the
+// workspace keeps none): it must fit what the workspace lays out for that level, ((max_w + 1) / 2 ...) x ((max_h + 1) / 2 ...).
+// Level 0 is the uploaded image itself.  VO_E_STATE while the workspace was never prepared.
+extern "C" int vo_test_klt_level(vo_ctx* ctx, int which, int level, int w_l, int h_l, uint8_t* out)
+{
+    if (!ctx || which < 0 || which > 1 || level < 0 || level >= VO_KLT_MAX_LEVELS || w_l <= 0 || h_l <= 0 || !out)
+        return vo_fail(ctx, VO_E_ARG, "vo_test_klt_level: bad argument");
+    int mw = ctx->max_w, mh = ctx->max_h;
+    for (int l = 0; l < level; l++) { mw = (mw + 1) / 2; mh = (mh + 1) / 2; }
+    if (w_l > mw || h_l > mh) return vo_fail(ctx, VO_E_CAP, "vo_test_klt_level: %dx%d exceeds level %d of the workspace (%dx%d)", w_l, h_l, level, mw, mh);
+    const KltWs& k = ctx->klt;
+    if (!k.ready) return vo_fail(ctx, VO_E_STATE, "vo_test_klt_level: no Lucas-Kanade call has prepared the workspace");
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = xfer_d2h(ctx, out, k.pyr[which] + k.off[level], (size_t)w_l * h_l)) { (void)xfer_flush(ctx); return rc; }
+    return xfer_flush(ctx);
+}
 #endif
