@@ -721,8 +721,9 @@ int vo_map_download(vo_ctx* ctx, int map, float* xyz /*cap*3*/, uint8_t* desc /*
  *   with (x', y') its float32 result and (x, y) the float32 input, d2 = (x' - x)(x' - x) + (y' - y)(y' - y) in float64; the point keeps
  *   status 0 iff the backward track has status 0 and d2 <= fb fb, and gets bit 8 otherwise; xy_out stays the forward result.
  * Both entries are synchronous on the context's stream; with vo_enable_timing on, the pyramid launches are bracketed under VO_T_ORB
- * and the tracking launches under VO_T_MATCH.  The two pyramids live in a workspace the context owns (allocated at the first call
- * from max_w, max_h and the keypoint capacity, freed by vo_destroy; nothing is allocated per call) and are rebuilt by every call.
+ * and the tracking launches under VO_T_MATCH.  The two pyramids live in the Lucas-Kanade workspace of the context's main match scratch
+ * (allocated at the first call from max_w, max_h and the keypoint capacity, freed by vo_destroy; nothing is allocated per call; a
+ * pose alternate that runs vo_klt_pnp_pair_begin owns another) and are rebuilt by every call.
  * vo_klt_track_host: two w x h host images and n points in full-image coordinates (0 <= n <= keypoint capacity = 2 max_kp + 1024;
  *   n = 0 is valid and launches nothing).  A bad parameter, a NULL pointer or n < 0: VO_E_ARG; w / h above max_w / max_h or n above
  *   the capacity: VO_E_CAP; nothing is launched and no output is written by a refused call.
@@ -737,6 +738,41 @@ int vo_klt_track_host(vo_ctx* ctx, const uint8_t* img_a, const uint8_t* img_b, i
                       int32_t* iters_out /*n*/);
 int vo_klt_track(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int iters, double eps, double min_eig, double fb,
                  float* xy_out /*cap*2*/, uint8_t* status_out /*cap*/, int32_t* iters_out /*cap*/, int cap, int* n_out);
+
+/* Lucas-Kanade PnP pair step (an extension, NOT part of the reference): vo_klt_track -> the filter "status 0" -> the 3-D points
+ * of the kept keypoints in slot_a -> vo_ransac_pnp, value for value, as ONE chain of launches on the context's stream with ONE
+ * host synchronisation and no copy command: the pyramid launches, the forward (fb > 0: and the backward) tracking launch,
+ * k_klt_pnp_prep, k_pnp_hyp, k_pnp_score, k_pnp_finish.  Nothing per keypoint is downloaded unless an array is asked for.
+ *   win .. fb: the tracker's parameters (klt_iters = its iteration limit), as vo_klt_track takes them.  K4, iters, thr, seed,
+ *   refine_iters: as vo_pnp_pair.  lo_rounds: as vo_pnp_pair_lo (0: the plain refit).
+ *   The 3-D point of keypoint i: slot_a's kp_xyz[i] where its keypoints carry depth (vo_sparse_stereo), else the bilinear lookup
+ *   of vo_points3d_at at the keypoint in slot_a's disparity.  A track is dropped -- never an error -- where that lookup has no
+ *   usable tap (flag bit 0 says that it happened), status 1, or a coordinate that is not finite.
+ *   counts4 = {M, n, best_iter, best_count}: M = tracks with status 0, n = correspondences that reached the RANSAC (n < 4: no pose,
+ *   best (0, 0), Rt all zero).  *flags: bit 0 as above, bit 1 never.  Rt12, Rt12_refined, refine2, lo2 (may be NULL): as
+ *   vo_pnp_pair_lo.  mask_out, q_idx, xy_out (each may be NULL; cap entries, cap >= slot_a's keypoint count or VO_E_CAP): per
+ *   compacted correspondence, in keypoint order, the winner's inlier byte (the set S_c behind completed rounds), the keypoint
+ *   index, and the tracked position in slot_b's ROI-cropped pixels as vo_klt_track returns it (the RANSAC was given that position
+ *   plus the ROI origin, a float32 add); q_idx reads -1 and mask_out 0 from n to the keypoint count, xy_out is written up to n.
+ *   VO_E_ARG: a bad slot or pointer, a tracker parameter vo_klt_track refuses, iters, thr, refine_iters or a focal length
+ *   vo_pnp_pair refuses, lo_rounds outside 0 .. 8 or above 0 without refine_iters.  VO_E_STATE: no pair in a slot, no keypoints in
+ *   slot_a (a slot whose extraction found none is fine: the cleared record, nothing launched), two slots of different shapes,
+ *   slot_a with neither disparity nor depth-carrying keypoints, no vo_set_Q.  slot_b needs neither keypoints nor disparity.
+ *   VO_E_SWEEP: slot_a's disparity is undefined.  A refused call launches nothing and writes no output.
+ * vo_klt_pnp_pair_begin / _end: the same step in two halves on a POSE alternate (the tickets, streams and scratch of
+ * vo_pose_pair_begin and vo_pnp_pair_begin: VO_NUM_POSE_ASYNC bounds the three kinds together, no stream is added); every alternate
+ * tracks in pyramids and track arrays of its own, allocated at its first Lucas-Kanade step.  want_arrays: the record carries
+ * mask / q / xy (without it _end refuses them with VO_E_CAP).  Both slots may be refilled once _begin has returned: the refill orders
+ * itself behind the step.  _end: VO_E_SWEEP as vo_pnp_pair_end; VO_E_STATE for a ticket of another kind -- and vo_pose_pair_end,
+ * vo_pnp_pair_end and vo_pnp_pair_end_lo refuse a ticket of this kind with VO_E_STATE; a refused ticket stays open. */
+int vo_klt_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int klt_iters, double eps, double min_eig, double fb,
+                    const double* K4, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds, int32_t* counts4, int32_t* flags,
+                    double* Rt12, double* Rt12_refined, int32_t* refine2, int32_t* lo2, uint8_t* mask_out /*cap*/, int32_t* q_idx /*cap*/,
+                    float* xy_out /*cap*2*/, int cap);
+int vo_klt_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int klt_iters, double eps, double min_eig, double fb,
+                          const double* K4, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds, int want_arrays, int* ticket_out);
+int vo_klt_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                        int32_t* lo2, uint8_t* mask_out /*cap*/, int32_t* q_idx /*cap*/, float* xy_out /*cap*2*/, int cap);
 
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without

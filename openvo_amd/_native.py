@@ -49,7 +49,7 @@ SYMBOLS = [
     "vo_map_create", "vo_map_destroy", "vo_map_reset", "vo_map_view", "vo_map_update", "vo_map_download",
     "vo_track_map",
     "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
-    "vo_klt_track_host", "vo_klt_track",
+    "vo_klt_track_host", "vo_klt_track", "vo_klt_pnp_pair", "vo_klt_pnp_pair_begin", "vo_klt_pnp_pair_end",
 ]
 
 
@@ -294,6 +294,15 @@ def lib():
             for name, proto in (("vo_klt_track_host", [vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, cd, cd, cd, vp, vp, vp]),
                                 ("vo_klt_track", [vp, ci, ci, ci, ci, ci, cd, cd, cd, vp, vp, vp, ci, vp])):
                 getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_klt_pnp_pair"):           # (likewise: an older build has no fused Lucas-Kanade PnP step)
+            cf, cu = ctypes.c_float, ctypes.c_uint32
+            front = [vp, ci, ci, ci, ci, ci, cd, cd, cd, vp, ci, cf, cu, ci, ci]
+            for name, proto in (("vo_klt_pnp_pair", front + [vp] * 9 + [ci]), ("vo_klt_pnp_pair_begin", front + [ci, vp]),
+                                ("vo_klt_pnp_pair_end", [vp, ci] + [vp] * 9 + [ci])):
+                getattr(L, name).argtypes = proto
+        plant = getattr(L, "vo_test_plant_dense_pair", None)     # (only the test-only build, libvo355_hooks.so, exports it)
+        if plant is not None:
+            plant.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp]
         plant = getattr(L, "vo_test_plant_keypoints", None)      # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, vp, vp, vp, vp]
@@ -966,6 +975,74 @@ class Context:
         self._ck(self._lib.vo_klt_track(self._h, slot_a, slot_b, *prm, _p(out), _p(st), _p(it), cap, ctypes.byref(n)))
         n = n.value
         return out[:n].copy(), st[:n].copy(), it[:n].copy()
+
+    # ---- the Lucas-Kanade PnP pair step (vo_klt_pnp_pair)
+    def _klt_pnp_front(self, slot_a, slot_b, K4, iters, thr, seed, refine, lo_rounds, klt):
+        """the input arguments the three entries share, checked as the library checks them"""
+        klt = dict(klt)
+        if "klt_iters" in klt:                   # (`iters` is the RANSAC's here: the tracker's iteration limit travels as klt_iters)
+            klt["iters"] = klt.pop("klt_iters")
+        prm = self.klt_params(**klt)
+        lo_rounds = self.lo_rounds_arg(lo_rounds, refine)
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        return [self._h, int(slot_a), int(slot_b), *prm, _p(K4), int(iters), float(thr), int(seed) & 0xFFFFFFFF, int(refine), lo_rounds], K4
+
+    def _klt_pnp_out(self, want_arrays):
+        head = [np.zeros(4, np.int32), np.zeros(1, np.int32), np.zeros(12, np.float64), np.zeros(12, np.float64), np.zeros(2, np.int32),
+                np.zeros(2, np.int32)]
+        arrays = [None, None, None]
+        if want_arrays:
+            arrays = self.__dict__.get("_klt_pnp_arrays")
+            if arrays is None or len(arrays[0]) != self.kp_cap:
+                arrays = self._klt_pnp_arrays = [np.empty(self.kp_cap, np.uint8), np.empty(self.kp_cap, np.int32), np.empty((self.kp_cap, 2), np.float32)]
+        return head, arrays
+
+    @staticmethod
+    def _klt_pnp_result(head, arrays):
+        out = Context._pnp_result(head[:5], [arrays[0], arrays[1], arrays[1]])
+        out.pop("t", None)
+        out.update(lo_rounds=int(head[5][0]), lo_support=int(head[5][1]))
+        if arrays[0] is not None:
+            out["xy"] = arrays[2][:out["n"]].copy()
+        return out
+
+    def klt_pnp_pair(self, slot_a, slot_b, K4, iters=256, thr=1.5, seed=4321, refine=0, lo_rounds=0, want_arrays=False, **klt):
+        """slot_a's keypoints tracked into slot_b (Lucas-Kanade: keywords win, levels, klt_iters, eps, min_eig, fb -- klt_track's,
+        its iteration limit as klt_iters), the 3-D points of the kept tracks in slot_a, P3P RANSAC (+ refit, + LO rounds), all on the device with one
+        synchronisation (vo_klt_pnp_pair).  -> the dict of pnp_pair (matches = the tracks with status 0; lo_rounds / lo_support as
+        pnp_pair_lo) [, mask, q, xy of length n: xy = the tracked positions, ROI-cropped pixels]."""
+        front, _keep = self._klt_pnp_front(slot_a, slot_b, K4, iters, thr, seed, refine, lo_rounds, klt)
+        head, arrays = self._klt_pnp_out(want_arrays)
+        self._ck(self._lib.vo_klt_pnp_pair(*front, *[_p(a) for a in head + arrays], self.kp_cap))
+        return self._klt_pnp_result(head, arrays)
+
+    def klt_pnp_pair_begin(self, slot_a, slot_b, K4, iters=256, thr=1.5, seed=4321, refine=0, lo_rounds=0, want_arrays=False, **klt):
+        """klt_pnp_pair in two halves -> a ticket for klt_pnp_pair_end (a pose ticket: VO_NUM_POSE_ASYNC bounds all kinds together)."""
+        front, _keep = self._klt_pnp_front(slot_a, slot_b, K4, iters, thr, seed, refine, lo_rounds, klt)
+        t = ctypes.c_int(-1)
+        self._ck(self._lib.vo_klt_pnp_pair_begin(*front, int(bool(want_arrays)), ctypes.byref(t)))
+        return t.value
+
+    def klt_pnp_pair_end(self, ticket, want_arrays=False):
+        head, arrays = self._klt_pnp_out(want_arrays)
+        self._ck(self._lib.vo_klt_pnp_pair_end(self._h, int(ticket), *[_p(a) for a in head + arrays], self.kp_cap))
+        return self._klt_pnp_result(head, arrays)
+
+    def plant_dense_pair(self, slot, left, disp16, xy, desc=None):
+        """Test-only build of the library: plant_dense, and the (h, w) uint8 image `left` as the slot's rectified pair
+        (vo_test_plant_dense_pair): a dense slot that can be tracked from.  desc defaults to zeros.  The product library has no such entry."""
+        if not hasattr(self._lib, "vo_test_plant_dense_pair"):
+            raise RuntimeError("plant_dense_pair needs the test-only build of the library (libvo355_hooks.so)")
+        left, disp16 = _c(left, np.uint8), _c(disp16, np.int16)
+        if left.ndim != 2 or left.shape != disp16.shape:
+            raise ValueError("left and disp16 are (h, w) images of one shape")
+        xy = _c(xy, np.float32).reshape(-1, 2)
+        n = len(xy)
+        desc = np.zeros((n, 32), np.uint8) if desc is None else _c(desc, np.uint8).reshape(-1, 32)
+        if len(desc) != n:
+            raise ValueError("one descriptor per keypoint")
+        h, w = disp16.shape
+        self._ck(self._lib.vo_test_plant_dense_pair(self._h, int(slot), w, h, _p(left), _p(disp16), n, _p(xy), _p(desc)))
 
     def klt_level(self, which, level, w_l, h_l):
         """Test-only build of the library: level `level` (w_l x h_l) of the pyramid of image `which` (0 = a, 1 = b) as the last

@@ -1502,7 +1502,7 @@ extern "C" int vo_pose_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
     if (slot_sparse(a)) p.gen_a = p.gen_b = 0;       // the step read no disparity: nothing to check at _end
-    p.pnp = false;
+    p.pnp = false; p.klt = false;
     return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }
 
@@ -1517,6 +1517,7 @@ extern "C" int vo_pose_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32
     int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && rc2 && T2_12, "vo_pose_pair_end");
     if (rc) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
+    if (p.klt) return vo_fail(ctx, VO_E_STATE, "vo_pose_pair_end: ticket %d belongs to vo_klt_pnp_pair_begin (end it with vo_klt_pnp_pair_end)", ticket);
     if (p.pnp) return vo_fail(ctx, VO_E_STATE, "vo_pose_pair_end: ticket %d belongs to vo_pnp_pair_begin (end it with vo_pnp_pair_end)", ticket);
     if ((rc = alt_wait(ctx, p))) return rc;
     // the step read the disparities the two slots held when it was begun: were those runs healthy?  (a slot refilled since
@@ -1625,6 +1626,79 @@ int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int c
                        ctx->mw->mq_idx, ctx->mw->mt_idx, ta, x1 - x0, y1 - y0, (float)x0, (float)y0, d.q, d.t, d.X, d.uv, d.hdr,
                        cross ? (const uint32_t*)match_colmin(ctx->mw->m_dist, ctx->kp_cap) : nullptr, nt_range,
                        slot_sparse(a) ? (const float*)a.kp_xyz : nullptr, g.rd_a, g.rd_b, g.max_h, nq_dev);
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
+// The link between Lucas-Kanade tracking and the RANSAC of vo_klt_pnp_pair, in ONE block shaped like k_pnp_prep's second half: the
+// block walks slot a's n_kp keypoints 256 at a time in keypoint order.  A track counts in M when its status byte is 0; of those the
+// 3-D point of keypoint i in slot a is looked up -- kp_xyz[i] where the keypoints carry depth (xyz_a), else bilinear_one at
+// kp_xy[i], the arithmetic of vo_points3d_at -- and the tracks with lookup status 0 and three finite coordinates are compacted by
+// ballot / popcount prefixes (per wave, then the earlier waves' counts from LDS) into X, uv = tracked position + the ROI origin
+// (float32 adds) and q = t = i.  xy_host (may be NULL): pinned host memory that receives the tracked positions of the compacted
+// tracks as the tracker left them (crop pixels).  hdr = {M, n, flags}: bit 0 = some lookup had no usable tap (the track is
+// dropped); bit 1 is never set.  Nothing is handed between workgroups, nothing is atomic, every loop is bounded by n_kp.
+// A keypoint is trusted to lie inside the crop, as ORB's do; one that does not (no slot of this library holds one) is read
+// through nowhere and counts as a lookup without a usable tap.
+__global__ void __launch_bounds__(256) k_klt_pnp_prep(const float* __restrict__ xy_trk, const uint8_t* __restrict__ status, int n_kp,
+                                                      const float* __restrict__ xy_a, const float* __restrict__ xyz_a, TapDisp ta, int cw, int ch,
+                                                      float x0f, float y0f, int32_t* __restrict__ q2, int32_t* __restrict__ t2, float* __restrict__ X,
+                                                      float* __restrict__ uv, int32_t* __restrict__ hdr, float* __restrict__ xy_host)
+{
+    __shared__ int s_cnt[4], s_m[4], s_bad[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int n = 0, m = 0, bad = 0;                  // n: block-uniform; m, bad: this wave's
+    for (int i0 = 0; i0 < n_kp; i0 += blockDim.x) {
+        const int i = i0 + threadIdx.x;
+        bool trk = false, use = false, notap = false;
+        float p[3] = { 0.f, 0.f, 0.f }, tx = 0.f, ty = 0.f;
+        if (i < n_kp && status[i] == 0) {
+            trk = true;
+            uint8_t st = 0;
+            if (xyz_a) { p[0] = xyz_a[3 * (size_t)i]; p[1] = xyz_a[3 * (size_t)i + 1]; p[2] = xyz_a[3 * (size_t)i + 2]; }
+            else {
+                const float kx = xy_a[2 * (size_t)i], ky = xy_a[2 * (size_t)i + 1];
+                if (kx >= 0.f && ky >= 0.f && kx < (float)cw && ky < (float)ch) bilinear_one(ta, cw, ch, kx, ky, p, &st);
+                else st = 2;
+            }
+            notap = st == 2;
+            use = st == 0 && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+            tx = xy_trk[2 * (size_t)i]; ty = xy_trk[2 * (size_t)i + 1];
+        }
+        const unsigned long long bal = __ballot(use);
+        m += __popcll(__ballot(trk));
+        bad |= __ballot(notap) != 0ull;
+        if (lane == 0) s_cnt[wv] = __popcll(bal);
+        __syncthreads();
+        int off = n;
+        for (int w = 0; w < wv; w++) off += s_cnt[w];
+        if (use) {
+            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+            X[3 * pos] = p[0]; X[3 * pos + 1] = p[1]; X[3 * pos + 2] = p[2];
+            uv[2 * pos] = tx + x0f; uv[2 * pos + 1] = ty + y0f;
+            q2[pos] = i; t2[pos] = i;
+            if (xy_host) { xy_host[2 * pos] = tx; xy_host[2 * pos + 1] = ty; }
+        }
+        n += (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        __syncthreads();
+    }
+    if (lane == 0) { s_m[wv] = m; s_bad[wv] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        hdr[0] = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+        hdr[1] = n;
+        hdr[2] = (s_bad[0] | s_bad[1]) | (s_bad[2] | s_bad[3]);
+    }
+}
+
+int klt_pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, const float* xy_trk, const uint8_t* status, const PnpDev& d, float* xy_host)
+{
+    int x0 = 0, y0 = 0, x1 = a.w, y1 = a.h;
+    if (ctx->has_roi) { x0 = ctx->roi[0]; y0 = ctx->roi[1]; x1 = ctx->roi[2] < a.w ? ctx->roi[2] : a.w; y1 = ctx->roi[3] < a.h ? ctx->roi[3] : a.h; }
+    TapDisp ta{ a.disp16, a.w, x0, y0, make_q(ctx->Q) };
+    hipLaunchKernelGGL(k_klt_pnp_prep, dim3(1), dim3(256), 0, ctx->stream, xy_trk, status, a.n_kp, a.kp_xy,
+                       slot_sparse(a) ? (const float*)a.kp_xyz : nullptr, ta, x1 - x0, y1 - y0, (float)x0, (float)y0, d.q, d.t, d.X, d.uv, d.hdr,
+                       xy_host);
     VO_CHECK_LAUNCH(ctx);
     return VO_OK;
 }

@@ -6,6 +6,8 @@
 //                    of J from the level image of B, int32 partial sums per lane, an int64 butterfly over the wave (integer sums are
 //                    order-free) and the scalar float64 step computed by every lane alike.  Nothing is handed between waves: no LDS,
 //                    no atomics, no counters, no waiting; every loop is bounded by levels, iters and the window; every read is clamped.
+// and the host side of vo_klt_pnp_pair / _begin / _end at the end of the file: the two kernels above, k_klt_pnp_prep (geom.hip) and the
+// tail of the stereo PnP step (ransac.hip) as one chain.
 #include <math.h>
 #include "vo_internal.h"
 
@@ -247,9 +249,10 @@ void klt_ws_free(KltWs& k)
     k = KltWs();
 }
 
+// completes the Lucas-Kanade members of the match workspace in force (the main one, or a pose alternate's under its AltScope)
 static int klt_ws_prepare(vo_ctx* ctx)
 {
-    KltWs& k = ctx->klt;
+    KltWs& k = ctx->mw->klt;
     if (k.ready) return VO_OK;
     size_t total = 0;
     int w = ctx->max_w, h = ctx->max_h;
@@ -288,7 +291,7 @@ static int klt_params(vo_ctx* ctx, int win, int levels, int iters, double eps, d
 // the pyramids above level 0 of both images, then the forward (and backward) pass of the n points at d_xy, all on ctx->stream
 static int klt_enqueue(vo_ctx* ctx, const uint8_t* a0, const uint8_t* b0, int w, int h, const KltPrm& prm, bool fb, const float* d_xy, int n)
 {
-    KltWs& k = ctx->klt;
+    KltWs& k = ctx->mw->klt;
     KltImgs P;
     for (int l = 0; l < VO_KLT_MAX_LEVELS; l++) { P.a[l] = a0; P.b[l] = b0; P.w[l] = w; P.h[l] = h; }     // (levels never read stay valid)
     {
@@ -325,7 +328,7 @@ extern "C" int vo_klt_track_host(vo_ctx* ctx, const uint8_t* img_a, const uint8_
     if (n == 0) return VO_OK;
     VO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = klt_ws_prepare(ctx)) return rc;
-    KltWs& k = ctx->klt;
+    KltWs& k = ctx->mw->klt;
     const size_t npx = (size_t)w * h;
     VO_HIP(ctx, hipMemcpyAsync(k.pyr[0], img_a, npx, hipMemcpyHostToDevice, ctx->stream));
     VO_HIP(ctx, hipMemcpyAsync(k.pyr[1], img_b, npx, hipMemcpyHostToDevice, ctx->stream));
@@ -356,7 +359,7 @@ extern "C" int vo_klt_track(vo_ctx* ctx, int slot_a, int slot_b, int win, int le
     VO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = klt_ws_prepare(ctx)) return rc;
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
-    KltWs& k = ctx->klt;
+    KltWs& k = ctx->mw->klt;
     if (ctx->has_roi) { prm.ox = (double)ctx->roi[0]; prm.oy = (double)ctx->roi[1]; }
     int rc = klt_enqueue(ctx, a.left, b.left, a.w, a.h, prm, fb > 0, a.kp_xy, n);
     if (!rc) rc = xfer_d2h(ctx, xy_out, k.xy_out, (size_t)n * 8);
@@ -366,4 +369,139 @@ extern "C" int vo_klt_track(vo_ctx* ctx, int slot_a, int slot_b, int win, int le
     if ((rc = xfer_flush(ctx))) return rc;
     *n_out = n;
     return VO_OK;
+}
+
+// =========================================================================================
+// Lucas-Kanade PnP pair step (vo_klt_pnp_pair / _begin / _end): what StereoOdometer(match="klt", pose_method="pnp") composes out of
+// vo_klt_track -> host filter -> vo_points3d_at -> vo_ransac_pnp, as ONE chain on ctx->stream -- the pyramid launches, the forward
+// (and backward) tracking launch, k_klt_pnp_prep (geom.hip), then the tail of the stereo PnP step (pnp_tail_enqueue: k_pnp_hyp,
+// k_pnp_score, k_pnp_finish).  No copy command, ONE host synchronisation; the record and the arrays are written into pinned
+// memory by the kernels.  The halves run the chain on a POSE alternate, in that alternate's own Lucas-Kanade workspace.
+// =========================================================================================
+static int klt_pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int klt_iters, double eps, double min_eig, double fb,
+                         const double* K4v, int iters, float thr, int refine_iters, int lo_rounds, const char* who, KltPrm* prm)
+{
+    if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v) return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
+    if (int rc = klt_params(ctx, win, levels, klt_iters, eps, min_eig, fb, who, prm)) return rc;
+    if (int rc = pnp_ranges_check(ctx, K4v, iters, thr, refine_iters, who)) return rc;
+    if (int rc = pnp_lo_check(ctx, lo_rounds, refine_iters, who)) return rc;
+    const FrameSlot& a = ctx->slots[slot_a];
+    const FrameSlot& b = ctx->slots[slot_b];
+    if (!a.has_pair || !b.has_pair) return vo_fail(ctx, VO_E_STATE, "%s: slots %d and %d must both hold a pair", who, slot_a, slot_b);
+    if (!a.has_kp) return vo_fail(ctx, VO_E_STATE, "%s: slot %d holds no keypoints", who, slot_a);
+    if (a.w != b.w || a.h != b.h) return vo_fail(ctx, VO_E_STATE, "%s: the slots' images differ in shape (%dx%d, %dx%d)", who, a.w, a.h, b.w, b.h);
+    if (!slot_sparse(a) && !a.has_disp) return vo_fail(ctx, VO_E_STATE, "%s: slot %d needs disparity (or keypoints that carry depth)", who, slot_a);
+    if (!ctx->has_Q) return vo_fail(ctx, VO_E_STATE, "vo_set_Q has not been called");
+    if (a.n_kp > ctx->kp_cap) return vo_fail(ctx, VO_E_CAP, "%s: %d keypoints exceed capacity %d", who, a.n_kp, ctx->kp_cap);
+    if (ctx->has_roi) { prm->ox = (double)ctx->roi[0]; prm->oy = (double)ctx->roi[1]; }
+    return VO_OK;
+}
+
+// the whole chain on ctx->stream, in the match scratch in force; rec / arr: pinned host memory the kernels write (arr may be NULL:
+// mask, q, t as the PnP step lays them out, then the tracked positions from byte 9 pnp_cap on)
+static int klt_pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, const KltPrm& prm, bool fb, const double* K4v, int iters, float thr, uint32_t seed,
+                           int refine_iters, int lo_rounds, PnpRec* rec, uint8_t* arr)
+{
+    int rc;
+    if ((rc = klt_ws_prepare(ctx))) return rc;
+    PnpWs w;
+    if ((rc = pnp_ws_take(ctx, a.n_kp, iters, &w))) return rc;
+    KltWs& k = ctx->mw->klt;
+    if ((rc = klt_enqueue(ctx, a.left, b.left, a.w, a.h, prm, fb, a.kp_xy, a.n_kp))) return rc;
+    StageTimer t(ctx, VO_T_POSE);
+    if ((rc = klt_pnp_prep_launch(ctx, a, k.xy_out, k.status, w.d, arr ? (float*)(arr + pnp_cap(ctx->kp_cap) * 9) : nullptr))) return rc;
+    return pnp_tail_enqueue(ctx, w, a.n_kp, K4v, iters, thr, seed, refine_iters, lo_rounds, rec, arr, nullptr);
+}
+
+static int klt_pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, int lo_rounds, int32_t* counts4, int32_t* flags, double* Rt12,
+                          double* Rt12_refined, int32_t* refine2, int32_t* lo2, uint8_t* mask_out, int32_t* q_idx, float* xy_out, const char* who)
+{
+    if (arr && xy_out && r->n > 0) memcpy(xy_out, arr + pnp_cap(ctx->kp_cap) * 9, (size_t)r->n * 8);
+    return pnp_unpack(ctx, r, arr, nq, counts4, flags, Rt12, Rt12_refined, refine2, mask_out, q_idx, nullptr, who, lo_rounds, lo2);
+}
+
+extern "C" int vo_klt_pnp_pair(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int klt_iters, double eps, double min_eig, double fb,
+                               const double* K4v, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds, int32_t* counts4,
+                               int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2, int32_t* lo2, uint8_t* mask_out,
+                               int32_t* q_idx, float* xy_out, int cap)
+{
+    const char* who = "vo_klt_pnp_pair";
+    if (ctx && (!counts4 || !flags || !Rt12 || !refine2)) return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
+    KltPrm prm;
+    int rc = klt_pnp_check(ctx, slot_a, slot_b, win, levels, klt_iters, eps, min_eig, fb, K4v, iters, thr, refine_iters, lo_rounds, who, &prm);
+    if (rc) return rc;
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    const bool want = mask_out || q_idx || xy_out;
+    if (want && cap < a.n_kp) return vo_fail(ctx, VO_E_CAP, "%s: outputs hold %d entries, %d keypoints", who, cap, a.n_kp);
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
+    PnpRec* rec = (PnpRec*)ctx->pinned;
+    pnp_rec_clear(rec);
+    uint8_t* arr = nullptr;
+    if (a.n_kp > 0) {
+        const size_t bytes = pnp_cap(ctx->kp_cap) * PNP_ARR;
+        if (want && !(arr = (uint8_t*)xfer_stage(ctx, bytes))) {
+            if ((rc = xfer_flush(ctx))) return rc;
+            if (!(arr = (uint8_t*)xfer_stage(ctx, bytes))) return vo_fail(ctx, VO_E_CAP, "%s: the transfer arena cannot hold %d keypoints", who, a.n_kp);
+        }
+        if ((rc = klt_pnp_enqueue(ctx, a, b, prm, fb > 0, K4v, iters, thr, seed, refine_iters, lo_rounds, rec, arr))) { (void)xfer_flush(ctx); return rc; }
+        if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
+        if (!slot_sparse(a) && (rc = slot_health(ctx, a, slot_a))) return rc;       // never a pose from an undefined disparity (b's is not read)
+    }
+    return klt_pnp_unpack(ctx, rec, arr, a.n_kp, lo_rounds, counts4, flags, Rt12, Rt12_refined, refine2, lo2, mask_out, q_idx, xy_out, who);
+}
+
+extern "C" int vo_klt_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, int win, int levels, int klt_iters, double eps, double min_eig, double fb,
+                                     const double* K4v, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds, int want_arrays,
+                                     int* ticket_out)
+{
+    const char* who = "vo_klt_pnp_pair_begin";
+    if (ctx && !ticket_out) return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
+    KltPrm prm;
+    int rc = klt_pnp_check(ctx, slot_a, slot_b, win, levels, klt_iters, eps, min_eig, fb, K4v, iters, thr, refine_iters, lo_rounds, who, &prm);
+    if (rc) return rc;
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    FrameSlot& a = ctx->slots[slot_a];
+    FrameSlot& b = ctx->slots[slot_b];
+    int k;
+    if ((rc = alt_open(ctx, vo_ctx::ALT_POSE, a, b, who, &k))) return rc;
+    vo_ctx::PoseAlt& p = ctx->pose_alt[k];
+    pnp_rec_clear((PnpRec*)p.result);
+    if (a.n_kp > 0) {
+        AltScope on_alt(ctx, p);
+        rc = klt_pnp_enqueue(ctx, a, b, prm, fb > 0, K4v, iters, thr, seed, refine_iters, lo_rounds, (PnpRec*)p.result,
+                             want_arrays ? p.result + PNP_HDR : nullptr);
+    }
+    if (rc) return rc;
+    p.slot_a = slot_a; p.slot_b = slot_b;
+    p.gen_a = slot_sparse(a) ? 0 : a.disp_gen;       // (keypoints that carry depth: the step read no disparity, nothing to check at _end)
+    p.gen_b = !slot_sparse(a) && b.has_disp ? b.disp_gen : 0;
+    p.pnp = true; p.klt = true; p.want = want_arrays != 0 && a.n_kp > 0; p.nq = a.n_kp; p.lo = lo_rounds;
+    return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
+}
+
+extern "C" int vo_klt_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
+                                   int32_t* lo2, uint8_t* mask_out, int32_t* q_idx, float* xy_out, int cap)
+{
+    const char* who = "vo_klt_pnp_pair_end";
+    int rc = alt_ticket(ctx, vo_ctx::ALT_POSE, ticket, counts4 && flags && Rt12 && refine2, who);
+    if (rc) return rc;
+    vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
+    if (!p.klt)
+        return vo_fail(ctx, VO_E_STATE, "%s: ticket %d belongs to %s (end it with %s)", who, ticket, p.pnp ? "vo_pnp_pair_begin" : "vo_pose_pair_begin",
+                       p.pnp ? "vo_pnp_pair_end" : "vo_pose_pair_end");
+    if ((mask_out || q_idx || xy_out) && p.nq > 0 && (!p.want || cap < p.nq))
+        return vo_fail(ctx, VO_E_CAP, "%s: outputs hold %d entries, %d keypoints (or the step was begun without want_arrays)", who, cap, p.nq);
+    if ((rc = alt_wait(ctx, p))) return rc;
+    const int32_t gens[2] = { p.gen_a, p.gen_b };
+    const int slots[2] = { p.slot_a, p.slot_b };
+    for (int i = 0; i < 2; i++) {
+        const FrameSlot& f = ctx->slots[slots[i]];
+        if (gens[i] != 0 && *(volatile int32_t*)f.sweep_word == gens[i])
+            return vo_fail(ctx, VO_E_SWEEP, "Lucas-Kanade PnP step %d: the aggregation sweep of the pair in slot %d gave up a strip hand-off: its "
+                                            "disparity is undefined and no pose is derived from it", ticket, slots[i]);
+    }
+    return klt_pnp_unpack(ctx, (const PnpRec*)p.result, p.want ? p.result + PNP_HDR : nullptr, p.nq, p.lo, counts4, flags, Rt12, Rt12_refined, refine2,
+                          lo2, mask_out, q_idx, xy_out, who);
 }

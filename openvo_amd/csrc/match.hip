@@ -357,6 +357,7 @@ void match_ws_free(vo_ctx::MatchWs& m)
 {
     void* ps[] = { m.m_idx, m.m_dist, m.m_count, m.mq_idx, m.mt_idx, m.xy_a, m.xy_b, m.pts_a, m.pts_b, m.st_a, m.st_b, m.clique_ws, m.ransac_ws };
     for (void* q : ps) if (q) (void)hipFree(q);
+    klt_ws_free(m.klt);
     m = vo_ctx::MatchWs();
 }
 
@@ -622,8 +623,9 @@ static int alt_prepare(vo_ctx* ctx, int kind, int k)
     } else
         e = hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p.done, hipEventDisableTiming);
-    // (a pose alternate serves vo_pose_pair_begin and vo_pnp_pair_begin alike: its record holds a PnpRec with its arrays)
-    const size_t record = pose ? PNP_HDR + pnp_cap(ctx->kp_cap) * 9 + 64 : MONO_HDR + (size_t)ctx->kp_cap * (1 + 4 + 4 + 8) + 64;
+    // (a pose alternate serves vo_pose_pair_begin, vo_pnp_pair_begin and vo_klt_pnp_pair_begin alike: its record holds a PnpRec with its
+    // arrays, the tracked positions of a Lucas-Kanade step included)
+    const size_t record = pose ? PNP_HDR + pnp_cap(ctx->kp_cap) * PNP_ARR + 64 : MONO_HDR + (size_t)ctx->kp_cap * (1 + 4 + 4 + 8) + 64;
     if (e == hipSuccess) e = hipHostMalloc((void**)&p.result, record, hipHostMallocDefault);
     if (e == hipSuccess) e = match_ws_alloc(ctx, p.mw, pose ? MATCH_WS_POSE : 0);
     if (e != hipSuccess) {

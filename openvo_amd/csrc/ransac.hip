@@ -1682,6 +1682,14 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
     }
 }
 
+int pnp_ranges_check(vo_ctx* ctx, const double* K4v, int iters, float thr, int refine_iters, const char* who)
+{
+    if (iters <= 0 || iters > (1 << 22)) return vo_fail(ctx, VO_E_ARG, "%s: need 0 < iters <= 4194304", who);
+    if (refine_iters < 0 || refine_iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: refine_iters is 0 .. 20", who);
+    if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
+    return VO_OK;
+}
+
 // lg: the loop gate of the step, as the context stands at this call (a ticket keeps it)
 int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double* K4v, int iters, float thr, int refine_iters, const char* who,
               LoopGate* lg, int view_n)
@@ -1689,9 +1697,7 @@ int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double
     if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v)
         return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
     if (int rcf = match_flags_check(ctx, match_flags, who, true)) return rcf;
-    if (iters <= 0 || iters > (1 << 22)) return vo_fail(ctx, VO_E_ARG, "%s: need 0 < iters <= 4194304", who);
-    if (refine_iters < 0 || refine_iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: refine_iters is 0 .. 20", who);
-    if (!(thr > 0.0f) || !(K4v[0] > 0.0) || !(K4v[1] > 0.0)) return vo_fail(ctx, VO_E_ARG, "%s: need thr > 0 and positive focal lengths", who);
+    if (int rcr = pnp_ranges_check(ctx, K4v, iters, thr, refine_iters, who)) return rcr;
     FrameSlot& a = ctx->slots[slot_a];
     FrameSlot& b = ctx->slots[slot_b];
     if (view_n >= 0) {                       // slot a will be a view: depth-carrying keypoints, view_n of them
@@ -1710,12 +1716,9 @@ int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double
     return match_loop_gate(ctx, a, b, match_flags, who, lg);
 }
 
-// the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
-// pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
-int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
-                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain, int lo_rounds)
+// the RANSAC workspace of the match scratch currently installed in ctx (the main one, or a pose alternate's), laid out for one step
+int pnp_ws_take(vo_ctx* ctx, int nq, int iters, PnpWs* ws)
 {
-    const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
     // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
     const size_t need = (size_t)iters * (96 + 48 + 4) + (size_t)nq * (12 + 8 + 4 + 4 + 1) + 4096;
     if (ctx->mw->ransac_ws_bytes < need) {       // first use of this workspace (or a larger step than any before): never on the steady path
@@ -1727,48 +1730,68 @@ int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match
         ctx->mw->ransac_ws_bytes = take;
     }
     uint8_t* w = ctx->mw->ransac_ws;
-    double* d_Rt = (double*)w; w += (size_t)iters * 96;
-    float* d_P = (float*)w; w += (size_t)iters * 48;
-    int32_t* d_counts = (int32_t*)w; w += (size_t)iters * 4;
+    ws->Rt = (double*)w; w += (size_t)iters * 96;
+    ws->P = (float*)w; w += (size_t)iters * 48;
+    ws->counts = (int32_t*)w; w += (size_t)iters * 4;
     w = (uint8_t*)(((uintptr_t)w + 255) & ~(uintptr_t)255);
-    PnpDev d;
+    PnpDev& d = ws->d;
     d.hdr = (int32_t*)w; w += 256;
     d.uv = (float*)w; w += (size_t)nq * 8;
     d.X = (float*)w; w += (size_t)nq * 12;
     d.q = (int32_t*)w; w += (size_t)nq * 4;
     d.t = (int32_t*)w; w += (size_t)nq * 4;
-    uint8_t* d_mask = w;
+    ws->mask = w;
+    return VO_OK;
+}
+
+// everything behind the prep launch: hypotheses, scores and the finish on ctx->stream, for the upper bound nq (the kernels read n)
+int pnp_tail_enqueue(vo_ctx* ctx, const PnpWs& w, int nq, const double* K4v, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds,
+                     PnpRec* rec, uint8_t* arr, PnpRec* rec_dev)
+{
+    const PnpDev& d = w.d;
+    const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
+    const float thr2 = thr * thr;
+    hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d.X, d.uv, nq, K, iters, seed, w.Rt, w.P, d.hdr + 1);
+    hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d.X, d.uv, nq, w.P, iters, thr2, w.counts, d.hdr + 1);
+    // (the plain form is launched whenever no round is asked for: the LO entries with lo_rounds == 0 ARE the plain entries)
+    auto finish = lo_rounds > 0 ? k_pnp_finish<true> : k_pnp_finish<false>;
+    hipLaunchKernelGGL(finish, dim3(1), dim3(256), 0, ctx->stream, w.counts, iters, w.Rt, w.P, d.X, d.uv, nq, d.hdr, d.q, d.t, thr2, K,
+                       refine_iters, lo_rounds, w.mask, rec, arr, pnp_cap(ctx->kp_cap), rec_dev);
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
+// the whole chain on ctx->stream with the match scratch and RANSAC workspace currently installed in ctx (the main ones, or a
+// pose alternate's); rec / arr: pinned host memory k_pnp_finish writes (arr may be NULL)
+int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
+                int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain, int lo_rounds)
+{
+    const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
+    PnpWs w;
     int rc;
+    if ((rc = pnp_ws_take(ctx, nq, iters, &w))) return rc;
     {
         StageTimer t(ctx, VO_T_MATCH);
         if ((rc = match_knn2_slots(ctx, a, b, match_flags))) return rc;
     }
     {
         StageTimer t(ctx, VO_T_POSE);
-        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, d, lg, chain ? chain->nq_dev : nullptr))) return rc;
-        const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
-        const float thr2 = thr * thr;
-        hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d.X, d.uv, nq, K, iters, seed, d_Rt, d_P, d.hdr + 1);
-        hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d.X, d.uv, nq, d_P, iters, thr2, d_counts, d.hdr + 1);
-        // (the plain form is launched whenever no round is asked for: the LO entries with lo_rounds == 0 ARE the plain entries)
-        auto finish = lo_rounds > 0 ? k_pnp_finish<true> : k_pnp_finish<false>;
-        hipLaunchKernelGGL(finish, dim3(1), dim3(256), 0, ctx->stream, d_counts, iters, d_Rt, d_P, d.X, d.uv, nq, d.hdr, d.q, d.t, thr2, K,
-                           refine_iters, lo_rounds, d_mask, rec, arr, pnp_cap(ctx->kp_cap), chain ? chain->rec_dev : nullptr);
-        VO_CHECK_LAUNCH(ctx);
+        if ((rc = pnp_prep_launch(ctx, a, b, ratio, cross, w.d, lg, chain ? chain->nq_dev : nullptr))) return rc;
+        if ((rc = pnp_tail_enqueue(ctx, w, nq, K4v, iters, thr, seed, refine_iters, lo_rounds, rec, arr, chain ? chain->rec_dev : nullptr))) return rc;
     }
-    if (chain) { chain->d = d; chain->mask = d_mask; }
+    if (chain) { chain->d = w.d; chain->mask = w.mask; }
     return VO_OK;
 }
 
-static void pnp_rec_clear(PnpRec* r)
+void pnp_rec_clear(PnpRec* r)
 {
     memset(r, 0, sizeof(PnpRec));
     r->rstatus = 1;
 }
 
 // record (+ arrays) -> the caller's outputs; VO_E_STATE for a pair the step refused.  lo2 (may be NULL) = {rounds completed, |S_c|}
-static int pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
-                      int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, const char* who, int lo_rounds = 0, int32_t* lo2 = nullptr)
+int pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+               int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, const char* who, int lo_rounds, int32_t* lo2)
 {
     counts4[0] = r->M; counts4[1] = r->n; counts4[2] = r->best_iter; counts4[3] = r->best_count;
     *flags = r->flags;
@@ -1867,7 +1890,7 @@ static int pnp_begin_impl(vo_ctx* ctx, int slot_a, int slot_b, double ratio, int
     p.slot_a = slot_a; p.slot_b = slot_b;
     p.gen_a = a.disp_gen; p.gen_b = b.disp_gen;
     if (slot_sparse(a)) p.gen_a = p.gen_b = 0;       // the step read no disparity: nothing to check at _end
-    p.pnp = true; p.want = want_matches != 0 && a.n_kp > 0; p.nq = a.n_kp; p.lo = lo_rounds;
+    p.pnp = true; p.klt = false; p.want = want_matches != 0 && a.n_kp > 0; p.nq = a.n_kp; p.lo = lo_rounds;
     return alt_close(ctx, vo_ctx::ALT_POSE, k, a, b, ticket_out);
 }
 
@@ -1893,6 +1916,7 @@ static int pnp_end_impl(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flag
     if (rc) return rc;
     vo_ctx::PoseAlt& p = ctx->pose_alt[ticket];
     if (!p.pnp) return vo_fail(ctx, VO_E_STATE, "%s: ticket %d belongs to vo_pose_pair_begin (end it with vo_pose_pair_end)", who, ticket);
+    if (p.klt) return vo_fail(ctx, VO_E_STATE, "%s: ticket %d belongs to vo_klt_pnp_pair_begin (end it with vo_klt_pnp_pair_end)", who, ticket);
     if ((mask_out || q_idx || t_idx) && p.nq > 0 && (!p.want || cap < p.nq))
         return vo_fail(ctx, VO_E_CAP, "%s: outputs hold %d entries, %d keypoints (or the step was begun without want_matches)", who, cap, p.nq);
     if ((rc = alt_wait(ctx, p))) return rc;

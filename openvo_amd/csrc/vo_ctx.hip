@@ -322,7 +322,6 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     for (void* p : ps) if (p) (void)hipFree(p);
     alt_free(ctx);
     for (LandmarkMap& m : ctx->maps) map_free(m);
-    klt_ws_free(ctx->klt);
     sparse_ws_free(ctx->sp_main);
     for (SparseWs& w : ctx->sp_alt) sparse_ws_free(w);
     match_ws_free(ctx->main_mw);
@@ -1587,6 +1586,22 @@ extern "C" int vo_test_plant_dense(vo_ctx* ctx, int slot, int w, int h, const in
     return VO_OK;
 }
 
+// ... and a dense slot that HOLDS ITS PAIR too: vo_test_plant_dense, then the w x h grey image `left` as the slot's rectified left
+// and right image -- the slot stands as an upload, a synchronous vo_sgbm_compute and an ORB extraction leave it.  The seam through
+// which the tests drive the Lucas-Kanade PnP step (vo_klt_pnp_pair), which tracks in the slot's image and looks its keypoints up in
+// the slot's disparity.
+extern "C" int vo_test_plant_dense_pair(vo_ctx* ctx, int slot, int w, int h, const uint8_t* left, const int16_t* disp16, int n, const float* xy,
+                                        const uint8_t* desc)
+{
+    if (ctx && !left) return vo_fail(ctx, VO_E_ARG, "vo_test_plant_dense_pair: null pointer");
+    if (int rc = vo_test_plant_dense(ctx, slot, w, h, disp16, n, xy, desc)) return rc;
+    FrameSlot& f = ctx->slots[slot];
+    int rc;
+    if ((rc = xfer_h2d(ctx, f.left, left, (size_t)w * h)) || (rc = xfer_h2d(ctx, f.right, left, (size_t)w * h)) || (rc = xfer_flush(ctx))) return rc;
+    f.has_pair = true;
+    return VO_OK;
+}
+
 // ... and n landmarks written straight into a map (vo_map_create), which then stands as n insertions would have left it -- with
 // any float32 bits as positions (NaN, inf: what no update ever inserts) and chosen obs / last.  The last view is void; the largest
 // `last` counts as a serial used.  xyz (n, 3) float32, desc / rdesc (n, 32), octave / obs / last (n) int32, last >= 0, obs >= 1.
@@ -1646,7 +1661,7 @@ extern "C" int vo_test_klt_level(vo_ctx* ctx, int which, int level, int w_l, int
     int mw = ctx->max_w, mh = ctx->max_h;
     for (int l = 0; l < level; l++) { mw = (mw + 1) / 2; mh = (mh + 1) / 2; }
     if (w_l > mw || h_l > mh) return vo_fail(ctx, VO_E_CAP, "vo_test_klt_level: %dx%d exceeds level %d of the workspace (%dx%d)", w_l, h_l, level, mw, mh);
-    const KltWs& k = ctx->klt;
+    const KltWs& k = ctx->main_mw.klt;
     if (!k.ready) return vo_fail(ctx, VO_E_STATE, "vo_test_klt_level: no Lucas-Kanade call has prepared the workspace");
     VO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = xfer_d2h(ctx, out, k.pyr[which] + k.off[level], (size_t)w_l * h_l)) { (void)xfer_flush(ctx); return rc; }

@@ -149,7 +149,9 @@ void map_free(LandmarkMap& m);
 
 // Lucas-Kanade tracking (klt.hip; include/vo355.h, vo_klt_*): the two pyramids of a call -- image 0 / 1, level l at byte off[l] of
 // pyr[k], laid out for max_w x max_h (level 0 is only used by the host entry: the slot entry reads the slots' own images) -- and the
-// per-point arrays, kp_cap entries each.  Allocated at the first call, freed by vo_destroy.
+// per-point arrays, kp_cap entries each.  A member of a match workspace (vo_ctx::MatchWs::klt): the context's main one serves
+// vo_klt_track / vo_klt_track_host / vo_klt_pnp_pair, a pose alternate's its own vo_klt_pnp_pair_begin step, so two steps in flight
+// never share pyramids or track arrays.  Allocated at the first Lucas-Kanade use of that workspace, freed with it (match_ws_free).
 #define VO_KLT_MAX_LEVELS 6
 struct KltWs {
     uint8_t* pyr[2] = {nullptr, nullptr};
@@ -273,7 +275,6 @@ struct vo_ctx {
     // engine k's own
     FrameSlot sparse_r;
     LandmarkMap maps[VO_NUM_MAPS];      // vo_map_create .. vo_map_destroy (freed by vo_destroy too)
-    KltWs klt;                          // vo_klt_track / vo_klt_track_host
     SparseWs sp_main;
     SparseWs sp_alt[MAX_ENGINES];
 
@@ -323,6 +324,7 @@ struct vo_ctx {
         size_t clique_ws_bytes = 0;
         uint8_t* ransac_ws = nullptr;    // grown on demand (mono_enqueue, vo_ransac_pnp)
         size_t ransac_ws_bytes = 0;
+        KltWs klt;                       // completed at the workspace's first Lucas-Kanade use (klt.hip)
     };
     MatchWs main_mw;
     MatchWs* mw = &main_mw;
@@ -371,6 +373,7 @@ struct vo_ctx {
         bool pnp = false, want = false;    // a vo_pnp_pair_begin step (its record is a PnpRec) / whose record carries mask, q, t
         int nq = 0;                        // query keypoints of that step
         int lo = 0;                        // its lo_rounds (vo_pnp_pair_begin_lo; 0: the plain step)
+        bool klt = false;                  // a vo_klt_pnp_pair_begin step (a PnpRec too; its arrays are mask, q, t and the tracked xy)
     } pose_alt[N_POSE_ALT];
     static const int N_MONO_ALT = VO_NUM_MONO_ASYNC;
     struct MonoAlt : AsyncAlt {
@@ -690,6 +693,26 @@ int pnp_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match
                 int refine_iters, PnpRec* rec, uint8_t* arr, const LoopGate& lg, PnpChain* chain = nullptr, int lo_rounds = 0);
 // lo_rounds of the _lo entries: 0 .. 8, and a value above 0 needs refine_iters >= 1 (VO_E_ARG otherwise)
 int pnp_lo_check(vo_ctx* ctx, int lo_rounds, int refine_iters, const char* who);
+// The two halves pnp_enqueue is made of, for a chain with another front (vo_klt_pnp_pair: klt.hip).  pnp_ws_take: the RANSAC
+// workspace of the match scratch in force laid out for nq keypoints and iters hypotheses (grown, behind a wait for ctx->stream,
+// where it is too small).  pnp_tail_enqueue: everything behind the prep launch -- k_pnp_hyp, k_pnp_score, k_pnp_finish<LO> on
+// ctx->stream, reading the compacted (X, uv, hdr, q, t) of w.d; rec / arr / rec_dev as in pnp_enqueue.
+struct PnpWs { double* Rt; float* P; int32_t* counts; PnpDev d; uint8_t* mask; };
+int pnp_ws_take(vo_ctx* ctx, int nq, int iters, PnpWs* w);
+int pnp_tail_enqueue(vo_ctx* ctx, const PnpWs& w, int nq, const double* K4v, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds,
+                     PnpRec* rec, uint8_t* arr, PnpRec* rec_dev);
+void pnp_rec_clear(PnpRec* r);
+// record (+ arrays) -> the caller's outputs; VO_E_STATE for a pair the step refused.  lo2 (may be NULL) = {rounds completed, |S_c|}
+int pnp_unpack(vo_ctx* ctx, const PnpRec* r, const uint8_t* arr, int nq, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined,
+               int32_t* refine2, uint8_t* mask_out, int32_t* q_idx, int32_t* t_idx, const char* who, int lo_rounds = 0, int32_t* lo2 = nullptr);
+// the ranges pnp_check allows for iters, thr, refine_iters and the focal lengths (VO_E_ARG with its messages)
+int pnp_ranges_check(vo_ctx* ctx, const double* K4v, int iters, float thr, int refine_iters, const char* who);
+// the link between Lucas-Kanade tracking and the RANSAC (k_klt_pnp_prep, geom.hip): the tracks of slot a's keypoints that ended
+// with status 0 (xy_trk / status: KltWs::xy_out / status), their 3-D points in slot a, compacted in keypoint order into d; xy_host
+// (may be NULL): pinned host memory that receives the tracked position of each compacted correspondence
+int klt_pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, const float* xy_trk, const uint8_t* status, const PnpDev& d, float* xy_host);
+// bytes per keypoint of a PnP record's arrays: mask (1), q, t (4 each) and, for a Lucas-Kanade step, the tracked xy (8)
+static const size_t PNP_ARR = 17;
 
 // ---- asynchronous steps (match.hip): see vo_ctx::AsyncAlt -------------------------------------------------------------------
 static const size_t MONO_HDR = 4096;             // monocular record: [0] M, [1..2] best, E9 at byte 64; arrays from MONO_HDR on

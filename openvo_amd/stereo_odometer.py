@@ -19,6 +19,7 @@ from .features import BFMatcher, DeviceImage, DisparityMask, KeyPointList, ORB
 # which trailing entry of the key is the match window (a plain (rx, ry) tuple) and which the threshold
 LoopCheck = collections.namedtuple("LoopCheck", "max_hamming")
 LoRounds = collections.namedtuple("LoRounds", "rounds")          # the marker of pnp_lo_rounds > 0 in _pose_params(): always the last entry
+KltTrack = collections.namedtuple("KltTrack", "win levels fb")   # the marker of klt_fused in _pose_params(): the tracker a step was begun with
 
 
 class StereoOdometer:
@@ -34,7 +35,7 @@ class StereoOdometer:
                  pose_method="umeyama", pnp_iters=256, pnp_threshold=1.5, pnp_seed=4321, cross_check=False, pnp_refine=0,
                  match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
                  loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False,
-                 pnp_lo_rounds=0, match="orb", klt_window=21, klt_levels=4, klt_fb=1.0):
+                 pnp_lo_rounds=0, match="orb", klt_window=21, klt_levels=4, klt_fb=1.0, klt_fused=False):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -107,9 +108,16 @@ class StereoOdometer:
         positions and point_cloud_transform runs unchanged.  A track whose 3-D lookup in either frame has no usable tap or no finite
         point, or which has left the crop, is DROPPED (the keypoint paths raise ZeroDivisionError there).  The new frame's ORB
         extraction still runs: its keypoints are what the next pair tracks.  Both frames must be on the device (ValueError
-        otherwise, as with pose_method="pnp"); no pose step is begun ahead, run() still submits pairs ahead; the one-frame-back
+        otherwise, as with pose_method="pnp"); no pose step is begun ahead (but see klt_fused), run() still submits pairs ahead; the one-frame-back
         fallback takes the same path.  cross_check, match_window, loop_check and track="map" belong to the descriptor matcher and
-        are refused with match="klt".  klt_counts = (keypoints tracked from, tracks kept) of the last pair."""
+        are refused with match="klt".  klt_counts = (keypoints tracked from, tracks kept) of the last pair.
+        klt_fused=True (match="klt" with pose_method="pnp" only; default False): the pair step -- tracking, the filter, the 3-D lookup
+        and the RANSAC -- is ONE native call with one synchronisation (vo_klt_pnp_pair) instead of three or four, nothing per
+        keypoint comes back, and steps are begun ahead on pairs that are already on the device, as with match="orb"
+        (_start_next_pose; klt_ahead counts the steps collected from a ticket begun ahead).  The decisions are those of the
+        composed path in its order; with pnp_refine / pnp_lo_rounds the gates see the refined pose where the refit succeeded (the
+        composed path does not refine).  Admitted per pair like the fused PnP step -- an exact StereoOdometer, no replaced seam,
+        frames on the device, at most 3800 keypoints in the older frame; otherwise the composed path runs."""
         if not isinstance(track, str) or track not in ("pair", "map"):
             raise ValueError("track must be 'pair' or 'map'")
         if track == "map" and (depth != "sparse" or pose_method != "pnp"):
@@ -182,6 +190,13 @@ class StereoOdometer:
             # (instance attributes only where the option is on: without it the object is what it was)
             self.match, self.klt_window, self.klt_levels, self.klt_fb = "klt", klt[0], klt[1], klt[5]
             self.klt_counts = None
+        if not isinstance(klt_fused, (bool, np.bool_)):
+            raise ValueError("klt_fused must be True or False")
+        if klt_fused and (match != "klt" or pose_method != "pnp"):
+            raise ValueError("klt_fused=True needs match='klt' and pose_method='pnp'")
+        if klt_fused:                # (instance attributes only where the option is on: without it the object is what it was)
+            self.klt_fused = True
+            self.klt_ahead = 0       # pair steps collected from a ticket begun ahead
         if isinstance(pnp_refine, (bool, np.bool_)) or not isinstance(pnp_refine, (int, np.integer)) or not 0 <= pnp_refine <= 20:
             raise ValueError("pnp_refine must be an int in 0 .. 20")
         self.pnp_refine = int(pnp_refine)
@@ -430,6 +445,8 @@ class StereoOdometer:
             pass
 
     match = "orb"            # "klt" (constructor): pairs are associated by Lucas-Kanade tracking (_pair_klt)
+    klt_fused = False        # True (constructor): the Lucas-Kanade pair step is one native call (_pair_klt_fused)
+    _KLT_CTX_SEAMS = ("klt_track", "points3d_at", "ransac_pnp")
     pnp_lo_rounds = 0        # 1 .. 8 (constructor): local-optimisation rounds of the fused PnP step (the _lo entries are called)
     pnp_lo_counts = None     # (rounds completed, support) of the last fused step with pnp_lo_rounds > 0
     map_fused = False        # True (constructor): the map step is one native call (_map_track_fused)
@@ -441,6 +458,11 @@ class StereoOdometer:
         """The two native calls the composed PnP path is made of are seams too: replaced on the context object (instrumented,
         say), they are what runs, so the fused step -- which would bypass them -- stands back."""
         return self._pnp_fused and not any(n in getattr(self._ctx, "__dict__", {}) for n in self._PNP_CTX_SEAMS)
+
+    def _klt_fused_ok(self):
+        """as _fused_ok for the Lucas-Kanade step: the three native calls the composed path is made of are its seams"""
+        return (self.klt_fused and type(self) is StereoOdometer and not any(n in self.__dict__ for n in self._SEAMS)
+                and not any(n in getattr(self._ctx, "__dict__", {}) for n in self._KLT_CTX_SEAMS))
 
     def _window(self, span=None):
         """The match window of a pair that spans `span` frames (None: the pair being tried, else skipped_frames + 1): the radii
@@ -454,6 +476,10 @@ class StereoOdometer:
     def _pose_params(self):
         """What a pose step begun ahead must have been begun with to be this odometer's step (part of its ticket's key).  With a
         match window its effective radii are the last entry: a step begun with another window (another span) is never reused."""
+        if self.klt_fused:
+            Q = self.stereo.Q
+            return ("klt", (float(Q[2, 3]), float(Q[2, 3]), float(-Q[0, 3]), float(-Q[1, 3])), int(self.pnp_iters), float(self.pnp_threshold),
+                    int(self.pnp_seed), int(self.pnp_refine), int(self.pnp_lo_rounds), KltTrack(self.klt_window, self.klt_levels, self.klt_fb))
         tail = () if self.match_window is None else (self._window(),)
         if self.loop_check is not None:
             tail += (LoopCheck(self.loop_check),)
@@ -495,7 +521,15 @@ class StereoOdometer:
             return params[:-1], {"loop": params[-1].max_hamming}
         return params, {}
 
+    @staticmethod
+    def _klt_kwargs(params):
+        """_pose_params() of the fused Lucas-Kanade mode as the keyword arguments of Context.klt_pnp_pair / klt_pnp_pair_begin"""
+        _, K4, iters, thr, seed, refine, lo_rounds, trk = params
+        return dict(K4=K4, iters=iters, thr=thr, seed=seed, refine=refine, lo_rounds=lo_rounds, win=trk.win, levels=trk.levels, fb=trk.fb)
+
     def _step_begin(self, slot_a, slot_b, params):
+        if params[0] == "klt":
+            return self._ctx.klt_pnp_pair_begin(slot_a, slot_b, **self._klt_kwargs(params))
         if params[0] == "pnp":
             kw = self._pnp_kwargs(params)
             if "lo_rounds" in kw:
@@ -506,6 +540,8 @@ class StereoOdometer:
 
     def _step_end(self, params, ticket):
         """Collect a step begun ahead with the _end of its kind."""
+        if params[0] == "klt":
+            return self._ctx.klt_pnp_pair_end(ticket)
         if params[0] == "pnp":
             if isinstance(params[-1], LoRounds):
                 return self._ctx.pnp_pair_end_lo(ticket)
@@ -548,10 +584,10 @@ class StereoOdometer:
         _pair_fused looks a step up by its slots and parameters and computes on the spot when the guess was wrong."""
         if self.track == "map":        # (the map step needs the pose of the frame before it: nothing to begin ahead)
             return
-        if self.match == "klt":        # (the tracking step is synchronous: nothing is begun ahead)
+        if self.match == "klt" and not self.klt_fused:      # (the composed tracking step is synchronous: nothing is begun ahead)
             return
         sparse = self.depth == "sparse"
-        if not self._fused_ok() or (not sparse and self.orb.last_slot_args is None):
+        if not (self._klt_fused_ok() if self.match == "klt" else self._fused_ok()) or (not sparse and self.orb.last_slot_args is None):
             return self._drop_specs()
         # what identifies the keypoints a pair begun ahead will hold: the ORB arguments, or the sparse request (collected by the
         # waiting form of sparse_stereo: the slot is ready, so it only reads the slot's record)
@@ -769,6 +805,8 @@ class StereoOdometer:
         if not (self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)):
             raise ValueError("match='klt' needs the device-resident frames compute_3d returns")
         fa, fb = kps_a.frame, kps_b.frame
+        if self.klt_fused and len(kps_a) <= 3800 and self._klt_fused_ok():
+            return self._pair_klt_fused(fa.slot, fb.slot, len(kps_a))
         xy_b, st, _ = self._ctx.klt_track(fa.slot, fb.slot, win=self.klt_window, levels=self.klt_levels, fb=self.klt_fb)
         idx = np.nonzero(st == 0)[0]
         self.klt_counts = (len(st), len(idx))
@@ -805,6 +843,32 @@ class StereoOdometer:
             self.skip_cause = "matches"
             return None
         return self.point_cloud_transform(pts_a, pts_b)
+
+    def _pair_klt_fused(self, slot_a, slot_b, n_kp):
+        """The PnP arm of _pair_klt in one native call (vo_klt_pnp_pair: one device synchronisation, nothing but the record comes
+        back): the same decisions in the same order.  A lookup without a usable tap drops its track (flag bit 0 never raises); with
+        pnp_refine > 0 the gates see the refined pose when the refinement succeeded."""
+        params = self._pose_params()
+        ticket = self._specs.pop((self.stereo.slot_key(slot_a), self.stereo.slot_key(slot_b), params), None)
+        if ticket is not None:
+            r = self._step_end(params, ticket)                           # started by an earlier update()
+            self.klt_ahead += 1
+        else:
+            r = self._ctx.klt_pnp_pair(slot_a, slot_b, **self._klt_kwargs(params))
+        if self.pnp_lo_rounds > 0:
+            self.pnp_lo_counts = (r["lo_rounds"], r["lo_support"])
+        self.klt_counts = (n_kp, r["matches"])
+        if r["matches"] < self.min_matches:
+            self.skip_cause = "matches"
+            return None
+        if r["n"] < max(self.min_matches, 4):
+            self.skip_cause = "matches"
+            return None
+        if r["best_count"] < self.min_matches:
+            self.skip_cause = "outlier"
+            return None
+        Rt = r["Rt_refined"] if r["refine_status"] == 0 else r["Rt"]
+        return self._gate(np.vstack([Rt, [0, 0, 0, 1]]))
 
     def _pair_pnp_fused(self, slot_a, slot_b, want_matches=False, record=None):
         """_pair_pnp in one native call (vo_pnp_pair: one device synchronisation, nothing but the record comes back): the same
