@@ -61,7 +61,17 @@ int vo_set_engines(vo_ctx* ctx, int n);
 int vo_set_rectify_maps(vo_ctx* ctx, int cam /*0=L,1=R*/, const int16_t* map1 /*h*w*2*/,
                         const uint16_t* map2 /*h*w*/, int w, int h);
 /* cv2.StereoSGBM_create positional parameters [stereo_camera.py:23-27]; mode 0 = MODE_SGBM
- * (5 paths, the reference's default), 1 = MODE_HH (8 paths) */
+ * (5 paths, the reference's default), 1 = MODE_HH (8 paths), 2 = MODE_SGBM_3WAY (3 paths; the reference's
+ * "# TODO: mode option", stereo_camera.py:26); any other value is VO_E_ARG (MODE_HH4 = 3 included) and leaves the
+ * parameters in force untouched.
+ * Mode 2 is MODE_SGBM with the direction set W, E, N in place of W, NW, N, NE, E, and nothing else changed: the cost
+ * volume (C carries + P2); L_r by Hirschmueller's eq. 13 with the zero vector as the predecessor outside the computed band;
+ * S = min(L_W + L_E + L_N, 32767); the first minimum, the uniqueness test and "every sum saturated = no winner"; the disp2
+ * arbitration, the sub-pixel step and the two-sided left-right check; medianBlur(3) and the speckle filter.  The N path runs
+ * from the top row of the image to the bottom row as ONE stripe.  Parity with OpenCV's computeDisparity3WAY is NOT claimed:
+ * that function, as recalled, cuts the image into horizontal stripes by thread count and restarts the vertical path in
+ * each, so its output depends on the machine; this definition does not.  Mode 2 runs on the look-ahead engines like
+ * MODE_HH, each pair's chain on its engine's stream: it joins no sweep group. */
 int vo_set_sgbm(vo_ctx* ctx, int minDisparity, int numDisparities, int blockSize, int P1, int P2,
                 int disp12MaxDiff, int preFilterCap, int uniquenessRatio, int speckleWindowSize,
                 int speckleRange, int mode);
@@ -790,13 +800,16 @@ int vo_get_timings(vo_ctx* ctx, double* ms_out /*VO_T_NSTAGES*/, int64_t* launch
  * following vo_get_timings accumulates the same brackets); *n_out = 0 while timing is off. */
 int vo_get_stage_timeline(vo_ctx* ctx, int cap, int32_t* stage_out, int32_t* entries_out, double* begin_ms_out, double* end_ms_out, int* n_out);
 /* algorithmic cost-volume cells (width1*H*D) of the last vo_sgbm_compute, and the number of path directions its dominant
- * aggregation kernel covers (3: NW / N / NE inside k_sgbm_diag; all of them for uniquenessRatio >= 100) */
+ * aggregation kernel covers (3: NW / N / NE inside k_sgbm_diag; 1 in mode 2: N inside k_sgbm_vert; all of them -- 5, 8 or,
+ * in mode 2, 3 -- for uniquenessRatio >= 100) */
 int vo_sgbm_last_geometry(vo_ctx* ctx, int64_t* cells, int* n_paths);
 /* which aggregation schedule the latest SGBM run of this context took -- it follows from the parameters alone (every
  * schedule gives the same bits: stereo_camera.py:51 only sees the disparity) */
 enum { VO_SCHED_DIAG = 1,          /* W + E as one volume (k_sgbm_we), NW / N / NE + WTA in the diagonal sweep */
        VO_SCHED_DIAG_RAGGED = 2,   /* the same with k_sgbm_pair for W + E (width - numDisparities not a multiple of 8) */
-       VO_SCHED_UNFUSED = 3 };     /* uniquenessRatio >= 100: one volume per direction + per-pixel winner search */
+       VO_SCHED_UNFUSED = 3,       /* uniquenessRatio >= 100: one volume per direction + per-pixel winner search */
+       VO_SCHED_VERT = 4,          /* mode 2: W + E as one volume (k_sgbm_we2 / k_sgbm_we), N + WTA in the vertical sweep (k_sgbm_vert) */
+       VO_SCHED_VERT_RAGGED = 5 }; /* the same with k_sgbm_pair for W + E */
 int vo_sgbm_last_schedule(vo_ctx* ctx, int* schedule_out);
 /* measurement aid (SURVEY 8(d) "device-copy ceiling"): `reps` streaming copies of `bytes` (<= one cost volume; 0 = a
  * whole one) between two of the context's volumes, timed with HIP events; *gb_per_s counts bytes read + bytes written.

@@ -19,6 +19,7 @@ VO_NUM_MONO_ASYNC = 5
 VO_NUM_POSE_ASYNC = 8
 VO_NUM_MAPS = 4
 SCHED_DIAG, SCHED_DIAG_RAGGED, SCHED_UNFUSED = 1, 2, 3
+SCHED_VERT, SCHED_VERT_RAGGED = 4, 5             # mode 2 (MODE_SGBM_3WAY): the vertical sweep in the diagonal sweep's place
 T_STAGES = ("upload", "sgbm_cost", "sgbm_agg", "sgbm_wta", "sgbm_post", "orb", "match", "pose", "knn")
 
 # every symbol include/vo355.h declares (checked by tests/test_abi.py)

@@ -23,6 +23,8 @@
 //   k_sgbm_diag    (sgbm_diag.inc) NW / N / NE computed together in skewed columns, added to the W + E volume,
 //                  winner-take-all on the total: leaves a 2-word record per pixel.  MODE_HH: a reverse pass
 //                  first adds SW / S / SE to the volume.  No direction of these three is ever stored
+//   k_sgbm_vert    (sgbm_vert.inc) MODE_SGBM_3WAY in the diagonal sweep's place: N alone, in independent columns, added to the
+//                  W + E volume, the same winner-take-all records; no hand-off between workgroups, nothing that can wait
 //   k_sgbm_fin     records -> sub-pixel disp1 + disp2 candidates via atomicMin on (cost, scan order) keys
 //   k_sgbm_paths + k_sgbm_wta   uniquenessRatio >= 100 only (no threshold form of the uniqueness test): one
 //                  stored volume per direction, per pixel (16 lanes) S = sat-sum of all of them, winner logic inline
@@ -1232,6 +1234,7 @@ __global__ void __launch_bounds__(256) k_sgbm_wta(const int16_t* __restrict__ Lb
 }
 
 #include "sgbm_diag.inc"
+#include "sgbm_vert.inc"
 
 // left-right check of one pixel on the WTA results: disp1 or INVALID
 __device__ __forceinline__ int lr_value(const int16_t* __restrict__ disp1, const int* __restrict__ d2key, const SgbmGeom& g, int x, int y)
@@ -1605,15 +1608,16 @@ __global__ void k_ccl_apply(PostJobs jobs, int n, int newVal, int maxSize)
 static PathPlan make_plan(const SgbmGeom& g, int mode)
 {
     // steps = negated predecessor offsets.  MODE_SGBM predecessors: (x-1,y) (x+1,y) (x-1,y-1) (x,y-1)
-    // (x+1,y-1); MODE_HH adds (x-1,y+1) (x,y+1) (x+1,y+1).  Longest lines first.
+    // (x+1,y-1); MODE_HH adds (x-1,y+1) (x,y+1) (x+1,y+1).  Longest lines first.  MODE_SGBM_3WAY: (x-1,y) (x+1,y) (x,y-1).
     static const int sx5[] = { 1, -1, 1, -1, 0 }, sy5[] = { 0, 0, 1, 1, 1 };
     static const int sx8[] = { 1, -1, 1, -1, 1, -1, 0, 0 }, sy8[] = { 0, 0, 1, 1, -1, -1, -1, 1 };
+    static const int sx3[] = { 1, -1, 0 }, sy3[] = { 0, 0, 1 };
     PathPlan p;
-    p.n_dirs = mode == 1 ? 8 : 5;
+    p.n_dirs = mode == 1 ? 8 : (mode == 2 ? 3 : 5);
     p.first_wave[0] = 0;
     for (int k = 0; k < p.n_dirs; k++) {
-        p.sx[k] = mode == 1 ? sx8[k] : sx5[k];
-        p.sy[k] = mode == 1 ? sy8[k] : sy5[k];
+        p.sx[k] = mode == 1 ? sx8[k] : (mode == 2 ? sx3[k] : sx5[k]);
+        p.sy[k] = mode == 1 ? sy8[k] : (mode == 2 ? sy3[k] : sy5[k]);
         p.nlines[k] = p.sy[k] == 0 ? g.H : (p.sx[k] == 0 ? g.W1 : g.W1 + g.H - 1);
         p.first_wave[k + 1] = p.first_wave[k] + div_up(p.nlines[k], 4);
     }
@@ -1770,6 +1774,28 @@ static int launch_diag(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1, int16
     return pad ? launch_diag_k<NP, true, 7, REV, WTA>(ctx, g, in1, sout, ctl) : launch_diag_k<NP, false, 7, REV, WTA>(ctx, g, in1, sout, ctl);
 }
 
+// ---- vertical sweep (sgbm_vert.inc) ------------------------------------------------------------------------------------
+// MODE_SGBM_3WAY: N + the W + E volume -> winner-take-all records, one wave per four columns.  The table carries one job; the
+// kernel takes the job from blockIdx.y, so a launch for several pairs needs no other kernel.  Nothing of the diagonal sweep's
+// hand-off is touched: no boundary granules, no tag, no control word.
+template <int NP>
+static int launch_vert(vo_ctx* ctx, const SgbmGeom& g, const int16_t* in1)
+{
+    DiagJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    jobs.n = 1;
+    DiagJob& j = jobs.j[0];
+    j.C = ctx->ws->C; j.in1 = in1; j.aux0 = ctx->ws->rec; j.aux1 = ctx->ws->rec + (size_t)ctx->max_w * ctx->max_h + 64;
+    j.vol_bytes = (uint32_t)((size_t)g.W1 * g.H * g.Dp * 2);            // one volume (no cell is read outside the image)
+    j.rec_bytes = (uint32_t)(((size_t)ctx->max_w * ctx->max_h + 64) * 4);
+    const dim3 grid(div_up(g.W1, 4), jobs.n);
+    const size_t lds = (size_t)4 * 2 * g.Dp * 2;                        // two rows of S per column
+    if (g.D != g.Dp) hipLaunchKernelGGL((k_sgbm_vert<NP, true>), grid, dim3(64), lds, ctx->stream, jobs, g);
+    else hipLaunchKernelGGL((k_sgbm_vert<NP, false>), grid, dim3(64), lds, ctx->stream, jobs, g);
+    VO_CHECK_LAUNCH(ctx);
+    return VO_OK;
+}
+
 // rows cut at their middle (k_sgbm_we2): the W + E geometry that a sweep group carries for all its members in one launch
 static bool we2_geometry(const vo_ctx* ctx, const SgbmGeom& g) { return g.W1 % 16 == 0 && g.W1 >= 32 && !(ctx->tune_diag_dbg & 8); }
 
@@ -1798,6 +1824,7 @@ static bool run_defers_front(const vo_ctx* ctx, const SgbmGeom& g, bool hh)
 //     2. MODE_HH: a reverse diagonal sweep adds SW / S / SE to that volume
 //     3. the forward diagonal sweep: NW / N / NE + the volume -> winner-take-all records; k_sgbm_fin turns them into
 //        disp1 + the disp2 candidates
+//        MODE_SGBM_3WAY (three directions in the plan): the vertical sweep (k_sgbm_vert: N + the volume) in its place
 //     volume passes over HBM: C written 1, W+E 3.25, (MODE_HH reverse 3,) forward 2 = 6.25 / 9.25
 //   uniquenessRatio >= 100 (the threshold form of the uniqueness test does not exist): every direction stored by
 //     k_sgbm_paths, per-pixel winner search over all of them (k_sgbm_wta)
@@ -1807,6 +1834,7 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
 {
     const bool pad = g.D != g.Dp;
     const bool hh = plan.n_dirs == 8;
+    const bool vert = plan.n_dirs == 3;          // MODE_SGBM_3WAY: never a member of a sweep group (sgbm_run asks for mode 0)
     int rc;
     if (g.ur < 100) {
         if ((rc = ensure_S(ctx, 3))) return rc;
@@ -1857,10 +1885,14 @@ static int launch_agg(vo_ctx* ctx, const SgbmGeom& g, const PathPlan& plan, size
         }
         {
             StageTimer t(ctx, VO_T_SGBM_WTA, ctx->grp && ctx->grp->want_defer ? 0 : 1);     // (a deferred sweep is timed where its group is launched)
-            if (!(ctx->tune_diag_dbg & 16) && (rc = launch_diag<NP, false, true>(ctx, g, hh ? Srev : Swe, nullptr, hh ? ctlB : ctlA))) return rc;
+            if (ctx->tune_diag_dbg & 16) {
+            } else if (vert) {
+                if ((rc = launch_vert<NP>(ctx, g, Swe))) return rc;
+            } else if ((rc = launch_diag<NP, false, true>(ctx, g, hh ? Srev : Swe, nullptr, hh ? ctlB : ctlA))) return rc;
         }
-        ctx->last_paths = 3;
-        ctx->last_schedule = (g.W1 % 8 == 0 && g.W1 >= 16) ? VO_SCHED_DIAG : VO_SCHED_DIAG_RAGGED;
+        const bool even = g.W1 % 8 == 0 && g.W1 >= 16;
+        ctx->last_paths = vert ? 1 : 3;
+        ctx->last_schedule = vert ? (even ? VO_SCHED_VERT : VO_SCHED_VERT_RAGGED) : (even ? VO_SCHED_DIAG : VO_SCHED_DIAG_RAGGED);
         return VO_OK;
     }
     if ((rc = ensure_S(ctx, plan.n_dirs))) return rc;

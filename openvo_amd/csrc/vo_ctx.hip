@@ -438,7 +438,7 @@ extern "C" int vo_set_sgbm(vo_ctx* ctx, int minDisparity, int numDisparities, in
     if (!ctx) return VO_E_ARG;
     if (numDisparities <= 0 || numDisparities % 16) return vo_fail(ctx, VO_E_ARG, "numDisparities must be a positive multiple of 16");
     if (numDisparities > ctx->max_disp) return vo_fail(ctx, VO_E_CAP, "numDisparities %d > max_disp %d", numDisparities, ctx->max_disp);
-    if (mode != 0 && mode != 1) return vo_fail(ctx, VO_E_ARG, "mode must be 0 (MODE_SGBM) or 1 (MODE_HH)");
+    if (mode != 0 && mode != 1 && mode != 2) return vo_fail(ctx, VO_E_ARG, "mode must be 0 (MODE_SGBM), 1 (MODE_HH) or 2 (MODE_SGBM_3WAY)");
     if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;     // its members finish under the parameters they began with
     // effective parameters exactly as computeDisparitySGBM derives them
     SgbmEff& e = ctx->sg;

@@ -9,7 +9,8 @@ Every name below is one call site of the reference (paths relative to /root/refe
 
   stereo_camera.py:17-18   stereoRectify            -> calib.stereo_rectify (host, numpy)
   stereo_camera.py:19-22   initUndistortRectifyMap  -> calib.init_undistort_rectify_map (CV_16SC2 maps)
-  stereo_camera.py:23-27   StereoSGBM_create        -> vo_set_sgbm + vo_sgbm_compute_host
+  stereo_camera.py:23-27   StereoSGBM_create        -> vo_set_sgbm + vo_sgbm_compute_host (mode=: 0, 1 or 2, the STEREO_SGBM_MODE_*
+                           constants below; the reference's "# TODO: mode option")
   stereo_camera.py:30,33   remap                    -> vo_set_rectify_maps + vo_remap
   stereo_camera.py:45,47   cvtColor(COLOR_BGR2GRAY) -> vo_cvt_bgr2gray
   stereo_camera.py:52      reprojectImageTo3D       -> vo_reproject_to_3d
@@ -38,6 +39,11 @@ INTER_LINEAR = 1
 COLOR_BGR2GRAY = 6
 NORM_HAMMING = 6
 FONT_HERSHEY_SIMPLEX = 0
+# the reference's "# TODO: mode option" (stereo_camera.py:26): the values StereoSGBM_create(mode=) takes, under both spellings
+# cv2 carries.  MODE_HH4 (3) is not implemented and has no name here: vo_set_sgbm refuses it.
+STEREO_SGBM_MODE_SGBM = StereoSGBM_MODE_SGBM = 0
+STEREO_SGBM_MODE_HH = StereoSGBM_MODE_HH = 1
+STEREO_SGBM_MODE_SGBM_3WAY = StereoSGBM_MODE_SGBM_3WAY = 2      # W, E, N over the whole image as one stripe (include/vo355.h)
 __version__ = "vo355-compat (OpenCV 4.x semantics)"
 
 _state = {"ctx": None, "geom": (0, 0, 0, 0), "device": 0}

@@ -458,7 +458,8 @@ class BFMatcher:
 
 
 class StereoSGBM:
-    """cv2.StereoSGBM_create(...) stand-in: compute(left, right) -> int16 disparity x16."""
+    """cv2.StereoSGBM_create(...) stand-in: compute(left, right) -> int16 disparity x16.  The mode -- 0 MODE_SGBM, 1 MODE_HH,
+    2 MODE_SGBM_3WAY (include/vo355.h) -- is params["mode"] where the dict has one, else the argument."""
 
     def __init__(self, ctx, params, mode=0):
         self._ctx, self.params, self.mode = ctx, dict(params), int(params.get("mode", mode))

@@ -119,6 +119,9 @@ class StereoCamera:
 
     SGBM_KEYS = ("minDisparity", "numDisparities", "blockSize", "P1", "P2", "disp12MaxDiff", "preFilterCap",
                  "uniquenessRatio", "speckleWindowSize", "speckleRange")
+    # "mode" (0 MODE_SGBM, 1 MODE_HH, 2 MODE_SGBM_3WAY; the reference's "# TODO: mode option") travels in the same dict when it is
+    # there -- through from_pfiles, from_files and save_files alike --; a dict or file without one means mode 0
+    SGBM_OPTIONAL_KEYS = ("mode",)
 
     @classmethod
     def from_files(cls, left_cam_file, right_cam_file, rect_file, sgbm_file, img_size, **kw):
@@ -132,7 +135,7 @@ class StereoCamera:
             missing = [k for k in keys if k not in d]
             if missing:
                 raise KeyError("%s file lacks %s" % (name, missing))
-        sgbm = {k: int(np.asarray(sgbm[k]).reshape(-1)[0]) for k in cls.SGBM_KEYS}
+        sgbm = {k: int(np.asarray(sgbm[k]).reshape(-1)[0]) for k in cls.SGBM_KEYS + tuple(k for k in cls.SGBM_OPTIONAL_KEYS if k in sgbm)}
         return cls(np.asarray(cam_l["K"], np.float64), np.asarray(cam_l["dist"], np.float64),
                    np.asarray(cam_r["K"], np.float64), np.asarray(cam_r["dist"], np.float64),
                    {"R": _rotation_3x3(rect["R"]), "T": np.asarray(rect["T"], np.float64)}, sgbm, img_size, **kw)
@@ -144,7 +147,7 @@ class StereoCamera:
         _save_plain(left_cam_file, {"K": K_left, "dist": dist_left})
         _save_plain(right_cam_file, {"K": K_right, "dist": dist_right})
         _save_plain(rect_file, {"R": rect_params["R"], "T": rect_params["T"]})
-        _save_plain(sgbm_file, {k: int(sgbm_params[k]) for k in StereoCamera.SGBM_KEYS})
+        _save_plain(sgbm_file, {k: int(sgbm_params[k]) for k in StereoCamera.SGBM_KEYS + tuple(k for k in StereoCamera.SGBM_OPTIONAL_KEYS if k in sgbm_params)})
 
     def __init__(self, K_left, dist_left, K_right, dist_right, rect_params, sgbm_params, img_size,
                  device=0, max_keypoints=2000, context=None, engines=None, lookahead=None):
