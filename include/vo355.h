@@ -17,6 +17,7 @@
  */
 #ifndef VO355_H
 #define VO355_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -75,6 +76,35 @@ int vo_set_rectify_maps(vo_ctx* ctx, int cam /*0=L,1=R*/, const int16_t* map1 /*
 int vo_set_sgbm(vo_ctx* ctx, int minDisparity, int numDisparities, int blockSize, int P1, int P2,
                 int disp12MaxDiff, int preFilterCap, int uniquenessRatio, int speckleWindowSize,
                 int speckleRange, int mode);
+/* The matching cost in front of the aggregation.  BT (Birchfield-Tomasi + SAD, OpenCV's) is what a fresh context has and the only
+ * cost for which parity with OpenCV is claimed.  CENSUS is an extra with no OpenCV counterpart and no oracle; its yardstick is the
+ * definition in tests/sgbm_census_def.py, which the device equals bit for bit:
+ *   signature   of pixel (x, y) for a window census_w x census_h (3, 5, 7 or 9 wide, 3, 5 or 7 high: at most 62 comparisons): the
+ *               set of offsets (dx, dy) != (0, 0), |dx| <= census_w / 2, |dy| <= census_h / 2, whose pixel is strictly darker,
+ *               I(x + dx, y + dy) < I(x, y).  Coordinates outside the image are clamped (rows and columns replicated).  The order
+ *               of the bits is unspecified: only the number of comparisons in which two signatures differ is observable.
+ *   pixel cost  the Hamming distance of sig_L(x, y) and sig_R(x - d, y), at the left columns of the computed band
+ *               [max(minD + D, 0), w + min(minD, 0)), where x - d never leaves the image
+ *   block cost  C = P2 + the blockSize x blockSize box sum of the pixel cost, its indices clamped to the band and to the image rows
+ *               exactly as with BT; blockSize 1 is the bare Hamming cost.  preFilterCap means nothing to this cost.
+ * Everything behind C -- the paths of modes 0, 1 and 2, the winner stage, both post filters -- is unchanged.  A signature depends
+ * only on the ORDER of the grey levels in its window, so any strictly increasing change of either image's intensities leaves the
+ * disparity image bit-identical.  P1 / P2 want rescaling to the Hamming range (some 2 / 8 x blockSize^2 in place of 8 / 32).
+ * The setting lives beside vo_set_sgbm's parameters and persists across vo_set_sgbm.  VO_E_ARG, the setting in force staying in
+ * force: a cost other than 0 or 1; with cost 1 a window outside {3,5,7,9} x {3,5,7}.  With cost 0 the window arguments are
+ * ignored.  A call that changes nothing does nothing; one that changes something first closes the open sweep group (pairs already
+ * enqueued finish under the cost they began with).  A census pair runs on the look-ahead engines like a mode 2 pair, its chain on
+ * its engine's stream: it joins no sweep group.  No overflow refusal is needed beyond vo_set_sgbm's: the largest census block cost
+ * is 121 x 62 = 7502, below the smallest BT bound vo_set_sgbm already admits (at the smallest preFilterCap a BT pixel cost reaches 2 x 15 + 63 = 93 where a census one reaches 62). */
+#define VO_SGBM_COST_BT      0   /* Birchfield-Tomasi + SAD, OpenCV's: the default */
+#define VO_SGBM_COST_CENSUS  1
+int vo_set_sgbm_cost(vo_ctx* ctx, int cost, int census_w, int census_h);
+int vo_get_sgbm_cost(const vo_ctx* ctx, int* cost, int* census_w, int* census_h);   /* all three pointers are required */
+/* C (block cost + P2, either cost) of the latest synchronous SGBM run (vo_sgbm_compute, vo_sgbm_compute_host, ...) in the main
+ * workspace, as [H][W1][D] without the padding of d to a multiple of 32; W1 is the width of the computed band.  cells must equal
+ * H * W1 * D (VO_E_ARG otherwise); VO_E_STATE when there is none (no run yet, an empty band, or a look-ahead pair has used the
+ * workspace since).  A seam for tests: it pins the cost stage directly instead of through the winner stage. */
+int vo_sgbm_cost_volume(vo_ctx* ctx, int16_t* out, size_t cells);
 /* Q of cv2.stereoRectify [stereo_camera.py:17-18], row-major 4x4 */
 int vo_set_Q(vo_ctx* ctx, const double* Q16);
 /* slice bounds used by crop_to_valid_region_left [stereo_camera.py:35-37]:

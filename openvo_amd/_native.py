@@ -20,6 +20,7 @@ VO_NUM_POSE_ASYNC = 8
 VO_NUM_MAPS = 4
 SCHED_DIAG, SCHED_DIAG_RAGGED, SCHED_UNFUSED = 1, 2, 3
 SCHED_VERT, SCHED_VERT_RAGGED = 4, 5             # mode 2 (MODE_SGBM_3WAY): the vertical sweep in the diagonal sweep's place
+COST_BT, COST_CENSUS = 0, 1                      # vo_set_sgbm_cost: the matching cost in front of the aggregation
 T_STAGES = ("upload", "sgbm_cost", "sgbm_agg", "sgbm_wta", "sgbm_post", "orb", "match", "pose", "knn")
 
 # every symbol include/vo355.h declares (checked by tests/test_abi.py)
@@ -51,6 +52,7 @@ SYMBOLS = [
     "vo_track_map",
     "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
     "vo_klt_track_host", "vo_klt_track", "vo_klt_pnp_pair", "vo_klt_pnp_pair_begin", "vo_klt_pnp_pair_end",
+    "vo_set_sgbm_cost", "vo_get_sgbm_cost", "vo_sgbm_cost_volume",
 ]
 
 
@@ -301,6 +303,10 @@ def lib():
             for name, proto in (("vo_klt_pnp_pair", front + [vp] * 9 + [ci]), ("vo_klt_pnp_pair_begin", front + [ci, vp]),
                                 ("vo_klt_pnp_pair_end", [vp, ci] + [vp] * 9 + [ci])):
                 getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_set_sgbm_cost"):          # (likewise: an older build has the BT cost alone)
+            for name, proto in (("vo_set_sgbm_cost", [vp, ci, ci, ci]), ("vo_get_sgbm_cost", [vp, vp, vp, vp]),
+                                ("vo_sgbm_cost_volume", [vp, vp, ctypes.c_size_t])):
+                getattr(L, name).argtypes = proto
         plant = getattr(L, "vo_test_plant_dense_pair", None)     # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp]
@@ -488,10 +494,46 @@ class Context:
         h, w = map2.shape
         self._ck(self._lib.vo_set_rectify_maps(self._h, cam, _p(map1), _p(map2), w, h))
 
+    _sgbm_band = (0, 0)
+
     def set_sgbm(self, p, mode=0):
-        self._ck(self._lib.vo_set_sgbm(self._h, *[int(p[k]) for k in (
-            "minDisparity", "numDisparities", "blockSize", "P1", "P2", "disp12MaxDiff", "preFilterCap",
-            "uniquenessRatio", "speckleWindowSize", "speckleRange")], int(p.get("mode", mode))))
+        """The ten StereoSGBM parameters, the mode (p["mode"] where there is one) and the matching cost: p["cost"] (COST_BT where
+        there is none: the dict is the whole truth at this level), p["censusWidth"] (9), p["censusHeight"] (7).  A refusal of
+        either part leaves both as they were."""
+        has_cost = hasattr(self._lib, "vo_set_sgbm_cost")            # (an older build loaded for an A/B run has the BT cost alone)
+        if not has_cost and int(p.get("cost", COST_BT)) != COST_BT:
+            raise VoError(-1, "this build of libvo355 has no vo_set_sgbm_cost: only the BT cost")
+        before = self.sgbm_cost() if has_cost else None
+        if has_cost:
+            self.set_sgbm_cost(int(p.get("cost", COST_BT)), (int(p.get("censusWidth", 9)), int(p.get("censusHeight", 7))))
+        try:
+            self._ck(self._lib.vo_set_sgbm(self._h, *[int(p[k]) for k in (
+                "minDisparity", "numDisparities", "blockSize", "P1", "P2", "disp12MaxDiff", "preFilterCap",
+                "uniquenessRatio", "speckleWindowSize", "speckleRange")], int(p.get("mode", mode))))
+        except VoError:
+            if has_cost:
+                self.set_sgbm_cost(*before)
+            raise
+        self._sgbm_band = (int(p["minDisparity"]), int(p["numDisparities"]))
+
+    def set_sgbm_cost(self, cost, window=(9, 7)):
+        """The matching cost of the SGBM front: COST_BT (OpenCV's, the default) or COST_CENSUS with a window (width, height) out of
+        {3, 5, 7, 9} x {3, 5, 7}.  Persists across the native vo_set_sgbm; Context.set_sgbm applies its dict's keys on every call."""
+        self._ck(self._lib.vo_set_sgbm_cost(self._h, int(cost), int(window[0]), int(window[1])))
+
+    def sgbm_cost(self):
+        """-> (cost, (width, height)) in force"""
+        c, w, h = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        self._ck(self._lib.vo_get_sgbm_cost(self._h, ctypes.byref(c), ctypes.byref(w), ctypes.byref(h)))
+        return c.value, (w.value, h.value)
+
+    def sgbm_cost_volume(self, w, h):
+        """C (block cost + P2) of the latest synchronous SGBM run on a w x h pair as int16 [h][W1][D], W1 the computed band's width"""
+        minD, D = self._sgbm_band
+        W1 = int(w) + min(minD, 0) - max(minD + D, 0)
+        out = np.empty((int(h), max(W1, 0), D), np.int16)
+        self._ck(self._lib.vo_sgbm_cost_volume(self._h, _p(out), out.size))
+        return out
 
     def set_Q(self, Q):
         Q = _c(Q, np.float64)

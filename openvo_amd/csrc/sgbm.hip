@@ -25,6 +25,7 @@
 //                  first adds SW / S / SE to the volume.  No direction of these three is ever stored
 //   k_sgbm_vert    (sgbm_vert.inc) MODE_SGBM_3WAY in the diagonal sweep's place: N alone, in independent columns, added to the
 //                  W + E volume, the same winner-take-all records; no hand-off between workgroups, nothing that can wait
+//   k_census + k_census_cost   (sgbm_census.inc) the census cost in the place of the two kernels above (vo_set_sgbm_cost): the same C
 //   k_sgbm_fin     records -> sub-pixel disp1 + disp2 candidates via atomicMin on (cost, scan order) keys
 //   k_sgbm_paths + k_sgbm_wta   uniquenessRatio >= 100 only (no threshold form of the uniqueness test): one
 //                  stored volume per direction, per pixel (16 lanes) S = sat-sum of all of them, winner logic inline
@@ -1925,9 +1926,13 @@ static int sgbm_post_launch(vo_ctx* ctx, const PostJobs& jobs, int n, const Sgbm
 static uint32_t pk_rep_host(int v) { return (uint32_t)(v & 0xFFFF) * 0x00010001u; }
 static int post_rows_per_block(int w) { return std::min(6, (int)(150 * 1024 / ((size_t)w * 6)) - 2); }
 
+#include "sgbm_census.inc"
+
 // planes and cost volume of n pairs of one geometry on the current stream: one launch each
+// (the census cost: its two kernels in their place -- a single pair always: a census pair joins no sweep group, see sgbm_run)
 static int front_launch(vo_ctx* ctx, const FrontJobs& jobs, int n, const SgbmGeom& g)
 {
+    if (ctx->sg_cost.cost == VO_SGBM_COST_CENSUS) return census_front_launch(ctx, jobs, n, g);
     const int w = g.W, h = g.H;
     hipLaunchKernelGGL(k_sgbm_planes, dim3(div_up(w, 256), std::min(h, 128), n), dim3(256), 0, ctx->stream, jobs, w, h, g.ftzero,
                        ctx->sw_ctl_words, g.Dp / 2, pk_rep_host(g.P2));
@@ -2037,7 +2042,7 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
     if (++ctx->sweep_gen_next <= 0) ctx->sweep_gen_next = 1;     // this run's generation: never 0 (FrameSlot::sweep_word)
     f.disp_gen = ctx->sweep_gen_next;
     const bool defer = deferred && ctx->cur_engine >= 0 && sweep_group_size(ctx) > 1 && ctx->sg.set && ctx->sg.ur < 100 && ctx->sg.mode == 0 &&
-                       ctx->ws_alt[ctx->cur_engine].mid != nullptr;
+                       ctx->sg_cost.cost == VO_SGBM_COST_BT && ctx->ws_alt[ctx->cur_engine].mid != nullptr;
     if (defer) {
         if (!ctx->grp) ctx->grp = new SweepGroup();
         ctx->grp->want_defer = true;
@@ -2080,8 +2085,8 @@ int sgbm_run(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t* srcL, const
 hipStream_t dense_stream(const vo_ctx* ctx, int engine)
 {
     // (a run that cannot defer whatever its geometry -- MODE_HH, the unfused schedule -- keeps to its engine's stream: a stream
-    //  of such pairs would otherwise travel on ONE lane, one pair after the other)
-    if (!lane_mode(ctx) || !ctx->sg.set || ctx->sg.ur >= 100 || ctx->sg.mode != 0) return ctx->la_stream[engine];
+    //  of such pairs would otherwise travel on ONE lane, one pair after the other; a census pair likewise: group fronts are BT fronts)
+    if (!lane_mode(ctx) || !ctx->sg.set || ctx->sg.ur >= 100 || ctx->sg.mode != 0 || ctx->sg_cost.cost != VO_SGBM_COST_BT) return ctx->la_stream[engine];
     const SweepGroup* const G = ctx->grp;
     return G && G->n > 0 && G->lane ? G->lane : ctx->lane[ctx->lane_next];
 }
@@ -2304,6 +2309,7 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
             VO_HIP(ctx, hipMemcpyAsync(f.left, srcL, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
             VO_HIP(ctx, hipMemcpyAsync(f.right, srcR, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
         }
+        if (ctx->ws == &ctx->main_ws) ctx->c_last.valid = false;
         std::vector<int16_t> inv((size_t)n, (int16_t)g.invalid16);  // every pixel invalid
         VO_HIP(ctx, hipMemcpyAsync(d_disp, inv.data(), (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
         VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2319,6 +2325,8 @@ static int sgbm_run_impl(vo_ctx* ctx, FrameSlot& f, int w, int h, const uint8_t*
         return vo_fail(ctx, VO_E_CAP, "cost volume of %zu bytes exceeds the 4 GiB a volume kernel addresses", ((size_t)g.W1 * h + 1) * g.Dp * 2);
     const PathPlan plan = make_plan(g, e.mode);
     ctx->last_cells = (int64_t)g.W1 * h * g.D;
+    // what vo_sgbm_cost_volume may hand out: C of a synchronous run in the main workspace (nothing behind the front writes C)
+    if (ctx->ws == &ctx->main_ws) { ctx->c_last.valid = ctx->cur_engine < 0; ctx->c_last.H = h; ctx->c_last.W1 = g.W1; ctx->c_last.D = g.D; ctx->c_last.Dp = g.Dp; }
     {
         FrontJobs fj;
         memset(&fj, 0, sizeof(fj));

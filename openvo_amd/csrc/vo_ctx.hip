@@ -466,6 +466,46 @@ extern "C" int vo_set_sgbm(vo_ctx* ctx, int minDisparity, int numDisparities, in
     return VO_OK;
 }
 
+// The matching cost of the SGBM front (include/vo355.h).  Lives beside SgbmEff and outlives vo_set_sgbm.
+extern "C" int vo_set_sgbm_cost(vo_ctx* ctx, int cost, int census_w, int census_h)
+{
+    if (!ctx) return VO_E_ARG;
+    if (cost != VO_SGBM_COST_BT && cost != VO_SGBM_COST_CENSUS) return vo_fail(ctx, VO_E_ARG, "cost must be 0 (VO_SGBM_COST_BT) or 1 (VO_SGBM_COST_CENSUS)");
+    if (cost == VO_SGBM_COST_CENSUS) {
+        const bool w_ok = census_w == 3 || census_w == 5 || census_w == 7 || census_w == 9;
+        const bool h_ok = census_h == 3 || census_h == 5 || census_h == 7;
+        if (!w_ok || !h_ok) return vo_fail(ctx, VO_E_ARG, "census window %d x %d: the width must be 3, 5, 7 or 9 and the height 3, 5 or 7", census_w, census_h);
+    } else {
+        census_w = ctx->sg_cost.cw; census_h = ctx->sg_cost.ch;      // (ignored with BT: the window on record stays)
+    }
+    if (cost == ctx->sg_cost.cost && census_w == ctx->sg_cost.cw && census_h == ctx->sg_cost.ch) return VO_OK;
+    if (int rc = sweep_group_close(ctx, VO_GRP_OTHER)) return rc;     // its members finish under the cost they began with
+    ctx->sg_cost.cost = cost; ctx->sg_cost.cw = census_w; ctx->sg_cost.ch = census_h;
+    return VO_OK;
+}
+
+extern "C" int vo_get_sgbm_cost(const vo_ctx* ctx, int* cost, int* census_w, int* census_h)
+{
+    if (!ctx || !cost || !census_w || !census_h) return VO_E_ARG;
+    *cost = ctx->sg_cost.cost;
+    *census_w = ctx->sg_cost.cw;
+    *census_h = ctx->sg_cost.ch;
+    return VO_OK;
+}
+
+// C of the latest synchronous run in the main workspace as [H][W1][D]: the padding to Dp stays behind
+extern "C" int vo_sgbm_cost_volume(vo_ctx* ctx, int16_t* out, size_t cells)
+{
+    if (!ctx || !out) return vo_fail(ctx, VO_E_ARG, "vo_sgbm_cost_volume: bad argument");
+    if (!ctx->c_last.valid || !ctx->main_ws.C) return vo_fail(ctx, VO_E_STATE, "vo_sgbm_cost_volume: no synchronous run has left a cost volume in the main workspace");
+    const size_t rows = (size_t)ctx->c_last.H * ctx->c_last.W1;
+    if (cells != rows * ctx->c_last.D) return vo_fail(ctx, VO_E_ARG, "vo_sgbm_cost_volume: %zu cells asked for, the volume has %zu", cells, rows * ctx->c_last.D);
+    VO_HIP(ctx, hipSetDevice(ctx->device));
+    VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VO_HIP(ctx, hipMemcpy2D(out, (size_t)ctx->c_last.D * 2, ctx->main_ws.C, (size_t)ctx->c_last.Dp * 2, (size_t)ctx->c_last.D * 2, rows, hipMemcpyDeviceToHost));
+    return VO_OK;
+}
+
 // Q or the ROI changes: a sparse chain begun ahead ran with the old one.  Its result is no longer what vo_sparse_stereo would
 // compute: the next call on such a slot recomputes (the chain itself finishes; the slot's `ready` still orders its consumers).
 static void sparse_void_ahead(vo_ctx* ctx)
@@ -1399,6 +1439,7 @@ extern "C" int vo_measure_copy(vo_ctx* ctx, int64_t bytes, int reps, int nontemp
     if (bytes <= 0 || !ctx->ws->C || !ctx->ws->S) return vo_fail(ctx, VO_E_STATE, "vo_measure_copy: no volumes to copy between");
     VO_HIP(ctx, hipSetDevice(ctx->device));
     // the volumes belong to the main workspace (engine 0 uses it too): nothing of the pipeline may still be running
+    ctx->c_last.valid = false;                              // (the copy lands in the cost volume)
     VO_HIP(ctx, engine_streams_sync(ctx));
     VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     hipEvent_t e0, e1;

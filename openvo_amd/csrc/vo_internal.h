@@ -258,6 +258,8 @@ struct vo_ctx {
     char devname[256] = {0};
 
     SgbmEff sg{};
+    struct { int cost = 0, cw = 9, ch = 7; } sg_cost;       // vo_set_sgbm_cost: VO_SGBM_COST_*, the census window; outlives vo_set_sgbm
+    struct { bool valid = false; int H = 0, W1 = 0, D = 0, Dp = 0; } c_last;   // C of the latest synchronous run in the main workspace (vo_sgbm_cost_volume)
     double Q[16];
     bool has_Q = false;
     int roi[4] = {0, 0, 0, 0};

@@ -10,7 +10,8 @@ Every name below is one call site of the reference (paths relative to /root/refe
   stereo_camera.py:17-18   stereoRectify            -> calib.stereo_rectify (host, numpy)
   stereo_camera.py:19-22   initUndistortRectifyMap  -> calib.init_undistort_rectify_map (CV_16SC2 maps)
   stereo_camera.py:23-27   StereoSGBM_create        -> vo_set_sgbm + vo_sgbm_compute_host (mode=: 0, 1 or 2, the STEREO_SGBM_MODE_*
-                           constants below; the reference's "# TODO: mode option")
+                           constants below; the reference's "# TODO: mode option"; cost=, censusWidth=, censusHeight=: an
+                           extension, the STEREO_SGBM_COST_* constants -> vo_set_sgbm_cost)
   stereo_camera.py:30,33   remap                    -> vo_set_rectify_maps + vo_remap
   stereo_camera.py:45,47   cvtColor(COLOR_BGR2GRAY) -> vo_cvt_bgr2gray
   stereo_camera.py:52      reprojectImageTo3D       -> vo_reproject_to_3d
@@ -44,6 +45,10 @@ FONT_HERSHEY_SIMPLEX = 0
 STEREO_SGBM_MODE_SGBM = StereoSGBM_MODE_SGBM = 0
 STEREO_SGBM_MODE_HH = StereoSGBM_MODE_HH = 1
 STEREO_SGBM_MODE_SGBM_3WAY = StereoSGBM_MODE_SGBM_3WAY = 2      # W, E, N over the whole image as one stripe (include/vo355.h)
+# an extension (cv2 has none): the matching cost StereoSGBM_create(cost=) takes; census with censusWidth x censusHeight out of
+# {3, 5, 7, 9} x {3, 5, 7} (include/vo355.h: vo_set_sgbm_cost; the yardstick is tests/sgbm_census_def.py, not OpenCV)
+STEREO_SGBM_COST_BT = 0
+STEREO_SGBM_COST_CENSUS = 1
 __version__ = "vo355-compat (OpenCV 4.x semantics)"
 
 _state = {"ctx": None, "geom": (0, 0, 0, 0), "device": 0}
@@ -92,10 +97,12 @@ class _StereoSGBM:
 
 
 def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0, preFilterCap=0,
-                      uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=0):
+                      uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=0, cost=0, censusWidth=9, censusHeight=7):
+    """cost / censusWidth / censusHeight are extensions (cv2 has none): STEREO_SGBM_COST_BT is OpenCV's cost and the default"""
     return _StereoSGBM(dict(minDisparity=minDisparity, numDisparities=numDisparities, blockSize=blockSize, P1=P1, P2=P2,
                             disp12MaxDiff=disp12MaxDiff, preFilterCap=preFilterCap, uniquenessRatio=uniquenessRatio,
-                            speckleWindowSize=speckleWindowSize, speckleRange=speckleRange), mode)
+                            speckleWindowSize=speckleWindowSize, speckleRange=speckleRange, cost=int(cost),
+                            censusWidth=int(censusWidth), censusHeight=int(censusHeight)), mode)
 
 
 def remap(src, map1, map2, interpolation, *args, **kw):

@@ -459,10 +459,14 @@ class BFMatcher:
 
 class StereoSGBM:
     """cv2.StereoSGBM_create(...) stand-in: compute(left, right) -> int16 disparity x16.  The mode -- 0 MODE_SGBM, 1 MODE_HH,
-    2 MODE_SGBM_3WAY (include/vo355.h) -- is params["mode"] where the dict has one, else the argument."""
+    2 MODE_SGBM_3WAY (include/vo355.h) -- is params["mode"] where the dict has one, else the argument.  The matching cost travels in
+    the dict alone: params["cost"] (0 BT, OpenCV's, where there is none; 1 census: an extension, cv2 has none) with
+    params["censusWidth"] / ["censusHeight"] (9 x 7); read back as .cost and .census_window."""
 
     def __init__(self, ctx, params, mode=0):
         self._ctx, self.params, self.mode = ctx, dict(params), int(params.get("mode", mode))
+        self.cost = int(params.get("cost", 0))
+        self.census_window = (int(params.get("censusWidth", 9)), int(params.get("censusHeight", 7)))
         ctx.set_sgbm(self.params, self.mode)
 
     def compute(self, left, right):

@@ -120,8 +120,10 @@ class StereoCamera:
     SGBM_KEYS = ("minDisparity", "numDisparities", "blockSize", "P1", "P2", "disp12MaxDiff", "preFilterCap",
                  "uniquenessRatio", "speckleWindowSize", "speckleRange")
     # "mode" (0 MODE_SGBM, 1 MODE_HH, 2 MODE_SGBM_3WAY; the reference's "# TODO: mode option") travels in the same dict when it is
-    # there -- through from_pfiles, from_files and save_files alike --; a dict or file without one means mode 0
-    SGBM_OPTIONAL_KEYS = ("mode",)
+    # there -- through from_pfiles, from_files and save_files alike --; a dict or file without one means mode 0.  Likewise the
+    # matching cost: "cost" (0 BT, 1 census; include/vo355.h: vo_set_sgbm_cost) with "censusWidth" / "censusHeight" (9 x 7 where
+    # absent); a dict or file without "cost" means BT
+    SGBM_OPTIONAL_KEYS = ("mode", "cost", "censusWidth", "censusHeight")
 
     @classmethod
     def from_files(cls, left_cam_file, right_cam_file, rect_file, sgbm_file, img_size, **kw):

@@ -103,11 +103,16 @@ class Corridor:
     def rect_params(self):
         return {"R": np.eye(3), "T": np.array([-self.B, 0.0, 0.0])}
 
-    def sgbm_params(self, mode=None):
+    def sgbm_params(self, mode=None, cost=None):
+        """cost=1: the census settings tools and tests share (9 x 7, P1 / P2 at a quarter of BT's: Hamming costs are smaller)"""
         p = dict(minDisparity=0, numDisparities=self.D, blockSize=5, P1=200, P2=800, disp12MaxDiff=1,
                  preFilterCap=63, uniquenessRatio=10, speckleWindowSize=100, speckleRange=2)
         if mode is not None:
             p["mode"] = mode
+        if cost is not None:
+            p["cost"] = int(cost)
+            if cost == 1:
+                p.update(P1=50, P2=200, censusWidth=9, censusHeight=7)
         return p
 
     def Q(self):
