@@ -814,6 +814,62 @@ int vo_klt_pnp_pair_begin(vo_ctx* ctx, int slot_a, int slot_b, int win, int leve
 int vo_klt_pnp_pair_end(vo_ctx* ctx, int ticket, int32_t* counts4, int32_t* flags, double* Rt12, double* Rt12_refined, int32_t* refine2,
                         int32_t* lo2, uint8_t* mask_out /*cap*/, int32_t* q_idx /*cap*/, float* xy_out /*cap*2*/, int cap);
 
+/* Dense direct alignment (an extension, NOT part of the reference): photometric refinement of the motion between two slots on the
+ * dense disparity of the older one.  Slot a holds a dense disparity and its rectified left image (the TEMPLATE), slot b a rectified
+ * left image of the same size; Rt0 is the initial a -> b motion in the PnP step's convention (X' = R X + t, X in frame a, pixel in b),
+ * K4 = {fx, fy, cx, cy} in full-image pixels, as vo_pnp_pair takes it.  Defined by this build, operation by operation
+ * (tests/direct_ref.py restates it): integer stages are exact, everything else is float64 in the order written below, every product
+ * and sum rounded on its own (no fused multiply-add); only the ORDER of the sums over the points is the kernel's own (per thread
+ * ascending, a tree over the wave, the waves in order), so the float64 results agree with the restatement to rounding, not in bits.
+ *   Parameters: levels 1 .. VO_DIRECT_MAX_LEVELS, iters 1 .. 20, max_points >= 1, grad_min 0 .. 255 (an integer), huber > 0,
+ *   0 < dmin <= dmax, z_min >= 0, min_pixels >= 6, all finite; Rt0 and K4 finite, fx, fy > 0.
+ *   Pyramid: vo_klt_track's, of both left images: levels 0 .. levels - 1, level l of size (w_l, h_l); level-l pixel (x, y) stands for
+ *   level-0 pixel (x 2^l, y 2^l); the level intrinsics are fx_l = fx / 2^l, fy_l, cx_l = cx / 2^l, cy_l (no half-pixel terms).
+ *   Rectangle of level l: [x_lo, x_hi) x [y_lo, y_hi) = the level image, or with a ROI (vo_set_roi, clipped to the image) x_lo =
+ *   ceil(x0 / 2^l), x_hi = floor(x1 / 2^l), and likewise in y.
+ *   Lattice of level l: x = x_lo + 1 + i s < x_hi - 1 (i = 0 .. nx - 1), y = y_lo + 1 + j s < y_hi - 1 (j = 0 .. ny - 1), s the smallest
+ *   positive integer with nx ny <= max_points (computed by the host, reported); the linear index of a point is j nx + i.
+ *   Selection (integer, independent of the pose), A = level l of slot a's image: d16 = disp16_a[y 2^l][x 2^l] with 16 dmin <= d16 <=
+ *   16 dmax; gx2 = A[y][x + 1] - A[y][x - 1], gy2 = A[y + 1][x] - A[y - 1][x] with gx2 gx2 + gy2 gy2 >= 4 grad_min grad_min.
+ *   The 3-D point, from the Q of vo_set_Q: d = d16 / 16, W = Q[3][2] d + Q[3][3], X = (x 2^l + Q[0][3]) / W, Y = (y 2^l + Q[1][3]) / W,
+ *   Z = Q[2][3] / W.
+ *   One iteration at the pose Rt = [R | t] (row-major 3 x 4), for every selected point:
+ *     x' = ((R00 X + R01 Y) + R02 Z) + t0, y', z' likewise; u = (fx_l x') / z' + cx_l, v = (fy_l y') / z' + cy_l;
+ *     the point TAKES PART iff z' > z_min and x_lo <= u < x_hi - 1 and y_lo <= v < y_hi - 1;
+ *     iu = floor(u), ax = u - iu, iv, ay likewise; b00 = B[iv][iu], b01 = B[iv][iu + 1], b10 = B[iv + 1][iu], b11 = B[iv + 1][iu + 1];
+ *     I_b = (b00 (1 - ax) + b01 ax) (1 - ay) + (b10 (1 - ax) + b11 ax) ay;  r = I_b - A[y][x];  w = 1 for |r| <= huber, else huber / |r|;
+ *     gx = gx2 / 2, gy = gy2 / 2 (the TEMPLATE's gradient);  a = ((gx fx_l) / z', (gy fy_l) / z', -(((gx fx_l) x' + (gy fy_l) y') / (z' z')));
+ *     j = [X' x a | a] = (y' a2 - z' a1, z' a0 - x' a2, x' a1 - y' a0, a0, a1, a2): the component order of the PnP refit;
+ *     sums: H[k] += (w j[p]) j[q] over p <= q in packed row order (21), g[p] += (w j[p]) r (6), count += 1, wr2 += (w r) r.
+ *   Then H d = -g by the Cholesky step of the PnP refit and Rt <- [Exp(d[0..2]) R | Exp(d[0..2]) t + d[3..5]], as the refit does.
+ *   Schedule: levels levels - 1 .. 0, `iters` iterations each, no early exit.  An iteration with count < min_pixels stops the step
+ *   with status 2 ("starved"); a sum or a new pose that is not finite, or a pivot that is not positive, stops it with status -1;
+ *   in both cases the pose returned is that of the last completed iteration (Rt0 when none completed).  Status 0: all ran.
+ *   The record: status, iterations completed (over all levels); per level its s, the number of selected points (0 for a level the
+ *   step never reached) and count and wr2 of the level's first and of its last evaluated iteration (an iteration that stopped the
+ *   step counts as evaluated); the final Rt; and the 21 + 6 sums, count and wr2 of the last COMPLETED iteration's linearisation
+ *   (zeros when none completed): H is the information matrix of the pose up to the noise scale.
+ * One launch of one workgroup (k_direct_align) behind the pyramid launches on the context's stream, ONE host synchronisation; the
+ * pyramids live in the Lucas-Kanade workspace of the main match scratch.  With vo_enable_timing on, the pyramid launches are
+ * bracketed under VO_T_ORB and the alignment under VO_T_POSE.
+ *   VO_E_ARG: a bad slot or pointer, a parameter outside the ranges above, a non-finite Rt0 / K4.  VO_E_STATE: slot a without a pair
+ *   or without a dense disparity, or with keypoints that carry depth (a sparse slot); slot b without a pair; two slots of different
+ *   shapes; no vo_set_Q.  VO_E_SWEEP: slot a's disparity is undefined (as vo_pose_pair_end).  A refused call writes no record. */
+#define VO_DIRECT_MAX_LEVELS 4
+typedef struct vo_direct_level {
+    int32_t s, selected, n_first, n_last;
+    double wr2_first, wr2_last;
+} vo_direct_level;
+typedef struct vo_direct_rec {
+    int32_t status, iters_done, levels, pad;
+    vo_direct_level lv[VO_DIRECT_MAX_LEVELS];
+    double Rt[12];
+    double sums[27]; /* H (21, packed upper triangle in row order), g (6) */
+    double count, wr2;
+} vo_direct_rec;
+int vo_direct_align(vo_ctx* ctx, int slot_a, int slot_b, const double* K4, const double* Rt0 /*12*/, int levels, int iters, int max_points,
+                    int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_rec* rec_out);
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */

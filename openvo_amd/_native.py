@@ -53,6 +53,7 @@ SYMBOLS = [
     "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
     "vo_klt_track_host", "vo_klt_track", "vo_klt_pnp_pair", "vo_klt_pnp_pair_begin", "vo_klt_pnp_pair_end",
     "vo_set_sgbm_cost", "vo_get_sgbm_cost", "vo_sgbm_cost_volume",
+    "vo_direct_align",
 ]
 
 
@@ -100,6 +101,36 @@ class MapTrackRec(ctypes.Structure):
                     matches=int(self.M), n=int(self.n), best_iter=int(self.best_iter), best_count=int(self.best_count), flags=int(self.flags),
                     refine_status=int(self.rstatus), refine_steps=int(self.rsteps), update=np.array(self.counts6[:], np.int32),
                     Rt=m34(self.Rt), Rt_refined=m34(self.Rtr), c_T_w=m34(self.c_T_w), w_T_c=m34(self.w_T_c))
+
+
+DIRECT_MAX_LEVELS = 4     # VO_DIRECT_MAX_LEVELS
+
+
+class DirectLevel(ctypes.Structure):
+    """vo_direct_level of include/vo355.h"""
+    _fields_ = [("s", ctypes.c_int32), ("selected", ctypes.c_int32), ("n_first", ctypes.c_int32), ("n_last", ctypes.c_int32),
+                ("wr2_first", ctypes.c_double), ("wr2_last", ctypes.c_double)]
+
+
+class DirectRec(ctypes.Structure):
+    """vo_direct_rec of include/vo355.h: the record of the dense direct alignment."""
+    _fields_ = [("status", ctypes.c_int32), ("iters_done", ctypes.c_int32), ("levels", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("lv", DirectLevel * DIRECT_MAX_LEVELS), ("Rt", ctypes.c_double * 12), ("sums", ctypes.c_double * 27),
+                ("count", ctypes.c_double), ("wr2", ctypes.c_double)]
+
+    def as_dict(self):
+        n = int(self.levels)
+        sums = np.array(self.sums[:], np.float64)
+        H = np.zeros((6, 6))
+        H[np.triu_indices(6)] = sums[:21]                # packed upper triangle in row order
+        H = H + np.triu(H, 1).T
+        lv = [self.lv[l] for l in range(n)]
+        return dict(status=int(self.status), iters_done=int(self.iters_done),
+                    s=np.array([v.s for v in lv], np.int32), selected=np.array([v.selected for v in lv], np.int32),
+                    n_first=np.array([v.n_first for v in lv], np.int32), n_last=np.array([v.n_last for v in lv], np.int32),
+                    wr2_first=np.array([v.wr2_first for v in lv], np.float64), wr2_last=np.array([v.wr2_last for v in lv], np.float64),
+                    Rt=np.array(self.Rt[:], np.float64).reshape(3, 4), sums=sums, information=H, g=sums[21:].copy(),
+                    count=int(self.count), wr2=float(self.wr2))
 
 
 MAP_TRACK_MAX = 3800     # VO_MAP_TRACK_MAX: the largest map the fused map step takes
@@ -306,6 +337,9 @@ def lib():
         if hasattr(L, "vo_set_sgbm_cost"):          # (likewise: an older build has the BT cost alone)
             for name, proto in (("vo_set_sgbm_cost", [vp, ci, ci, ci]), ("vo_get_sgbm_cost", [vp, vp, vp, vp]),
                                 ("vo_sgbm_cost_volume", [vp, vp, ctypes.c_size_t])):
+                getattr(L, name).argtypes = proto
+        if hasattr(L, "vo_direct_align"):           # (likewise: an older build has no dense direct alignment)
+            for name, proto in (("vo_direct_align", [vp, ci, ci, vp, vp, ci, ci, ci, ci, cd, cd, cd, cd, ci, vp]),):
                 getattr(L, name).argtypes = proto
         plant = getattr(L, "vo_test_plant_dense_pair", None)     # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
@@ -1070,6 +1104,52 @@ class Context:
         head, arrays = self._klt_pnp_out(want_arrays)
         self._ck(self._lib.vo_klt_pnp_pair_end(self._h, int(ticket), *[_p(a) for a in head + arrays], self.kp_cap))
         return self._klt_pnp_result(head, arrays)
+
+    # ---- dense direct alignment (vo_direct_align)
+    @staticmethod
+    def direct_params(levels=3, iters=8, max_points=16384, grad_min=8, huber=10.0, dmin=4.0, dmax=100.0, z_min=0.1, min_pixels=64):
+        """the parameters of direct_align as the library takes them, checked as the library checks them (ValueError)"""
+        def _int(v, lo, hi):
+            return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and lo <= v <= hi
+
+        def _num(v):
+            return not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+        if not _int(levels, 1, DIRECT_MAX_LEVELS):
+            raise ValueError("levels is an int in 1 .. %d, not %r" % (DIRECT_MAX_LEVELS, levels))
+        if not _int(iters, 1, 20):
+            raise ValueError("iters is an int in 1 .. 20, not %r" % (iters,))
+        if not _int(max_points, 1, 2 ** 31 - 1):
+            raise ValueError("max_points is an int >= 1, not %r" % (max_points,))
+        if not _int(grad_min, 0, 255):
+            raise ValueError("grad_min is an int in 0 .. 255, not %r" % (grad_min,))
+        if not _int(min_pixels, 6, 2 ** 31 - 1):
+            raise ValueError("min_pixels is an int >= 6, not %r" % (min_pixels,))
+        if not (_num(huber) and huber > 0):
+            raise ValueError("huber is a finite number > 0, not %r" % (huber,))
+        if not (_num(dmin) and _num(dmax) and 0 < dmin <= dmax):
+            raise ValueError("dmin and dmax are finite numbers with 0 < dmin <= dmax, not %r, %r" % (dmin, dmax))
+        if not (_num(z_min) and z_min >= 0):
+            raise ValueError("z_min is a finite number >= 0, not %r" % (z_min,))
+        return (int(levels), int(iters), int(max_points), int(grad_min), float(huber), float(dmin), float(dmax), float(z_min), int(min_pixels))
+
+    def direct_align(self, slot_a, slot_b, K4, Rt0=None, levels=3, iters=8, max_points=16384, grad_min=8, huber=10.0, dmin=4.0, dmax=100.0,
+                     z_min=0.1, min_pixels=64):
+        """Photometric refinement of the a -> b motion on slot_a's dense disparity (vo_direct_align, include/vo355.h): slot_a's
+        rectified left image and disparity against slot_b's rectified left image, from Rt0 (3 x 4 or 4 x 4, X' = R X + t; None: the
+        identity), one launch and one synchronisation.  -> dict: status (0 all iterations ran | 2 starved | -1 numeric), iters_done,
+        per level s / selected / n_first / n_last / wr2_first / wr2_last, Rt (3, 4), information (6, 6: sum w j j^T of the last
+        completed linearisation, rotation then translation), g (6), count, wr2, sums (the 27 raw sums)."""
+        if not hasattr(self._lib, "vo_direct_align"):
+            raise RuntimeError("this build of the library has no dense direct alignment (vo_direct_align)")
+        prm = self.direct_params(levels, iters, max_points, grad_min, huber, dmin, dmax, z_min, min_pixels)
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        Rt = np.eye(4)[:3] if Rt0 is None else np.asarray(Rt0, np.float64)
+        if Rt.shape == (4, 4):
+            Rt = Rt[:3]
+        Rt = _c(Rt.reshape(12), np.float64)
+        rec = DirectRec()
+        self._ck(self._lib.vo_direct_align(self._h, int(slot_a), int(slot_b), _p(K4), _p(Rt), *prm, ctypes.byref(rec)))
+        return rec.as_dict()
 
     def plant_dense_pair(self, slot, left, disp16, xy, desc=None):
         """Test-only build of the library: plant_dense, and the (h, w) uint8 image `left` as the slot's rectified pair

@@ -250,7 +250,7 @@ void klt_ws_free(KltWs& k)
 }
 
 // completes the Lucas-Kanade members of the match workspace in force (the main one, or a pose alternate's under its AltScope)
-static int klt_ws_prepare(vo_ctx* ctx)
+int klt_ws_prepare(vo_ctx* ctx)
 {
     KltWs& k = ctx->mw->klt;
     if (k.ready) return VO_OK;
@@ -288,23 +288,31 @@ static int klt_params(vo_ctx* ctx, int win, int levels, int iters, double eps, d
     return VO_OK;
 }
 
+// the pyramids above level 0 of both images into the Lucas-Kanade workspace of the match scratch in force (prepared by the caller:
+// klt_ws_prepare), one launch per level on ctx->stream; a / b / lw / lh: VO_KLT_MAX_LEVELS entries each, level l's images and size
+// (the levels from `levels` on repeat level 0: never read, always valid).  Shared with the direct alignment (direct.hip).
+int klt_pyr_enqueue(vo_ctx* ctx, const uint8_t* a0, const uint8_t* b0, int w, int h, int levels, const uint8_t** a, const uint8_t** b, int* lw, int* lh)
+{
+    KltWs& k = ctx->mw->klt;
+    for (int l = 0; l < VO_KLT_MAX_LEVELS; l++) { a[l] = a0; b[l] = b0; lw[l] = w; lh[l] = h; }     // (levels never read stay valid)
+    StageTimer t(ctx, VO_T_ORB, levels > 1 ? levels - 1 : 1);
+    for (int l = 1; l < levels; l++) {
+        const int ow = (lw[l - 1] + 1) / 2, oh = (lh[l - 1] + 1) / 2;
+        uint8_t *da = k.pyr[0] + k.off[l], *db = k.pyr[1] + k.off[l];
+        hipLaunchKernelGGL(k_klt_pyr_down, dim3(div_up(ow, 32), div_up(oh, 8), 2), dim3(32, 8), 0, ctx->stream, a[l - 1], b[l - 1], da, db,
+                           lw[l - 1], lh[l - 1], ow, oh);
+        VO_CHECK_LAUNCH(ctx);
+        a[l] = da; b[l] = db; lw[l] = ow; lh[l] = oh;
+    }
+    return VO_OK;
+}
+
 // the pyramids above level 0 of both images, then the forward (and backward) pass of the n points at d_xy, all on ctx->stream
 static int klt_enqueue(vo_ctx* ctx, const uint8_t* a0, const uint8_t* b0, int w, int h, const KltPrm& prm, bool fb, const float* d_xy, int n)
 {
     KltWs& k = ctx->mw->klt;
     KltImgs P;
-    for (int l = 0; l < VO_KLT_MAX_LEVELS; l++) { P.a[l] = a0; P.b[l] = b0; P.w[l] = w; P.h[l] = h; }     // (levels never read stay valid)
-    {
-        StageTimer t(ctx, VO_T_ORB, prm.levels > 1 ? prm.levels - 1 : 1);
-        for (int l = 1; l < prm.levels; l++) {
-            const int ow = (P.w[l - 1] + 1) / 2, oh = (P.h[l - 1] + 1) / 2;
-            uint8_t *da = k.pyr[0] + k.off[l], *db = k.pyr[1] + k.off[l];
-            hipLaunchKernelGGL(k_klt_pyr_down, dim3(div_up(ow, 32), div_up(oh, 8), 2), dim3(32, 8), 0, ctx->stream, P.a[l - 1], P.b[l - 1], da, db,
-                               P.w[l - 1], P.h[l - 1], ow, oh);
-            VO_CHECK_LAUNCH(ctx);
-            P.a[l] = da; P.b[l] = db; P.w[l] = ow; P.h[l] = oh;
-        }
-    }
+    if (int rc = klt_pyr_enqueue(ctx, a0, b0, w, h, prm.levels, P.a, P.b, P.w, P.h)) return rc;
     const int trips = div_up(prm.win * prm.win, 64);
     auto kern = trips <= 2 ? k_klt_track<2> : trips <= 4 ? k_klt_track<4> : trips <= 7 ? k_klt_track<7> : trips <= 10 ? k_klt_track<10> : k_klt_track<16>;
     StageTimer t(ctx, VO_T_MATCH, fb ? 2 : 1);

@@ -1421,68 +1421,7 @@ extern "C" int vo_ransac_pnp(vo_ctx* ctx, const float* pts3d, const float* pts2d
 // for the upper bound and read it), plus an optional refinement of the winner on its inliers.
 // =========================================================================================
 
-// One Gauss-Newton step's solve in one lane: H (6x6, symmetric, upper triangle in packed row order) d = -g by Cholesky, every index
-// a compile-time constant so that the factor stays in registers.  false: a pivot was not positive.
-__device__ __forceinline__ bool pn_solve6(const double* Hp, const double* g, double* d)
-{
-    double L[6][6];
-#pragma unroll
-    for (int i = 0, k = 0; i < 6; i++)
-#pragma unroll
-        for (int j = i; j < 6; j++, k++) L[j][i] = Hp[k];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double s = L[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
-        ok = ok && s > 0.0;
-        const double dj = sqrt(s);
-        L[j][j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double v = L[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
-            L[i][j] = v / dj;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double v = -g[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) v -= L[k][i] * d[k];
-        d[i] = v / L[i][i];
-    }
-    return ok;
-}
-
-// Rt <- [Exp(w) R | Exp(w) t + v]   (Rodrigues; the series below 1e-4 rad, where sin / cos lose digits in the quotients)
-__device__ __forceinline__ void pn_apply_twist(double* Rt, const double* d)
-{
-    const double wx = d[0], wy = d[1], wz = d[2];
-    const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
-    double A, B;
-    if (th < 1e-4) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
-    else { A = sin(th) / th; B = (1.0 - cos(th)) / th2; }
-    const double W[9] = { 0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0 };
-    const double w3[3] = { wx, wy, wz };
-    double E[9], out[12];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) E[r * 3 + c] = ((r == c ? 1.0 : 0.0) + A * W[r * 3 + c]) + B * (w3[r] * w3[c] - (r == c ? th2 : 0.0));
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 4; c++) out[r * 4 + c] = (E[r * 3] * Rt[c] + E[r * 3 + 1] * Rt[4 + c]) + E[r * 3 + 2] * Rt[8 + c];
-    for (int r = 0; r < 3; r++) out[r * 4 + 3] += d[3 + r];
-    for (int k = 0; k < 12; k++) Rt[k] = out[k];
-}
+#include "pn_solve.h"
 
 // One Gauss-Newton step of the refit by the whole block (256 threads): every thread sums its points of `mask` (i = thread + 256 k,
 // ascending) into the 21 + 6 sums of J^T J and J^T r, a DPP tree sums the wave, thread 0 adds the four waves' values from LDS in

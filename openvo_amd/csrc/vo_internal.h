@@ -162,6 +162,12 @@ struct KltWs {
     bool ready = false;
 };
 void klt_ws_free(KltWs& k);
+struct vo_ctx;
+// completes the Lucas-Kanade members of the match workspace in force at their first use (klt.hip): the caller of klt_pyr_enqueue does it
+int klt_ws_prepare(vo_ctx* ctx);
+// the pyramids above level 0 of two images of one size into that workspace (k_klt_pyr_down, one launch per level on ctx->stream);
+// a / b / lw / lh receive VO_KLT_MAX_LEVELS entries each (klt.hip; used by direct.hip too)
+int klt_pyr_enqueue(vo_ctx* ctx, const uint8_t* a0, const uint8_t* b0, int w, int h, int levels, const uint8_t** a, const uint8_t** b, int* lw, int* lh);
 
 struct vo_ctx {
     int device = 0;

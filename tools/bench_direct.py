@@ -1,0 +1,108 @@
+"""The dense direct alignment on a C2 stream (1280x720, 500 features, dense depth, host pairs), one GPU, ONE process: the step alone
+(Context.direct_align on two slots of the stream, from the identity: wall time of the synchronous call -- pyramid launches, the one
+k_direct_align launch, the synchronisation -- and the library's event bracket around the kernel, median of --step-calls calls after
+10 warm-up calls, at the default 16384 points per level and at 65536); then frames per second of synchronous
+StereoOdometer.update() loops and of StereoOdometer.run() with and without direct_refine, for both pose methods, the modes
+alternating inside every round.  Prints one JSON line.  Needs a GPU: there is no fallback.  Reads nothing but the package (the
+synthetic corridor).
+
+    python tools/bench_direct.py [--pairs 240] [--rounds 3] [--step-calls 200]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--pairs", type=int, default=240, help="pairs per timed pass")
+ap.add_argument("--rounds", type=int, default=3, help="timed passes per mode, after one warm-up pass")
+ap.add_argument("--step-calls", type=int, default=200, help="timed calls of the step per point count")
+args = ap.parse_args()
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+import numpy as np                                    # noqa: E402
+from openvo_amd import StereoCamera, StereoOdometer   # noqa: E402
+from openvo_amd.synth import Corridor                 # noqa: E402
+
+c = Corridor("C2")
+frames = c.pairs(0, 48)
+cam = StereoCamera(c.K(), c.dist(), c.K(), c.dist(), c.rect_params(), c.sgbm_params(), (c.w, c.h), max_keypoints=500)
+ctx = cam._ctx
+result = {"tool": "bench_direct", "device": ctx.device_name()}
+order = list(range(48)) + list(range(46, 0, -1))       # there and back: every step is a small motion
+stream = [frames[order[k % len(order)]] for k in range(args.pairs)]
+Q = cam.Q
+K4 = [Q[2, 3], Q[2, 3], -Q[0, 3], -Q[1, 3]]
+
+
+def stats(v):
+    return {"median": round(float(np.median(v)), 1), "p10": round(float(np.percentile(v, 10)), 1), "p90": round(float(np.percentile(v, 90)), 1)}
+
+
+# ---------------------------------------------------------------------------------------------- the step alone
+def step_alone():
+    x3a, _, _ = cam.compute_3d(*stream[0], preprocessed=True)
+    x3b, _, _ = cam.compute_3d(*stream[1], preprocessed=True)
+    sa, sb = x3a.frame.slot, x3b.frame.slot
+    kw = dict(dmin=StereoOdometer.MIN_VALID_DISPARITY, dmax=StereoOdometer.MAX_VALID_DISPARITY)
+    out = {}
+    for n in (16384, 65536):
+        wall, kern, r = [], [], None
+        for step in range(-10, args.step_calls):
+            ctx.enable_timing(step >= 0)
+            t0 = time.perf_counter()
+            r = ctx.direct_align(sa, sb, K4, max_points=n, **kw)
+            dt = 1e6 * (time.perf_counter() - t0)
+            if step < 0:
+                continue
+            t = ctx.timings(reset=True)
+            wall.append(dt)
+            kern.append(1e3 * t["pose"][0])
+        ctx.enable_timing(False)
+        out[str(n)] = dict(status=r["status"], iters_done=r["iters_done"], s=r["s"].tolist(), selected=r["selected"].tolist(),
+                           participants_last=r["n_last"].tolist(), call_us=stats(wall), kernel_us=stats(kern))
+    return out
+
+
+result["step"] = step_alone()
+
+# ---------------------------------------------------------------------------------------------- the loops
+BASE = dict(nfeatures=500, preprocessed_frames=True)
+MODES = {"umeyama": dict(rigidity_threshold=0.1, outlier_threshold=0.02), "umeyama_direct": dict(rigidity_threshold=0.1, outlier_threshold=0.02, direct_refine=True),
+         "pnp": dict(pose_method="pnp"), "pnp_direct": dict(pose_method="pnp", direct_refine=True)}
+
+
+def one_pass(kw, run):
+    odo = StereoOdometer(cam, **BASE, **kw)
+    ctx.synchronize()
+    accepted = taken = 0
+    t0 = time.perf_counter()
+    for ok in (odo.run(iter(stream)) if run else (odo.update(L, R) for L, R in stream)):
+        accepted += bool(ok)
+        taken += bool(ok and odo.direct_refine and odo.direct_accepted)
+    ctx.synchronize()
+    dt = time.perf_counter() - t0
+    odo.reset_lookahead()
+    return len(stream) / dt, accepted, taken
+
+
+def report(rates):
+    return {k: {"per_round": [round(x[0], 1) for x in v], "median": round(float(np.median([x[0] for x in v])), 1),
+                "accepted": [x[1] for x in v], "refined_poses_taken": [x[2] for x in v]} for k, v in rates.items()}
+
+
+result["workload"] = ("C2 1280x720, 500 features, dense depth, %d host pairs per pass (synthetic corridor, one GPU); umeyama with the clique "
+                      "and outlier filters (0.1, 0.02)" % len(stream))
+result["rounds"] = args.rounds
+for name, run in (("update_frames_per_s", False), ("run_frames_per_s", True)):
+    for kw in MODES.values():
+        one_pass(kw, run)                              # warm-up: allocations, clocks
+    rates = {k: [] for k in MODES}
+    for r in range(args.rounds):                       # the modes alternate inside every round
+        for k, kw in MODES.items():
+            rates[k].append(one_pass(kw, run))
+    result[name] = report(rates)
+    for m in ("umeyama", "pnp"):
+        result[name][m + "_direct_over_plain_per_round"] = [round(a_[0] / b_[0], 3) for a_, b_ in zip(rates[m + "_direct"], rates[m])]
+ctx.close()
+print(json.dumps(result))
