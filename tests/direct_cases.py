@@ -9,10 +9,22 @@ Every case carries its inputs, its keywords for direct_align and the regime its 
 asserts, without a GPU, that the restatement (tests/direct_ref.py) reaches that regime with a decision margin >= MARGIN, which is
 what lets the device's integer fields be compared exactly.
 
+Rigs.  rig(w, h) is the plain one (fx == fy, the principal point at the image centre, the same in K4 and Q, Q[3][3] == 0).  A case
+with rig="generic" takes camera_cases.direct_rig(w, h): fx != fy, K4's principal point 1.75 / -1.25 px off Q's, Q[3][3] = 0.8.  The
+alignment reads five entries of Q, so the plane's pixel-to-ray map is ray_map(Q), not K^-1, and B is rendered with it (rendered with
+K^-1 the pair is physically inconsistent for fx != fy and the fit walks away: rejected).
+
 Seeds.  A case's texture seed is to be changed until its margin holds, and the rejected seeds written down here.  Rejected (margin
 below 1e-6 in the restatement): none -- the first seed tried for every case (its index in CASES + 11) held; the smallest margin is
-8.2e-05 (levels4), the others lie between 1e-4 and 3e-2 (printed by tests/test_direct_ref.py)."""
+8.2e-05 (levels4), the others lie between 1e-4 and 3e-2 (printed by tests/test_direct_ref.py); the generic cases reuse the seeds
+of the plain cases they are named after and hold 3.5e-3 ... 1.8e-1."""
+import os
+import sys
+
 import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import camera_cases as CC                  # noqa: E402
 
 MARGIN = 1e-6
 BASELINE = 0.25
@@ -67,11 +79,16 @@ def pose(rvec, t):
     return np.hstack([exp_so3(rvec), np.asarray(t, np.float64)[:, None]])
 
 
-def render_b(w, h, K4, n, Rt, seed):
-    """image B by the inverse warp: B(p_b) = texture(H^-1 p_b) with H = K (R + t n^T) K^-1"""
+def ray_map(Q):
+    """M with X ~ M (x, y, 1): the pixel-to-ray map of the five entries of Q the header reads -- K^-1 only where Q is K4's"""
+    return np.array([[1, 0, Q[0, 3]], [0, 1, Q[1, 3]], [0, 0, Q[2, 3]]], np.float64)
+
+
+def render_b(w, h, K4, n, Rt, seed, M=None):
+    """image B by the inverse warp: B(p_b) = texture(H^-1 p_b) with H = K (R + t n^T) M, M = K^-1 unless given (ray_map(Q))"""
     fx, fy, cx, cy = K4
     K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
-    Hm = K @ (Rt[:, :3] + np.outer(Rt[:, 3], n)) @ np.linalg.inv(K)
+    Hm = K @ (Rt[:, :3] + np.outer(Rt[:, 3], n)) @ (np.linalg.inv(K) if M is None else M)
     y, x = np.mgrid[0:h, 0:w].astype(np.float64)
     p = np.linalg.inv(Hm) @ np.stack([x.ravel(), y.ravel(), np.ones(w * h)])
     return quantise(texture(p[0] / p[2], p[1] / p[2], seed).reshape(h, w))
@@ -96,13 +113,14 @@ class Case:
         """-> (A, B, disp16, Q, K4, Rt0, truth): built once, the arrays read-only"""
         if self._built is None:
             w, h, o = self.w, self.h, self.opt
-            Q, K4 = rig(w, h)
+            generic = o.get("rig") == "generic"        # fx != fy, K4's principal point != Q's, Q[3][3] != 0 (tests/camera_cases.py)
+            Q, K4 = CC.direct_rig(w, h) if generic else rig(w, h)
             d0, ramp = o.get("d0", 12.0), o.get("ramp", (0.03, 0.02))
             y, x = np.mgrid[0:h, 0:w].astype(np.float64)
             kind = o.get("image", "texture")
             if kind == "texture":
                 A = quantise(texture(x, y, self.seed))
-                B = render_b(w, h, K4, plane_normal(Q, d0, ramp, w, h), PLANTED, self.seed)
+                B = render_b(w, h, K4, plane_normal(Q, d0, ramp, w, h), PLANTED, self.seed, ray_map(Q) if generic else None)
             elif kind == "constant":
                 A = np.full((h, w), 120, np.uint8)
                 B = A.copy()
@@ -147,5 +165,12 @@ CASES = [
     Case("starved_midway", 96, 72, 24, _k(levels=3, iters=8), dict(status=2, done=(1, 23)), planted=False,
          Rt0=pose((0.0, 0.0, 0.0), (1.2, 0.0, 0.0))),
     Case("bad_pivot", 96, 72, 25, _k(levels=2), dict(status=-1, done=(0, 0)), image="columns", planted=False),
+    # the generic rig (fx != fy, K4's principal point != Q's, Q[3][3] != 0): the seeds and keywords of levels3, odd_levels3, small, roi
+    # and step2
+    Case("generic_levels3", 96, 72, 13, _k(levels=3), dict(status=0, improves=True), rig="generic"),
+    Case("generic_odd_levels3", 97, 61, 15, _k(levels=3), dict(status=0, improves=True), rig="generic"),
+    Case("generic_small", 64, 48, 17, _k(levels=2), dict(status=0, improves=True), rig="generic"),
+    Case("generic_roi", 96, 72, 20, _k(levels=3), dict(status=0, improves=True), roi=(9, 6, 90, 67), rig="generic"),
+    Case("generic_step2", 96, 72, 18, _k(levels=3, max_points=1700), dict(status=0, improves=True, s0=2), rig="generic"),
 ]
 BY_NAME = {c.name: c for c in CASES}

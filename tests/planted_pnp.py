@@ -55,7 +55,7 @@ class PnpCase:
     n_in inliers among the usable ones (None: 70 %), at the compacted positions `inliers` lists (None: drawn); scene: the seed of
     the construction; dup: that many further queries copy the descriptor of a train that is already matched (what the cross-check
     must remove); loop / window / cross / roi: the match flags and the ROI origin; collinear: the matched 3-D points lie on one line.
-    K4: the intrinsics the model scores under (a subclass with another camera sets its own)."""
+    K4: the intrinsics the scene is projected with and the model scores under (a subclass with another camera sets its own)."""
     K4 = K4
 
     def __init__(self, name, nq, M, bad=(), n_in=None, noise=0.0, iters=ITERS, seed=SEED, refine=0, scene=0, inliers=None, cross=False, loop=None,
@@ -113,11 +113,12 @@ class PnpCase:
         else:
             inl = np.sort(rng.choice(pos, n_in, replace=False))
         self.inl_pos = inl
-        uv = project(self.xyz_a[q[inl]]) + self.noise * rng.normal(0, 1, (len(inl), 2))
+        uv = project(self.xyz_a[q[inl]], self.K4) + self.noise * rng.normal(0, 1, (len(inl), 2))
         self.xy_b[t[inl]] = uv.astype(np.float32)
         if self.window is not None:                     # slot a sees every matched point where it is: most partners lie inside a window
             R0 = self.xyz_a[q].astype(np.float64)
-            self.xy_a[q] = np.stack([K4[0] * R0[:, 0] / R0[:, 2] + K4[2], K4[1] * R0[:, 1] / R0[:, 2] + K4[3]], 1).astype(np.float32)
+            Ka = self.K4
+            self.xy_a[q] = np.stack([Ka[0] * R0[:, 0] / R0[:, 2] + Ka[2], Ka[1] * R0[:, 1] / R0[:, 2] + Ka[3]], 1).astype(np.float32)
         if self.loop is not None:                       # right partners: nine in ten agree up to two bits, the rest are unrelated
             agree = rng.random(len(q)) < 0.9
             for k in np.flatnonzero(agree & first):

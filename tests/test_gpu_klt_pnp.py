@@ -85,27 +85,27 @@ def _disp16():
     return d
 
 
-def _cloud(xy, roi, special):
-    """the per-keypoint 3-D points of the plane (float32), a NaN and an inf coordinate at the special keypoints"""
+def _cloud(xy, roi, special, k4=K4):
+    """the per-keypoint 3-D points of the plane (float32) under the camera k4, a NaN and an inf coordinate at the special keypoints"""
     x0, y0 = _crop(roi)[:2]
-    X = np.stack([(xy[:, 0].astype(np.float64) + x0 - CX) * Z / F, (xy[:, 1].astype(np.float64) + y0 - CY) * Z / F,
+    X = np.stack([(xy[:, 0].astype(np.float64) + x0 - k4[2]) * Z / k4[0], (xy[:, 1].astype(np.float64) + y0 - k4[3]) * Z / k4[1],
                   np.full(len(xy), Z)], 1).astype(np.float32)
     for k, i in enumerate(special):
         X[i, k] = (np.nan, np.inf)[k]
     return X
 
 
-def _plant(ctx, slot, img, xy, roi, dense, special):
+def _plant(ctx, slot, img, xy, roi, dense, special, k4=K4):
     if dense:
         ctx.plant_dense_pair(slot, img, _disp16(), xy)
         return None
     ctx.upload_pair(slot, img, img, True)
-    X = _cloud(xy, roi, special)
+    X = _cloud(xy, roi, special, k4)
     ctx.plant_keypoints(slot, xy, np.zeros((len(xy), 32), np.uint8), X)
     return X
 
 
-def _composed(ctx, sa, sb, xy_a, cloud, roi, klt, pnp):
+def _composed(ctx, sa, sb, xy_a, cloud, roi, klt, pnp, k4=K4):
     """the chain StereoOdometer._pair_klt composes, link by link -> the record the fused step must return"""
     xy_b, st, _ = ctx.klt_track(sa, sb, **klt)
     idx = np.nonzero(st == 0)[0]
@@ -121,7 +121,7 @@ def _composed(ctx, sa, sb, xy_a, cloud, roi, klt, pnp):
     uv = xy_b[idx] + np.array(_crop(roi)[:2], np.float32)
     out = dict(status=st, matches=int((st == 0).sum()), n=len(idx), flags=flags, q=idx.astype(np.int32), xy=xy_b[idx], X=pts, uv=uv)
     if len(idx) >= 4:
-        r = ctx.ransac_pnp(pts, uv, K4, pnp["iters"], pnp["thr"], pnp["seed"])
+        r = ctx.ransac_pnp(pts, uv, k4, pnp["iters"], pnp["thr"], pnp["seed"])
         out.update(best_iter=r["best_iter"], best_count=r["best_count"], mask=r["mask"], Rt=r["Rt"])
     else:
         out.update(best_iter=0, best_count=0, mask=np.zeros(len(idx), np.uint8), Rt=np.zeros((3, 4)))
@@ -160,14 +160,14 @@ def _hold(r, want, nq, what):
     assert np.array_equal(r["Rt"], want["Rt"]), "%s: Rt is not that of ransac_pnp on the composed arrays" % what
 
 
-def _planted_route(ctx, want, roi, pnp, refine, lo_rounds):
+def _planted_route(ctx, want, roi, pnp, refine, lo_rounds, k4=K4):
     """the refit of ctx.pnp_pair[_lo] on the compacted arrays planted as two sparse slots (slots 6, 7)"""
     n = want["n"]
     desc = np.random.default_rng(5).integers(0, 256, (n, 32)).astype(np.uint8)
     ctx.plant_keypoints(6, np.zeros((n, 2), np.float32), desc, want["X"])
     ctx.plant_keypoints(7, want["xy"], desc, np.ones((n, 3), np.float32))
     kw = dict(iters=pnp["iters"], thr=pnp["thr"], seed=pnp["seed"], refine=refine, want_matches=True)
-    r = ctx.pnp_pair_lo(6, 7, 0.8, K4, lo_rounds, **kw) if lo_rounds else ctx.pnp_pair(6, 7, 0.8, K4, **kw)
+    r = ctx.pnp_pair_lo(6, 7, 0.8, k4, lo_rounds, **kw) if lo_rounds else ctx.pnp_pair(6, 7, 0.8, k4, **kw)
     assert r["n"] == n and np.array_equal(r["q"], np.arange(n)) and np.array_equal(r["t"], np.arange(n)), "the planted route lost a correspondence"
     return r
 
@@ -183,15 +183,16 @@ CASE_NAMES = [c["name"] for c in CASES]
 
 def _check_case(ctx, a, b, c):
     roi, dense, n = c.get("roi"), c["dense"], c["n"]
+    k4 = c.get("K4", K4)                                    # (a sparse case may bring its own camera: its cloud is planted under it)
     klt = dict(win=c.get("win", 21), levels=c.get("levels", 3), fb=c.get("fb", 1.0))
     pnp = dict(iters=256, thr=1.5, seed=4321)
     refine, lo = c.get("refine", 0), c.get("lo_rounds", 0)
     ctx.set_roi(*(roi if roi is not None else (0, 0, 320, 240)))
     try:
         xy, special = _keypoints(n, roi)
-        cloud = _plant(ctx, 0, a, xy, roi, dense, special)
+        cloud = _plant(ctx, 0, a, xy, roi, dense, special, k4)
         ctx.upload_pair(1, b, b, True)
-        want = _composed(ctx, 0, 1, xy, cloud, roi, klt, pnp)
+        want = _composed(ctx, 0, 1, xy, cloud, roi, klt, pnp, k4)
         st = want["status"]
         line = "%s: N %d  status 0 / 1 / 2 / 8: %d / %d / %d / %d  composed (M, n, flags) = (%d, %d, %d) best %d @ %d" % (
             c["name"], n, (st == 0).sum(), (st & 1).astype(bool).sum(), (st & 2).astype(bool).sum(), (st & 8).astype(bool).sum(),
@@ -209,17 +210,17 @@ def _check_case(ctx, a, b, c):
             assert want["flags"] == (1 if dense else 0)
         kw = dict(refine=refine, lo_rounds=lo, want_arrays=True, **pnp, **klt)
         _poison(ctx)
-        r = _full(ctx, ctx.klt_pnp_pair(0, 1, K4, **kw), n)
+        r = _full(ctx, ctx.klt_pnp_pair(0, 1, k4, **kw), n)
         _hold(r, want, n, "klt_pnp_pair")
-        tk = ctx.klt_pnp_pair_begin(0, 1, K4, **kw)
+        tk = ctx.klt_pnp_pair_begin(0, 1, k4, **kw)
         _poison(ctx)
         r2 = _full(ctx, ctx.klt_pnp_pair_end(tk, want_arrays=True), n)
         _same_record(r, r2, "klt_pnp_pair and klt_pnp_pair_begin / _end")
-        bare = ctx.klt_pnp_pair(0, 1, K4, **dict(kw, want_arrays=False))
+        bare = ctx.klt_pnp_pair(0, 1, k4, **dict(kw, want_arrays=False))
         assert all(bare[k] == r[k] for k in SCALARS) and np.array_equal(bare["Rt"], r["Rt"]) and "xy" not in bare
         if refine:
             assert want["n"] >= 6
-            ref = _planted_route(ctx, want, roi, pnp, refine, lo)
+            ref = _planted_route(ctx, want, roi, pnp, refine, lo, k4)
             keys = ("refine_status", "refine_steps", "best_iter", "best_count") + (("lo_rounds", "lo_support") if lo else ())
             for k in keys:
                 assert r[k] == ref[k], "%s: %s, the planted route %s" % (k, r[k], ref[k])

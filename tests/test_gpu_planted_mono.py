@@ -36,8 +36,8 @@ def _rel(a, b, rel=1e-12):
     return bool(np.all(np.abs(np.asarray(a) - np.asarray(b)) <= rel * np.abs(b)))
 
 
-def _check(ctx, E, p1, p2, mask=None, q=None, t=None, na=None, nb=None, depth_a=None, gate=0.0):
-    """one call of the device against the restatement -> (device, restatement)"""
+def _check(ctx, E, p1, p2, mask=None, q=None, t=None, na=None, nb=None, depth_a=None, gate=0.0, K4=K4):
+    """one call of the device against the restatement -> (device, restatement); K4: the camera of both (the module's unless given)"""
     got = ctx.recover_pose(E, p1, p2, K4, mask, q, t, na, nb, depth_a, gate)
     r = ref.recover_pose(E, p1, p2, K4, mask, q, t, na, nb, depth_a, gate)
     n = len(p1)

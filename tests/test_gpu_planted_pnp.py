@@ -76,7 +76,7 @@ def _plant(ctx, c, sa=0, sb=1):
 
 def _args(c, sa, sb):
     kw = dict(iters=c.iters, thr=PP.THR, seed=c.seed, refine=c.refine, want_matches=True, cross_check=c.cross)
-    return (sa, sb, PP.RATIO, PP.K4), kw
+    return (sa, sb, PP.RATIO, c.K4), kw
 
 
 def _full(ctx, r, nq):
@@ -129,7 +129,7 @@ def _hold_to_model(ctx, c, m, r):
     d = float(np.abs(r["Rt"] - m["Rt"]).max())
     assert d <= BAR_RT, "Rt differs from the oracle by %.3g" % d
     if n >= 4:
-        ref = ctx.ransac_pnp(m["X"], m["uv"], PP.K4, c.iters, PP.THR, c.seed)
+        ref = ctx.ransac_pnp(m["X"], m["uv"], c.K4, c.iters, PP.THR, c.seed)
         assert (ref["best_iter"], ref["best_count"]) == (r["best_iter"], r["best_count"]) and np.array_equal(ref["mask"], r["mask"][:n])
         assert np.array_equal(ref["Rt"], r["Rt"]), "Rt is not bit-identical with ransac_pnp on the compacted arrays"
     else:
