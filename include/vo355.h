@@ -870,6 +870,37 @@ typedef struct vo_direct_rec {
 int vo_direct_align(vo_ctx* ctx, int slot_a, int slot_b, const double* K4, const double* Rt0 /*12*/, int levels, int iters, int max_points,
                     int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_rec* rec_out);
 
+/* The dense direct alignment with an AFFINE BRIGHTNESS term: a gain k and an offset m of image B are estimated beside the pose, for
+ * pairs whose exposure moved (vo_direct_align assumes brightness constancy).  Defined operation by operation like vo_direct_align
+ * (tests/direct_ab_ref.py restates it); EVERYTHING through I_b is vo_direct_align's: pyramid, rectangle, lattice, selection, the 3-D
+ * point, the test of taking part, the bilinear sample; so are the float64 rules (every product and sum rounded on its own) and the
+ * order of the sums over the points.  What differs:
+ *   State: (k, m) starts at (1, 0) and is carried over iterations AND levels (the brightness of a pair does not depend on the level).
+ *   Residual: r = (k I_b + m) - A[y][x]; w = 1 for |r| <= huber, else huber / |r|, on this r.  The correction is applied to B so that
+ *   the pose columns can stay the TEMPLATE's: at the solution k grad I_b = grad A.
+ *   Columns: j[0..5] exactly vo_direct_align's; j[6] = I_b (dr / dk), j[7] = 1 (dr / dm).
+ *   The iteration index within a level is it = 0 .. iters - 1.  it < 2: the iteration is HELD -- the 21 + 6 sums of j[0..5], count and
+ *   wr2 with the r above, the 6 x 6 solve and the twist of vo_direct_align; (k, m) keep their values.  Otherwise it is FREE: H[k] +=
+ *   (w j[p]) j[q] over p <= q < 8 in packed row order (36), g[p] += (w j[p]) r (8), count, wr2; H d = -g by the same Cholesky scheme
+ *   on 8 unknowns; the twist from d[0..5] as ever; k <- k + d[6], m <- m + d[7].  (Why held iterations: against an image that is
+ *   still misaligned the best linear brightness fit has a slope below 1, and a pose freed together with it settles there.)
+ *   Parameters: iters 3 .. 20 (with fewer than three iterations none would be free); all other ranges are vo_direct_align's.
+ *   Status: vo_direct_align's, and -1 also when the new k or m is not finite or the new k <= 0.  The new pose, k and m are committed
+ *   together or not at all: the record returns those of the last completed iteration ((1, 0) and Rt0 when none completed).
+ *   The record: vo_direct_align's fields; k, m; unknowns = 6 or 8, the size of the last COMPLETED iteration's linearisation (6 when
+ *   none completed); sums = its H then its g: 36 + 8 for unknowns 8, 21 + 6 followed by zeros for unknowns 6; its count and wr2.
+ * One launch of one workgroup (k_direct_align_ab), ONE host synchronisation, timing brackets and errors as vo_direct_align. */
+typedef struct vo_direct_ab_rec {
+    int32_t status, iters_done, levels, unknowns;
+    vo_direct_level lv[VO_DIRECT_MAX_LEVELS];
+    double Rt[12];
+    double k, m;
+    double sums[44]; /* H (packed upper triangle in row order), g: 36 + 8, or 21 + 6 and zeros */
+    double count, wr2;
+} vo_direct_ab_rec;
+int vo_direct_align_ab(vo_ctx* ctx, int slot_a, int slot_b, const double* K4, const double* Rt0 /*12*/, int levels, int iters, int max_points,
+                       int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_ab_rec* rec_out);
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */

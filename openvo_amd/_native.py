@@ -53,7 +53,7 @@ SYMBOLS = [
     "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
     "vo_klt_track_host", "vo_klt_track", "vo_klt_pnp_pair", "vo_klt_pnp_pair_begin", "vo_klt_pnp_pair_end",
     "vo_set_sgbm_cost", "vo_get_sgbm_cost", "vo_sgbm_cost_volume",
-    "vo_direct_align",
+    "vo_direct_align", "vo_direct_align_ab",
 ]
 
 
@@ -131,6 +131,37 @@ class DirectRec(ctypes.Structure):
                     wr2_first=np.array([v.wr2_first for v in lv], np.float64), wr2_last=np.array([v.wr2_last for v in lv], np.float64),
                     Rt=np.array(self.Rt[:], np.float64).reshape(3, 4), sums=sums, information=H, g=sums[21:].copy(),
                     count=int(self.count), wr2=float(self.wr2))
+
+
+class DirectAbRec(ctypes.Structure):
+    """vo_direct_ab_rec of include/vo355.h: the record of the dense direct alignment with the affine brightness term."""
+    _fields_ = [("status", ctypes.c_int32), ("iters_done", ctypes.c_int32), ("levels", ctypes.c_int32), ("unknowns", ctypes.c_int32),
+                ("lv", DirectLevel * DIRECT_MAX_LEVELS), ("Rt", ctypes.c_double * 12), ("k", ctypes.c_double), ("m", ctypes.c_double),
+                ("sums", ctypes.c_double * 44), ("count", ctypes.c_double), ("wr2", ctypes.c_double)]
+
+    def as_dict(self):
+        n, nu = int(self.levels), int(self.unknowns)
+        if nu not in (6, 8):
+            raise ValueError("vo_direct_ab_rec: unknowns is %d, neither 6 nor 8" % nu)
+        nh = nu * (nu + 1) // 2
+        sums = np.array(self.sums[:], np.float64)
+        full = np.zeros((8, 8))
+        tri = np.zeros((nu, nu))
+        tri[np.triu_indices(nu)] = sums[:nh]             # packed upper triangle in row order
+        full[:nu, :nu] = tri + np.triu(tri, 1).T
+        g = np.zeros(8)
+        g[:nu] = sums[nh:nh + nu]
+        info = full[:6, :6].copy()
+        if nu == 8:                                      # the pose information marginalised over the brightness
+            info = info - full[:6, 6:] @ np.linalg.solve(full[6:, 6:], full[6:, :6])
+            info = 0.5 * (info + info.T)
+        lv = [self.lv[l] for l in range(n)]
+        return dict(status=int(self.status), iters_done=int(self.iters_done),
+                    s=np.array([v.s for v in lv], np.int32), selected=np.array([v.selected for v in lv], np.int32),
+                    n_first=np.array([v.n_first for v in lv], np.int32), n_last=np.array([v.n_last for v in lv], np.int32),
+                    wr2_first=np.array([v.wr2_first for v in lv], np.float64), wr2_last=np.array([v.wr2_last for v in lv], np.float64),
+                    Rt=np.array(self.Rt[:], np.float64).reshape(3, 4), gain=float(self.k), offset=float(self.m), unknowns=nu, sums=sums,
+                    information_full=full, information=info, g=g, count=int(self.count), wr2=float(self.wr2))
 
 
 MAP_TRACK_MAX = 3800     # VO_MAP_TRACK_MAX: the largest map the fused map step takes
@@ -338,9 +369,9 @@ def lib():
             for name, proto in (("vo_set_sgbm_cost", [vp, ci, ci, ci]), ("vo_get_sgbm_cost", [vp, vp, vp, vp]),
                                 ("vo_sgbm_cost_volume", [vp, vp, ctypes.c_size_t])):
                 getattr(L, name).argtypes = proto
-        if hasattr(L, "vo_direct_align"):           # (likewise: an older build has no dense direct alignment)
-            for name, proto in (("vo_direct_align", [vp, ci, ci, vp, vp, ci, ci, ci, ci, cd, cd, cd, cd, ci, vp]),):
-                getattr(L, name).argtypes = proto
+        for name in ("vo_direct_align", "vo_direct_align_ab"):      # (likewise: an older build has no dense direct alignment, or no affine term)
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, cd, cd, cd, cd, ci, vp]
         plant = getattr(L, "vo_test_plant_dense_pair", None)     # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp]
@@ -1133,22 +1164,32 @@ class Context:
         return (int(levels), int(iters), int(max_points), int(grad_min), float(huber), float(dmin), float(dmax), float(z_min), int(min_pixels))
 
     def direct_align(self, slot_a, slot_b, K4, Rt0=None, levels=3, iters=8, max_points=16384, grad_min=8, huber=10.0, dmin=4.0, dmax=100.0,
-                     z_min=0.1, min_pixels=64):
+                     z_min=0.1, min_pixels=64, affine=False):
         """Photometric refinement of the a -> b motion on slot_a's dense disparity (vo_direct_align, include/vo355.h): slot_a's
         rectified left image and disparity against slot_b's rectified left image, from Rt0 (3 x 4 or 4 x 4, X' = R X + t; None: the
         identity), one launch and one synchronisation.  -> dict: status (0 all iterations ran | 2 starved | -1 numeric), iters_done,
         per level s / selected / n_first / n_last / wr2_first / wr2_last, Rt (3, 4), information (6, 6: sum w j j^T of the last
-        completed linearisation, rotation then translation), g (6), count, wr2, sums (the 27 raw sums)."""
-        if not hasattr(self._lib, "vo_direct_align"):
-            raise RuntimeError("this build of the library has no dense direct alignment (vo_direct_align)")
+        completed linearisation, rotation then translation), g (6), count, wr2, sums (the 27 raw sums).
+        affine=True (vo_direct_align_ab; iters 3 .. 20): a gain and an offset of slot_b's brightness are estimated beside the pose,
+        from the third iteration of every level on.  The dict then adds gain, offset, unknowns (6 or 8: the size of the last completed
+        linearisation), information_full (8, 8: pose, gain, offset; zero outside the 6 x 6 block when unknowns == 6); sums are the 44
+        raw sums, g has 8 entries, and information is the pose information MARGINALISED over the brightness, H_pp - H_pb H_bb^-1 H_bp
+        (the plain 6 x 6 when unknowns == 6)."""
+        if not isinstance(affine, (bool, np.bool_)):
+            raise ValueError("affine must be True or False")
+        entry = "vo_direct_align_ab" if affine else "vo_direct_align"
+        if not hasattr(self._lib, entry):
+            raise RuntimeError("this build of the library has no dense direct alignment (%s)" % entry)
         prm = self.direct_params(levels, iters, max_points, grad_min, huber, dmin, dmax, z_min, min_pixels)
+        if affine and prm[1] < 3:
+            raise ValueError("affine=True needs iters in 3 .. 20 (the first two iterations of a level hold the brightness), not %r" % (iters,))
         K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
         Rt = np.eye(4)[:3] if Rt0 is None else np.asarray(Rt0, np.float64)
         if Rt.shape == (4, 4):
             Rt = Rt[:3]
         Rt = _c(Rt.reshape(12), np.float64)
-        rec = DirectRec()
-        self._ck(self._lib.vo_direct_align(self._h, int(slot_a), int(slot_b), _p(K4), _p(Rt), *prm, ctypes.byref(rec)))
+        rec = DirectAbRec() if affine else DirectRec()
+        self._ck(getattr(self._lib, entry)(self._h, int(slot_a), int(slot_b), _p(K4), _p(Rt), *prm, ctypes.byref(rec)))
         return rec.as_dict()
 
     def plant_dense_pair(self, slot, left, disp16, xy, desc=None):

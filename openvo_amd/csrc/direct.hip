@@ -164,17 +164,194 @@ __global__ void __launch_bounds__(BLOCK) k_direct_align(DirectPrm P, vo_direct_r
     }
 }
 
+// ---- the affine brightness form (include/vo355.h, vo_direct_align_ab; tests/direct_ab_ref.py restates it) -------------------------------
+//   k_direct_align_ab  a sibling of k_direct_align with the same ownership, loops, reads and sum order; the state carries the gain k
+//                      and the offset m of image B beside the pose (LDS, thread 0 commits all three together), the residual is
+//                      (k I_b + m) - A, and an iteration is HELD (it < 2: the 29 sums of the six pose unknowns) or FREE (the 46 sums
+//                      of eight unknowns: j[6] = I_b, j[7] = 1).  `it` is the same in every thread, so the branch between the two
+//                      accumulation loops is uniform; a held iteration touches 29 accumulators, a free one 46.
+template <int NU> struct DirectAbN { static constexpr int NH = NU * (NU + 1) / 2, NS = NH + NU + 2; };
+#define VO_DIRECT_AB_NS 46
+
+// One thread's part of an iteration with NU unknowns, then the wave's: the NS sums of wave wv into red[wv], its selected count into sel.
+template <int BLOCK, int NU>
+__device__ __forceinline__ void direct_ab_sums(const DirectPrm& P, const DirectLevel& lv, int L, const double* __restrict__ pose, double bk, double bm,
+                                               double (*red)[VO_DIRECT_AB_NS], int* s_sel)
+{
+    constexpr int NH = DirectAbN<NU>::NH, NS = DirectAbN<NU>::NS;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint8_t* __restrict__ A = lv.A;
+    const uint8_t* __restrict__ B = lv.B;
+    const double xlo = (double)lv.x_lo, xhi1 = (double)(lv.x_hi - 1), ylo = (double)lv.y_lo, yhi1 = (double)(lv.y_hi - 1);
+    double R[12], acc[NS];
+#pragma unroll
+    for (int k = 0; k < 12; k++) R[k] = pose[k];
+#pragma unroll
+    for (int k = 0; k < NS; k++) acc[k] = 0.0;
+    int sel = 0;
+    for (int idx = threadIdx.x; idx < lv.n; idx += BLOCK) {
+        const int j = idx / lv.nx, i = idx - j * lv.nx;
+        const int x = lv.x_lo + 1 + i * lv.s, y = lv.y_lo + 1 + j * lv.s;
+        const int d16 = P.disp16[(size_t)(y << L) * P.w0 + (x << L)];
+        if (!((double)d16 >= P.d16_lo && (double)d16 <= P.d16_hi)) continue;
+        const uint8_t* a = A + (size_t)y * lv.w + x;
+        const int gx2 = (int)a[1] - (int)a[-1], gy2 = (int)a[lv.w] - (int)a[-lv.w];
+        if (gx2 * gx2 + gy2 * gy2 < P.g2min) continue;
+        sel++;
+        const double d = (double)d16 / 16.0;
+        const double W = P.q32 * d + P.q33;
+        const double X = ((double)(x << L) + P.q03) / W, Y = ((double)(y << L) + P.q13) / W, Z = P.q23 / W;
+        const double xc = ((R[0] * X + R[1] * Y) + R[2] * Z) + R[3];
+        const double yc = ((R[4] * X + R[5] * Y) + R[6] * Z) + R[7];
+        const double zc = ((R[8] * X + R[9] * Y) + R[10] * Z) + R[11];
+        if (!(zc > P.z_min)) continue;
+        const double u = (lv.fx * xc) / zc + lv.cx, v = (lv.fy * yc) / zc + lv.cy;
+        if (!(u >= xlo && u < xhi1 && v >= ylo && v < yhi1)) continue;       // (false for a NaN: nothing is read for it)
+        const double fu = floor(u), fv = floor(v);
+        const double ax = u - fu, ay = v - fv;
+        const uint8_t* b = B + (size_t)(int)fv * lv.w + (int)fu;
+        const double b00 = (double)b[0], b01 = (double)b[1], b10 = (double)b[lv.w], b11 = (double)b[lv.w + 1];
+        const double Ib = (b00 * (1.0 - ax) + b01 * ax) * (1.0 - ay) + (b10 * (1.0 - ax) + b11 * ax) * ay;
+        const double r = (bk * Ib + bm) - (double)a[0];
+        const double ar = fabs(r);
+        const double wt = ar <= P.huber ? 1.0 : P.huber / ar;
+        const double gfx = (0.5 * (double)gx2) * lv.fx, gfy = (0.5 * (double)gy2) * lv.fy;
+        const double a0 = gfx / zc, a1 = gfy / zc, a2 = -((gfx * xc + gfy * yc) / (zc * zc));
+        double jv[NU];
+        jv[0] = yc * a2 - zc * a1; jv[1] = zc * a0 - xc * a2; jv[2] = xc * a1 - yc * a0; jv[3] = a0; jv[4] = a1; jv[5] = a2;
+        if constexpr (NU == 8) { jv[6] = Ib; jv[7] = 1.0; }
+        double wj[NU];
+#pragma unroll
+        for (int p = 0; p < NU; p++) wj[p] = wt * jv[p];
+#pragma unroll
+        for (int p = 0, k = 0; p < NU; p++)
+#pragma unroll
+            for (int q = p; q < NU; q++, k++) acc[k] += wj[p] * jv[q];
+#pragma unroll
+        for (int p = 0; p < NU; p++) acc[NH + p] += wj[p] * r;
+        acc[NH + NU] += 1.0;
+        acc[NH + NU + 1] += (wt * r) * r;
+    }
+#pragma unroll
+    for (int k = 0; k < NS; k++) {
+        const double sum = wave_sum_f64_dpp(acc[k]);
+        if (lane == 0) red[wv][k] = sum;
+    }
+    for (int o = 32; o > 0; o >>= 1) sel += __shfl_xor(sel, o, 64);
+    if (lane == 0) s_sel[wv] = sel;
+}
+
+// The end of an iteration with NU unknowns in one lane, as direct_step: S = the NS sums of the block.  The new pose, k and m are
+// committed together or not at all; km = {k, m}; last = the sums of the last completed linearisation, *unknowns its size.
+template <int NU>
+__device__ __noinline__ void direct_ab_step(const double* S, const int* sel, int nw, bool first, int min_pixels, double* pose, double* km, double* last,
+                                            int* unknowns, vo_direct_level* lv, int* status, int* done)
+{
+    constexpr int NH = DirectAbN<NU>::NH, NS = DirectAbN<NU>::NS;
+    const int n = (int)S[NH + NU];
+    if (first) {
+        int nsel = 0;
+        for (int q = 0; q < nw; q++) nsel += sel[q];
+        lv->selected = nsel; lv->n_first = n; lv->wr2_first = S[NH + NU + 1];
+    }
+    lv->n_last = n; lv->wr2_last = S[NH + NU + 1];
+    if (n < min_pixels) { *status = 2; return; }
+    double H[NH], g[NU], d[NU];
+#pragma unroll
+    for (int k = 0; k < NU; k++) d[k] = 0.0;
+    bool ok = isfinite(S[NH + NU + 1]);
+#pragma unroll
+    for (int k = 0; k < NH; k++) { H[k] = S[k]; ok = ok && isfinite(H[k]); }
+#pragma unroll
+    for (int k = 0; k < NU; k++) { g[k] = S[NH + k]; ok = ok && isfinite(g[k]); }
+    ok = ok && pn_solve<NU>(H, g, d);
+    double Rn[12], kn = km[0], mn = km[1];
+#pragma unroll
+    for (int k = 0; k < 12; k++) Rn[k] = pose[k];
+    if (ok) {
+        pn_apply_twist(Rn, d);
+        if constexpr (NU == 8) { kn = kn + d[6]; mn = mn + d[7]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) ok = ok && isfinite(Rn[k]);
+    ok = ok && isfinite(kn) && isfinite(mn) && kn > 0.0;
+    if (!ok) { *status = -1; return; }
+#pragma unroll
+    for (int k = 0; k < 12; k++) pose[k] = Rn[k];
+    km[0] = kn; km[1] = mn;
+    for (int k = 0; k < NS; k++) last[k] = S[k];
+    *unknowns = NU;
+    *done = *done + 1;
+}
+
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_direct_align_ab(DirectPrm P, vo_direct_ab_rec* __restrict__ rec)
+{
+    constexpr int NW = BLOCK / 64, NS = VO_DIRECT_AB_NS;
+    static_assert(DirectAbN<8>::NS == NS && DirectAbN<6>::NS == 29, "the sums of a free and of a held iteration");
+    __shared__ double s_red[NW][NS], s_sum[NS], s_pose[12], s_km[2], s_last[NS];
+    __shared__ int s_sel[NW], s_status, s_done, s_unknowns;
+    __shared__ vo_direct_level s_lv[VO_DIRECT_MAX_LEVELS];
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 12; k++) s_pose[k] = P.Rt0[k];
+        for (int k = 0; k < NS; k++) s_last[k] = 0.0;
+        s_km[0] = 1.0; s_km[1] = 0.0;
+        for (int l = 0; l < VO_DIRECT_MAX_LEVELS; l++) {
+            s_lv[l].s = l < P.levels ? P.lv[l].s : 0;
+            s_lv[l].selected = s_lv[l].n_first = s_lv[l].n_last = 0;
+            s_lv[l].wr2_first = s_lv[l].wr2_last = 0.0;
+        }
+        s_status = 0; s_done = 0; s_unknowns = 6;
+    }
+    __syncthreads();
+    bool stop = false;
+    for (int L = P.levels - 1; L >= 0 && !stop; --L) {
+        const DirectLevel lv = P.lv[L];
+        for (int it = 0; it < P.iters; it++) {
+            const bool held = it < 2;                  // (the same in every thread)
+            const int ns = held ? DirectAbN<6>::NS : NS;
+            if (held) direct_ab_sums<BLOCK, 6>(P, lv, L, s_pose, s_km[0], s_km[1], s_red, s_sel);
+            else direct_ab_sums<BLOCK, 8>(P, lv, L, s_pose, s_km[0], s_km[1], s_red, s_sel);
+            __syncthreads();
+            if ((int)threadIdx.x < ns) {               // the waves' values in wave order, one sum per thread
+                double sum = s_red[0][threadIdx.x];
+#pragma unroll
+                for (int q = 1; q < NW; q++) sum += s_red[q][threadIdx.x];
+                s_sum[threadIdx.x] = sum;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                if (held) direct_ab_step<6>(s_sum, s_sel, NW, it == 0, P.min_pixels, s_pose, s_km, s_last, &s_unknowns, &s_lv[L], &s_status, &s_done);
+                else direct_ab_step<8>(s_sum, s_sel, NW, it == 0, P.min_pixels, s_pose, s_km, s_last, &s_unknowns, &s_lv[L], &s_status, &s_done);
+            }
+            __syncthreads();
+            if (s_status != 0) { stop = true; break; }
+        }
+    }
+    if (threadIdx.x == 0) {
+        const int nu = s_unknowns, nh = nu * (nu + 1) / 2;
+        rec->status = s_status; rec->iters_done = s_done; rec->levels = P.levels; rec->unknowns = nu;
+        for (int l = 0; l < VO_DIRECT_MAX_LEVELS; l++) rec->lv[l] = s_lv[l];
+        for (int k = 0; k < 12; k++) rec->Rt[k] = s_pose[k];
+        rec->k = s_km[0]; rec->m = s_km[1];
+        for (int k = 0; k < 44; k++) rec->sums[k] = k < nh + nu ? s_last[k] : 0.0;
+        rec->count = s_last[nh + nu]; rec->wr2 = s_last[nh + nu + 1];
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 static inline int direct_lattice_n(int lo, int hi, int s) { return hi - lo - 2 > 0 ? (hi - lo - 2 + s - 1) / s : 0; }
 
-extern "C" int vo_direct_align(vo_ctx* ctx, int slot_a, int slot_b, const double* K4v, const double* Rt0, int levels, int iters, int max_points,
-                               int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_rec* rec_out)
+// Both entries: the checks, the pyramids, the parameters, the one launch (ab: k_direct_align_ab, whose iters start at 3) and the
+// one synchronisation; rec_out is a vo_direct_rec or a vo_direct_ab_rec.
+static int direct_align_run(vo_ctx* ctx, const char* who, bool ab, int slot_a, int slot_b, const double* K4v, const double* Rt0, int levels, int iters,
+                            int max_points, int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, void* rec_out)
 {
-    const char* who = "vo_direct_align";
+    const int iters_lo = ab ? 3 : 1;
     if (!ctx || slot_a < 0 || slot_a >= VO_NUM_SLOTS || slot_b < 0 || slot_b >= VO_NUM_SLOTS || !K4v || !Rt0 || !rec_out)
         return vo_fail(ctx, VO_E_ARG, "%s: bad argument", who);
     if (levels < 1 || levels > VO_DIRECT_MAX_LEVELS) return vo_fail(ctx, VO_E_ARG, "%s: levels %d (1 .. %d)", who, levels, VO_DIRECT_MAX_LEVELS);
-    if (iters < 1 || iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: iters %d (1 .. 20)", who, iters);
+    if (iters < iters_lo || iters > 20) return vo_fail(ctx, VO_E_ARG, "%s: iters %d (%d .. 20)", who, iters, iters_lo);
     if (max_points < 1) return vo_fail(ctx, VO_E_ARG, "%s: max_points %d (>= 1)", who, max_points);
     if (grad_min < 0 || grad_min > 255) return vo_fail(ctx, VO_E_ARG, "%s: grad_min %d (0 .. 255)", who, grad_min);
     if (min_pixels < 6) return vo_fail(ctx, VO_E_ARG, "%s: min_pixels %d (>= 6)", who, min_pixels);
@@ -223,15 +400,30 @@ extern "C" int vo_direct_align(vo_ctx* ctx, int slot_a, int slot_b, const double
     P.d16_lo = 16.0 * dmin; P.d16_hi = 16.0 * dmax; P.huber = huber; P.z_min = z_min;
     P.q03 = ctx->Q[3]; P.q13 = ctx->Q[7]; P.q23 = ctx->Q[11]; P.q32 = ctx->Q[14]; P.q33 = ctx->Q[15];
     for (int k = 0; k < 12; k++) P.Rt0[k] = Rt0[k];
-    vo_direct_rec* rec = (vo_direct_rec*)ctx->pinned;
-    memset(rec, 0, sizeof(*rec));
+    const size_t rec_bytes = ab ? sizeof(vo_direct_ab_rec) : sizeof(vo_direct_rec);
+    memset(ctx->pinned, 0, rec_bytes);
     {
         StageTimer t(ctx, VO_T_POSE);
-        hipLaunchKernelGGL(k_direct_align<VO_DIRECT_BLOCK>, dim3(1), dim3(VO_DIRECT_BLOCK), 0, ctx->stream, P, rec);
+        if (ab) hipLaunchKernelGGL(k_direct_align_ab<VO_DIRECT_BLOCK>, dim3(1), dim3(VO_DIRECT_BLOCK), 0, ctx->stream, P, (vo_direct_ab_rec*)ctx->pinned);
+        else hipLaunchKernelGGL(k_direct_align<VO_DIRECT_BLOCK>, dim3(1), dim3(VO_DIRECT_BLOCK), 0, ctx->stream, P, (vo_direct_rec*)ctx->pinned);
         VO_CHECK_LAUNCH(ctx);
     }
     if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
     if ((rc = slot_health(ctx, a, slot_a))) return rc;       // never a pose from an undefined disparity (b's is not read)
-    memcpy(rec_out, rec, sizeof(*rec));
+    memcpy(rec_out, ctx->pinned, rec_bytes);
     return VO_OK;
+}
+
+extern "C" int vo_direct_align(vo_ctx* ctx, int slot_a, int slot_b, const double* K4v, const double* Rt0, int levels, int iters, int max_points,
+                               int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_rec* rec_out)
+{
+    return direct_align_run(ctx, "vo_direct_align", false, slot_a, slot_b, K4v, Rt0, levels, iters, max_points, grad_min, huber, dmin, dmax, z_min,
+                            min_pixels, rec_out);
+}
+
+extern "C" int vo_direct_align_ab(vo_ctx* ctx, int slot_a, int slot_b, const double* K4v, const double* Rt0, int levels, int iters, int max_points,
+                                  int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_ab_rec* rec_out)
+{
+    return direct_align_run(ctx, "vo_direct_align_ab", true, slot_a, slot_b, K4v, Rt0, levels, iters, max_points, grad_min, huber, dmin, dmax, z_min,
+                            min_pixels, rec_out);
 }

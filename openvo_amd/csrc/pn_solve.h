@@ -1,20 +1,22 @@
-// The 6 x 6 solve and the twist update of a Gauss-Newton step, shared by the PnP refit (ransac.hip: pn_gn_step) and the direct
-// alignment (direct.hip: k_direct_align): both compile this text.
+// The N x N solve and the twist update of a Gauss-Newton step, shared by the PnP refit (ransac.hip: pn_gn_step) and the direct
+// alignment (direct.hip: k_direct_align with 6 unknowns, k_direct_align_ab with 6 and 8): all compile this text.
 #pragma once
 #include <math.h>
 
-// One Gauss-Newton step's solve in one lane: H (6x6, symmetric, upper triangle in packed row order) d = -g by Cholesky, every index
-// a compile-time constant so that the factor stays in registers.  false: a pivot was not positive.
-__device__ __forceinline__ bool pn_solve6(const double* Hp, const double* g, double* d)
+// One Gauss-Newton step's solve in one lane: H (N x N, symmetric, upper triangle in packed row order) d = -g by Cholesky, every index
+// a compile-time constant so that the factor stays in registers.  false: a pivot was not positive.  The operations of an unknown
+// depend on N only through the loop bounds, so N = 6 is the sequence of operations pn_solve6 has always been.
+template <int N>
+__device__ __forceinline__ bool pn_solve(const double* Hp, const double* g, double* d)
 {
-    double L[6][6];
+    double L[N][N];
 #pragma unroll
-    for (int i = 0, k = 0; i < 6; i++)
+    for (int i = 0, k = 0; i < N; i++)
 #pragma unroll
-        for (int j = i; j < 6; j++, k++) L[j][i] = Hp[k];
+        for (int j = i; j < N; j++, k++) L[j][i] = Hp[k];
     bool ok = true;
 #pragma unroll
-    for (int j = 0; j < 6; j++) {
+    for (int j = 0; j < N; j++) {
         double s = L[j][j];
 #pragma unroll
         for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
@@ -22,30 +24,32 @@ __device__ __forceinline__ bool pn_solve6(const double* Hp, const double* g, dou
         const double dj = sqrt(s);
         L[j][j] = dj;
 #pragma unroll
-        for (int i = j + 1; i < 6; i++) {
+        for (int i = j + 1; i < N; i++) {
             double v = L[i][j];
 #pragma unroll
             for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
             L[i][j] = v / dj;
         }
     }
-    double y[6];
+    double y[N];
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
+    for (int i = 0; i < N; i++) {
         double v = -g[i];
 #pragma unroll
         for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
         y[i] = v / L[i][i];
     }
 #pragma unroll
-    for (int i = 5; i >= 0; i--) {
+    for (int i = N - 1; i >= 0; i--) {
         double v = y[i];
 #pragma unroll
-        for (int k = i + 1; k < 6; k++) v -= L[k][i] * d[k];
+        for (int k = i + 1; k < N; k++) v -= L[k][i] * d[k];
         d[i] = v / L[i][i];
     }
     return ok;
 }
+
+__device__ __forceinline__ bool pn_solve6(const double* Hp, const double* g, double* d) { return pn_solve<6>(Hp, g, d); }
 
 // Rt <- [Exp(w) R | Exp(w) t + v]   (Rodrigues; the series below 1e-4 rad, where sin / cos lose digits in the quotients)
 __device__ __forceinline__ void pn_apply_twist(double* Rt, const double* d)

@@ -36,7 +36,8 @@ class StereoOdometer:
                  match_window=None, depth="dense", sparse_row_tol=2.0, sparse_max_hamming=75, sparse_mutual=False, sparse_ratio=None,
                  loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False,
                  pnp_lo_rounds=0, match="orb", klt_window=21, klt_levels=4, klt_fb=1.0, klt_fused=False,
-                 direct_refine=False, direct_levels=3, direct_iters=8, direct_max_points=16384, direct_guard=(0.1, 0.05)):
+                 direct_refine=False, direct_levels=3, direct_iters=8, direct_max_points=16384, direct_guard=(0.1, 0.05),
+                 direct_affine=False):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -134,7 +135,13 @@ class StereoOdometer:
         The default is sized for pose_method="pnp", whose poses are centimetres off.  With pose_method="umeyama" WIDEN IT: the
         3-D / 3-D fit can be decimetres off per pair, the default guard then refuses most refined poses, and a chain in which
         only some pairs are corrected can end farther from the truth than the unrefined one (measured on the synthetic corridor
-        T0: 0.3655 m against 0.3197 m unrefined with the default guard, 0.0025 m with direct_guard=(0.5, 0.1))."""
+        T0: 0.3655 m against 0.3197 m unrefined with the default guard, 0.0025 m with direct_guard=(0.5, 0.1)).
+        direct_affine=True (default False; read only with direct_refine=True; needs direct_iters >= 3): the alignment estimates a
+        gain and an offset of the newer image's brightness beside the pose (vo_direct_align_ab), for streams whose exposure moves
+        between frames: the plain alignment assumes brightness constancy and walks away from the pose when it does not hold.
+        direct_brightness is (gain, offset) of the last step, None when that step completed fewer than three iterations (none that estimates them);
+        pose_information is then the pose information marginalised over the brightness.  Guard, gates and status handling are
+        unchanged."""
         if not isinstance(track, str) or track not in ("pair", "map"):
             raise ValueError("track must be 'pair' or 'map'")
         if track == "map" and (depth != "sparse" or pose_method != "pnp"):
@@ -246,6 +253,13 @@ class StereoOdometer:
             self.direct_status = self.direct_record = self.pose_information = None
             self.direct_accepted = False
             self._direct_pair = None     # (slot a, slot b) of the pair being tried, None while its frames are not on the device
+            if not isinstance(direct_affine, (bool, np.bool_)):
+                raise ValueError("direct_affine must be True or False")
+            if direct_affine:
+                if self.direct_iters < 3:
+                    raise ValueError("direct_affine=True needs direct_iters >= 3 (the first two iterations of a level hold the brightness)")
+                self.direct_affine = True        # (instance attributes only in affine mode, as above)
+                self.direct_brightness = None
         self.pose_method, self.pnp_iters, self.pnp_threshold, self.pnp_seed = pose_method, pnp_iters, pnp_threshold, pnp_seed
         self.stereo = stereo_camera
         self.current_img = self.current_disparity = self.current_3d = None
@@ -490,6 +504,8 @@ class StereoOdometer:
     pnp_lo_counts = None     # (rounds completed, support) of the last fused step with pnp_lo_rounds > 0
     map_fused = False        # True (constructor): the map step is one native call (_map_track_fused)
     direct_refine = False    # True (constructor): every pair pose goes through the dense direct alignment before the gates (_direct)
+    direct_affine = False    # True (constructor): the alignment estimates a gain and an offset of the newer image beside the pose
+    direct_brightness = None  # (gain, offset) of the last step in affine mode; None when the step gave none
     _map_size = 0            # landmarks in the map as its last update reported (set with the first fold)
     _pnp_fused = True        # False: pose_method="pnp" takes the composed path (_pair_pnp) whatever the conditions
     _PNP_CTX_SEAMS = ("point_clouds", "ransac_pnp")
@@ -1098,8 +1114,11 @@ class StereoOdometer:
         Q = self.stereo.Q
         K4 = [Q[2, 3], Q[2, 3], -Q[0, 3], -Q[1, 3]]
         r = self._ctx.direct_align(self._direct_pair[0], self._direct_pair[1], K4, T[:3], levels=self.direct_levels, iters=self.direct_iters,
-                                   max_points=self.direct_max_points, dmin=self.MIN_VALID_DISPARITY, dmax=self.MAX_VALID_DISPARITY)
+                                   max_points=self.direct_max_points, dmin=self.MIN_VALID_DISPARITY, dmax=self.MAX_VALID_DISPARITY,
+                                   **(dict(affine=True) if self.direct_affine else {}))
         self.direct_status, self.direct_record, self.direct_accepted = r["status"], r, False
+        if self.direct_affine:                          # (an estimate exists once a free iteration completed: the third is the first)
+            self.direct_brightness = (r["gain"], r["offset"]) if r["iters_done"] >= 3 else None
         self.pose_information = None                    # (of the pose this step delivers, never of an older one)
         if r["status"] != 0 or not np.isfinite(r["Rt"]).all():
             return T

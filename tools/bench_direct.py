@@ -6,7 +6,11 @@ StereoOdometer.update() loops and of StereoOdometer.run() with and without direc
 alternating inside every round.  Prints one JSON line.  Needs a GPU: there is no fallback.  Reads nothing but the package (the
 synthetic corridor).
 
-    python tools/bench_direct.py [--pairs 240] [--rounds 3] [--step-calls 200]"""
+    python tools/bench_direct.py [--pairs 240] [--rounds 3] [--step-calls 200]
+
+--affine: the step alone and nothing else, plain (vo_direct_align) and affine (vo_direct_align_ab: a gain and an offset estimated beside
+the pose) ALTERNATING inside every one of --rounds rounds of the same process, at both point counts; per round the medians of both and
+the ratio affine / plain of that round."""
 import argparse
 import json
 import os
@@ -17,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--pairs", type=int, default=240, help="pairs per timed pass")
 ap.add_argument("--rounds", type=int, default=3, help="timed passes per mode, after one warm-up pass")
 ap.add_argument("--step-calls", type=int, default=200, help="timed calls of the step per point count")
+ap.add_argument("--affine", action="store_true", help="the step alone, plain and affine alternating in every round")
 args = ap.parse_args()
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
@@ -40,29 +45,59 @@ def stats(v):
 
 
 # ---------------------------------------------------------------------------------------------- the step alone
-def step_alone():
-    x3a, _, _ = cam.compute_3d(*stream[0], preprocessed=True)
-    x3b, _, _ = cam.compute_3d(*stream[1], preprocessed=True)
-    sa, sb = x3a.frame.slot, x3b.frame.slot
-    kw = dict(dmin=StereoOdometer.MIN_VALID_DISPARITY, dmax=StereoOdometer.MAX_VALID_DISPARITY)
-    out = {}
-    for n in (16384, 65536):
-        wall, kern, r = [], [], None
-        for step in range(-10, args.step_calls):
-            ctx.enable_timing(step >= 0)
-            t0 = time.perf_counter()
-            r = ctx.direct_align(sa, sb, K4, max_points=n, **kw)
-            dt = 1e6 * (time.perf_counter() - t0)
-            if step < 0:
-                continue
-            t = ctx.timings(reset=True)
-            wall.append(dt)
-            kern.append(1e3 * t["pose"][0])
-        ctx.enable_timing(False)
-        out[str(n)] = dict(status=r["status"], iters_done=r["iters_done"], s=r["s"].tolist(), selected=r["selected"].tolist(),
-                           participants_last=r["n_last"].tolist(), call_us=stats(wall), kernel_us=stats(kern))
+def timed_step(sa, sb, n, **kw):
+    """median / p10 / p90 of --step-calls synchronous calls after 10 warm-up calls: the call's wall time and the kernel's event bracket"""
+    wall, kern, r = [], [], None
+    for step in range(-10, args.step_calls):
+        ctx.enable_timing(step >= 0)
+        t0 = time.perf_counter()
+        r = ctx.direct_align(sa, sb, K4, max_points=n, dmin=StereoOdometer.MIN_VALID_DISPARITY, dmax=StereoOdometer.MAX_VALID_DISPARITY, **kw)
+        dt = 1e6 * (time.perf_counter() - t0)
+        if step < 0:
+            continue
+        t = ctx.timings(reset=True)
+        wall.append(dt)
+        kern.append(1e3 * t["pose"][0])
+    ctx.enable_timing(False)
+    out = dict(status=r["status"], iters_done=r["iters_done"], s=r["s"].tolist(), selected=r["selected"].tolist(),
+               participants_last=r["n_last"].tolist(), call_us=stats(wall), kernel_us=stats(kern))
+    if "gain" in r:
+        out.update(gain=round(r["gain"], 5), offset=round(r["offset"], 4), unknowns=r["unknowns"])
     return out
 
+
+def step_slots():
+    x3a, _, _ = cam.compute_3d(*stream[0], preprocessed=True)
+    x3b, _, _ = cam.compute_3d(*stream[1], preprocessed=True)
+    return x3a.frame.slot, x3b.frame.slot
+
+
+def step_alone():
+    sa, sb = step_slots()
+    return {str(n): timed_step(sa, sb, n) for n in (16384, 65536)}
+
+
+def step_plain_and_affine():
+    sa, sb = step_slots()
+    out = {}
+    for n in (16384, 65536):
+        rounds = []
+        for _ in range(args.rounds):                   # plain and affine alternate inside every round
+            plain, affine = timed_step(sa, sb, n), timed_step(sa, sb, n, affine=True)
+            rounds.append(dict(plain=plain, affine=affine,
+                               kernel_affine_over_plain=round(affine["kernel_us"]["median"] / plain["kernel_us"]["median"], 3),
+                               call_affine_over_plain=round(affine["call_us"]["median"] / plain["call_us"]["median"], 3)))
+        out[str(n)] = rounds
+    return out
+
+
+if args.affine:
+    result["workload"] = "C2 1280x720, two slots of the stream, from the identity, 3 levels x 8 iterations (synthetic corridor, one GPU)"
+    result["rounds"] = args.rounds
+    result["step_plain_and_affine"] = step_plain_and_affine()
+    ctx.close()
+    print(json.dumps(result))
+    sys.exit(0)
 
 result["step"] = step_alone()
 
