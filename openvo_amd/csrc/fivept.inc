@@ -116,8 +116,7 @@ __device__ __forceinline__ int fp_roots_unit_par(const double* c, double* brk, i
 
 // what k_ransac_hyp5 hands to k_ransac_roots5 per hypothesis, element-major ([element][hypothesis]: lanes write neighbours):
 // det B(z) scaled to max |coefficient| 1 (11), B (3 x 3 polynomials of degree 4: 45), the entries of E as polynomials in
-// (x, y, z, 1) (36), the sixth match (4), a flag (1: the reductions did not hit a singular system)
-#define FP_REC_DOUBLES 97
+// (x, y, z, 1) (36), the sixth match (4), a flag (1: the reductions did not hit a singular system): FP_REC_DOUBLES (ransac_ws.h)
 
 // x1, x2: 5 normalised points each (interleaved) -> this hypothesis' record (rec[e * stride]); false when a reduction hits a
 // singular system (the hypothesis then scores nothing).  lds: this lane's column of the wave's LDS block (element e at
@@ -383,16 +382,7 @@ __global__ void __launch_bounds__(64) k_ransac_hyp5(const float* __restrict__ p1
     const size_t stride = (size_t)iters;
     if (n < 6) { my[96 * stride] = 0.0; return; }
     int idx[6];
-    for (int j = 0; j < 6; j++) {
-        uint32_t attempt = 0;
-        for (;;) {
-            uint32_t r = lowbias32(seed ^ lowbias32((uint32_t)h * 0x9E3779B9u + (uint32_t)j * 0x85EBCA6Bu + attempt * 0xC2B2AE35u));
-            int cand = (int)(r % (uint32_t)n), dup = 0;
-            for (int k = 0; k < j; k++) dup |= idx[k] == cand;
-            if (!dup || attempt >= 64) { idx[j] = cand; break; }
-            attempt++;
-        }
-    }
+    rs_sample_distinct<6>(seed, h, n, idx);
     double a[12], b[12];
     for (int s = 0; s < 6; s++) {
         const int i = idx[s];

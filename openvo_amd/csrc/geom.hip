@@ -689,12 +689,7 @@ extern "C" int vo_rigid_clique(vo_ctx* ctx, const float* prev, const float* cur,
     if (m > ctx->kp_cap || (size_t)m * 12 > 150 * 1024) return vo_fail(ctx, VO_E_CAP, "m=%d exceeds capacity", m);
     VO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t need = (size_t)m * m + (size_t)m * 4 * 3 + (size_t)m * 8 + 1024;
-    if (ctx->mw->clique_ws_bytes < need) {
-        if (ctx->mw->clique_ws) (void)hipFree(ctx->mw->clique_ws);
-        ctx->mw->clique_ws = nullptr; ctx->mw->clique_ws_bytes = 0;
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->clique_ws, need));
-        ctx->mw->clique_ws_bytes = need;
-    }
+    if (int rcw = ws_reserve(ctx, &ctx->mw->clique_ws, &ctx->mw->clique_ws_bytes, need)) return rcw;
     StageTimer t(ctx, VO_T_POSE);
     // carve: mask(8m) | ncons(4m) | clique(4m) | compat(4m) | cons(m*m)
     long long* d_mask = (long long*)ctx->mw->clique_ws;
@@ -1364,12 +1359,7 @@ static int pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
     // for kp_cap query keypoints, so the branch below (a device-wide synchronisation) is never taken on the hot path
     const int words = (nq + 63) / 64;
     const size_t need = pose_ws_bytes(nq);
-    if (ctx->mw->clique_ws_bytes < need) {
-        if (ctx->mw->clique_ws) { VO_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->mw->clique_ws); }
-        ctx->mw->clique_ws = nullptr; ctx->mw->clique_ws_bytes = 0;
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->clique_ws, need));
-        ctx->mw->clique_ws_bytes = need;
-    }
+    if (int rcw = ws_reserve(ctx, &ctx->mw->clique_ws, &ctx->mw->clique_ws_bytes, need)) return rcw;
     uint8_t* wsp = ctx->mw->clique_ws;
     PoseOut* d_out = (PoseOut*)wsp; wsp += 1024;
     int* d_flags = (int*)wsp; wsp += 256;

@@ -353,6 +353,18 @@ hipError_t match_ws_alloc(vo_ctx* ctx, vo_ctx::MatchWs& m, int what)
     return hipSuccess;
 }
 
+int ws_reserve(vo_ctx* ctx, uint8_t** ptr, size_t* bytes, size_t need, size_t floor)
+{
+    if (*bytes >= need) return VO_OK;
+    VO_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (work in flight may still use the old buffer)
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr; *bytes = 0;
+    const size_t take = need > floor ? need : floor;
+    VO_HIP(ctx, hipMalloc((void**)ptr, take));
+    *bytes = take;
+    return VO_OK;
+}
+
 void match_ws_free(vo_ctx::MatchWs& m)
 {
     void* ps[] = { m.m_idx, m.m_dist, m.m_count, m.mq_idx, m.mt_idx, m.xy_a, m.xy_b, m.pts_a, m.pts_b, m.st_a, m.st_b, m.clique_ws, m.ransac_ws };

@@ -13,6 +13,9 @@
 //                   count by __ballot + popcount -- 40 M residuals at config 5
 //   k_ransac_best   argmax (ties -> lowest hypothesis) with a DPP-free shuffle reduction, then the
 //                   winner's inlier mask
+// What every step shares is written once: rs_sample_distinct (the sampler of all three generators), rs_block_argmax (the winner
+// rule), rs_score_wave / rs_winner_model / rs_inlier_of over a model trait (SampsonModel, ReprojModel), pnp_project, and the
+// workspace layouts of ransac_ws.h.
 #include <math.h>
 #include "vo_internal.h"
 
@@ -20,6 +23,45 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t a)
 {
     a ^= a >> 16; a *= 0x7feb352du; a ^= a >> 15; a *= 0x846ca68bu; a ^= a >> 16;
     return a;
+}
+
+// N distinct indices in [0, n) for hypothesis h by counter-based hash draws: a draw that repeats an earlier index is drawn
+// again, and the 65th attempt is kept whatever it is (n < N cannot loop for ever)
+template <int N>
+__device__ __forceinline__ void rs_sample_distinct(uint32_t seed, int h, int n, int* idx)
+{
+    for (int j = 0; j < N; j++) {
+        uint32_t attempt = 0;
+        for (;;) {
+            uint32_t r = lowbias32(seed ^ lowbias32((uint32_t)h * 0x9E3779B9u + (uint32_t)j * 0x85EBCA6Bu + attempt * 0xC2B2AE35u));
+            int cand = (int)(r % (uint32_t)n), dup = 0;
+            for (int k = 0; k < j; k++) dup |= idx[k] == cand;
+            if (!dup || attempt >= 64) { idx[j] = cand; break; }
+            attempt++;
+        }
+    }
+}
+
+// The winner rule, spelled out here alone: the hypothesis with the most inliers, the lowest index among equals.  For one block
+// of 1 .. 16 whole waves; s_key: one word of LDS per wave.  Ends behind a barrier: every thread holds the winner and its count.
+__device__ __forceinline__ void rs_block_argmax(const int32_t* __restrict__ counts, int iters, long long* s_key, int& best, int& best_count)
+{
+    long long key = -1;
+    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
+        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);
+        key = k > key ? k : key;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
+    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < (int)(blockDim.x >> 6); q++) key = s_key[q] > key ? s_key[q] : key;
+        s_key[0] = key;
+    }
+    __syncthreads();
+    key = s_key[0];
+    best = 0x7fffffff - (int)(key & 0x7fffffffLL);
+    best_count = (int)(key >> 32);
 }
 
 __device__ void rs_cross3(const double* a, const double* b, double* c)
@@ -131,16 +173,7 @@ __global__ void __launch_bounds__(64) k_ransac_hyp(const float* __restrict__ p1,
         return;
     }
     int idx[8];
-    for (int j = 0; j < 8; j++) {
-        uint32_t attempt = 0;
-        for (;;) {
-            uint32_t r = lowbias32(seed ^ lowbias32((uint32_t)h * 0x9E3779B9u + (uint32_t)j * 0x85EBCA6Bu + attempt * 0xC2B2AE35u));
-            int cand = (int)(r % (uint32_t)n), dup = 0;
-            for (int k = 0; k < j; k++) dup |= idx[k] == cand;
-            if (!dup || attempt >= 64) { idx[j] = cand; break; }
-            attempt++;
-        }
-    }
+    rs_sample_distinct<8>(seed, h, n, idx);
     double a[9][9];
     for (int i = 0; i < 9; i++) for (int j = 0; j < 9; j++) a[i][j] = 0.0;
     for (int s = 0; s < 8; s++) {
@@ -192,69 +225,91 @@ __device__ __forceinline__ bool sampson_inlier(const float* F, float u1, float v
     return (num * num) / den < thr2;
 }
 
-// one wave per hypothesis
-__global__ void __launch_bounds__(256) k_ransac_score(const float* __restrict__ p1, const float* __restrict__ p2, int n,
-                                                     const float* __restrict__ F_all, int iters, float thr2, int32_t* __restrict__ counts,
-                                                     const int* __restrict__ n_dev, int min_n)
+// A model trait names what the score and mask bodies below need of a model: W floats per hypothesis, the per-point test on the
+// step's point arrays, and the live count -- fewer correspondences than a sample score nothing.
+struct SampsonModel {                       // F (9 floats) on two streams of pixels
+    static constexpr int W = 9;
+    const float *p1, *p2;
+    int min_n;                              // 8, or 6 for the five-point solver
+    __device__ __forceinline__ int live(int n) const { return n < min_n ? 0 : n; }
+    __device__ __forceinline__ bool inlier(const float* F, int i, float thr2) const
+    {
+        const float2 a = ((const float2*)p1)[i], b = ((const float2*)p2)[i];
+        return sampson_inlier(F, a.x, a.y, b.x, b.y, thr2);
+    }
+};
+
+template <class Model>
+__device__ __forceinline__ void rs_winner_model(const float* __restrict__ M_all, int h, float* M)
+{
+#pragma unroll
+    for (int k = 0; k < Model::W; k++) M[k] = M_all[(size_t)h * Model::W + k];
+}
+
+// point i under model M: an inlier only below the live count
+template <class Model>
+__device__ __forceinline__ bool rs_inlier_of(const Model& md, const float* M, int i, int live, float thr2)
+{
+    return i < live && md.inlier(M, i, thr2);
+}
+
+// one wave per hypothesis: lanes stride over the points, ballot + popcount.  n_dev (may be NULL): the count only the device knows
+template <class Model>
+__device__ __forceinline__ void rs_score_wave(const Model& md, int n, const float* __restrict__ M_all, int iters, float thr2,
+                                              int32_t* __restrict__ counts, const int* __restrict__ n_dev)
 {
     const int lane = threadIdx.x & 63;
     const int h = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (h >= iters) return;
-    if (n_dev) n = *n_dev < min_n ? 0 : *n_dev;
-    float F[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) F[k] = F_all[(size_t)h * 9 + k];
+    if (n_dev) n = md.live(*n_dev);
+    float M[Model::W];
+    rs_winner_model<Model>(M_all, h, M);
     int cnt = 0;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        bool in = false;
-        if (i < n) {
-            const float2 a = ((const float2*)p1)[i], b = ((const float2*)p2)[i];
-            in = sampson_inlier(F, a.x, a.y, b.x, b.y, thr2);
-        }
-        cnt += __popcll(__ballot(in));
-    }
+    for (int i0 = 0; i0 < n; i0 += 64) cnt += __popcll(__ballot(rs_inlier_of(md, M, i0 + lane, n, thr2)));
     if (lane == 0) counts[h] = cnt;
+}
+
+// the winner's mask, one thread per point; with n_dev the points behind the live count are cleared
+template <class Model>
+__device__ __forceinline__ void rs_mask_point(const Model& md, int n, const float* __restrict__ M_all, const int32_t* __restrict__ best,
+                                              float thr2, uint8_t* __restrict__ mask, const int* __restrict__ n_dev)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n_dev) { const int live = md.live(*n_dev); if (i < n && i >= live) mask[i] = 0; n = live; }
+    if (i >= n) return;
+    float M[Model::W];
+    rs_winner_model<Model>(M_all, best[0], M);
+    mask[i] = md.inlier(M, i, thr2) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256) k_ransac_score(const float* __restrict__ p1, const float* __restrict__ p2, int n,
+                                                     const float* __restrict__ F_all, int iters, float thr2, int32_t* __restrict__ counts,
+                                                     const int* __restrict__ n_dev, int min_n)
+{
+    rs_score_wave(SampsonModel{ p1, p2, min_n }, n, F_all, iters, thr2, counts, n_dev);
 }
 
 __global__ void __launch_bounds__(1024) k_ransac_best(const int32_t* __restrict__ counts, int iters, int32_t* __restrict__ best /*[2]: index, count*/)
 {
     __shared__ long long s_key[16];
-    long long key = -1;
-    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
-        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);   // most inliers, then lowest index
-        key = k > key ? k : key;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
-    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < (int)(blockDim.x >> 6); q++) key = s_key[q] > key ? s_key[q] : key;
-        best[0] = 0x7fffffff - (int)(key & 0x7fffffffLL);
-        best[1] = (int)(key >> 32);
-    }
+    int b, c;
+    rs_block_argmax(counts, iters, s_key, b, c);
+    if (threadIdx.x == 0) { best[0] = b; best[1] = c; }
 }
 
 __global__ void k_ransac_mask(const float* __restrict__ p1, const float* __restrict__ p2, int n, const float* __restrict__ F_all,
                               const int32_t* __restrict__ best, float thr2, uint8_t* __restrict__ mask, const int* __restrict__ n_dev, int min_n)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n_dev) { const int m = *n_dev; if (i < n && (i >= m || m < min_n)) mask[i] = 0; n = m < min_n ? 0 : m; }
-    if (i >= n) return;
-    const float* F = F_all + (size_t)best[0] * 9;
-    float Fl[9];
-    for (int k = 0; k < 9; k++) Fl[k] = F[k];
-    const float2 a = ((const float2*)p1)[i], b = ((const float2*)p2)[i];
-    mask[i] = sampson_inlier(Fl, a.x, a.y, b.x, b.y, thr2) ? 1 : 0;
+    rs_mask_point(SampsonModel{ p1, p2, min_n }, n, F_all, best, thr2, mask, n_dev);
 }
 
 // the five-point kernel keeps its matrices in 100 KB of LDS per wave: above the 64 KB a launch may ask for by default
+// (the attribute belongs to the device's copy of the code object; a context lives on one device and in one thread: set once each)
 static int hyp5_prepare(vo_ctx* ctx)
 {
-    static unsigned long long done = 0;         // per device (the attribute belongs to the device's copy of the code object)
-    if ((done >> (ctx->device & 63)) & 1ull) return VO_OK;
+    if (ctx->hyp5_ready) return VO_OK;
     VO_HIP(ctx, hipFuncSetAttribute((const void*)k_ransac_hyp5, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FP_LDS_DOUBLES * sizeof(double))));
-    done |= 1ull << (ctx->device & 63);
+    ctx->hyp5_ready = true;
     return VO_OK;
 }
 
@@ -266,47 +321,34 @@ static int ransac_essential(vo_ctx* ctx, const float* pts1, const float* pts2, i
     if (n < min_n || iters <= 0 || iters > (1 << 22) || n > (1 << 24))
         return vo_fail(ctx, VO_E_ARG, "vo_ransac_essential: need n >= %d and 0 < iters <= 4194304", min_n);
     VO_HIP(ctx, hipSetDevice(ctx->device));
-    // workspace: points (2 x n x 8 B), E (iters x 72 B), F (iters x 36 B), counts, mask, best
-    const size_t need = (size_t)n * 16 + (size_t)iters * (72 + 36 + 4 + FP_REC_DOUBLES * 8) + (size_t)n + 4096;
-    if (ctx->mw->ransac_ws_bytes < need) {
-        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
-        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, need));
-        ctx->mw->ransac_ws_bytes = need;
-    }
-    uint8_t* w = ctx->mw->ransac_ws;
-    double* d_E = (double*)w; w += (size_t)iters * 72;
-    double* d_rec = (double*)w; w += (size_t)iters * FP_REC_DOUBLES * 8;       // five-point solver: k_ransac_hyp5 -> k_ransac_roots5
-    float* d_p1 = (float*)w; w += (size_t)n * 8;
-    float* d_p2 = (float*)w; w += (size_t)n * 8;
-    float* d_F = (float*)w; w += (size_t)iters * 36;
-    int32_t* d_counts = (int32_t*)w; w += (size_t)iters * 4;
-    int32_t* d_best = (int32_t*)w; w += 256;
-    uint8_t* d_mask = w;
+    EssWs w;
+    int rc = ws_reserve(ctx, &ctx->mw->ransac_ws, &ctx->mw->ransac_ws_bytes, ess_ws_layout(nullptr, n, iters, &w));
+    if (rc) return rc;
+    ess_ws_layout(ctx->mw->ransac_ws, n, iters, &w);
     StageTimer t(ctx, VO_T_POSE);
-    int rc = xfer_h2d(ctx, d_p1, pts1, (size_t)n * 8);
-    if (!rc) rc = xfer_h2d(ctx, d_p2, pts2, (size_t)n * 8);
+    rc = xfer_h2d(ctx, w.p1, pts1, (size_t)n * 8);
+    if (!rc) rc = xfer_h2d(ctx, w.p2, pts2, (size_t)n * 8);
     if (rc) return rc;
     const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
     const float thr2 = thr * thr;
     if (solver == 5) {
         if (int rc5 = hyp5_prepare(ctx)) return rc5;
-        hipLaunchKernelGGL(k_ransac_hyp5, dim3(div_up(iters, 64)), dim3(64), FP_LDS_DOUBLES * sizeof(double), ctx->stream, d_p1, d_p2, n, K, iters, seed, d_rec, nullptr);
-        hipLaunchKernelGGL(k_ransac_roots5, dim3(div_up(iters, 8)), dim3(256), 0, ctx->stream, d_rec, K, iters, d_E, d_F);
+        hipLaunchKernelGGL(k_ransac_hyp5, dim3(div_up(iters, 64)), dim3(64), FP_LDS_DOUBLES * sizeof(double), ctx->stream, w.p1, w.p2, n, K, iters, seed, w.rec, nullptr);
+        hipLaunchKernelGGL(k_ransac_roots5, dim3(div_up(iters, 8)), dim3(256), 0, ctx->stream, w.rec, K, iters, w.E, w.F);
     }
     else
-        hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d_p1, d_p2, n, K, iters, seed, d_E, d_F, nullptr);
-    hipLaunchKernelGGL(k_ransac_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d_p1, d_p2, n, d_F, iters, thr2, d_counts, nullptr, min_n);
-    hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, d_counts, iters, d_best);
-    hipLaunchKernelGGL(k_ransac_mask, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_p1, d_p2, n, d_F, d_best, thr2, d_mask, nullptr, min_n);
+        hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, w.p1, w.p2, n, K, iters, seed, w.E, w.F, nullptr);
+    hipLaunchKernelGGL(k_ransac_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, w.p1, w.p2, n, w.F, iters, thr2, w.counts, nullptr, min_n);
+    hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, w.counts, iters, w.best);
+    hipLaunchKernelGGL(k_ransac_mask, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w.p1, w.p2, n, w.F, w.best, thr2, w.mask, nullptr, min_n);
     VO_CHECK_LAUNCH(ctx);
-    VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (mask_out && (rc = xfer_d2h(ctx, mask_out, d_mask, (size_t)n))) return rc;
-    if (counts_out && (rc = xfer_d2h(ctx, counts_out, d_counts, (size_t)iters * 4))) return rc;
+    VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, w.best, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_out && (rc = xfer_d2h(ctx, mask_out, w.mask, (size_t)n))) return rc;
+    if (counts_out && (rc = xfer_d2h(ctx, counts_out, w.counts, (size_t)iters * 4))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;
     best2_out[0] = ((int32_t*)ctx->pinned)[0];
     best2_out[1] = ((int32_t*)ctx->pinned)[1];
-    VO_HIP(ctx, hipMemcpy(E9_out, d_E + (size_t)best2_out[0] * 9, 72, hipMemcpyDeviceToHost));
+    VO_HIP(ctx, hipMemcpy(E9_out, w.E + (size_t)best2_out[0] * 9, 72, hipMemcpyDeviceToHost));
     return VO_OK;
 }
 
@@ -333,14 +375,13 @@ __global__ void k_ransac_pick(const double* __restrict__ E_all, const int32_t* _
 // surviving correspondences, every stage on the device.  mono_enqueue puts the whole chain on ctx->stream with the
 // context's CURRENT match scratch (m_idx .. xy_b, m_count) and RANSAC workspace -- the main ones (vo_mono_pair: one
 // host synchronisation at the end) or those of an asynchronous alternate (vo_mono_pair_begin / _end).
-struct MonoDev { int32_t* d_best; double* d_E9; uint8_t* d_mask; };
+struct MonoStep { MonoWs w; float thr2; int min_n; };       // the step's workspace and what a tail kernel needs beside it
 
 // The end of an asynchronous pair step as ONE launch (was three kernels and seven copy commands: at 8000 keypoints the
 // monocular loop is bound by the host thread's queue entries): argmax of the hypotheses' inlier counts (most inliers, then the
 // lowest index) -> the winner's E -> its inlier mask over the M correspondences -> the whole record -- M, winner, count, E,
 // mask, the surviving index pairs and the second frame's keypoint positions -- written straight into the alternate's PINNED
-// host record (one block: the record is 140 KB at 8000 keypoints).  Element for element the arithmetic of k_ransac_best /
-// k_ransac_mask / k_ransac_pick.
+// host record (one block: the record is 140 KB at 8000 keypoints).
 __global__ void __launch_bounds__(1024) k_mono_finish(const int32_t* __restrict__ counts, int iters, const double* __restrict__ E_all,
                                                       const float* __restrict__ F_all, const float* __restrict__ p1, const float* __restrict__ p2,
                                                       int nq, const int* __restrict__ n_dev, int min_n, float thr2, const int32_t* __restrict__ mq,
@@ -348,67 +389,37 @@ __global__ void __launch_bounds__(1024) k_mono_finish(const int32_t* __restrict_
                                                       uint8_t* __restrict__ rec, size_t hdr)
 {
     __shared__ long long s_key[16];
-    __shared__ int s_best[2];
-    long long key = -1;
-    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
-        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);   // most inliers, then lowest index
-        key = k > key ? k : key;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
-    if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < (int)(blockDim.x >> 6); q++) key = s_key[q] > key ? s_key[q] : key;
-        s_best[0] = 0x7fffffff - (int)(key & 0x7fffffffLL);
-        s_best[1] = (int)(key >> 32);
-    }
-    __syncthreads();
-    const int best = s_best[0], m = *n_dev;
+    int best, best_count;
+    rs_block_argmax(counts, iters, s_key, best, best_count);
+    const int m = *n_dev;
     int32_t* const h32 = (int32_t*)rec;
-    if (threadIdx.x == 0) { h32[0] = m; h32[1] = best; h32[2] = s_best[1]; }
+    if (threadIdx.x == 0) { h32[0] = m; h32[1] = best; h32[2] = best_count; }
     if (threadIdx.x < 9) ((double*)(rec + 64))[threadIdx.x] = E_all[(size_t)best * 9 + threadIdx.x];
     if (!want) return;
     uint8_t* const q = rec + hdr;
+    const SampsonModel md{ p1, p2, min_n };
     float Fl[9];
-    for (int k = 0; k < 9; k++) Fl[k] = F_all[(size_t)best * 9 + k];
-    const int live = m < min_n ? 0 : m;
+    rs_winner_model<SampsonModel>(F_all, best, Fl);
+    const int live = md.live(m);
     for (int i = threadIdx.x; i < nq; i += blockDim.x) {
-        uint8_t in = 0;
-        if (i < live) {
-            const float2 a = ((const float2*)p1)[i], b = ((const float2*)p2)[i];
-            in = sampson_inlier(Fl, a.x, a.y, b.x, b.y, thr2) ? 1 : 0;
-        }
-        q[i] = in;
+        q[i] = rs_inlier_of(md, Fl, i, live, thr2) ? 1 : 0;
         ((int32_t*)(q + cap))[i] = mq[i];
         ((int32_t*)(q + cap * 5))[i] = mt[i];
     }
     for (int i = threadIdx.x; i < nb; i += blockDim.x) ((float2*)(q + cap * 9))[i] = ((const float2*)xy_b)[i];
 }
 
-// (extra / scratch: `extra` more bytes of the workspace behind the mask, 256-byte aligned, for a tail that needs them)
-struct MonoTail { const int32_t* counts; const double* E; const float* F; float thr2; int min_n; uint8_t* scratch; };
+// fused_tail: the caller ends the chain with one kernel of its own (k_mono_finish, k_mono_pose_finish) that finds the winner;
+// extra: bytes of scratch (o.w.scratch) that kernel needs
 static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
-                        int solver, MonoDev& o, MonoTail* tail = nullptr, size_t extra = 0)
+                        int solver, MonoStep& o, bool fused_tail = false, size_t extra = 0)
 {
     const int min_n = solver == 5 ? 6 : 8;
     const int nq = a.n_kp, cross = match_flags & VO_MATCH_CROSSCHECK;
-    const size_t need = (size_t)iters * (72 + 36 + 4 + FP_REC_DOUBLES * 8) + (size_t)nq + 4096 + (extra ? extra + 256 : 0);
-    if (ctx->mw->ransac_ws_bytes < need) {
-        VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
-        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, need));
-        ctx->mw->ransac_ws_bytes = need;
-    }
-    uint8_t* w = ctx->mw->ransac_ws;
-    double* d_E = (double*)w; w += (size_t)iters * 72;
-    double* d_rec = (double*)w; w += (size_t)iters * FP_REC_DOUBLES * 8;       // five-point solver: k_ransac_hyp5 -> k_ransac_roots5
-    float* d_F = (float*)w; w += (size_t)iters * 36;
-    int32_t* d_counts = (int32_t*)w; w += (size_t)iters * 4;
-    o.d_best = (int32_t*)w; w += 256;
-    o.d_E9 = (double*)w; w += 256;
-    o.d_mask = w;
-    int rc;
+    MonoWs& w = o.w;
+    int rc = ws_reserve(ctx, &ctx->mw->ransac_ws, &ctx->mw->ransac_ws_bytes, mono_ws_layout(nullptr, nq, iters, extra, &w));
+    if (rc) return rc;
+    mono_ws_layout(ctx->mw->ransac_ws, nq, iters, extra, &w);
     {
         StageTimer t(ctx, VO_T_MATCH);
         if ((rc = match_knn2_slots(ctx, a, b, match_flags))) return rc;
@@ -421,22 +432,20 @@ static int mono_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, i
     {
         StageTimer t(ctx, VO_T_POSE);
         const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
-        const float thr2 = thr * thr;
+        const float thr2 = o.thr2 = thr * thr;
+        o.min_n = min_n;
         if (solver == 5) {
             if (int rc5 = hyp5_prepare(ctx)) return rc5;
-            hipLaunchKernelGGL(k_ransac_hyp5, dim3(div_up(iters, 64)), dim3(64), FP_LDS_DOUBLES * sizeof(double), ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, K, iters, seed, d_rec, ctx->mw->m_count);
-            hipLaunchKernelGGL(k_ransac_roots5, dim3(div_up(iters, 8)), dim3(256), 0, ctx->stream, d_rec, K, iters, d_E, d_F);
+            hipLaunchKernelGGL(k_ransac_hyp5, dim3(div_up(iters, 64)), dim3(64), FP_LDS_DOUBLES * sizeof(double), ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, K, iters, seed, w.rec, ctx->mw->m_count);
+            hipLaunchKernelGGL(k_ransac_roots5, dim3(div_up(iters, 8)), dim3(256), 0, ctx->stream, w.rec, K, iters, w.E, w.F);
         }
         else
-            hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, K, iters, seed, d_E, d_F, ctx->mw->m_count);
-        hipLaunchKernelGGL(k_ransac_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, d_F, iters, thr2, d_counts, ctx->mw->m_count, min_n);
-        if (tail) {                                  // the asynchronous step ends with k_mono_finish (one launch, record written in place)
-            tail->counts = d_counts; tail->E = d_E; tail->F = d_F; tail->thr2 = thr2; tail->min_n = min_n;
-            tail->scratch = (uint8_t*)(((uintptr_t)(o.d_mask + nq) + 255) & ~(uintptr_t)255);
-        } else {
-            hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, d_counts, iters, o.d_best);
-            hipLaunchKernelGGL(k_ransac_mask, dim3(div_up(nq, 256)), dim3(256), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, d_F, o.d_best, thr2, o.d_mask, ctx->mw->m_count, min_n);
-            hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, ctx->stream, d_E, o.d_best, o.d_E9);
+            hipLaunchKernelGGL(k_ransac_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, K, iters, seed, w.E, w.F, ctx->mw->m_count);
+        hipLaunchKernelGGL(k_ransac_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, w.F, iters, thr2, w.counts, ctx->mw->m_count, min_n);
+        if (!fused_tail) {
+            hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, w.counts, iters, w.best);
+            hipLaunchKernelGGL(k_ransac_mask, dim3(div_up(nq, 256)), dim3(256), 0, ctx->stream, ctx->mw->xy_a, ctx->mw->xy_b, nq, w.F, w.best, thr2, w.mask, ctx->mw->m_count, min_n);
+            hipLaunchKernelGGL(k_ransac_pick, dim3(1), dim3(64), 0, ctx->stream, w.E, w.best, w.E9);
         }
         VO_CHECK_LAUNCH(ctx);
     }
@@ -473,13 +482,13 @@ extern "C" int vo_mono_pair_ex(vo_ctx* ctx, int slot_a, int slot_b, double ratio
     VO_HIP(ctx, hipSetDevice(ctx->device));
     { int rcw = slot_wait(ctx, a); if (!rcw) rcw = slot_wait(ctx, b); if (rcw) return rcw; }
     const int nq = a.n_kp;
-    MonoDev o;
+    MonoStep o;
     if ((rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o))) return rc;
     int32_t* h = (int32_t*)ctx->pinned;         // [0] M, [1..2] best, then E9 at byte 64
     VO_HIP(ctx, hipMemcpyAsync(h, ctx->mw->m_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VO_HIP(ctx, hipMemcpyAsync(h + 1, o.d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
-    VO_HIP(ctx, hipMemcpyAsync((uint8_t*)ctx->pinned + 64, o.d_E9, 72, hipMemcpyDeviceToHost, ctx->stream));
-    if (mask_out && (rc = xfer_d2h(ctx, mask_out, o.d_mask, (size_t)nq))) return rc;
+    VO_HIP(ctx, hipMemcpyAsync(h + 1, o.w.best, 8, hipMemcpyDeviceToHost, ctx->stream));
+    VO_HIP(ctx, hipMemcpyAsync((uint8_t*)ctx->pinned + 64, o.w.E9, 72, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_out && (rc = xfer_d2h(ctx, mask_out, o.w.mask, (size_t)nq))) return rc;
     if (q_idx && (rc = xfer_d2h(ctx, q_idx, ctx->mw->mq_idx, (size_t)nq * 4))) return rc;
     if (t_idx && (rc = xfer_d2h(ctx, t_idx, ctx->mw->mt_idx, (size_t)nq * 4))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
@@ -516,13 +525,12 @@ extern "C" int vo_mono_pair_begin_ex(vo_ctx* ctx, int slot_a, int slot_b, double
     p.nq = a.n_kp; p.nb = b.n_kp; p.min_n = solver == 5 ? 6 : 8; p.want = want_matches != 0; p.pose = false;
     if (a.n_kp > 0) {
         AltScope on_alt(ctx, p);
-        MonoDev o;
-        MonoTail tl;
-        rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o, &tl);
+        MonoStep o;
+        rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o, true);
         if (!rc) {
             // (p.result is pinned host memory: the kernel writes the record across the link itself -- no copy command)
-            hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(1024), 0, ctx->stream, tl.counts, iters, tl.E, tl.F, ctx->mw->xy_a, ctx->mw->xy_b, a.n_kp,
-                               ctx->mw->m_count, tl.min_n, tl.thr2, ctx->mw->mq_idx, ctx->mw->mt_idx, b.kp_xy, b.n_kp, p.want ? 1 : 0, (size_t)ctx->kp_cap,
+            hipLaunchKernelGGL(k_mono_finish, dim3(1), dim3(1024), 0, ctx->stream, o.w.counts, iters, o.w.E, o.w.F, ctx->mw->xy_a, ctx->mw->xy_b, a.n_kp,
+                               ctx->mw->m_count, o.min_n, o.thr2, ctx->mw->mq_idx, ctx->mw->mt_idx, b.kp_xy, b.n_kp, p.want ? 1 : 0, (size_t)ctx->kp_cap,
                                p.result, MONO_HDR);
             if (hipGetLastError() != hipSuccess) rc = vo_fail(ctx, VO_E_HIP, "k_mono_finish: launch failed");
         }
@@ -573,7 +581,7 @@ extern "C" int vo_mono_pair_end(vo_ctx* ctx, int ticket, double* E9_out, int32_t
 //            doubles order like their patterns)
 // Float64, three-term sums left to right, no contraction: tests/mono_pose_ref.py restates it value for value.
 // =========================================================================================
-struct RpArgs {
+struct RpArgs : RpScratch {               // (the scratch z1, z2, ratio, owner: ransac_ws.h)
     const float *p1, *p2;                 // n x 2 pixels
     const int32_t *q, *t;                 // keypoint indices of the correspondences in frames a / b (both NULL: the identity)
     int na, nb;
@@ -585,9 +593,6 @@ struct RpArgs {
     double* depth_b;                      // nb, written whole
     uint32_t* serial_b;                   // stamped with `serial` (NULL: no stamp)
     uint32_t serial;
-    double *z1, *z2;                      // n each: the winner's depths of the inliers, 0 elsewhere
-    unsigned long long* ratio;            // n: scratch of the select
-    int32_t* owner;                       // nb: scratch of the scatter
     vo_mono_pose* rec;                    // pinned host memory
 };
 
@@ -808,14 +813,6 @@ __device__ void rp_tail(const RpArgs& A, int n, const double* E9, int M, int bes
 }
 
 static inline size_t rp_lds_bytes(int n) { return (size_t)((n + 63) >> 6) * 16; }
-// device scratch of one tail behind `base` (256-byte aligned): z1, z2, ratio (n x 8 B each), owner (nb x 4 B)
-static inline size_t rp_scratch_bytes(int n, int nb) { return (size_t)n * 24 + (size_t)nb * 4 + 256; }
-static void rp_scratch(RpArgs& A, uint8_t* base, int n)
-{
-    A.z1 = (double*)base; A.z2 = A.z1 + n;
-    A.ratio = (unsigned long long*)(A.z2 + n);
-    A.owner = (int32_t*)(A.ratio + n);
-}
 
 __global__ void __launch_bounds__(1024) k_recover_pose(RpArgs A, int n, const double* __restrict__ E9, const uint8_t* __restrict__ mask)
 {
@@ -831,50 +828,31 @@ __global__ void __launch_bounds__(1024) k_recover_pose(RpArgs A, int n, const do
 }
 
 // The end of a monocular pose step as ONE launch: argmax of the hypotheses' inlier counts, the winner's E and its inlier mask
-// exactly as k_mono_finish computes them (the mask as ballot words in LDS instead of bytes in the record), then rp_tail on the
-// M surviving correspondences.  Nothing per match crosses the link: the record is a vo_mono_pose.
+// (the mask as ballot words in LDS instead of bytes in a record), then rp_tail on the M surviving correspondences.  Nothing per
+// match crosses the link: the record is a vo_mono_pose.
 __global__ void __launch_bounds__(1024) k_mono_pose_finish(const int32_t* __restrict__ counts, int iters, const double* __restrict__ E_all,
                                                            const float* __restrict__ F_all, int nq, const int* __restrict__ n_dev, int min_n,
                                                            float thr2, RpArgs A)
 {
     extern __shared__ unsigned long long s_bits[];
     __shared__ long long s_key[16];
-    __shared__ int s_best[2];
     __shared__ double s_E[9];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    long long key = -1;
-    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
-        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);   // most inliers, then lowest index
-        key = k > key ? k : key;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
-    if (lane == 0) s_key[wv] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < (int)(blockDim.x >> 6); q++) key = s_key[q] > key ? s_key[q] : key;
-        s_best[0] = 0x7fffffff - (int)(key & 0x7fffffffLL);
-        s_best[1] = (int)(key >> 32);
-    }
-    __syncthreads();
-    const int best = s_best[0];
+    int best, best_count;
+    rs_block_argmax(counts, iters, s_key, best, best_count);
     int m = *n_dev;
     m = m < 0 ? 0 : (m > nq ? nq : m);      // (the LDS words and the scratch are sized for nq)
     if (threadIdx.x < 9) s_E[threadIdx.x] = E_all[(size_t)best * 9 + threadIdx.x];
+    const SampsonModel md{ A.p1, A.p2, min_n };
     float Fl[9];
-    for (int k = 0; k < 9; k++) Fl[k] = F_all[(size_t)best * 9 + k];
-    const int live = m < min_n ? 0 : m;
+    rs_winner_model<SampsonModel>(F_all, best, Fl);
+    const int live = md.live(m);
     for (int i0 = wv * 64; i0 < m; i0 += blockDim.x) {
-        const int i = i0 + lane;
-        bool in = false;
-        if (i < live) {
-            const float2 a = ((const float2*)A.p1)[i], b = ((const float2*)A.p2)[i];
-            in = sampson_inlier(Fl, a.x, a.y, b.x, b.y, thr2);
-        }
-        const unsigned long long bits = __ballot(in);
+        const unsigned long long bits = __ballot(rs_inlier_of(md, Fl, i0 + lane, live, thr2));
         if (lane == 0) s_bits[i0 >> 6] = bits;
     }
     __syncthreads();
-    rp_tail(A, m, s_E, m, best, live ? s_best[1] : 0, s_bits, s_bits + ((nq + 63) >> 6));
+    rp_tail(A, m, s_E, m, best, live ? best_count : 0, s_bits, s_bits + ((nq + 63) >> 6));
 }
 
 static int rp_check_out(vo_ctx* ctx, const vo_mono_pose* r, const char* who)
@@ -901,45 +879,30 @@ extern "C" int vo_recover_pose(vo_ctx* ctx, const double* E9, const float* pts1,
     if (!q_idx) na = nb = n;
     if (na < 1 || nb < 1 || na > (1 << 24) || nb > (1 << 24)) return vo_fail(ctx, VO_E_ARG, "vo_recover_pose: need 1 <= na, nb <= 16777216");
     VO_HIP(ctx, hipSetDevice(ctx->device));
-    // workspace: E, the points, mask, indices, depth_a, depth_b, then the tail's scratch
-    const size_t need = 256 + (size_t)n * (8 + 8 + 1 + 4 + 4) + (size_t)(na + nb) * 8 + 2048 + rp_scratch_bytes(n, nb);
-    if (ctx->mw->ransac_ws_bytes < need) {
-        VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
-        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, need));
-        ctx->mw->ransac_ws_bytes = need;
-    }
-    auto align = [](uint8_t* p) { return (uint8_t*)(((uintptr_t)p + 255) & ~(uintptr_t)255); };
-    uint8_t* w = ctx->mw->ransac_ws;
-    double* d_E = (double*)w; w += 256;
-    float* d_p1 = (float*)w; w += (size_t)n * 8;
-    float* d_p2 = (float*)w; w += (size_t)n * 8;
-    int32_t* d_q = (int32_t*)w; w += (size_t)n * 4;
-    int32_t* d_t = (int32_t*)w; w += (size_t)n * 4;
-    double* d_da = (double*)align(w); w = (uint8_t*)(d_da + na);
-    double* d_db = (double*)w; w = (uint8_t*)(d_db + nb);
-    uint8_t* d_mask = w; w = align(w + n);
+    RecoverWs w;
+    int rc = ws_reserve(ctx, &ctx->mw->ransac_ws, &ctx->mw->ransac_ws_bytes, recover_ws_layout(nullptr, n, na, nb, &w));
+    if (rc) return rc;
+    recover_ws_layout(ctx->mw->ransac_ws, n, na, nb, &w);
     StageTimer t(ctx, VO_T_POSE);
-    int rc = xfer_h2d(ctx, d_E, E9, 72);
-    if (!rc) rc = xfer_h2d(ctx, d_p1, pts1, (size_t)n * 8);
-    if (!rc) rc = xfer_h2d(ctx, d_p2, pts2, (size_t)n * 8);
-    if (!rc && mask) rc = xfer_h2d(ctx, d_mask, mask, (size_t)n);
-    if (!rc && q_idx) rc = xfer_h2d(ctx, d_q, q_idx, (size_t)n * 4);
-    if (!rc && t_idx) rc = xfer_h2d(ctx, d_t, t_idx, (size_t)n * 4);
-    if (!rc && depth_a) rc = xfer_h2d(ctx, d_da, depth_a, (size_t)na * 8);
+    rc = xfer_h2d(ctx, w.E, E9, 72);
+    if (!rc) rc = xfer_h2d(ctx, w.p1, pts1, (size_t)n * 8);
+    if (!rc) rc = xfer_h2d(ctx, w.p2, pts2, (size_t)n * 8);
+    if (!rc && mask) rc = xfer_h2d(ctx, w.mask, mask, (size_t)n);
+    if (!rc && q_idx) rc = xfer_h2d(ctx, w.q, q_idx, (size_t)n * 4);
+    if (!rc && t_idx) rc = xfer_h2d(ctx, w.t, t_idx, (size_t)n * 4);
+    if (!rc && depth_a) rc = xfer_h2d(ctx, w.da, depth_a, (size_t)na * 8);
     if (rc) return rc;
     vo_mono_pose* rec = (vo_mono_pose*)ctx->pinned;
     rp_rec_clear(rec);
     RpArgs A{};
-    A.p1 = d_p1; A.p2 = d_p2; A.q = q_idx ? d_q : nullptr; A.t = t_idx ? d_t : nullptr; A.na = na; A.nb = nb;
-    A.depth_a = depth_a ? d_da : nullptr; A.serial_a = nullptr; A.prev_serial = 0; A.gate = min_parallax_sin2;
+    A.p1 = w.p1; A.p2 = w.p2; A.q = q_idx ? w.q : nullptr; A.t = t_idx ? w.t : nullptr; A.na = na; A.nb = nb;
+    A.depth_a = depth_a ? w.da : nullptr; A.serial_a = nullptr; A.prev_serial = 0; A.gate = min_parallax_sin2;
     A.K = K4{ K4v[0], K4v[1], K4v[2], K4v[3] };
-    A.depth_b = d_db; A.serial_b = nullptr; A.serial = 0; A.rec = rec;
-    rp_scratch(A, w, n);
-    hipLaunchKernelGGL(k_recover_pose, dim3(1), dim3(1024), rp_lds_bytes(n), ctx->stream, A, n, d_E, mask ? d_mask : nullptr);
+    A.depth_b = w.db; A.serial_b = nullptr; A.serial = 0; A.rec = rec;
+    rp_scratch_layout(w.scratch, n, nb, &A);
+    hipLaunchKernelGGL(k_recover_pose, dim3(1), dim3(1024), rp_lds_bytes(n), ctx->stream, A, n, w.E, mask ? w.mask : nullptr);
     VO_CHECK_LAUNCH(ctx);
-    if (depth_b && (rc = xfer_d2h(ctx, depth_b, d_db, (size_t)nb * 8))) return rc;
+    if (depth_b && (rc = xfer_d2h(ctx, depth_b, w.db, (size_t)nb * 8))) return rc;
     if (z1_out && (rc = xfer_d2h(ctx, z1_out, A.z1, (size_t)n * 8))) return rc;
     if (z2_out && (rc = xfer_d2h(ctx, z2_out, A.z2, (size_t)n * 8))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;       // the one synchronisation
@@ -973,24 +936,23 @@ static uint32_t mono_next_serial(vo_ctx* ctx)
 static int mono_pose_enqueue(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int match_flags, const double* K4v, int iters, float thr, uint32_t seed,
                              int solver, uint32_t prev_serial, double gate, uint32_t serial, vo_mono_pose* rec)
 {
-    MonoDev o;
-    MonoTail tl;
-    int rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o, &tl, rp_scratch_bytes(a.n_kp, b.n_kp));
+    MonoStep o;
+    RpArgs A{};
+    int rc = mono_enqueue(ctx, a, b, ratio, match_flags, K4v, iters, thr, seed, solver, o, true, rp_scratch_layout(nullptr, a.n_kp, b.n_kp, &A));
     if (rc) return rc;
     if (a.depth_writer) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, a.depth_writer, 0));
     if (b.depth_writer) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, b.depth_writer, 0));
     for (hipEvent_t r : b.readers) if (r) VO_HIP(ctx, hipStreamWaitEvent(ctx->stream, r, 0));
-    RpArgs A{};
     A.p1 = ctx->mw->xy_a; A.p2 = ctx->mw->xy_b; A.q = ctx->mw->mq_idx; A.t = ctx->mw->mt_idx; A.na = a.n_kp; A.nb = b.n_kp;
     // depths of slot a are offered only under the serial the HOST still holds for them (a refill clears it at once)
     const bool offer = prev_serial != 0 && a.mono_serial == prev_serial;
     A.depth_a = offer ? a.mono_depth : nullptr; A.serial_a = a.mono_serial_dev; A.prev_serial = prev_serial; A.gate = gate;
     A.K = K4{ K4v[0], K4v[1], K4v[2], K4v[3] };
     A.depth_b = b.mono_depth; A.serial_b = b.mono_serial_dev; A.serial = serial; A.rec = rec;
-    rp_scratch(A, tl.scratch, a.n_kp);
+    rp_scratch_layout(o.w.scratch, a.n_kp, b.n_kp, &A);
     StageTimer t(ctx, VO_T_POSE);
-    hipLaunchKernelGGL(k_mono_pose_finish, dim3(1), dim3(1024), rp_lds_bytes(a.n_kp), ctx->stream, tl.counts, iters, tl.E, tl.F, a.n_kp,
-                       ctx->mw->m_count, tl.min_n, tl.thr2, A);
+    hipLaunchKernelGGL(k_mono_pose_finish, dim3(1), dim3(1024), rp_lds_bytes(a.n_kp), ctx->stream, o.w.counts, iters, o.w.E, o.w.F, a.n_kp,
+                       ctx->mw->m_count, o.min_n, o.thr2, A);
     VO_CHECK_LAUNCH(ctx);
     b.mono_serial = serial;
     return VO_OK;
@@ -1255,6 +1217,19 @@ __device__ int pn_p3p(const double* y, const double* x, double* Rs, double* ts)
     return ns;
 }
 
+// column c of P = K [R | t], rounded to float32 (Rt, P: 3 x 4, row-major)
+__device__ __forceinline__ void pnp_project_col(const K4& K, const double* Rt, int c, float* P)
+{
+    P[c] = (float)(K.fx * Rt[c] + K.cx * Rt[8 + c]);
+    P[4 + c] = (float)(K.fy * Rt[4 + c] + K.cy * Rt[8 + c]);
+    P[8 + c] = (float)Rt[8 + c];
+}
+
+__device__ __forceinline__ void pnp_project(const K4& K, const double* Rt, float* P)
+{
+    for (int c = 0; c < 4; c++) pnp_project_col(K, Rt, c, P);
+}
+
 __global__ void __launch_bounds__(64) k_pnp_hyp(const float* __restrict__ X, const float* __restrict__ uv, int n, K4 K, int iters,
                                                 uint32_t seed, double* __restrict__ Rt_out, float* __restrict__ P_out,
                                                 const int* __restrict__ n_dev)
@@ -1271,16 +1246,7 @@ __global__ void __launch_bounds__(64) k_pnp_hyp(const float* __restrict__ X, con
         }
     }
     int idx[4];
-    for (int j = 0; j < 4; j++) {
-        uint32_t attempt = 0;
-        for (;;) {
-            uint32_t r = lowbias32(seed ^ lowbias32((uint32_t)h * 0x9E3779B9u + (uint32_t)j * 0x85EBCA6Bu + attempt * 0xC2B2AE35u));
-            int cand = (int)(r % (uint32_t)n), dup = 0;
-            for (int k = 0; k < j; k++) dup |= idx[k] == cand;
-            if (!dup || attempt >= 64) { idx[j] = cand; break; }
-            attempt++;
-        }
-    }
+    rs_sample_distinct<4>(seed, h, n, idx);
     double y[9], x[9], Rs[36], ts[12];
     for (int s = 0; s < 3; s++) {
         const int i = idx[s];
@@ -1313,11 +1279,7 @@ __global__ void __launch_bounds__(64) k_pnp_hyp(const float* __restrict__ X, con
         const double* R = Rs + 9 * best;
         const double* t = ts + 3 * best;
         for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) Rt[r * 4 + c] = R[r * 3 + c]; Rt[r * 4 + 3] = t[r]; }
-        for (int c = 0; c < 4; c++) {
-            P[c] = (float)(K.fx * Rt[c] + K.cx * Rt[8 + c]);
-            P[4 + c] = (float)(K.fy * Rt[4 + c] + K.cy * Rt[8 + c]);
-            P[8 + c] = (float)Rt[8 + c];
-        }
+        pnp_project(K, Rt, P);
     }
     for (int k = 0; k < 12; k++) { Rt_out[(size_t)h * 12 + k] = Rt[k]; P_out[(size_t)h * 12 + k] = P[k]; }
 }
@@ -1333,40 +1295,28 @@ __device__ __forceinline__ bool reproj_inlier(const float* P, float X, float Y, 
     return zc > 0.0f && e < lim;
 }
 
-// one wave per hypothesis
+struct ReprojModel {                        // P (12 floats) on 3-D points and their pixels
+    static constexpr int W = 12;
+    const float *X, *uv;
+    __device__ __forceinline__ int live(int n) const { return n < 4 ? 0 : n; }
+    __device__ __forceinline__ bool inlier(const float* P, int i, float thr2) const
+    {
+        const float2 b = ((const float2*)uv)[i];
+        return reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2);
+    }
+};
+
 __global__ void __launch_bounds__(256) k_pnp_score(const float* __restrict__ X, const float* __restrict__ uv, int n,
                                                   const float* __restrict__ P_all, int iters, float thr2, int32_t* __restrict__ counts,
                                                   const int* __restrict__ n_dev)
 {
-    const int lane = threadIdx.x & 63;
-    const int h = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (h >= iters) return;
-    if (n_dev) n = *n_dev < 4 ? 0 : *n_dev;
-    float P[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) P[k] = P_all[(size_t)h * 12 + k];
-    int cnt = 0;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        bool in = false;
-        if (i < n) {
-            const float2 b = ((const float2*)uv)[i];
-            in = reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2);
-        }
-        cnt += __popcll(__ballot(in));
-    }
-    if (lane == 0) counts[h] = cnt;
+    rs_score_wave(ReprojModel{ X, uv }, n, P_all, iters, thr2, counts, n_dev);
 }
 
 __global__ void k_pnp_mask(const float* __restrict__ X, const float* __restrict__ uv, int n, const float* __restrict__ P_all,
                            const int32_t* __restrict__ best, float thr2, uint8_t* __restrict__ mask)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float P[12];
-    for (int k = 0; k < 12; k++) P[k] = P_all[(size_t)best[0] * 12 + k];
-    const float2 b = ((const float2*)uv)[i];
-    mask[i] = reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2) ? 1 : 0;
+    rs_mask_point(ReprojModel{ X, uv }, n, P_all, best, thr2, mask, nullptr);
 }
 
 extern "C" int vo_ransac_pnp(vo_ctx* ctx, const float* pts3d, const float* pts2d, int n, const double* K4v, int iters, float thr,
@@ -1375,41 +1325,28 @@ extern "C" int vo_ransac_pnp(vo_ctx* ctx, const float* pts3d, const float* pts2d
     if (!ctx || !pts3d || !pts2d || !K4v || !Rt12_out || !best2_out) return vo_fail(ctx, VO_E_ARG, "vo_ransac_pnp: bad argument");
     if (n < 4 || iters <= 0 || iters > (1 << 22) || n > (1 << 24)) return vo_fail(ctx, VO_E_ARG, "vo_ransac_pnp: need n >= 4 and 0 < iters <= 4194304");
     VO_HIP(ctx, hipSetDevice(ctx->device));
-    // workspace: Rt (iters x 96 B), points (n x 12 B + n x 8 B), P (iters x 48 B), counts, best, mask
-    const size_t need = (size_t)n * 24 + (size_t)iters * (96 + 48 + 4) + (size_t)n + 4096;
-    if (ctx->mw->ransac_ws_bytes < need) {
-        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
-        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, need));
-        ctx->mw->ransac_ws_bytes = need;
-    }
-    uint8_t* w = ctx->mw->ransac_ws;
-    double* d_Rt = (double*)w; w += (size_t)iters * 96;
-    float* d_uv = (float*)w; w += (size_t)n * 8;
-    float* d_X = (float*)w; w += (size_t)n * 12 + 8;
-    w = (uint8_t*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
-    float* d_P = (float*)w; w += (size_t)iters * 48;
-    int32_t* d_counts = (int32_t*)w; w += (size_t)iters * 4;
-    int32_t* d_best = (int32_t*)w; w += 256;
-    uint8_t* d_mask = w;
+    PnpHostWs w;
+    int rc = ws_reserve(ctx, &ctx->mw->ransac_ws, &ctx->mw->ransac_ws_bytes, pnp_host_ws_layout(nullptr, n, iters, &w));
+    if (rc) return rc;
+    pnp_host_ws_layout(ctx->mw->ransac_ws, n, iters, &w);
     StageTimer t(ctx, VO_T_POSE);
-    int rc = xfer_h2d(ctx, d_X, pts3d, (size_t)n * 12);
-    if (!rc) rc = xfer_h2d(ctx, d_uv, pts2d, (size_t)n * 8);
+    rc = xfer_h2d(ctx, w.X, pts3d, (size_t)n * 12);
+    if (!rc) rc = xfer_h2d(ctx, w.uv, pts2d, (size_t)n * 8);
     if (rc) return rc;
     const K4 K{ K4v[0], K4v[1], K4v[2], K4v[3] };
     const float thr2 = thr * thr;
-    hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, d_X, d_uv, n, K, iters, seed, d_Rt, d_P, nullptr);
-    hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, d_X, d_uv, n, d_P, iters, thr2, d_counts, nullptr);
-    hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, d_counts, iters, d_best);
-    hipLaunchKernelGGL(k_pnp_mask, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_X, d_uv, n, d_P, d_best, thr2, d_mask);
+    hipLaunchKernelGGL(k_pnp_hyp, dim3(div_up(iters, 64)), dim3(64), 0, ctx->stream, w.X, w.uv, n, K, iters, seed, w.Rt, w.P, nullptr);
+    hipLaunchKernelGGL(k_pnp_score, dim3(div_up(iters, 4)), dim3(256), 0, ctx->stream, w.X, w.uv, n, w.P, iters, thr2, w.counts, nullptr);
+    hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(1024), 0, ctx->stream, w.counts, iters, w.best);
+    hipLaunchKernelGGL(k_pnp_mask, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w.X, w.uv, n, w.P, w.best, thr2, w.mask);
     VO_CHECK_LAUNCH(ctx);
-    VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_best, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (mask_out && (rc = xfer_d2h(ctx, mask_out, d_mask, (size_t)n))) return rc;
-    if (counts_out && (rc = xfer_d2h(ctx, counts_out, d_counts, (size_t)iters * 4))) return rc;
+    VO_HIP(ctx, hipMemcpyAsync(ctx->pinned, w.best, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_out && (rc = xfer_d2h(ctx, mask_out, w.mask, (size_t)n))) return rc;
+    if (counts_out && (rc = xfer_d2h(ctx, counts_out, w.counts, (size_t)iters * 4))) return rc;
     if ((rc = xfer_flush(ctx))) return rc;
     best2_out[0] = ((int32_t*)ctx->pinned)[0];
     best2_out[1] = ((int32_t*)ctx->pinned)[1];
-    VO_HIP(ctx, hipMemcpy(Rt12_out, d_Rt + (size_t)best2_out[0] * 12, 96, hipMemcpyDeviceToHost));
+    VO_HIP(ctx, hipMemcpy(Rt12_out, w.Rt + (size_t)best2_out[0] * 12, 96, hipMemcpyDeviceToHost));
     return VO_OK;
 }
 
@@ -1486,8 +1423,8 @@ __device__ __forceinline__ void pn_gn_step(double* s_pose, double (*s_red)[27], 
     __syncthreads();
 }
 
-// The end of the step in ONE block of four waves: argmax of the inlier counts (most inliers, then the lowest index: k_ransac_best)
-// -> the winner's mask (k_pnp_mask's arithmetic) -> refine_iters Gauss-Newton steps in float64 on the winner's inliers: residual
+// The end of the step in ONE block of four waves: argmax of the inlier counts (rs_block_argmax) -> the winner's mask ->
+// refine_iters Gauss-Newton steps in float64 on the winner's inliers: residual
 // (fx X'/Z' + cx - u, fy Y'/Z' + cy - v), X' = R X + t, d X' / d (w, v) = [-[X']x | I]; the sums of a step are taken in a fixed
 // order (pn_gn_step), so the result is a function of the inputs alone; no early exit -> the whole
 // record (and the mask / q / t arrays when `arr` is given) written straight into pinned host memory.
@@ -1505,34 +1442,19 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
 {
     // rec_dev (may be NULL): device memory that receives the record too, for a kernel that follows on the stream (vo_track_map)
     __shared__ long long s_key[4];
-    __shared__ int s_best[2], s_status;
+    __shared__ int s_status;
     __shared__ double s_pose[12], s_red[4][27];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    long long key = -1;
-    for (int h = threadIdx.x; h < iters; h += blockDim.x) {
-        const long long k = ((long long)counts[h] << 32) | (long long)(0x7fffffff - h);   // most inliers, then lowest index
-        key = k > key ? k : key;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const long long other = __shfl_xor(key, o, 64); key = other > key ? other : key; }
-    if (lane == 0) s_key[wv] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 4; q++) key = s_key[q] > key ? s_key[q] : key;
-        s_best[0] = 0x7fffffff - (int)(key & 0x7fffffffLL);
-        s_best[1] = (int)(key >> 32);
-        s_status = 1;
-    }
-    __syncthreads();
-    const int best = s_best[0], best_count = s_best[1], n = hdr[1], live = n < 4 ? 0 : n;
+    if (threadIdx.x == 0) s_status = 1;
+    int best, best_count;
+    rs_block_argmax(counts, iters, s_key, best, best_count);
+    const ReprojModel md{ X, uv };
+    const int n = hdr[1], live = md.live(n);
     if (threadIdx.x < 12) s_pose[threadIdx.x] = Rt_all[(size_t)best * 12 + threadIdx.x];
     float P[12];
-    for (int k = 0; k < 12; k++) P[k] = P_all[(size_t)best * 12 + k];
+    rs_winner_model<ReprojModel>(P_all, best, P);
     for (int i = threadIdx.x; i < nq; i += blockDim.x) {
-        uint8_t in = 0;
-        if (i < live) {
-            const float2 b = ((const float2*)uv)[i];
-            in = reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2) ? 1 : 0;
-        }
+        const uint8_t in = rs_inlier_of(md, P, i, live, thr2) ? 1 : 0;
         mask[i] = in;                       // (read back below by the thread that wrote it)
         if (arr) {
             arr[i] = in;
@@ -1578,22 +1500,13 @@ __global__ void __launch_bounds__(256) k_pnp_finish(const int32_t* __restrict__ 
                 if (threadIdx.x < 12) s_pose[threadIdx.x] = s_prev[threadIdx.x];
                 break;
             }
-            if (threadIdx.x < 4) {              // P = K [R | t] rounded to float32, as k_pnp_hyp forms a hypothesis's
-                const int c = threadIdx.x;
-                s_P[c] = (float)(K.fx * s_pose[c] + K.cx * s_pose[8 + c]);
-                s_P[4 + c] = (float)(K.fy * s_pose[4 + c] + K.cy * s_pose[8 + c]);
-                s_P[8 + c] = (float)s_pose[8 + c];
-            }
+            if (threadIdx.x < 4) pnp_project_col(K, s_pose, threadIdx.x, s_P);      // one column a thread
             __syncthreads();
             for (int k = 0; k < 12; k++) P[k] = s_P[k];
             int cnt = 0;
             for (int i0 = 0; i0 < nq; i0 += blockDim.x) {       // (uniform trip count: every lane takes part in the ballot)
                 const int i = i0 + threadIdx.x;
-                bool in = false;
-                if (i < live) {
-                    const float2 b = ((const float2*)uv)[i];
-                    in = reproj_inlier(P, X[3 * i], X[3 * i + 1], X[3 * i + 2], b.x, b.y, thr2);
-                }
+                const bool in = rs_inlier_of(md, P, i, live, thr2);
                 if (i < nq) mask[i] = in ? 1 : 0;              // (its own points: read back by the thread that wrote them)
                 cnt += __popcll(__ballot(in));
             }
@@ -1658,28 +1571,10 @@ int pnp_check(vo_ctx* ctx, int slot_a, int slot_b, int match_flags, const double
 // the RANSAC workspace of the match scratch currently installed in ctx (the main one, or a pose alternate's), laid out for one step
 int pnp_ws_take(vo_ctx* ctx, int nq, int iters, PnpWs* ws)
 {
-    // workspace: Rt (iters x 96 B), P (iters x 48 B), counts, hdr, the compacted correspondences (X, uv, q, t), mask
-    const size_t need = (size_t)iters * (96 + 48 + 4) + (size_t)nq * (12 + 8 + 4 + 4 + 1) + 4096;
-    if (ctx->mw->ransac_ws_bytes < need) {       // first use of this workspace (or a larger step than any before): never on the steady path
-        VO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->mw->ransac_ws) (void)hipFree(ctx->mw->ransac_ws);
-        ctx->mw->ransac_ws = nullptr; ctx->mw->ransac_ws_bytes = 0;
-        const size_t take = std::max(need, (size_t)256 * (96 + 48 + 4) + (size_t)ctx->kp_cap * 29 + 4096);
-        VO_HIP(ctx, hipMalloc((void**)&ctx->mw->ransac_ws, take));
-        ctx->mw->ransac_ws_bytes = take;
-    }
-    uint8_t* w = ctx->mw->ransac_ws;
-    ws->Rt = (double*)w; w += (size_t)iters * 96;
-    ws->P = (float*)w; w += (size_t)iters * 48;
-    ws->counts = (int32_t*)w; w += (size_t)iters * 4;
-    w = (uint8_t*)(((uintptr_t)w + 255) & ~(uintptr_t)255);
-    PnpDev& d = ws->d;
-    d.hdr = (int32_t*)w; w += 256;
-    d.uv = (float*)w; w += (size_t)nq * 8;
-    d.X = (float*)w; w += (size_t)nq * 12;
-    d.q = (int32_t*)w; w += (size_t)nq * 4;
-    d.t = (int32_t*)w; w += (size_t)nq * 4;
-    ws->mask = w;
+    // the floor (256 hypotheses on kp_cap keypoints) makes the first allocation the last one on the steady path
+    const size_t need = pnp_ws_layout(nullptr, nq, iters, ws), floor = pnp_ws_layout(nullptr, ctx->kp_cap, 256, ws);
+    if (int rc = ws_reserve(ctx, &ctx->mw->ransac_ws, &ctx->mw->ransac_ws_bytes, need, floor)) return rc;
+    pnp_ws_layout(ctx->mw->ransac_ws, nq, iters, ws);
     return VO_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <condition_variable>
 #include "../../include/vo355.h"
+#include "ransac_ws.h"
 
 #define VO_ORB_LEVELS 8
 #define VO_ORB_EDGE 31
@@ -172,6 +173,7 @@ int klt_pyr_enqueue(vo_ctx* ctx, const uint8_t* a0, const uint8_t* b0, int w, in
 struct vo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    bool hyp5_ready = false;       // k_ransac_hyp5 may ask for its 100 KB of LDS: set at this context's first five-point launch
     // look-ahead engines (vo_prefetch_*): each has its own stream and staging; engine 0 shares the main
     // SGBM workspace, engines 1.. own an alternate one, so several pairs' SGBM can be in flight (one
     // pair's latency-bound kernels overlap another's bandwidth-bound ones)
@@ -330,7 +332,7 @@ struct vo_ctx {
         float *pts_a = nullptr, *pts_b = nullptr, *xy_a = nullptr, *xy_b = nullptr;
         uint8_t *st_a = nullptr, *st_b = nullptr, *clique_ws = nullptr;
         size_t clique_ws_bytes = 0;
-        uint8_t* ransac_ws = nullptr;    // grown on demand (mono_enqueue, vo_ransac_pnp)
+        uint8_t* ransac_ws = nullptr;    // grown on demand (ws_reserve), laid out per step (ransac_ws.h)
         size_t ransac_ws_bytes = 0;
         KltWs klt;                       // completed at the workspace's first Lucas-Kanade use (klt.hip)
     };
@@ -644,6 +646,9 @@ __device__ __forceinline__ bool knn_mutual(int t, int i, const uint32_t* __restr
 enum { MATCH_WS_POSE = 1 };
 hipError_t match_ws_alloc(vo_ctx* ctx, vo_ctx::MatchWs& m, int what);
 void match_ws_free(vo_ctx::MatchWs& m);
+// The one grow step of the workspaces sized on demand (ransac_ws, clique_ws): *ptr holds `need` bytes on return.  A buffer that
+// is too small is freed behind a wait for ctx->stream and replaced by max(need, floor) bytes.
+int ws_reserve(vo_ctx* ctx, uint8_t** ptr, size_t* bytes, size_t need, size_t floor = 0);
 int match_knn2(vo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int32_t* d_idx,
                int32_t* d_dist, int cross = 0, const float* xy_q = nullptr, const float* xy_t = nullptr, float rx = 0.f, float ry = 0.f);
 // match_flags of an _ex / fused entry: VO_E_ARG for an unknown bit, and for VO_MATCH_WINDOW while the context has no window
@@ -683,8 +688,7 @@ struct PnpRec {
 };
 static const size_t PNP_HDR = 1024;
 static inline size_t pnp_cap(int kp_cap) { return ((size_t)kp_cap + 15) & ~(size_t)15; }
-// device scratch of one step behind the RANSAC arrays: hdr {M, n, flags}, the n usable correspondences in match order
-struct PnpDev { int32_t *hdr, *q, *t; float *X, *uv; };
+// (PnpDev, the step's device scratch, and PnpWs: ransac_ws.h)
 // kNN-2 is done (m_idx / m_dist of the current match scratch): ratio test (+ cross-check), 3-D lookup in slot a, compaction
 // nq_dev (may be NULL): a device word that bounds the query rows the kernel looks at (vo_track_map: the rows behind it are padding)
 int pnp_prep_launch(vo_ctx* ctx, FrameSlot& a, FrameSlot& b, double ratio, int cross, const PnpDev& d, const LoopGate& g,
@@ -705,7 +709,6 @@ int pnp_lo_check(vo_ctx* ctx, int lo_rounds, int refine_iters, const char* who);
 // workspace of the match scratch in force laid out for nq keypoints and iters hypotheses (grown, behind a wait for ctx->stream,
 // where it is too small).  pnp_tail_enqueue: everything behind the prep launch -- k_pnp_hyp, k_pnp_score, k_pnp_finish<LO> on
 // ctx->stream, reading the compacted (X, uv, hdr, q, t) of w.d; rec / arr / rec_dev as in pnp_enqueue.
-struct PnpWs { double* Rt; float* P; int32_t* counts; PnpDev d; uint8_t* mask; };
 int pnp_ws_take(vo_ctx* ctx, int nq, int iters, PnpWs* w);
 int pnp_tail_enqueue(vo_ctx* ctx, const PnpWs& w, int nq, const double* K4v, int iters, float thr, uint32_t seed, int refine_iters, int lo_rounds,
                      PnpRec* rec, uint8_t* arr, PnpRec* rec_dev);

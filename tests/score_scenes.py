@@ -211,6 +211,32 @@ def check_p3p(r, s, bar=1e-6):
     return d
 
 
+# ---- ties, and a second trip of the block-wide argmax -----------------------------------------------------------------------------
+# At n = 8 (6 for the five-point solver, 4 for PnP) every hypothesis sees every point of a noise-free scene, so many hypotheses hold
+# the full count and the winner is decided by the tie-break alone; 257 and 1025 hypotheses give a 256-thread and a 1024-thread
+# block a second trip through the counts.  The scenes are exact_scene's: TIE_K4 for the stand-alone entries, the small camera
+# for the slots of the fused steps.
+TIE_ITERS = (257, 1025)
+TIE_N = {8: 8, 5: 6, "pnp": 4}             # solver -> n
+TIE_SCENE_SEED = 3
+
+
+def tie_scene(solver, K4=GEN_K4):
+    return exact_scene(TIE_N[solver], TIE_SCENE_SEED, K4=K4)
+
+
+def ties(counts):
+    """-> how many hypotheses hold the largest count"""
+    counts = np.asarray(counts)
+    return int((counts == counts.max()).sum())
+
+
+def tie_rule(r):
+    """winner_rule on a run whose winner the tie-break decided"""
+    assert ties(r["counts"]) >= 2, "only one hypothesis holds the largest count %d" % int(np.asarray(r["counts"]).max())
+    winner_rule(r)
+
+
 # ---- the scenes planted into slots for the fused steps ---------------------------------------------------------------------------
 FUSED_NQ, FUSED_M, FUSED_ITERS, FUSED_THR, FUSED_RATIO = 230, 200, 300, 1.0, 0.8     # 200 matches: three trips of a wave and a tail
 

@@ -13,6 +13,9 @@
                  the planted pose (to 1e-6 where points and pixels are exact in float32: score_scenes.dyadic_pnp_scene says why;
                  on generic points every count is asserted and the distance printed).
     NaN          three of 65 correspondences NaN in both views: outliers, and the other 62 as the definition has them.
+    ties         n = 8 / 6 / 4 noise-free points and 257 or 1025 hypotheses: many hold the full count, so the winner is the tie-break's
+                 (the lowest index, np.argmax's), and the block-wide argmax of every entry takes a second trip through the counts.
+                 The fused steps return no counts: theirs are the stand-alone entry's on the same correspondences.
 
 The cases are tests/score_scenes.py.  The fused steps run on planted slots in one child process against the test-only library.
 Every test prints its figures (undecidable share, hypotheses with a full count, residual ratio)."""
@@ -81,6 +84,30 @@ def test_nan_correspondences_are_outliers_and_leave_the_rest_alone(ctx_small, so
     SS.winner_rule(r)
 
 
+# ---- ties: the winner is the lowest index of the largest count ----------------------------------------------------------------
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("iters", SS.TIE_ITERS)
+def test_essential_winner_among_ties_is_the_lowest_index(ctx_small, iters, solver):
+    s = SS.tie_scene(solver)
+    r = ctx_small.ransac_essential(s["p1"], s["p2"], s["K4"], iters, SS.GEN_THR, SS.SEED, want_counts=True, solver=solver)
+    assert len(r["mask"]) == SS.TIE_N[solver] and len(r["counts"]) == iters
+    _hold_mask(SR.sampson(r["E"], s["K4"], s["p1"], s["p2"], SS.GEN_THR), r["mask"], "ties, solver %d, %d hypotheses" % (solver, iters))
+    SS.tie_rule(r)
+    assert r["best_iter"] == int(np.argmax(r["counts"]))
+    print("%d hypotheses hold the largest count %d, the winner is %d" % (SS.ties(r["counts"]), r["best_count"], r["best_iter"]))
+
+
+@pytest.mark.parametrize("iters", SS.TIE_ITERS)
+def test_pnp_winner_among_ties_is_the_lowest_index(ctx_small, iters):
+    s = SS.tie_scene("pnp")
+    r = ctx_small.ransac_pnp(s["X"], s["p2"], s["K4"], iters, SS.GEN_THR, SS.SEED, want_counts=True)
+    assert len(r["mask"]) == SS.TIE_N["pnp"] and len(r["counts"]) == iters
+    _hold_mask(SR.reproj(r["Rt"], s["K4"], s["X"], s["p2"], SS.GEN_THR), r["mask"], "ties, PnP, %d hypotheses" % iters)
+    SS.tie_rule(r)
+    assert r["best_iter"] == int(np.argmax(r["counts"]))
+    print("%d hypotheses hold the largest count %d, the winner is %d" % (SS.ties(r["counts"]), r["best_count"], r["best_iter"]))
+
+
 # ---- the hypothesis generators ------------------------------------------------------------------------------------------------
 def test_eight_point_hypotheses_are_exact_at_n8(ctx_small):
     worst_full, worst_ratio = SS.GEN_ITERS, 0.0
@@ -120,17 +147,22 @@ def test_p3p_hypotheses_are_exact_at_n4(ctx_small):
 # ---- masks of the fused steps: in the child process -----------------------------------------------------------------------------
 FUSED_NQ, FUSED_M, FUSED_ITERS, FUSED_THR, FUSED_RATIO = SS.FUSED_NQ, SS.FUSED_M, SS.FUSED_ITERS, SS.FUSED_THR, SS.FUSED_RATIO
 FUSED_STEPS = ["mono_pair_8", "mono_pair_5", "mono_pair_async_8", "mono_pair_async_5", "mono_pose_pair_8", "mono_pose_pair_5", "pnp_pair", "map_track"]
+# the tie scenes through the fused entries: "<step>@<hypotheses>"
+TIE_STEPS = ["%s@%d" % (step, iters) for iters in SS.TIE_ITERS for step in ("mono_pair_async_8", "mono_pair_async_5", "mono_pose_pair_8",
+                                                                            "mono_pose_pair_5", "pnp_pair")]
+TIE_PAD = 7                                # keypoints of slot a beside the matched ones
 
 
-def _plant_matches(ctx, rng, pa, pb, xyz_a=None, sa=0, sb=1):
-    """two slots whose matches are the FUSED_M planted pairs: slot a's keypoint q[k] at pa[k] (3-D point xyz_a[k]), slot b's t[k] at pb[k]"""
+def _plant_matches(ctx, rng, pa, pb, xyz_a=None, sa=0, sb=1, nq=FUSED_NQ):
+    """two slots whose matches are the len(pa) planted pairs (FUSED_M of FUSED_NQ keypoints unless the caller has fewer): slot a's
+    keypoint q[k] at pa[k] (3-D point xyz_a[k]), slot b's t[k] at pb[k]"""
     import planted as P
-    dq, dt, q, t = P.descriptors(FUSED_NQ, FUSED_M, rng)
+    dq, dt, q, t = P.descriptors(nq, len(pa), rng)
     mq, mt = P.matches(dq, dt, FUSED_RATIO)
     assert np.array_equal(mq, q) and np.array_equal(mt, t)
-    xy_a = rng.uniform(0, 600, (FUSED_NQ, 2)).astype(np.float32)
+    xy_a = rng.uniform(0, 600, (nq, 2)).astype(np.float32)
     xy_b = rng.uniform(0, 600, (len(dt), 2)).astype(np.float32)
-    Xa = P._cloud(FUSED_NQ, rng).astype(np.float32)
+    Xa = P._cloud(nq, rng).astype(np.float32)
     xy_a[q], xy_b[t] = pa, pb
     if xyz_a is not None:
         Xa[q] = xyz_a
@@ -139,29 +171,36 @@ def _plant_matches(ctx, rng, pa, pb, xyz_a=None, sa=0, sb=1):
     return q, t, xy_a, xy_b, Xa
 
 
-def _mono_case(ctx, name):
+def _mono_case(ctx, name, tie_iters=0):
+    """tie_iters: the tie scene of the solver under that many hypotheses in place of the planted scene"""
     import mono_pose_ref as MR
     solver = int(name.rsplit("_", 1)[1])
-    s = SS.fused_essential_scene(solver)
-    q, t, xy_a, xy_b, _ = _plant_matches(ctx, np.random.default_rng([13, solver]), s["p1"], s["p2"])
+    s = SS.tie_scene(solver, SS.K_VGA) if tie_iters else SS.fused_essential_scene(solver)
+    m, iters, thr = (len(s["p1"]), tie_iters, SS.GEN_THR) if tie_iters else (FUSED_M, FUSED_ITERS, FUSED_THR)
+    q, t, xy_a, xy_b, _ = _plant_matches(ctx, np.random.default_rng([13, solver]), s["p1"], s["p2"], nq=m + TIE_PAD if tie_iters else FUSED_NQ)
     a = (0, 1, FUSED_RATIO, s["K4"])
-    kw = dict(iters=FUSED_ITERS, thr=FUSED_THR, seed=SS.SEED, solver=solver)
+    kw = dict(iters=iters, thr=thr, seed=SS.SEED, solver=solver)
     sync = ctx.mono_pair(*a, want_matches=True, **kw)
+    if tie_iters:                                  # the counts of these correspondences: the stand-alone entry draws the same hypotheses
+        ref = ctx.ransac_essential(xy_a[q], xy_b[t], s["K4"], tie_iters, thr, SS.SEED, want_counts=True, solver=solver)
+        SS.tie_rule(ref)
+        assert sync["best_iter"] == ref["best_iter"] == int(np.argmax(ref["counts"])) and sync["best_count"] == ref["best_count"]
+        print("%s: %d of %d hypotheses hold the largest count %d, the winner is %d" % (name, SS.ties(ref["counts"]), tie_iters, ref["best_count"], ref["best_iter"]))
     if name.startswith("mono_pair_async"):
         r = ctx.mono_pair_end(ctx.mono_pair_begin(*a, want_matches=True, **kw), want_matches=True)
-        assert np.array_equal(r["E"], sync["E"]) and np.array_equal(r["mask"], sync["mask"])
+        assert np.array_equal(r["E"], sync["E"]) and np.array_equal(r["mask"], sync["mask"]) and r["best_iter"] == sync["best_iter"]
     else:
         r = sync
-    assert r["matches"] == FUSED_M and np.array_equal(r["q"], q) and np.array_equal(r["t"], t)
-    d = SR.sampson(r["E"], s["K4"], xy_a[r["q"]], xy_b[r["t"]], FUSED_THR)
+    assert r["matches"] == m and np.array_equal(r["q"], q) and np.array_equal(r["t"], t)
+    d = SR.sampson(r["E"], s["K4"], xy_a[r["q"]], xy_b[r["t"]], thr)
     if not name.startswith("mono_pose"):
         share = _hold_mask(d, r["mask"], name)
-        assert r["best_count"] == int(r["mask"].sum()) and r["best_count"] >= FUSED_M // 2
+        assert r["best_count"] == int(r["mask"].sum()) and r["best_count"] >= m // 2
         return dict(share=share, best_count=r["best_count"])
     # the pose step hands out no mask: its winner, its count, and the depths it leaves on the inliers' keypoints in slot b
     p = ctx.mono_pose_pair(*a, **kw)
-    assert p["matches"] == FUSED_M and p["best_iter"] == r["best_iter"] and np.array_equal(p["E"], r["E"]) and p["flags"] & 3 == 0
-    lo, hi = int(d.sure_in.sum()), FUSED_M - int(d.sure_out.sum())
+    assert p["matches"] == m and p["best_iter"] == r["best_iter"] and np.array_equal(p["E"], r["E"]) and p["flags"] & 3 == 0
+    lo, hi = int(d.sure_in.sum()), m - int(d.sure_out.sum())
     assert lo <= p["best_count"] <= hi and p["best_count"] == r["best_count"], "best_count %d, the definition allows %d .. %d" % (p["best_count"], lo, hi)
     depth, serial = ctx.download_mono_depth(1)
     assert serial == p["serial"] != 0
@@ -171,7 +210,7 @@ def _mono_case(ctx, name):
     front = (z1 > 1e-6) & (z2 > 1e-6)
     missing = d.sure_in & front & ~has
     assert not missing.any(), "%d sure inliers in front of both cameras carry no depth" % int(missing.sum())
-    assert int(has.sum()) == p["n_depth"] <= p["best_count"] and p["n_depth"] >= FUSED_M // 2
+    assert int(has.sum()) == p["n_depth"] <= p["best_count"] and p["n_depth"] >= m // 2
     share = float(SR.undecidable(d).mean())
     print("%s: best_count %d in %d .. %d, %d depths, undecidable share %.4f" % (name, p["best_count"], lo, hi, p["n_depth"], share))
     assert share <= SS.CAP
@@ -191,6 +230,23 @@ def _pnp_case(ctx, org):
     assert not r["mask"][s["behind"]].any(), "a point behind the camera or on its plane is an inlier"
     moved = len(SR.disagreements(SR.reproj(r["Rt_refined"], s["K4"], X, uv, FUSED_THR), r["mask"]))
     print("pnp_pair: under Rt_refined %d decidable points would disagree" % moved)
+    return dict(share=share, best_count=r["best_count"])
+
+
+def _pnp_tie_case(ctx, org, iters):
+    s = SS.tie_scene("pnp", SS.K_VGA)
+    m, o32 = len(s["X"]), np.float32(org)
+    q, t, xy_a, xy_b, Xa = _plant_matches(ctx, np.random.default_rng(16), np.zeros((m, 2), np.float32), s["p2"] - o32, xyz_a=s["X"], nq=m + TIE_PAD)
+    r = ctx.pnp_pair(0, 1, FUSED_RATIO, s["K4"], iters=iters, thr=SS.GEN_THR, seed=SS.SEED, refine=3, want_matches=True)
+    assert (r["matches"], r["n"]) == (m, m) and np.array_equal(r["q"], q) and np.array_equal(r["t"], t)
+    X, uv = Xa[r["q"]], (xy_b[r["t"]] + o32).astype(np.float32)
+    ref = ctx.ransac_pnp(X, uv, s["K4"], iters, SS.GEN_THR, SS.SEED, want_counts=True)
+    SS.tie_rule(ref)
+    assert r["best_iter"] == ref["best_iter"] == int(np.argmax(ref["counts"])) and r["best_count"] == ref["best_count"]
+    assert np.array_equal(r["Rt"], ref["Rt"]) and np.array_equal(r["mask"], ref["mask"])
+    share = _hold_mask(SR.reproj(r["Rt"], s["K4"], X, uv, SS.GEN_THR), r["mask"], "pnp_pair@%d" % iters)
+    assert r["best_count"] == int(r["mask"].sum()) >= m // 2
+    print("pnp_pair@%d: %d hypotheses hold the largest count %d, the winner is %d" % (iters, SS.ties(ref["counts"]), ref["best_count"], ref["best_iter"]))
     return dict(share=share, best_count=r["best_count"])
 
 
@@ -228,6 +284,9 @@ def _fused_body():
     for name in FUSED_STEPS:
         fn = (lambda: _pnp_case(ctx, G.ORG)) if name == "pnp_pair" else (lambda: _map_case(ctx)) if name == "map_track" else (lambda: _mono_case(ctx, name))
         G._guard(out, name, fn)
+    for name in TIE_STEPS:
+        step, iters = name.split("@")
+        G._guard(out, name, (lambda: _pnp_tie_case(ctx, G.ORG, int(iters))) if step == "pnp_pair" else (lambda: _mono_case(ctx, step, int(iters))))
     ctx.close()
     print("FUSED-RESULT " + json.dumps(out))
 
@@ -250,7 +309,7 @@ def _child():
     return _RESULT[0]
 
 
-@pytest.mark.parametrize("name", FUSED_STEPS)
+@pytest.mark.parametrize("name", FUSED_STEPS + TIE_STEPS)
 def test_fused_step_mask_is_the_definition(name):
     res = _child()[name]
     assert res["ok"], res["err"]

@@ -201,6 +201,23 @@ def test_the_planted_and_the_nan_scenes_are_valid_too(oracle):
     assert moved and all(moved.values()), moved
 
 
+@pytest.mark.parametrize("K4", [SS.GEN_K4, SS.K_VGA], ids=["hd", "vga"])
+@pytest.mark.parametrize("iters", SS.TIE_ITERS)
+def test_the_tie_scenes_give_ties(oracle, iters, K4):
+    """the scenes of the device's tie cases: several hypotheses hold the largest count, and the oracle picks the first of them"""
+    for solver in SOLVERS:
+        s = SS.tie_scene(solver, K4)
+        r = oracle.ransac_essential(s["p1"], s["p2"], s["K4"], iters, SS.GEN_THR, SS.SEED, solver=solver)
+        assert len(SR.disagreements(SR.sampson(r["E"], s["K4"], s["p1"], s["p2"], SS.GEN_THR), r["mask"])) == 0
+        SS.tie_rule(r)
+        print("solver %d, %d hypotheses: %d hold the largest count %d" % (solver, iters, SS.ties(r["counts"]), r["best_count"]))
+    s = SS.tie_scene("pnp", K4)
+    r = oracle.ransac_pnp(s["X"], s["p2"], s["K4"], iters, SS.GEN_THR, SS.SEED)
+    assert len(SR.disagreements(SR.reproj(r["Rt"], s["K4"], s["X"], s["p2"], SS.GEN_THR), r["mask"])) == 0
+    SS.tie_rule(r)
+    print("PnP, %d hypotheses: %d hold the largest count %d" % (iters, SS.ties(r["counts"]), r["best_count"]))
+
+
 def test_every_wrong_definition_has_a_valid_scene(ess_runs, pnp_runs):
     for name in SR.WRONG_SAMPSON:
         for solver in SOLVERS:
