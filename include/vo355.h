@@ -901,6 +901,38 @@ typedef struct vo_direct_ab_rec {
 int vo_direct_align_ab(vo_ctx* ctx, int slot_a, int slot_b, const double* K4, const double* Rt0 /*12*/, int levels, int iters, int max_points,
                        int grad_min, double huber, double dmin, double dmax, double z_min, int min_pixels, vo_direct_ab_rec* rec_out);
 
+/* PATCH ALIGNMENT (an extension, NOT part of the reference): the photometric refinement for SPARSE stereo depth -- sparse model-based
+ * image alignment.  The points are small pixel patches around slot a's depth-carrying keypoints, every pixel of a patch sharing its
+ * keypoint's depth; no disparity image is read.  Defined operation by operation like vo_direct_align (tests/direct_kp_ref.py restates
+ * it); EVERYTHING not stated here is vo_direct_align's, word for word: the pyramid, the level intrinsics, the rectangle of a level with
+ * and without a ROI, one iteration from x' on (the test of taking part, the bilinear sample, r, the Huber weight, the TEMPLATE's
+ * gradient in the Jacobian, the 21 + 6 + 2 sums), the Cholesky solve and the twist, the schedule, the statuses 0 / 2 / -1, "the pose
+ * of the last completed iteration", the float64 rules and the order of the sums over the points (per thread ascending in the point
+ * index below, a tree over the wave, the waves in order).
+ *   Inputs: slot a holds a pair and keypoints that carry depth (vo_sparse_stereo); n, kp_xy (pixels of the ROI crop) and the Z of
+ *   kp_xyz are read, kp_disp is NOT.  Slot b holds a pair of the same shape; it needs no keypoints.  patch is 3, 5 or 7, hp = patch / 2
+ *   (integer); all other parameter ranges are vo_direct_align's.  Q[2][3] must be finite and not zero.
+ *   Keypoint i (x_i, y_i float32, Z_i float32): vx = (double)(x_i + (float)ox), vy = (double)(y_i + (float)oy), the additions in
+ *   float32 as step d of vo_sparse_stereo, (ox, oy) the origin of the ROI crop ((0, 0) without a ROI).  The keypoint is USABLE iff
+ *   vx, vy and Z_i are finite, Z_i > 0, 0 <= vx < w and 0 <= vy < h -- tested in floating point BEFORE any conversion to an integer.
+ *   s_i = (double)Z_i / Q[2][3].
+ *   Level l: cx = (int)rint(vx / 2^l), cy = (int)rint(vy / 2^l) (half to even).  A usable keypoint is IN USE at level l iff its patch
+ *   and the one-pixel ring the gradient reads lie in the level's rectangle: cx - hp >= x_lo + 1, cx + hp <= x_hi - 2, cy - hp >= y_lo + 1,
+ *   cy + hp <= y_hi - 2.  Its points: (x, y) = (cx + dx, cy + dy) for dx, dy = -hp .. hp, point index i patch^2 + (dy + hp) patch +
+ *   (dx + hp).  Overlapping patches and duplicate keypoints each contribute: nothing is de-duplicated.
+ *   Selection: gx2 = A[y][x + 1] - A[y][x - 1], gy2 = A[y + 1][x] - A[y - 1][x] with gx2 gx2 + gy2 gy2 >= 4 grad_min grad_min.
+ *   The 3-D point: X = (x 2^l + Q[0][3]) s_i, Y = (y 2^l + Q[1][3]) s_i, Z = (double)Z_i.
+ *   The record: vo_direct_rec; lv[l].s = the number of keypoints in use at level l (0 for a level the step never reached), pad = patch;
+ *   everything else as vo_direct_align fills it.
+ * One launch of one workgroup (k_direct_align_kp) behind the pyramid launches, ONE host synchronisation, the timing brackets of
+ * vo_direct_align.
+ *   VO_E_ARG: a bad slot or pointer, a parameter outside its range (patch other than 3, 5, 7), a non-finite Rt0 / K4.  VO_E_STATE:
+ *   a slot without a pair; slot a's keypoints carry no depth (a dense slot, or none extracted); two slots of different shapes; no
+ *   vo_set_Q, or a Q[2][3] that is zero or not finite.  VO_E_CAP: slot a holds more keypoints than the context's capacity, or
+ *   n patch^2 does not fit the 31-bit point index.  A refused call writes no record. */
+int vo_direct_align_kp(vo_ctx* ctx, int slot_a, int slot_b, const double* K4, const double* Rt0 /*12*/, int levels, int iters, int patch,
+                       int grad_min, double huber, double z_min, int min_pixels, vo_direct_rec* rec_out);
+
 /* instrumentation ------------------------------------------------------------------------ */
 /* hipEvent timing of the kernels launched on the context stream (events are recorded without
  * blocking and resolved by vo_get_timings).  Stage ids: */

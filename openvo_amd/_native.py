@@ -53,7 +53,7 @@ SYMBOLS = [
     "vo_pnp_pair_lo", "vo_pnp_pair_begin_lo", "vo_pnp_pair_end_lo", "vo_track_map_lo",
     "vo_klt_track_host", "vo_klt_track", "vo_klt_pnp_pair", "vo_klt_pnp_pair_begin", "vo_klt_pnp_pair_end",
     "vo_set_sgbm_cost", "vo_get_sgbm_cost", "vo_sgbm_cost_volume",
-    "vo_direct_align", "vo_direct_align_ab",
+    "vo_direct_align", "vo_direct_align_ab", "vo_direct_align_kp",
 ]
 
 
@@ -372,6 +372,9 @@ def lib():
         for name in ("vo_direct_align", "vo_direct_align_ab"):      # (likewise: an older build has no dense direct alignment, or no affine term)
             if hasattr(L, name):
                 getattr(L, name).argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, cd, cd, cd, cd, ci, vp]
+        for name in ("vo_direct_align_kp",):        # (likewise: an older build has no patch alignment)
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, cd, cd, ci, vp]
         plant = getattr(L, "vo_test_plant_dense_pair", None)     # (only the test-only build, libvo355_hooks.so, exports it)
         if plant is not None:
             plant.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp]
@@ -1191,6 +1194,36 @@ class Context:
         rec = DirectAbRec() if affine else DirectRec()
         self._ck(getattr(self._lib, entry)(self._h, int(slot_a), int(slot_b), _p(K4), _p(Rt), *prm, ctypes.byref(rec)))
         return rec.as_dict()
+
+    # ---- patch alignment (vo_direct_align_kp)
+    @staticmethod
+    def direct_kp_params(levels=3, iters=4, patch=5, grad_min=8, huber=10.0, z_min=0.1, min_pixels=64):
+        """the parameters of direct_align_kp as the library takes them, checked as the library checks them (ValueError)"""
+        if isinstance(patch, (bool, np.bool_)) or not isinstance(patch, (int, np.integer)) or patch not in (3, 5, 7):
+            raise ValueError("patch is 3, 5 or 7, not %r" % (patch,))
+        p = Context.direct_params(levels=levels, iters=iters, grad_min=grad_min, huber=huber, z_min=z_min, min_pixels=min_pixels)
+        return (p[0], p[1], int(patch), p[3], p[4], p[7], p[8])
+
+    def direct_align_kp(self, slot_a, slot_b, K4, Rt0=None, levels=3, iters=4, patch=5, grad_min=8, huber=10.0, z_min=0.1, min_pixels=64):
+        """Photometric refinement of the a -> b motion on slot_a's depth-carrying keypoints (vo_direct_align_kp, include/vo355.h): a
+        patch x patch pixel patch around every keypoint of slot_a (a sparse slot), each pixel at its keypoint's depth, against slot_b's
+        rectified left image, from Rt0 (3 x 4 or 4 x 4; None: the identity); one launch and one synchronisation.  -> the dict of
+        direct_align, with `keypoints` (per level: the keypoints whose patch lies in the level's rectangle) in the place of `s`, and
+        `patch`."""
+        if not hasattr(self._lib, "vo_direct_align_kp"):
+            raise RuntimeError("this build of the library has no patch alignment (vo_direct_align_kp)")
+        prm = self.direct_kp_params(levels, iters, patch, grad_min, huber, z_min, min_pixels)
+        K4 = _c(np.asarray(K4, np.float64).reshape(4), np.float64)
+        Rt = np.eye(4)[:3] if Rt0 is None else np.asarray(Rt0, np.float64)
+        if Rt.shape == (4, 4):
+            Rt = Rt[:3]
+        Rt = _c(Rt.reshape(12), np.float64)
+        rec = DirectRec()
+        self._ck(self._lib.vo_direct_align_kp(self._h, int(slot_a), int(slot_b), _p(K4), _p(Rt), *prm, ctypes.byref(rec)))
+        d = rec.as_dict()
+        d["keypoints"] = d.pop("s")
+        d["patch"] = int(rec.pad)
+        return d
 
     def plant_dense_pair(self, slot, left, disp16, xy, desc=None):
         """Test-only build of the library: plant_dense, and the (h, w) uint8 image `left` as the slot's rectified pair

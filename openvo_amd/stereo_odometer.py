@@ -37,7 +37,7 @@ class StereoOdometer:
                  loop_check=None, track="pair", map_max_age=5, map_capacity=None, map_max_obs=8, map_z_min=0.1, map_fused=False,
                  pnp_lo_rounds=0, match="orb", klt_window=21, klt_levels=4, klt_fb=1.0, klt_fused=False,
                  direct_refine=False, direct_levels=3, direct_iters=8, direct_max_points=16384, direct_guard=(0.1, 0.05),
-                 direct_affine=False):
+                 direct_affine=False, patch_refine=False, patch_size=5, patch_levels=3, patch_iters=4, patch_guard=(0.1, 0.05)):
         """Arguments up to min_matches are the reference's [reference :14-15].  pose_method="pnp" is an
         extension (not in openVO): the pair's pose comes from RANSAC solvePnP on the previous frame's 3-D
         points and the new frame's keypoint pixels (vo_ransac_pnp) instead of the 3-D/3-D Umeyama fit;
@@ -141,7 +141,20 @@ class StereoOdometer:
         between frames: the plain alignment assumes brightness constancy and walks away from the pose when it does not hold.
         direct_brightness is (gain, offset) of the last step, None when that step completed fewer than three iterations (none that estimates them);
         pose_information is then the pose information marginalised over the brightness.  Guard, gates and status handling are
-        unchanged."""
+        unchanged.
+        patch_refine=True (an extension, NOT in the reference; default False; needs depth="sparse" and track="pair"; not together
+        with direct_refine): the photometric refinement for sparse stereo depth.  Every pose that reaches the motion gates --
+        either pose method, match="orb" or "klt" (klt_fused included), the one-frame-back fallback too -- is first handed to the
+        PATCH alignment (include/vo355.h, vo_direct_align_kp) as its start: a patch_size x patch_size pixel patch (3, 5 or 7)
+        around every keypoint of the older frame, each pixel at its keypoint's sparse depth, against the newer frame's rectified
+        left image, patch_levels pyramid levels (1 .. 4), patch_iters iterations per level (1 .. 20).  No disparity image is
+        computed.  The refined pose replaces the feature pose iff the step ended with status 0 and moved it by no more than
+        patch_guard = (metres, radians), scaled by skipped_frames + 1: direct_refine's rule exactly, and what is said there about
+        the guard and pose_method="umeyama" holds here.  patch_status is the status of the last step, patch_record its whole record,
+        patch_accepted whether its pose was taken, pose_information the 6 x 6 information matrix of the pose the last step
+        delivered: None whenever that pose was not taken or the gates refused it.  The call is synchronous, under run() as well:
+        one more synchronisation per frame.  Both frames must be on the device (ValueError otherwise).  track="map" is refused:
+        the view slot holds no image."""
         if not isinstance(track, str) or track not in ("pair", "map"):
             raise ValueError("track must be 'pair' or 'map'")
         if track == "map" and (depth != "sparse" or pose_method != "pnp"):
@@ -260,6 +273,31 @@ class StereoOdometer:
                     raise ValueError("direct_affine=True needs direct_iters >= 3 (the first two iterations of a level hold the brightness)")
                 self.direct_affine = True        # (instance attributes only in affine mode, as above)
                 self.direct_brightness = None
+        if not isinstance(patch_refine, (bool, np.bool_)):
+            raise ValueError("patch_refine must be True or False")
+        if patch_refine:
+            if depth != "sparse":
+                raise ValueError("patch_refine=True needs depth='sparse' (the alignment reads the keypoints' sparse depth; direct_refine is the dense one)")
+            if track == "map":
+                raise ValueError("patch_refine=True needs track='pair' (the view slot of track='map' holds no image)")
+            if direct_refine:
+                raise ValueError("patch_refine=True and direct_refine=True exclude each other")
+            try:
+                prm = _native.Context.direct_kp_params(levels=patch_levels, iters=patch_iters, patch=patch_size)
+                guard = tuple(patch_guard)
+                if len(guard) != 2 or any(isinstance(g, (bool, np.bool_, str, bytes)) or not np.isfinite(g) or g < 0 for g in guard):
+                    raise TypeError
+            except ValueError as e:
+                raise ValueError("patch_levels / patch_iters / patch_size: %s" % e)
+            except TypeError:
+                raise ValueError("patch_guard is a pair (metres, radians) of finite numbers >= 0, not %r" % (patch_guard,))
+            # (instance attributes only where the option is on: without it the object is what it was)
+            self.patch_refine = True
+            self.patch_levels, self.patch_iters, self.patch_size = prm[0], prm[1], prm[2]
+            self.patch_guard = (float(guard[0]), float(guard[1]))
+            self.patch_status = self.patch_record = self.pose_information = None
+            self.patch_accepted = False
+            self._patch_pair = None      # (slot a, slot b) of the pair being tried, None while its frames are not on the device
         self.pose_method, self.pnp_iters, self.pnp_threshold, self.pnp_seed = pose_method, pnp_iters, pnp_threshold, pnp_seed
         self.stereo = stereo_camera
         self.current_img = self.current_disparity = self.current_3d = None
@@ -506,6 +544,7 @@ class StereoOdometer:
     direct_refine = False    # True (constructor): every pair pose goes through the dense direct alignment before the gates (_direct)
     direct_affine = False    # True (constructor): the alignment estimates a gain and an offset of the newer image beside the pose
     direct_brightness = None  # (gain, offset) of the last step in affine mode; None when the step gave none
+    patch_refine = False     # True (constructor): every pair pose goes through the patch alignment before the gates (_patch)
     _map_size = 0            # landmarks in the map as its last update reported (set with the first fold)
     _pnp_fused = True        # False: pose_method="pnp" takes the composed path (_pair_pnp) whatever the conditions
     _PNP_CTX_SEAMS = ("point_clouds", "ransac_pnp")
@@ -811,9 +850,13 @@ class StereoOdometer:
             self._pair_span = None
 
     def _try_pair_span(self, kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b):
-        if self.direct_refine:
+        if self.direct_refine or self.patch_refine:     # (the two exclude each other) the slots of the pair being tried, for the alignment
             on_dev = self._on_device(kps_a, desc_a, im3d_a) and self._on_device(kps_b, desc_b, im3d_b)
-            self._direct_pair = (kps_a.frame.slot, kps_b.frame.slot) if on_dev else None
+            pair = (kps_a.frame.slot, kps_b.frame.slot) if on_dev else None
+            if self.direct_refine:
+                self._direct_pair = pair
+            else:
+                self._patch_pair = pair
         if self.match == "klt":
             return self._pair_klt(kps_a, desc_a, im3d_a, kps_b, desc_b, im3d_b)
         # fused device path when nothing along the way was replaced by the user
@@ -1091,6 +1134,8 @@ class StereoOdometer:
             return None
         if self.direct_refine:
             T = self._direct(T)
+        if self.patch_refine:
+            T = self._patch(T)
         scale = self.skipped_frames + 1
         dist = np.linalg.norm(T[0:3, 3])
         angle = np.linalg.norm(self._ctx.rodrigues(T[0:3, 0:3]))
@@ -1101,10 +1146,38 @@ class StereoOdometer:
         if too_turned:
             self.skip_cause = "bigrot"
         if too_far or too_turned:
-            if self.direct_refine:
+            if self.direct_refine or self.patch_refine:
                 self.pose_information = None            # (the pose it belongs to was refused)
             return None
         return T
+
+    def _guarded(self, T, Tr, guard):
+        """whether the refined pose Tr lies within guard = (metres, radians) x (skipped_frames + 1) of the feature pose T"""
+        D = Tr @ np.linalg.inv(T)                       # what the alignment moved the pose by
+        scale = self.skipped_frames + 1
+        dist = np.linalg.norm(D[0:3, 3])
+        angle = np.arccos(min(1.0, max(-1.0, (np.trace(D[0:3, 0:3]) - 1.0) / 2.0)))
+        return not (dist > guard[0] * scale or angle > guard[1] * scale)
+
+    def _patch(self, T):
+        """patch_refine: the feature pose T (4 x 4, a -> b) of the pair being tried -> the pose the gates see: the patch alignment's
+        where it ended with status 0 and within patch_guard of T, T itself otherwise (_direct's rule)."""
+        if self._patch_pair is None:
+            raise ValueError("patch_refine=True needs the device-resident frames compute_sparse returns")
+        Q = self.stereo.Q
+        K4 = [Q[2, 3], Q[2, 3], -Q[0, 3], -Q[1, 3]]
+        r = self._ctx.direct_align_kp(self._patch_pair[0], self._patch_pair[1], K4, T[:3], levels=self.patch_levels, iters=self.patch_iters,
+                                      patch=self.patch_size)
+        self.patch_status, self.patch_record, self.patch_accepted = r["status"], r, False
+        self.pose_information = None                    # (of the pose this step delivers, never of an older one)
+        if r["status"] != 0 or not np.isfinite(r["Rt"]).all():
+            return T
+        Tr = np.vstack([r["Rt"], [0, 0, 0, 1]])
+        if not self._guarded(T, Tr, self.patch_guard):
+            return T
+        self.patch_accepted = True
+        self.pose_information = r["information"]
+        return Tr
 
     def _direct(self, T):
         """direct_refine: the feature pose T (4 x 4, a -> b) of the pair being tried -> the pose the gates see: the dense direct
@@ -1123,11 +1196,7 @@ class StereoOdometer:
         if r["status"] != 0 or not np.isfinite(r["Rt"]).all():
             return T
         Tr = np.vstack([r["Rt"], [0, 0, 0, 1]])
-        D = Tr @ np.linalg.inv(T)                       # what the alignment moved the pose by
-        scale = self.skipped_frames + 1
-        dist = np.linalg.norm(D[0:3, 3])
-        angle = np.arccos(min(1.0, max(-1.0, (np.trace(D[0:3, 0:3]) - 1.0) / 2.0)))
-        if dist > self.direct_guard[0] * scale or angle > self.direct_guard[1] * scale:
+        if not self._guarded(T, Tr, self.direct_guard):
             return T
         self.direct_accepted = True
         self.pose_information = r["information"]

@@ -10,7 +10,13 @@ synthetic corridor).
 
 --affine: the step alone and nothing else, plain (vo_direct_align) and affine (vo_direct_align_ab: a gain and an offset estimated beside
 the pose) ALTERNATING inside every one of --rounds rounds of the same process, at both point counts; per round the medians of both and
-the ratio affine / plain of that round."""
+the ratio affine / plain of that round.
+
+--keypoints: the PATCH alignment of sparse stereo depth (Context.direct_align_kp, StereoOdometer(depth="sparse", patch_refine=True)).
+The step alone on two sparse slots of the stream, from the identity, at the odometer's defaults (3 levels x 4 iterations, patch 5),
+ALTERNATING with the dense step (3 x 8, 16384 points) on two dense slots inside every one of --rounds rounds: call time, kernel time,
+keypoints and points per level.  Then frames per second of synchronous update() loops and of run() in sparse mode with and without
+patch_refine, both pose methods, the modes alternating inside every round."""
 import argparse
 import json
 import os
@@ -22,6 +28,7 @@ ap.add_argument("--pairs", type=int, default=240, help="pairs per timed pass")
 ap.add_argument("--rounds", type=int, default=3, help="timed passes per mode, after one warm-up pass")
 ap.add_argument("--step-calls", type=int, default=200, help="timed calls of the step per point count")
 ap.add_argument("--affine", action="store_true", help="the step alone, plain and affine alternating in every round")
+ap.add_argument("--keypoints", action="store_true", help="the patch alignment of sparse stereo depth: the step beside the dense one, then the sparse loops")
 args = ap.parse_args()
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
@@ -99,13 +106,50 @@ if args.affine:
     print(json.dumps(result))
     sys.exit(0)
 
-result["step"] = step_alone()
+
+def timed_step_kp(sa, sb, **kw):
+    """timed_step for the patch alignment (Context.direct_align_kp)"""
+    wall, kern, r = [], [], None
+    for step in range(-10, args.step_calls):
+        ctx.enable_timing(step >= 0)
+        t0 = time.perf_counter()
+        r = ctx.direct_align_kp(sa, sb, K4, **kw)
+        dt = 1e6 * (time.perf_counter() - t0)
+        if step < 0:
+            continue
+        t = ctx.timings(reset=True)
+        wall.append(dt)
+        kern.append(1e3 * t["pose"][0])
+    ctx.enable_timing(False)
+    return dict(status=r["status"], iters_done=r["iters_done"], patch=r["patch"], keypoints=r["keypoints"].tolist(), selected=r["selected"].tolist(),
+                participants_last=r["n_last"].tolist(), call_us=stats(wall), kernel_us=stats(kern))
+
+
+def step_keypoints_and_dense():
+    da, db = step_slots()
+    ka = cam.compute_sparse(*stream[0], 500, preprocessed=True)[2].frame.slot
+    kb = cam.compute_sparse(*stream[1], 500, preprocessed=True)[2].frame.slot
+    rounds = []
+    for _ in range(args.rounds):                       # the patch step and the dense step alternate inside every round
+        kp, dense = timed_step_kp(ka, kb), timed_step(da, db, 16384)
+        rounds.append(dict(keypoints=kp, dense=dense, kernel_keypoints_over_dense=round(kp["kernel_us"]["median"] / dense["kernel_us"]["median"], 3),
+                           call_keypoints_over_dense=round(kp["call_us"]["median"] / dense["call_us"]["median"], 3)))
+    return rounds
+
 
 # ---------------------------------------------------------------------------------------------- the loops
 BASE = dict(nfeatures=500, preprocessed_frames=True)
-MODES = {"umeyama": dict(rigidity_threshold=0.1, outlier_threshold=0.02), "umeyama_direct": dict(rigidity_threshold=0.1, outlier_threshold=0.02, direct_refine=True),
-         "pnp": dict(pose_method="pnp"), "pnp_direct": dict(pose_method="pnp", direct_refine=True)}
-
+if args.keypoints:
+    result["step_keypoints_and_dense"] = step_keypoints_and_dense()
+    MODES = {"umeyama": dict(depth="sparse"), "umeyama_patch": dict(depth="sparse", patch_refine=True),
+             "pnp": dict(depth="sparse", pose_method="pnp"), "pnp_patch": dict(depth="sparse", pose_method="pnp", patch_refine=True)}
+    REFINED, WORKLOAD = "_patch", "sparse depth, %d host pairs per pass (synthetic corridor, one GPU); patch_refine at its defaults (3 x 4, patch 5)"
+else:
+    result["step"] = step_alone()
+    MODES = {"umeyama": dict(rigidity_threshold=0.1, outlier_threshold=0.02), "umeyama_direct": dict(rigidity_threshold=0.1, outlier_threshold=0.02, direct_refine=True),
+             "pnp": dict(pose_method="pnp"), "pnp_direct": dict(pose_method="pnp", direct_refine=True)}
+    REFINED, WORKLOAD = "_direct", ("dense depth, %d host pairs per pass (synthetic corridor, one GPU); umeyama with the clique "
+                                    "and outlier filters (0.1, 0.02)")
 
 def one_pass(kw, run):
     odo = StereoOdometer(cam, **BASE, **kw)
@@ -114,7 +158,7 @@ def one_pass(kw, run):
     t0 = time.perf_counter()
     for ok in (odo.run(iter(stream)) if run else (odo.update(L, R) for L, R in stream)):
         accepted += bool(ok)
-        taken += bool(ok and odo.direct_refine and odo.direct_accepted)
+        taken += bool(ok and ((odo.direct_refine and odo.direct_accepted) or (odo.patch_refine and odo.patch_accepted)))
     ctx.synchronize()
     dt = time.perf_counter() - t0
     odo.reset_lookahead()
@@ -126,8 +170,7 @@ def report(rates):
                 "accepted": [x[1] for x in v], "refined_poses_taken": [x[2] for x in v]} for k, v in rates.items()}
 
 
-result["workload"] = ("C2 1280x720, 500 features, dense depth, %d host pairs per pass (synthetic corridor, one GPU); umeyama with the clique "
-                      "and outlier filters (0.1, 0.02)" % len(stream))
+result["workload"] = "C2 1280x720, 500 features, " + WORKLOAD % len(stream)
 result["rounds"] = args.rounds
 for name, run in (("update_frames_per_s", False), ("run_frames_per_s", True)):
     for kw in MODES.values():
@@ -138,6 +181,6 @@ for name, run in (("update_frames_per_s", False), ("run_frames_per_s", True)):
             rates[k].append(one_pass(kw, run))
     result[name] = report(rates)
     for m in ("umeyama", "pnp"):
-        result[name][m + "_direct_over_plain_per_round"] = [round(a_[0] / b_[0], 3) for a_, b_ in zip(rates[m + "_direct"], rates[m])]
+        result[name][m + REFINED + "_over_plain_per_round"] = [round(a_[0] / b_[0], 3) for a_, b_ in zip(rates[m + REFINED], rates[m])]
 ctx.close()
 print(json.dumps(result))
